@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the per-pixel render loop on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c5tile|c4|c5]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c5tile|c4|c5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one renderFrame(): all spp samples of every pixel of the frame (scene, path state and RNG streams resident
@@ -230,6 +230,26 @@ def load_profile(name, scale_from=None, scale=1.0):
     return prof, None
 
 
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, images):
+    """--dump-outputs: `images` (name -> H x W x 3 array) as out_dir/<name>.npy in float32.  Over DUMP_MAX_BYTES in all, the
+    same fixed, seeded sample of pixels is taken from every image (rows of 3 channels) and its flat pixel indices are written
+    as pixel_index.npy (float64, exact below 2^53), so two runs with the same arguments write the same pixels."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in images.items()}
+    n_px = next(iter(arrays.values())).shape[0] * next(iter(arrays.values())).shape[1]
+    assert all(a.shape[0] * a.shape[1] == n_px and a.shape[2] == 3 for a in arrays.values())
+    if sum(a.nbytes for a in arrays.values()) > DUMP_MAX_BYTES:
+        per_px = 12 * len(arrays) + 8                     # 3 float32 per image + the float64 index
+        idx = np.sort(np.random.default_rng(2023).choice(n_px, size=(DUMP_MAX_BYTES - 4096) // per_px, replace=False))
+        arrays = {k: a.reshape(n_px, 3)[idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def roofline_block(name, cfg, m, exact_workload):
     """roofline of the dominant kernel of one measured workload `m` (see measure())."""
     kernel_s = m["kernel_ms"] * 1e-3
@@ -379,6 +399,8 @@ def main():
     ap.add_argument("--gather", choices=("rgb8", "radiance", "both"), default="rgb8", help="what the frame-end gather moves (N > 1)")
     ap.add_argument("--pipeline", action="store_true", help="render the K steps as ONE pipelined batch (ptmi_render_frames) instead of one "
                     "ptmi_render_frame call per step; without it the batch rate is still reported as value_pipelined_batch (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the image of the last timed step as DIR/rgb8.npy and "
+                    "DIR/radiance.npy (float32; a fixed sample of pixels + DIR/pixel_index.npy above 64 MB); N > 1: rank 0's gathered frame")
     # profile pass (tools/profile.sh): exactly `steps` frames of the timing build of the kernel, nothing else on the GPU
     ap.add_argument("--profile-pass", action="store_true", help=argparse.SUPPRESS)
     # rehearsal of the N > 1 control flow on a box with fewer GPUs than ranks: ranks share devices and the gather
@@ -390,6 +412,8 @@ def main():
     # exercise the RCCL code path (comm init, gather, barrier) even with one rank; never used for reported numbers
     ap.add_argument("--force-dist", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -501,6 +525,17 @@ def main():
         return
 
     m = measure(r, cfg, args.steps, args.warmup, run_steps, barrier, args.segments, reduce_max, pipelined)
+    if args.dump_outputs:
+        # the last timed step's image, read before any later pass renders another frame: what the caller of the timed path
+        # receives - the local rows (N = 1), rank 0's gathered frame (N > 1)
+        if not use_dist:
+            rgb, rad = r.read_image()
+            dump_outputs(args.dump_outputs, {"rgb8": rgb, "radiance": rad})
+        elif rank == 0 and rccl:
+            rgb, rad = r.read_frame(rgb8=bool(what & 1), radiance=bool(what & 2))
+            dump_outputs(args.dump_outputs, {k: v for k, v in (("rgb8", rgb), ("radiance", rad)) if v is not None})
+        elif rank == 0:
+            dump_outputs(args.dump_outputs, {"rgb8": fg.frame_rgb.numpy(), "radiance": fg.frame_rad.numpy()})
     total_samples = float(cfg["width"]) * cfg["height"] * cfg["spp"] * args.steps if not (cfg["tiling"] and world == 1) \
         else m["local_samples_per_step"] * args.steps
     value = total_samples / m["elapsed"] / 1e6

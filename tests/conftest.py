@@ -2,6 +2,11 @@ import os
 import sys
 
 import pytest
+# before anything loads libptmi.so: torch ships its own HIP and HSA runtimes and asks for them by a name that the system's
+# libamdhip64.so.7 does not answer to, so a torch imported after libptmi.so (as a test that asks torch for the GPU does)
+# would put a second pair into the process, and both would tear down the device at exit.  Imported first, torch's pair is
+# the one libptmi.so binds to, as in bench.py.
+import torch  # noqa: F401,E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)

@@ -8,6 +8,8 @@ fixtures for this path and its integrator.h cannot be compiled here).  These fil
 ORACLE (regression) and give the GPU tests a fixture that does not need the oracle library.
 
 Run from the repo root:  python tests/golden/make_golden.py
+With --ref-only, only what the compiled reference (oracle/_ref) answers to tests/test_oracle_vs_ref.py and
+tests/test_pbrt_loader.py: golden/ref_geometry.npz and golden/ref_pbrt.npz.
 """
 import json
 import os
@@ -18,6 +20,12 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 from oracle_binding import OracleScene, SCENES, default_camera  # noqa: E402
+
+if "--ref-only" in sys.argv:
+    import subprocess
+    sys.exit(subprocess.call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(os.path.dirname(HERE), "test_oracle_vs_ref.py"),
+                             os.path.join(os.path.dirname(HERE), "test_pbrt_loader.py")],
+                             env=dict(os.environ, PTMI_RECORD_REF_ANSWERS="1")))
 
 CASES = [  # scene, subdivision, convert_quads, W, H, spp, max_depth
     ("cbox.obj", 0, False, 64, 64, 4, 5),

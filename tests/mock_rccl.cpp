@@ -20,8 +20,9 @@
 // not a blocking call.  The worker thread - one per process, batches strictly in posting order - makes NO call that needs a
 // GPU queue (HIP multiplexes a process's streams onto a few hardware queues; a copy of the worker's queued behind the gate it
 // is meant to open would never run): it waits for the event, writes the sends' files, reads the receives' files, sets the flag.
-// Run the processes with GPU_MAX_HW_QUEUES=8 so that the exchange stream does not share a hardware queue with a render
-// stream (sharing only delays, but it would also hide the very race the asynchronous test is there to catch).
+// The processes keep the hardware-queue count the machine gives them: where the exchange stream shares a hardware queue with
+// a render stream, the render work only waits behind the gate (every wait points at work posted earlier, so it cannot close a
+// cycle), and the asynchronous test then exercises less overlap than with a queue per stream.
 // PTMI_MOCK_RCCL_FAIL=recv|send makes that call return ncclInvalidArgument (fault injection for the product's error path).
 //
 // Build (the tests do it): hipcc -shared -fPIC -o <dir>/librccl.so.1 tests/mock_rccl.cpp

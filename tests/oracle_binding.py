@@ -5,6 +5,7 @@ oracle/_ref/libptmi_ref.so - the reference's own geometry headers compiled from
                              /root/reference (present only where it was built)
 """
 import ctypes as C
+import hashlib
 import os
 
 import numpy as np
@@ -433,3 +434,49 @@ def ref_obj_load(path):
         out = dict(type=t, verts=v, normal=nr, bsdf=b, Le=le, warnings=L.ref_obj_warning_count(h))
     L.ref_obj_free(h)
     return out
+
+
+# ---- the compiled reference's answers, live or recorded ---------------------------------------------------------------------
+RECORD_REF_ENV = "PTMI_RECORD_REF_ANSWERS"      # set by tests/golden/make_golden.py --ref-only: the fixture writes its golden file
+
+
+def sha(a):
+    """SHA-256 of an array's bytes (bit-exact equality for answers too bulky to record whole)."""
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)
+
+
+class RefAnswers:
+    """ref(key, ask): the compiled reference's answer, a dict of arrays.  ask() queries the live library; it is only called where
+    that library exists (`live` and `available`), and then its answer must also be the recorded one, bit for bit.  Everywhere
+    else the recorded answer is returned."""
+
+    def __init__(self, golden, live, recorded, record):
+        self.golden, self.live, self.recorded, self.record, self.fresh = golden, live, recorded, record, {}
+
+    def __call__(self, key, ask, available=True):
+        if self.live and available:
+            got = {k: np.ascontiguousarray(v) for k, v in ask().items()}
+            for k, v in got.items():
+                self.fresh[f"{key}/{k}"] = v
+                if not self.record:
+                    want = self.recorded.get(f"{key}/{k}")
+                    assert want is not None, f"{key}/{k} is not in {self.golden}: re-record it"
+                    assert want.dtype == v.dtype and want.shape == v.shape and want.tobytes() == v.tobytes(), \
+                        f"the compiled reference no longer answers {key}/{k} as recorded in {self.golden}"
+            return got
+        pre = f"{key}/"
+        got = {k[len(pre):]: v for k, v in self.recorded.items() if k.startswith(pre)}
+        assert got, f"{key} is not recorded in {self.golden}"
+        return got
+
+
+def recorded_reference(golden, live):
+    """Body of a module-scoped fixture: yields the RefAnswers of `golden` (an .npz); in record mode (RECORD_REF_ENV set, the
+    live library required) writes what was asked into `golden` when the module is done."""
+    record = bool(os.environ.get(RECORD_REF_ENV))
+    if record and not live:
+        raise RuntimeError(f"{RECORD_REF_ENV} is set but the compiled reference is not built")
+    r = RefAnswers(golden, live, {} if record else dict(np.load(golden)), record)
+    yield r
+    if record:
+        np.savez_compressed(golden, **r.fresh)

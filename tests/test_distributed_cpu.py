@@ -54,7 +54,7 @@ def test_gather_frame_with_several_ranks_over_a_mock_transport(tmp_path, world, 
     hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
     subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-o", str(lib_dir / "librccl.so.1"),
                     os.path.join(HERE, "mock_rccl.cpp")], check=True, timeout=600)
-    env = dict(os.environ, OMP_NUM_THREADS="2", PTMI_MOCK_RCCL_DIR=str(wire), GPU_MAX_HW_QUEUES="8",
+    env = dict(os.environ, OMP_NUM_THREADS="2", PTMI_MOCK_RCCL_DIR=str(wire),
                LD_LIBRARY_PATH=str(lib_dir) + os.pathsep + os.environ.get("LD_LIBRARY_PATH", ""))
     procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "dist_mock_worker.py"), str(W), str(H), "3", str(row_block), str(world), str(k),
                                str(dst), str(what), str(tmp_path / "id.bin")], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
@@ -71,8 +71,7 @@ def _mock_env(tmp_path, **extra):
     hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
     subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-o", str(lib_dir / "librccl.so.1"),
                     os.path.join(HERE, "mock_rccl.cpp")], check=True, timeout=600)
-    # GPU_MAX_HW_QUEUES=8: every stream of a rank on a hardware queue of its own (tests/mock_rccl.cpp says why)
-    return dict(os.environ, OMP_NUM_THREADS="2", PTMI_MOCK_RCCL_DIR=str(wire), GPU_MAX_HW_QUEUES="8",
+    return dict(os.environ, OMP_NUM_THREADS="2", PTMI_MOCK_RCCL_DIR=str(wire),
                 LD_LIBRARY_PATH=str(lib_dir) + os.pathsep + os.environ.get("LD_LIBRARY_PATH", ""), **extra)
 
 
@@ -120,7 +119,7 @@ def test_bench_with_three_ranks_over_the_mock_transport(tmp_path):
     hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
     subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-o", str(lib_dir / "librccl.so.1"),
                     os.path.join(HERE, "mock_rccl.cpp")], check=True, timeout=600)
-    env = dict(os.environ, OMP_NUM_THREADS="2", PTMI_MOCK_RCCL_DIR=str(wire), PTMI_RCCL_LIB=str(lib_dir / "librccl.so.1"), GPU_MAX_HW_QUEUES="8")
+    env = dict(os.environ, OMP_NUM_THREADS="2", PTMI_MOCK_RCCL_DIR=str(wire), PTMI_RCCL_LIB=str(lib_dir / "librccl.so.1"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "3", "--steps", "3", "--warmup", "1",
            "--rehearse-shared-gpu", "--no-cpu", "--spp", "4", "--side", "192"]

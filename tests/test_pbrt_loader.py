@@ -2,8 +2,10 @@
 against the REFERENCE's own loadPBRT - utils/pbrt_loader.h:178-422 compiled with the vendored pbrtParser into
 oracle/_ref/libptmi_ref_pbrt.so - bit for bit on the primitive arrays:
   * committed goldens (tests/golden/pbrt/*.npz, written by make_golden.py from the compiled reference) - these run anywhere;
-  * live, where oracle/_ref exists: the fixtures again, 300 random scenes (transform stacks incl. Rotate, instancing two
-    levels deep, area-light scoping, every convertible material) and the > 2,000,000-triangle proxy path.
+  * the fixtures again, 650 random scenes (transform stacks incl. Rotate, instancing two levels deep, area-light scoping, every
+    convertible material, .ply meshes, .spd spectra) and the > 2,000,000-triangle proxy path: against the compiled reference
+    where oracle/_ref exists, and against its answers recorded in tests/golden/ref_pbrt.npz (accepted or not, and a digest
+    of the primitive arrays per file; make_golden.py --ref-only) everywhere else - and where both exist, they must agree.
 A file the reference rejects (returns false, throws, or would crash) must be rejected by the product with PTMI_E_IO."""
 import glob
 import os
@@ -12,12 +14,43 @@ import numpy as np
 import pytest
 
 import ptmi
-from oracle_binding import ref_pbrt_available, ref_pbrt_load
+from oracle_binding import recorded_reference, ref_pbrt_available, ref_pbrt_load, sha
 from pbrt_fuzz import random_scene, random_scene_with_ply, random_scene_with_spd
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PBRT = os.path.join(HERE, "golden", "pbrt")
 F = np.float32
+GOLDEN = os.path.join(HERE, "golden", "ref_pbrt.npz")
+FIELDS = ("type", "verts", "normal", "bsdf", "Le")
+
+
+@pytest.fixture(scope="module")
+def ref():
+    yield from recorded_reference(GOLDEN, ref_pbrt_available())
+
+
+def digests(prims_list):
+    """per file: accepted or not, its primitive count, and the digest of its primitive arrays (bit for bit, one record)"""
+    def one(p):
+        if p is None:
+            return 0, 0, np.zeros(32, np.uint8)
+        return 1, len(p["type"]), sha(np.concatenate([np.ascontiguousarray(p["type"], np.int32).view(np.uint8).ravel()] +
+                                                     [np.ascontiguousarray(p[k], F).view(np.uint8).ravel() for k in FIELDS[1:]]))
+    rows = [one(p) for p in prims_list]
+    return dict(accepted=np.array([r[0] for r in rows], np.int32), n=np.array([r[1] for r in rows], np.int64),
+                sha=np.stack([r[2] for r in rows]) if rows else np.zeros((0, 32), np.uint8))
+
+
+def same_as_reference(ref, key, paths, what):
+    """the product's loads of `paths` against the reference's: returns, per file, whether the reference accepted it"""
+    want = ref(key, lambda: digests([ref_pbrt_load(str(f)) for f in paths]))
+    assert len(want["accepted"]) == len(paths), key
+    mine = digests([product_load(str(f)) for f in paths])
+    for i in range(len(paths)):
+        assert mine["accepted"][i] == want["accepted"][i], (what, i)
+        assert mine["n"][i] == want["n"][i], (what, i, mine["n"][i], want["n"][i])
+        assert (mine["sha"][i] == want["sha"][i]).all(), (what, i)
+    return want["accepted"].astype(bool)
 
 
 def same(got, want, what):
@@ -112,56 +145,40 @@ def test_pbrt_scene_goes_through_the_rest_of_load_scene():
     assert info["n_prims"] == 5 * 16 and info["n_tris"] == 80 and info["n_bvh_nodes"] > 20
 
 
-@pytest.mark.skipif(not ref_pbrt_available(), reason="oracle/_ref/libptmi_ref_pbrt.so not built (needs /root/reference)")
-def test_live_against_the_compiled_reference(tmp_path):
-    for f in sorted(glob.glob(os.path.join(PBRT, "*.pbrt"))):
-        want, got = ref_pbrt_load(f), product_load(f)
-        assert (want is None) == (got is None), os.path.basename(f)
-        if want is not None:
-            same(got, want, os.path.basename(f))
-    n_loaded = 0
-    for seed in range(300):
-        f = tmp_path / f"fuzz{seed}.pbrt"
-        f.write_text(random_scene(seed))
-        want, got = ref_pbrt_load(str(f)), product_load(str(f))
-        assert (want is None) == (got is None), seed
-        if want is not None:
-            same(got, want, f"fuzz seed {seed}")
-            n_loaded += 1
-    assert n_loaded > 200
-    n_loaded = 0
-    for seed in range(200):                                   # the same scenes plus "plymesh" shapes over random .ply files
-        f = tmp_path / f"plyfuzz{seed}.pbrt"
-        f.write_text(random_scene_with_ply(seed, str(tmp_path)))
-        want, got = ref_pbrt_load(str(f)), product_load(str(f))
-        assert (want is None) == (got is None), seed
-        if want is not None:
-            same(got, want, f"ply fuzz seed {seed}")
-            n_loaded += 1
-    assert n_loaded > 120
-    n_loaded = n_rejected = 0
-    for seed in range(150):                                   # the same scenes plus materials with "spectrum" parameters from .spd files
-        f = tmp_path / f"spdfuzz{seed}.pbrt"
-        f.write_text(random_scene_with_spd(seed, str(tmp_path)))
-        want, got = ref_pbrt_load(str(f)), product_load(str(f))
-        assert (want is None) == (got is None), seed
-        if want is not None:
-            same(got, want, f"spd fuzz seed {seed}")
-            n_loaded += 1
-        else:
-            n_rejected += 1
-    assert n_loaded > 45 and n_rejected > 15
+def test_live_against_the_compiled_reference(tmp_path, ref):
+    files = sorted(glob.glob(os.path.join(PBRT, "*.pbrt")))
+    same_as_reference(ref, "fixtures", files, [os.path.basename(f) for f in files])
+
+    def write(prefix, n, text):
+        out = []
+        for seed in range(n):
+            f = tmp_path / f"{prefix}{seed}.pbrt"
+            f.write_text(text(seed))
+            out.append(f)
+        return out
+    loaded = same_as_reference(ref, "fuzz", write("fuzz", 300, random_scene), "fuzz seed")
+    assert loaded.sum() > 200
+    # the same scenes plus "plymesh" shapes over random .ply files
+    loaded = same_as_reference(ref, "plyfuzz", write("plyfuzz", 200, lambda seed: random_scene_with_ply(seed, str(tmp_path))), "ply fuzz seed")
+    assert loaded.sum() > 120
+    # the same scenes plus materials with "spectrum" parameters from .spd files
+    loaded = same_as_reference(ref, "spdfuzz", write("spdfuzz", 150, lambda seed: random_scene_with_spd(seed, str(tmp_path))), "spd fuzz seed")
+    assert loaded.sum() > 45 and (~loaded).sum() > 15
 
 
-@pytest.mark.skipif(not ref_pbrt_available(), reason="oracle/_ref/libptmi_ref_pbrt.so not built (needs /root/reference)")
-def test_oversized_scene_becomes_the_bounding_box_proxy(tmp_path):
+def test_oversized_scene_becomes_the_bounding_box_proxy(tmp_path, ref):
     """more than 2,000,000 triangles: a 12-triangle box over the scene bounds (utils/pbrt_loader.h:205-270)"""
     f = tmp_path / "big.pbrt"
     with open(f, "w") as out:
         out.write('WorldBegin\nTranslate 1 2 3\nRotate 30 0 1 0\nObjectBegin "m"\nShape "trianglemesh" "point P" [0 0 0  2 0 0.5  0 3 1  -1 -1 -2] "integer indices" [\n')
         out.write("0 1 2 1 2 3\n" * 500001)
         out.write(']\nObjectEnd\nObjectInstance "m"\nScale 2 2 2\nObjectInstance "m"\nWorldEnd\n')
-    want, got = ref_pbrt_load(str(f)), product_load(str(f))
-    assert want is not None and len(want["type"]) == 12
+
+    def ask():
+        got = ref_pbrt_load(str(f))
+        assert got is not None
+        return got
+    want, got = ref("proxy", ask), product_load(str(f))
+    assert len(want["type"]) == 12
     same(got, want, "proxy")
     assert np.allclose(got["bsdf"], [[0.8, 0.2, 0.2]] * 12)
