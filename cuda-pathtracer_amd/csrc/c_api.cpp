@@ -89,6 +89,7 @@ int ptmi_load_scene(ptmi_ctx* c, const char* filename, int subdivision_count, in
         PTMI_HIP(hipSetDevice(c->app.device_id));
         c->app.config.convert_quads_to_triangles = convert_quads != 0;
         c->app.radiosity.cleanup();                       // a solution belongs to the scene it was computed for
+        accumReset(c->app);
         c->app.scene.loadScene(filename, subdivision_count, convert_quads != 0);
     });
 }
@@ -99,6 +100,7 @@ int ptmi_load_scene_arrays(ptmi_ctx* c, int n, const int* type, const float* ver
         need(c != nullptr, "ctx is NULL");
         PTMI_HIP(hipSetDevice(c->app.device_id));
         c->app.radiosity.cleanup();
+        accumReset(c->app);
         c->app.scene.loadSceneArrays(prims_from_arrays(n, type, verts, normal, bsdf, Le));
     });
 }
@@ -240,6 +242,7 @@ int ptmi_set_radiosity_grids(ptmi_ctx* c, int n_prims, const float* rgb) {
         need(rgb == nullptr || n_prims == (int)c->app.scene.h_primitives.size(), "n_prims does not match the loaded scene");
         PTMI_HIP(hipSetDevice(c->app.device_id));
         c->app.radiosity.grids_are_scene_grids = false;               // the caller's grids replace the solver's
+        accumReset(c->app);
         c->app.scene.precomputeCDFs(rgb);
     });
 }
@@ -249,6 +252,7 @@ int ptmi_set_radiosity(ptmi_ctx* c, int n_prims, const float* rgb) {
         need(c->app.scene.d_nodes != nullptr, "no scene loaded");
         need(rgb == nullptr || n_prims == (int)c->app.scene.h_primitives.size(), "n_prims does not match the loaded scene");
         PTMI_HIP(hipSetDevice(c->app.device_id));
+        accumReset(c->app);
         c->app.scene.setRadiosity(rgb);
     });
 }
@@ -268,6 +272,7 @@ int ptmi_run_radiosity_solver(ptmi_ctx* c, const ptmi_radiosity_params* p, ptmi_
         need(prm.filter_sigma_spatial > 0.0f && prm.filter_sigma_range > 0.0f, "filter sigmas must be positive");
         PTMI_HIP(hipSetDevice(c->app.device_id));
         RadiosityState& r = c->app.radiosity;
+        accumReset(c->app);
         r.num_iterations = prm.num_iterations; r.mc_samples = prm.mc_samples; r.use_monte_carlo = prm.use_monte_carlo != 0;
         RadiosityStats st;
         r.runSolver(c->app.scene, c->app.render.d_jump, prm.enable_filtering != 0, prm.use_bilateral != 0,
@@ -314,6 +319,7 @@ int ptmi_apply_grid_filter(ptmi_ctx* c, int use_bilateral, float sigma_spatial, 
         need(sigma_spatial > 0.0f && sigma_range > 0.0f, "filter sigmas must be positive");
         PTMI_HIP(hipSetDevice(c->app.device_id));
         sync_solver_grids(c);
+        accumReset(c->app);
         c->app.scene.precomputeCDFsFromFiltered(use_bilateral != 0, sigma_spatial, sigma_range, c->app.render.stream);
     });
 }
@@ -323,6 +329,7 @@ int ptmi_use_raw_cdfs(ptmi_ctx* c) {
         PTMI_HIP(hipSetDevice(c->app.device_id));
         sync_solver_grids(c);
         need(!c->app.scene.h_radiosity_grids.empty(), "the scene has no radiosity grids");
+        accumReset(c->app);
         c->app.scene.precomputeCDFs(c->app.scene.h_radiosity_grids.data());
     });
 }
@@ -351,6 +358,7 @@ int ptmi_update_resolution(ptmi_ctx* c, int width, int height, const ptmi_tiling
         TileMap tm;
         if (tiling) { tm.n_ranks = tiling->n_ranks; tm.rank = tiling->rank; tm.row_block = tiling->row_block; }
         c->app.render.seed_base = c->app.config.seed_base;
+        accumReset(c->app);
         c->app.render.updateResolution(width, height, tiling ? &tm : nullptr);
     });
 }
@@ -361,6 +369,7 @@ int ptmi_set_camera(ptmi_ctx* c, const ptmi_camera* cam) {
         AppConfig& cfg = c->app.config;
         cfg.camera_origin = v3(cam->origin); cfg.look_at = v3(cam->lookat); cfg.up = v3(cam->vup);
         cfg.fov = cam->vfov_deg; cfg.orbit = cam->orbit != 0;
+        accumReset(c->app);
         Sensor& s = c->app.render.h_camera;
         const int w = s.image_width, h = s.image_height; const float aspect = s.aspect;
         s = Sensor(cfg.camera_origin, cfg.look_at, cfg.up, cfg.fov, 1.0f);    // application.h:107-113
@@ -389,6 +398,7 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
         c->app.render.want_chunks = cfg->streams;
         c->app.render.download_image = cfg->download_image != 0;
         a.fast_tree = cfg->fast_tree != 0;
+        accumReset(c->app);
     });
 }
 
@@ -755,6 +765,36 @@ int ptmi_debug_cosine_sample(ptmi_ctx* c, int n, const float* normals, const flo
         PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
         d_o.download(out_dirs, 3 * (size_t)n);
     });
+}
+
+// ---- progressive and adaptive accumulation ----
+void ptmi_default_adaptive_params(ptmi_adaptive_params* p) {
+    if (!p) return;
+    const AdaptiveParams d;
+    p->min_passes = d.min_passes; p->max_passes = d.max_passes; p->threshold = d.threshold; p->floor = d.floor;
+}
+int ptmi_accum_reset(ptmi_ctx* c) {
+    return guarded([&] { need(c != nullptr, "ctx is NULL"); accumReset(c->app); });
+}
+int ptmi_accum_pass(ptmi_ctx* c, const ptmi_adaptive_params* params, ptmi_pass_stats* stats) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        AdaptiveParams prm;
+        if (params) { prm.min_passes = params->min_passes; prm.max_passes = params->max_passes; prm.threshold = params->threshold; prm.floor = params->floor; }
+        PassStats ps;
+        accumPass(c->app, params ? &prm : nullptr, stats ? &ps : nullptr);
+        if (stats) {
+            const FrameStats& fs = ps.frame;
+            stats->pass = ps.pass; stats->active_before = ps.active_before; stats->active_after = ps.active_after;
+            stats->samples = fs.samples; stats->seconds = fs.seconds; stats->bounce_kernel_ms = fs.bounce_kernel_ms;
+            stats->bounce_launches = fs.bounce_launches; stats->path_visits = fs.path_visits; stats->rays = fs.rays;
+            stats->node_visits = fs.node_visits; stats->prim_tests = fs.prim_tests; stats->hits = fs.hits;
+            stats->top_node_visits = fs.top_node_visits; stats->cert_chain = fs.cert_chain; stats->cert_fallback = fs.cert_fallback;
+        }
+    });
+}
+int ptmi_read_sample_counts(const ptmi_ctx* c, uint32_t* counts) {
+    return guarded([&] { need(c && counts, "NULL argument"); readSampleCounts(c->app, counts); });
 }
 
 }  // extern "C"

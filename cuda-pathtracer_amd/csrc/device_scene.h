@@ -181,6 +181,30 @@ void launch_render_radiosity(const DeviceScene& sc, const TileMap& tm, const Pat
 void launch_resolve(const TileMap& tm, const PathState& st, int spp, unsigned char* rgb8, float* radiance, hipStream_t s,
                     const float4* color_src = nullptr);
 
+// ---- accumulation passes (include/ptmi.h: ptmi_accum_pass) -------------------------------------------------------------
+// Per-pixel state of the stopping test, by slot, n_local each (RenderState::Accum allocates it at the first pass).
+struct AccumBuffers {
+    float4* prev = nullptr;          // S_{k-1}.xyz (the colour sum after the pixel's last pass), mean of the pass means
+    float* m2 = nullptr;             // sum of squared deviations of the pass means (Welford)
+    unsigned int* passes = nullptr;  // passes the pixel has taken in this accumulation
+};
+struct AdaptRule {
+    int first;                       // 1: pass 1 (no state read)
+    int stopping;                    // 0: plain progressive, no pixel stops
+    int min_passes, max_passes;
+    float threshold, floor_, inv_spp;
+};
+// ptmi_frame_begin for the n pixels of queue (nullptr: all local pixels): first camera ray of the pass, sample index 0, colour
+// sum kept (first: zeroed)
+void launch_pass_begin(const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s);
+// the stopping test of the n pixels of queue_in that took the pass; the ones that go on are appended to queue_out (*count_out,
+// zeroed by the caller)
+void launch_adapt(const PathState& st, const AccumBuffers& ab, const AdaptRule& rule, const int* queue_in, int n, int* queue_out,
+                  int* count_out, hipStream_t s);
+// launch_resolve with each pixel's own count passes[slot] * spp (all local pixels); counts: that count, local row-major
+void launch_resolve_counts(const TileMap& tm, const PathState& st, const unsigned int* passes, int spp, unsigned char* rgb8,
+                           float* radiance, unsigned int* counts, hipStream_t s);
+
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)
 

@@ -1397,16 +1397,8 @@ void launch_frame_begin(const TileMap& tm, const PathState& st, const FrameParam
 // ---------------------------------------------------------------------------------------------
 // resolve: color /= spp; Reinhard; gamma 1/2.2; 8-bit (integrator.h:393-407)
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void ptmi_resolve(TileMap tm, PathState st, int spp, unsigned char* __restrict__ rgb8,
-                                                       float* __restrict__ radiance, const float4* __restrict__ color_src) {
-    const int n = tm.local_rows * tm.width;
-    const int slot = blockIdx.x * kBlock + threadIdx.x;
-    if (slot >= n) return;
-    const float4 D = color_src ? color_src[slot] : st.D[slot];
-    int ox, olr;
-    slot_to_local(tm, slot, ox, olr);
-    const size_t out = (size_t)olr * (size_t)tm.width + (size_t)ox;      // images are local-row-major whatever the slot order
-    const float k = rcp_rn((float)spp);                    // Vector::operator/=(T): T k = 1.0 / t (vector.h:90-94)
+__device__ __forceinline__ void resolve_pixel(const float4& D, float k, size_t out, unsigned char* __restrict__ rgb8,
+                                              float* __restrict__ radiance) {
     const float c[3] = {D.x * k, D.y * k, D.z * k};
     const float gamma = 1.0f / 2.2f;
 #pragma unroll
@@ -1419,12 +1411,116 @@ __global__ __launch_bounds__(kBlock) void ptmi_resolve(TileMap tm, PathState st,
         }
     }
 }
+__global__ __launch_bounds__(kBlock) void ptmi_resolve(TileMap tm, PathState st, int spp, unsigned char* __restrict__ rgb8,
+                                                       float* __restrict__ radiance, const float4* __restrict__ color_src) {
+    const int n = tm.local_rows * tm.width;
+    const int slot = blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= n) return;
+    const float4 D = color_src ? color_src[slot] : st.D[slot];
+    int ox, olr;
+    slot_to_local(tm, slot, ox, olr);
+    const size_t out = (size_t)olr * (size_t)tm.width + (size_t)ox;      // images are local-row-major whatever the slot order
+    const float k = rcp_rn((float)spp);                    // Vector::operator/=(T): T k = 1.0 / t (vector.h:90-94)
+    resolve_pixel(D, k, out, rgb8, radiance);
+}
 
 void launch_resolve(const TileMap& tm, const PathState& st, int spp, unsigned char* rgb8, float* radiance, hipStream_t s,
                     const float4* color_src) {
     const int n = tm.local_rows * tm.width;
     if (n <= 0) return;
     hipLaunchKernelGGL(ptmi_resolve, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, tm, st, spp, rgb8, radiance, color_src);
+}
+
+// ---------------------------------------------------------------------------------------------
+// accumulation passes (include/ptmi.h: ptmi_accum_pass; device_scene.h: AccumBuffers)
+// ---------------------------------------------------------------------------------------------
+// ptmi_frame_begin for the queued pixels of a pass: the same draws, the same first camera ray; the sample index starts at 0
+// again and the colour sum goes on (first pass: from zero)
+__global__ __launch_bounds__(kBlock) void ptmi_pass_begin(TileMap tm, PathState st, FrameParams fp, const int* __restrict__ queue, int n, int first) {
+    const int idx = blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= n) return;
+    const int slot = queue ? queue[idx] : idx;
+    int x, y;
+    global_pixel(tm, slot, x, y);
+    const uint4 e = st.E[slot]; const uint2 f = st.F[slot];
+    Rng rng = {e.x, e.y, e.z, e.w, f.x, f.y};
+    f3 o, d;
+    camera_ray(fp, tm, x, y, rng, o, d);
+    const float4 D = first ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : st.D[slot];
+    st.A[slot] = make_float4(o.x, o.y, o.z, 1.0f);
+    st.B[slot] = make_float4(d.x, d.y, d.z, 1.0f);
+    st.C[slot] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    st.D[slot] = make_float4(D.x, D.y, D.z, __uint_as_float(0u));
+    st.E[slot] = make_uint4(rng.v0, rng.v1, rng.v2, rng.v3);
+    st.F[slot] = make_uint2(rng.v4, rng.d);
+}
+
+// The stopping test of the pass's pixels (the rule of include/ptmi.h, float32 in the order written there) and the next pass's
+// queue: the pixels that go on, in their input order inside a wave (ballot + prefix popcount, one atomic per wave)
+__global__ __launch_bounds__(kBlock) void ptmi_adapt(PathState st, AccumBuffers ab, AdaptRule rule, const int* __restrict__ queue_in, int n,
+                                                     int* __restrict__ queue_out, int* __restrict__ count_out) {
+    const int idx = blockIdx.x * kBlock + threadIdx.x;
+    const bool active = idx < n;
+    const int slot = active ? (queue_in ? queue_in[idx] : idx) : 0;
+    bool more = false;
+    if (active) {
+        const float4 S = st.D[slot];
+        const float4 prev = rule.first ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : ab.prev[slot];    // S_{k-1}.xyz, mean
+        float M2 = rule.first ? 0.0f : ab.m2[slot];
+        const unsigned int k = (rule.first ? 0u : ab.passes[slot]) + 1u;
+        const float dx = S.x - prev.x, dy = S.y - prev.y, dz = S.z - prev.z;
+        const float y = (0.2126f * dx + 0.7152f * dy + 0.0722f * dz) * rule.inv_spp;
+        const float nf = (float)k;
+        const float delta = y - prev.w;
+        const float mean = prev.w + delta / nf;
+        M2 = M2 + delta * (y - mean);
+        const float a = rule.threshold * (mean + rule.floor_);
+        const bool stop = rule.stopping && ((int)k >= rule.max_passes ||
+                                            ((int)k >= rule.min_passes && M2 <= a * a * (float)(k * (k - 1u))));
+        ab.prev[slot] = make_float4(S.x, S.y, S.z, mean);
+        ab.m2[slot] = M2;
+        ab.passes[slot] = k;
+        more = !stop;
+    }
+    const unsigned long long mask = __ballot(more);
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0 && mask) base = atomicAdd(count_out, __popcll(mask));
+    base = __shfl(base, 0);
+    if (more) queue_out[base + __popcll(mask & ((1ull << lane) - 1ull))] = slot;
+}
+
+// ptmi_resolve with every pixel's own sample count (passes x spp), over all local pixels: the ones that stopped keep their
+// image; also the count map, local row-major
+__global__ __launch_bounds__(kBlock) void ptmi_resolve_counts(TileMap tm, PathState st, const unsigned int* __restrict__ passes, int spp,
+                                                              unsigned char* __restrict__ rgb8, float* __restrict__ radiance,
+                                                              unsigned int* __restrict__ counts) {
+    const int n = tm.local_rows * tm.width;
+    const int slot = blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= n) return;
+    const float4 D = st.D[slot];
+    int ox, olr;
+    slot_to_local(tm, slot, ox, olr);
+    const size_t out = (size_t)olr * (size_t)tm.width + (size_t)ox;
+    const unsigned int samples = passes[slot] * (unsigned int)spp;          // < 2^24 (host check): exact as a float
+    counts[out] = samples;
+    resolve_pixel(D, rcp_rn((float)samples), out, rgb8, radiance);
+}
+
+void launch_pass_begin(const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_pass_begin, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, tm, st, fp, queue, n, first ? 1 : 0);
+}
+void launch_adapt(const PathState& st, const AccumBuffers& ab, const AdaptRule& rule, const int* queue_in, int n, int* queue_out,
+                  int* count_out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_adapt, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, st, ab, rule, queue_in, n, queue_out, count_out);
+}
+void launch_resolve_counts(const TileMap& tm, const PathState& st, const unsigned int* passes, int spp, unsigned char* rgb8,
+                           float* radiance, unsigned int* counts, hipStream_t s) {
+    const int n = tm.local_rows * tm.width;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_resolve_counts, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, tm, st, passes, spp, rgb8, radiance, counts);
 }
 
 // The proof of the certified walk for ONE hit (bounce_wide_body, VERIFY, in straight-line form): the hit point inside the hit leaf's

@@ -706,6 +706,7 @@ void RenderState::freeBuffers() {
     d_frame_color = nullptr; frame_color_frames = 0; batch_frames = 1; batch_spp = 0;
     if (h_image) { (void)hipHostFree(h_image); h_image = nullptr; }
     freeChunks();
+    freeAccum();
     d_state = PathState();
     d_image = nullptr; d_radiance = nullptr; d_stats = nullptr;
     n_local = 0;
@@ -745,6 +746,36 @@ void RenderState::setupChunks(int n) {
         PTMI_HIP(hipHostGetDevicePointer((void**)&ch.d_hcount, ch.h_count, 0));
         if (ch.n) PTMI_HIP(hipMemcpy(ch.d_queue_init, slots[c].data(), slots[c].size() * sizeof(int), hipMemcpyHostToDevice));
     }
+}
+
+void RenderState::freeAccum() {
+    Accum& a = accum;
+    void* ptrs[] = {a.d_active[0], a.d_active[1], a.ab.prev, a.ab.m2, a.ab.passes, a.d_counts, a.d_out_count,
+                    a.chunk.d_queue[0], a.chunk.d_queue[1], a.chunk.d_count};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (a.chunk.h_count) (void)hipHostFree(a.chunk.h_count);
+    a = Accum();
+}
+
+void RenderState::allocateAccum() {
+    freeAccum();
+    Accum& a = accum;
+    try {
+        const size_t n = std::max<size_t>(n_local, 1);
+        for (int k = 0; k < 2; k++) a.d_active[k] = (int*)hipMallocSafe(n * sizeof(int), "accum.active");
+        a.ab.prev = (float4*)hipMallocSafe(n * sizeof(float4), "accum.prev");
+        a.ab.m2 = (float*)hipMallocSafe(n * sizeof(float), "accum.m2");
+        a.ab.passes = (unsigned int*)hipMallocSafe(n * sizeof(unsigned int), "accum.passes");
+        a.d_out_count = (int*)hipMallocSafe(sizeof(int), "accum.out_count");
+        Chunk& ch = a.chunk;
+        ch.d_queue[0] = (int*)hipMallocSafe(n * sizeof(int), "accum.queue0");
+        ch.d_queue[1] = (int*)hipMallocSafe(n * sizeof(int), "accum.queue1");
+        ch.d_count = (int*)hipMallocSafe((4 * kCountRing + 1) * sizeof(int), "accum.count");
+        PTMI_HIP(hipMemset(ch.d_count, 0, (4 * kCountRing + 1) * sizeof(int)));
+        PTMI_HIP(hipHostMalloc((void**)&ch.h_count, kCountRing * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+        PTMI_HIP(hipHostGetDevicePointer((void**)&ch.d_hcount, ch.h_count, 0));
+        a.d_counts = (unsigned int*)hipMallocSafe(n * sizeof(unsigned int), "accum.counts");   // last: allocated() means complete
+    } catch (...) { freeAccum(); throw; }
 }
 
 void RenderState::allocateBuffers() {
@@ -831,6 +862,7 @@ void renderFrame(ApplicationState& g, FrameStats* stats) { renderFrames(g, 1, st
 
 void selectFrame(ApplicationState& g, int frame) {
     RenderState& r = g.render;
+    if (r.accum.pass > 0) throw ArgError("selectFrame: the image buffers hold an accumulation pass, not a frame batch");
     if (!r.d_state.A || r.batch_spp <= 0) throw ArgError("selectFrame: nothing rendered yet");
     if (frame < 0 || frame >= r.batch_frames) throw ArgError("selectFrame: frame index outside the last batch");
     PTMI_HIP(hipSetDevice(g.device_id));
@@ -842,7 +874,20 @@ void selectFrame(ApplicationState& g, int frame) {
     PTMI_HIP(hipStreamSynchronize(r.stream));
 }
 
+namespace {
+// One accumulation pass through renderRun: its queue is r.accum.chunk (d_queue_init / n: the pixels still active)
+struct PassRun { AdaptRule rule; int active_after = 0; };
+}  // namespace
+
+static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pass);
+
 void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
+    accumReset(g);                                     // a frame starts its sums from zero (ptmi_frame_begin)
+    renderRun(g, n_frames, stats, nullptr);
+}
+
+// A frame (pass == nullptr) or an accumulation pass: the same launch loop, a frame's launches exactly as they always were
+static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pass) {
     RenderState& r = g.render;
     if (n_frames < 1 || n_frames > 256) throw ArgError("renderFrames: n_frames must be in [1, 256]");
     if (n_frames > 1 && g.config.spp >= (1 << 16)) throw ArgError("renderFrames: a batch needs spp < 65536");
@@ -952,10 +997,14 @@ void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
     // With refill one launch keeps every wave slot busy by itself: a second chunk's kernel only competes with it (an eighth of the
     // 1 M-triangle frame 1 661 -> 1 716 Msamples/s with one chunk, the whole frame 2 600 -> 2 795; three chunks: 1 628 / 2 501).  The
     // automatic choice follows the walk; a forced count (config.streams) stays.
-    if (r.want_chunks == 0 && g.config.current_integrator == IntegratorType::PathTracing) {
+    if (!pass && r.want_chunks == 0 && g.config.current_integrator == IntegratorType::PathTracing) {
         const int want = refill ? 1 : (r.n_local >= (size_t)(1 << 18) ? 2 : 1);
         if (want != r.n_chunks) { PTMI_HIP(hipStreamSynchronize(r.stream)); r.setupChunks(want); }
     }
+    // a pass runs its queue as one chunk on chunk 0's stream
+    if (pass) r.accum.chunk.stream = r.chunk[0].stream;
+    RenderState::Chunk* chunks = pass ? &r.accum.chunk : r.chunk;
+    const int n_chunks = pass ? 1 : r.n_chunks;
 
     auto event = [&](size_t i) {
         while (g.event_pool.size() <= i) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
@@ -985,7 +1034,8 @@ void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
         return;
     }
 
-    launch_frame_begin(r.tile, r.d_state, fp, s);
+    if (pass) launch_pass_begin(r.tile, r.d_state, fp, chunks[0].d_queue_init, chunks[0].n, pass->rule.first != 0, s);
+    else launch_frame_begin(r.tile, r.d_state, fp, s);
 
     // Launch order of a refill frame: the pixels that took the most segments in the last frame first.  A pixel has ONE path in
     // flight, so the heaviest pixels are as long as the frame whatever the GPU does meanwhile; started last - in image order the
@@ -993,10 +1043,10 @@ void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
     // the rest.  The costs are the last frame's (same pixels, usually the same view); a first frame runs in image order.
     const int* first_queue = nullptr;
     unsigned int *cost_now = nullptr, *cost_max_now = nullptr;
-    if (refill && r.n_chunks == 1 && n_frames == 1 && order_by_cost) {
+    if (refill && n_chunks == 1 && n_frames == 1 && order_by_cost) {
         const int cur = (int)(r.cost_frame & 1), prev = cur ^ 1;
         if (r.cost_valid) {
-            launch_order_by_cost(r.chunk[0].d_queue_init, r.chunk[0].n, r.d_cost[prev], r.d_cost_max + prev, r.d_cost_hist, r.d_queue_ordered, order_classes, s);
+            launch_order_by_cost(chunks[0].d_queue_init, chunks[0].n, r.d_cost[prev], r.d_cost_max + prev, r.d_cost_hist, r.d_queue_ordered, order_classes, s);
             first_queue = r.d_queue_ordered;
         }
         PTMI_HIP(hipMemsetAsync(r.d_cost[cur], 0, std::max<size_t>(r.n_local, 1) * sizeof(unsigned int), s));
@@ -1015,18 +1065,18 @@ void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
     Run run[RenderState::kMaxChunks];
     const hipEvent_t ev_ready = event(n_ev++);
     PTMI_HIP(hipEventRecord(ev_ready, s));             // frame_begin (and the stats reset) precede every chunk's first launch
-    for (int c = 0; c < r.n_chunks; c++) {
-        run[c].bound = r.chunk[c].n; run[c].finished = r.chunk[c].n == 0;
+    for (int c = 0; c < n_chunks; c++) {
+        run[c].bound = chunks[c].n; run[c].finished = chunks[c].n == 0;
         for (int i = 0; i < kRing; i++) run[c].done[i] = event(n_ev++);
-        PTMI_HIP(hipStreamWaitEvent(r.chunk[c].stream, ev_ready, 0));
-        if (publish) PTMI_HIP(hipMemsetAsync(r.chunk[c].d_count, 0, (4 * kRing + 1) * sizeof(int), r.chunk[c].stream));   // once per frame
+        PTMI_HIP(hipStreamWaitEvent(chunks[c].stream, ev_ready, 0));
+        if (publish) PTMI_HIP(hipMemsetAsync(chunks[c].d_count, 0, (4 * kRing + 1) * sizeof(int), chunks[c].stream));   // once per frame
     }
     uint64_t launches = 0, visits = 0;
     const size_t first_pair_event = n_ev;
-    auto busy = [&] { for (int c = 0; c < r.n_chunks; c++) if (!run[c].finished || run[c].retired < run[c].issued) return true; return false; };
+    auto busy = [&] { for (int c = 0; c < n_chunks; c++) if (!run[c].finished || run[c].retired < run[c].issued) return true; return false; };
     while (busy()) {
-        for (int c = 0; c < r.n_chunks; c++) {
-            Run& u = run[c]; RenderState::Chunk& ch = r.chunk[c];
+        for (int c = 0; c < n_chunks; c++) {
+            Run& u = run[c]; RenderState::Chunk& ch = chunks[c];
             // (a refill launch takes the frame to its end: nothing to run ahead with)
             while (!u.finished && u.issued - u.retired < (refill ? 1 : kRunAhead)) {
                 const int slot_out = u.issued % kRing;
@@ -1038,7 +1088,7 @@ void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
                 const hipEvent_t e0 = stats ? event(n_ev++) : nullptr;
                 if (stats) PTMI_HIP(hipEventRecord(e0, ch.stream));
                 long long active = 0;                   // pixels still in flight, as far as the host has seen (counts only shrink)
-                for (int k = 0; k < r.n_chunks; k++) active += run[k].finished ? 0 : run[k].bound;
+                for (int k = 0; k < n_chunks; k++) active += run[k].finished ? 0 : run[k].bound;
                 const bool fits = wave_slots > 0 && (active + 63) / 64 * 100 <= wave_slots * fit_pct;
                 LaunchSchedule sched;
                 if (refill && active > 0) {
@@ -1062,8 +1112,8 @@ void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
                 u.issued++;
             }
         }
-        for (int c = 0; c < r.n_chunks; c++) {         // retire each chunk's oldest outstanding launch: its count is the new bound
-            Run& u = run[c]; RenderState::Chunk& ch = r.chunk[c];
+        for (int c = 0; c < n_chunks; c++) {         // retire each chunk's oldest outstanding launch: its count is the new bound
+            Run& u = run[c]; RenderState::Chunk& ch = chunks[c];
             if (u.retired == u.issued) continue;
             const int slot = u.retired % kRing;
             if (publish) {
@@ -1089,24 +1139,34 @@ void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
             if (out_count == 0) u.finished = true;
         }
     }
-    for (int c = 0; c < r.n_chunks; c++) {             // the resolve pass waits for every chunk
+    for (int c = 0; c < n_chunks; c++) {             // the resolve pass waits for every chunk
         const hipEvent_t ev = event(n_ev++);
-        PTMI_HIP(hipEventRecord(ev, r.chunk[c].stream));
+        PTMI_HIP(hipEventRecord(ev, chunks[c].stream));
         PTMI_HIP(hipStreamWaitEvent(s, ev, 0));
     }
     const size_t after_pairs = n_ev;
+    int active_after = 0;
+    if (pass) {                                        // the stopping test: the next pass's queue and its length
+        RenderState::Accum& a = r.accum;
+        PTMI_HIP(hipMemsetAsync(a.d_out_count, 0, sizeof(int), s));
+        launch_adapt(r.d_state, a.ab, pass->rule, chunks[0].d_queue_init, chunks[0].n, a.d_active[a.cur ^ 1], a.d_out_count, s);
+        PTMI_HIP(hipGetLastError());
+    }
 #ifndef PTMI_EXPERIMENT_NO_RESOLVE_GATE      // (never defined in the shipped build: make ab-host-lib, to see the asynchronous-exchange test fail without it)
     if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(s, r.resolve_gate, 0));   // a gather of the previous frame may still read the tile
 #endif
-    launch_resolve(r.tile, r.d_state, g.config.spp, r.d_image, r.d_radiance, s);
+    if (pass) launch_resolve_counts(r.tile, r.d_state, r.accum.ab.passes, g.config.spp, r.d_image, r.d_radiance, r.accum.d_counts, s);
+    else launch_resolve(r.tile, r.d_state, g.config.spp, r.d_image, r.d_radiance, s);
     const hipEvent_t ev_end = event(n_ev++);
     PTMI_HIP(hipEventRecord(ev_end, s));
+    if (pass) PTMI_HIP(hipMemcpyAsync(&active_after, r.accum.d_out_count, sizeof(int), hipMemcpyDeviceToHost, s));
     // cudaMemcpy(h_image, d_image, img_size, DeviceToHost), application.h:211 ("Memory Transfer" stage)
     if (r.download_image && n_local) PTMI_HIP(hipMemcpyAsync(r.h_image, r.d_image, (size_t)n_local * 3, hipMemcpyDeviceToHost, s));
     PTMI_HIP(hipStreamSynchronize(s));                 // cudaDeviceSynchronize, application.h:199
     PTMI_HIP(hipGetLastError());
     drain.armed = false;
-    r.batch_frames = n_frames; r.batch_spp = g.config.spp;
+    if (pass) pass->active_after = active_after;       // (select_frame has nothing to resolve after a pass: batch_spp stays 0)
+    else { r.batch_frames = n_frames; r.batch_spp = g.config.spp; }
     if (cost_now) { r.cost_valid = true; r.cost_frame++; }
 
     if (stats) {
@@ -1114,7 +1174,7 @@ void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
         PTMI_HIP(hipEventElapsedTime(&ms, ev_begin, ev_end));
         stats->seconds = ms * 1e-3;
         double kms = 0.0;
-        for (size_t i = first_pair_event; i + 1 < after_pairs - (size_t)r.n_chunks; i += 2) {
+        for (size_t i = first_pair_event; i + 1 < after_pairs - (size_t)n_chunks; i += 2) {
             float k = 0.0f;
             PTMI_HIP(hipEventElapsedTime(&k, g.event_pool[i], g.event_pool[i + 1]));
             kms += k;
@@ -1122,7 +1182,7 @@ void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
         stats->bounce_kernel_ms = kms;
         stats->bounce_launches = launches;
         stats->path_visits = visits;
-        stats->samples = (uint64_t)n_local * (uint64_t)g.config.spp * (uint64_t)n_frames;
+        stats->samples = (uint64_t)(pass ? chunks[0].n : n_local) * (uint64_t)g.config.spp * (uint64_t)n_frames;
         if (want_stats) {
             StatCounters c;
             PTMI_HIP(hipMemcpy(&c, r.d_stats, sizeof c, hipMemcpyDeviceToHost));
@@ -1130,6 +1190,71 @@ void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
             stats->top_node_visits = c.top_node_visits; stats->cert_chain = c.cert_chain; stats->cert_fallback = c.cert_fallback;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// progressive / adaptive accumulation (include/ptmi.h: ptmi_accum_pass)
+// ------------------------------------------------------------------------------------------------
+void accumReset(ApplicationState& g) {
+    g.render.accum.pass = 0;
+    g.render.accum.n_active = 0;
+}
+
+void accumPass(ApplicationState& g, const AdaptiveParams* params, PassStats* stats) {
+    RenderState& r = g.render;
+    RenderState::Accum& a = r.accum;
+    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError("accumPass: the Radiosity integrator has no accumulation passes");
+    if (!g.scene.d_nodes) throw ArgError("accumPass: no scene loaded");
+    if (!r.d_state.A) throw ArgError("accumPass: buffers not allocated (call updateResolution first)");
+    if (g.config.spp < 1 || g.config.spp >= (1 << 24)) throw ArgError("spp must be in [1, 2^24)");
+    if (params) {
+        const AdaptiveParams& p = *params;
+        if (p.min_passes < 2) throw ArgError("accumPass: min_passes must be >= 2");
+        if (p.max_passes < p.min_passes || p.max_passes > 65536) throw ArgError("accumPass: max_passes must be in [min_passes, 65536]");
+        if ((long long)p.max_passes * g.config.spp >= (1ll << 24)) throw ArgError("accumPass: max_passes * spp must stay below 2^24");
+        if (!(p.threshold >= 0.0f) || !std::isfinite(p.threshold)) throw ArgError("accumPass: threshold must be finite and >= 0");
+        if (!(p.floor > 0.0f) || !std::isfinite(p.floor)) throw ArgError("accumPass: floor must be finite and > 0");
+        if (a.pass >= p.max_passes) throw ArgError("accumPass: the accumulation has reached max_passes (ptmi_accum_reset starts another)");
+    }
+    if (a.pass > 0 && a.n_active == 0) throw ArgError("accumPass: the accumulation is finished (ptmi_accum_reset starts another)");
+    if ((long long)(a.pass + 1) * g.config.spp >= (1ll << 24)) throw ArgError("accumPass: a pixel's sample count must stay below 2^24");
+    PTMI_HIP(hipSetDevice(g.device_id));
+    const bool first = a.pass == 0;
+    if (first) {
+        if (!a.allocated()) r.allocateAccum();
+        a.n_active = (int)r.n_local;
+        a.cur = 0;
+    }
+    PassRun run;
+    run.rule.first = first ? 1 : 0;
+    run.rule.stopping = params ? 1 : 0;
+    run.rule.min_passes = params ? params->min_passes : 0;
+    run.rule.max_passes = params ? params->max_passes : 0;
+    run.rule.threshold = params ? params->threshold : 0.0f;
+    run.rule.floor_ = params ? params->floor : 0.0f;
+    run.rule.inv_spp = rcp_rn((float)g.config.spp);
+    a.chunk.d_queue_init = first ? nullptr : a.d_active[a.cur];       // pass 1: every local pixel (identity queue)
+    a.chunk.n = a.n_active;
+    const int before = a.n_active, k = a.pass + 1;
+    FrameStats fs;
+    a.pass = 0;                                        // until this pass is through: a pass that throws leaves no accumulation
+    renderRun(g, 1, &fs, &run);
+    a.pass = k;
+    a.cur ^= 1;
+    a.n_active = run.active_after;
+    if (stats) {
+        stats->pass = k;
+        stats->active_before = (uint64_t)before; stats->active_after = (uint64_t)run.active_after;
+        stats->frame = fs;
+    }
+}
+
+void readSampleCounts(const ApplicationState& g, uint32_t* counts) {
+    const RenderState& r = g.render;
+    if (!r.d_state.A) throw ArgError("readSampleCounts: buffers not allocated");
+    if (r.accum.pass == 0 || !r.accum.allocated()) { std::memset(counts, 0, r.n_local * sizeof(uint32_t)); return; }
+    PTMI_HIP(hipSetDevice(g.device_id));
+    PTMI_HIP(hipMemcpy(counts, r.accum.d_counts, r.n_local * sizeof(uint32_t), hipMemcpyDeviceToHost));
 }
 
 }  // namespace ptmi

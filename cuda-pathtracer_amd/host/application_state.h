@@ -198,12 +198,28 @@ struct RenderState {
     hipStream_t stream = nullptr;
     size_t n_local = 0;
     bool allow_tile8 = false;                        // scheduling knob (test/benchmark override)
+    // Progressive / adaptive accumulation (accumPass): the colour sums of D go on from pass to pass; per pixel the state of the
+    // stopping test, the queue of the pixels the next pass renders and the bounce queues of a pass (one chunk of n_local entries,
+    // driven through chunk[0]'s stream).  Allocated by the first pass, freed with the other buffers.
+    struct Accum {
+        int pass = 0;                                // passes of the current accumulation (0: none; the next pass is pass 1)
+        int n_active = 0;                            // pixels the next pass renders (the last stopping test's count)
+        int cur = 0;                                 // d_active[cur]: the next pass's queue
+        int* d_active[2] = {nullptr, nullptr};
+        AccumBuffers ab;
+        unsigned int* d_counts = nullptr;            // samples per pixel, local row-major (ptmi_read_sample_counts)
+        int* d_out_count = nullptr;                  // the stopping test's output count
+        Chunk chunk;                                 // d_queue_init is not owned: it points at the pass's queue (nullptr at pass 1)
+        bool allocated() const { return d_counts != nullptr; }
+    } accum;
 
-    void allocateBuffers();                          // application_state.h:91-123 (+ render_init)
+    void allocateBuffers();                         // application_state.h:91-123 (+ render_init)
     void updateResolution(int w, int h, const TileMap* tiling);   // application_state.h:125-129
     void freeBuffers();
     void setupChunks(int n);                         // deals the local pixels to n queues (allocateBuffers; renderFrames when the walk's launch rule wants another count)
     void freeChunks();
+    void allocateAccum();
+    void freeAccum();
     ~RenderState() { freeBuffers(); }
 };
 
@@ -270,6 +286,18 @@ void renderFrame(ApplicationState& g_state, FrameStats* stats);
 // buffers hold the LAST frame and selectFrame(j) resolves any frame of the batch into them.
 void renderFrames(ApplicationState& g_state, int n_frames, FrameStats* stats);
 void selectFrame(ApplicationState& g_state, int frame);
+
+// Progressive / adaptive accumulation (include/ptmi.h: ptmi_accum_pass): one pass adds config.spp samples to every pixel still
+// active, applies the stopping test (rule == nullptr: none) and resolves every pixel by its own sample count.
+struct AdaptiveParams { int min_passes = 4, max_passes = 64; float threshold = 0.02f, floor = 0.01f; };
+struct PassStats {
+    int pass = 0;
+    uint64_t active_before = 0, active_after = 0;
+    FrameStats frame;                                // seconds: the whole pass, stopping test and resolve included
+};
+void accumReset(ApplicationState& g_state);
+void accumPass(ApplicationState& g_state, const AdaptiveParams* params, PassStats* stats);
+void readSampleCounts(const ApplicationState& g_state, uint32_t* counts);
 
 bool packBvhNodes(const std::vector<BVHNode>& bvh_nodes, int top_records, std::vector<float4>& g, int& n_pos, int& n_top, int& top_depth);
 

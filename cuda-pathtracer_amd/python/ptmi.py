@@ -30,6 +30,7 @@ EXPORTS = [
     "ptmi_read_frame", "ptmi_dist_barrier", "ptmi_dist_allreduce_max", "ptmi_debug_place_tiles", "ptmi_debug_set_packed_min_nodes", "ptmi_debug_set_packed_top", "ptmi_render_frames", "ptmi_select_frame",
     "ptmi_debug_set_fast_tree", "ptmi_debug_intersect_fast", "ptmi_dist_comm_count", "ptmi_host_fast_tree_build", "ptmi_host_fast_tree_intersect", "ptmi_host_fast_tree_stats",
     "ptmi_debug_set_solver_walk", "ptmi_debug_get_traversal",
+    "ptmi_default_adaptive_params", "ptmi_accum_reset", "ptmi_accum_pass", "ptmi_read_sample_counts",
 ]
 
 
@@ -64,6 +65,17 @@ class Stats(C.Structure):
                 ("samples", C.c_uint64), ("rays", C.c_uint64), ("node_visits", C.c_uint64),
                 ("prim_tests", C.c_uint64), ("hits", C.c_uint64), ("top_node_visits", C.c_uint64),
                 ("cert_chain", C.c_uint64), ("cert_fallback", C.c_uint64)]
+
+
+class AdaptiveParams(C.Structure):
+    _fields_ = [("min_passes", C.c_int), ("max_passes", C.c_int), ("threshold", C.c_float), ("floor", C.c_float)]
+
+
+class PassStats(C.Structure):
+    _fields_ = [("pass_", C.c_int), ("active_before", C.c_uint64), ("active_after", C.c_uint64), ("samples", C.c_uint64),
+                ("seconds", C.c_double), ("bounce_kernel_ms", C.c_double), ("bounce_launches", C.c_uint64), ("path_visits", C.c_uint64),
+                ("rays", C.c_uint64), ("node_visits", C.c_uint64), ("prim_tests", C.c_uint64), ("hits", C.c_uint64),
+                ("top_node_visits", C.c_uint64), ("cert_chain", C.c_uint64), ("cert_fallback", C.c_uint64)]
 
 
 class PtmiError(RuntimeError):
@@ -153,6 +165,10 @@ def lib():
         L.ptmi_host_fast_tree_build.argtypes = [vp, C.c_int, C.c_float, C.c_float, ip, ip, C.POINTER(C.c_double)]
         L.ptmi_host_fast_tree_stats.argtypes = [vp, vp]
         L.ptmi_host_fast_tree_intersect.argtypes = [vp, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp, vp]
+        L.ptmi_default_adaptive_params.argtypes = [C.POINTER(AdaptiveParams)]; L.ptmi_default_adaptive_params.restype = None
+        L.ptmi_accum_reset.argtypes = [vp]
+        L.ptmi_accum_pass.argtypes = [vp, C.POINTER(AdaptiveParams), C.POINTER(PassStats)]
+        L.ptmi_read_sample_counts.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -259,6 +275,16 @@ def default_camera():
 
 def default_config():
     c = Config(); lib().ptmi_default_config(C.byref(c)); return c
+
+
+def default_adaptive_params(**params):
+    """ptmi_default_adaptive_params, with any field overridden by keyword (min_passes, max_passes, threshold, floor)."""
+    p = AdaptiveParams(); lib().ptmi_default_adaptive_params(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(AdaptiveParams._fields_):
+            raise TypeError(f"unknown adaptive parameter {k}")
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
 
 
 class Renderer:
@@ -423,6 +449,41 @@ class Renderer:
 
     def select_frame(self, frame):
         self._ck(self.L.ptmi_select_frame(self.h, int(frame)))
+
+    # --- progressive / adaptive accumulation (include/ptmi.h: ptmi_accum_pass) ---
+    def accum_reset(self):
+        self._ck(self.L.ptmi_accum_reset(self.h))
+
+    def accum_pass(self, params=None):
+        """One pass: config.spp more samples for every pixel still active, the stopping test (params: an AdaptiveParams or a
+        dict of its fields; None = plain progressive, nothing stops) and the resolve by each pixel's own count.  Returns
+        PassStats (the pass number is its `pass_` field)."""
+        if isinstance(params, dict):
+            params = default_adaptive_params(**params)
+        st = PassStats()
+        self._ck(self.L.ptmi_accum_pass(self.h, C.byref(params) if params is not None else None, C.byref(st)))
+        return st
+
+    def render_adaptive(self, **params):
+        """A fresh accumulation run to its end: with keyword parameters (fields of AdaptiveParams over the defaults) passes
+        until no pixel is active; without, max_passes plain progressive passes.  Returns the list of PassStats."""
+        self.accum_reset()
+        prm = default_adaptive_params(**params)
+        out = []
+        if not params:
+            for _ in range(prm.max_passes):
+                out.append(self.accum_pass(None))
+            return out
+        while True:
+            out.append(self.accum_pass(prm))
+            if out[-1].active_after == 0:
+                return out
+
+    def sample_counts(self):
+        """Samples per local pixel of the current accumulation, (local rows, width) uint32, rows as read_image returns them."""
+        counts = np.zeros((len(self.local_rows()), self.width), np.uint32)
+        self._ck(self.L.ptmi_read_sample_counts(self.h, counts.ctypes.data))
+        return counts
 
     def device_image(self):
         a = C.c_void_p(); b = C.c_void_p()

@@ -371,6 +371,62 @@ int ptmi_debug_rcp_check(ptmi_ctx*, uint32_t first_bits, uint64_t count, uint64_
 /* sampleCosineHemisphere (integrator.h:62-85) with explicit (u, v). */
 int ptmi_debug_cosine_sample(ptmi_ctx*, int n, const float* normals, const float* u, const float* v, float* out_dirs);
 
+/* ---- progressive and adaptive accumulation (new in this implementation) -------------------------------------------------
+ * A frame is an independent estimate of config.spp samples per pixel.  An ACCUMULATION instead goes on from pass to pass:
+ * ptmi_accum_pass adds config.spp samples to every local pixel that is still active, applies the stopping test below and
+ * resolves the image buffers that ptmi_read_image / ptmi_copy_image_device / ptmi_gather_frame / ptmi_host_image (with
+ * download_image) read: every pixel as mean -> Reinhard -> gamma -> 8 bit of ITS OWN sample count n, with the arithmetic of a
+ * frame's resolve and rcp_rn((float)n) as the factor.  A pixel's colour sum after k passes of spp samples is the float a single
+ * frame of k * spp samples from the same stream position sums, bit for bit, so every pixel equals the frame at its own count.
+ *
+ * Streams are not re-seeded: an accumulation starts wherever the streams stand, as a frame does (after
+ * ptmi_update_resolution: freshly seeded).  The accumulation is RESET - the next pass is pass 1 and starts from zero sums - by
+ * ptmi_accum_reset and by every call that changes what a frame would show: ptmi_set_camera, a successful ptmi_set_config,
+ * ptmi_update_resolution, the scene loads, ptmi_set_radiosity_grids, ptmi_set_radiosity, ptmi_apply_grid_filter,
+ * ptmi_use_raw_cdfs, ptmi_run_radiosity_solver, and ptmi_render_frame / ptmi_render_frames (which behave exactly as before).
+ * PTMI_E_INVALID: the Radiosity integrator (config.integrator = 1), ptmi_select_frame after a pass, parameters out of range
+ * or NaN, a pass after the accumulation has finished (no pixel active) or reached params->max_passes, and a pass that would
+ * take a pixel to 2^24 samples.
+ *
+ * THE STOPPING RULE, per pixel after its pass k, in float32 in the order written (the library is built with
+ * -ffp-contract=off; S = the pixel's colour sum after the pass, S_0 = 0, mean_0 = M2_0 = 0):
+ *     d     = S_k - S_{k-1}                                         (per channel)
+ *     y     = (0.2126f * d.x + 0.7152f * d.y + 0.0722f * d.z) * inv_spp        inv_spp = rcp_rn((float)spp)
+ *     delta = y - mean;  mean = mean + delta / (float)k;  M2 = M2 + delta * (y - mean)
+ *     a     = threshold * (mean + floor)
+ *     stop  <=>  k == max_passes  or  (k >= min_passes  and  M2 <= a * a * (float)(k * (k - 1)))   (k * (k - 1): uint32)
+ * i.e. the standard error of the mean of the pass means, sqrt(M2 / (k (k - 1))), is at most threshold x (mean + floor).  It
+ * reads nothing but the pixel's own sums: neighbours, launch order, tiling and the walk never change a decision.
+ * params == NULL: a plain progressive pass - every pixel renders, none stops.
+ *
+ * Multi-GPU: every rank adapts its own rows.  The distributed loop, per pass on every rank:
+ *     ptmi_accum_pass(ctx, &params, &st); double a = (double)st.active_after; ptmi_dist_allreduce_max(ctx, &a);
+ *     if (a == 0) break;   (then ptmi_gather_frame as after a frame; a rank that has finished skips its further passes)
+ * The gather is unchanged. */
+typedef struct {
+    int   min_passes;   /* passes every pixel takes before it may stop; >= 2 (a spread needs two pass means) */
+    int   max_passes;   /* >= min_passes, <= 65536; max_passes * config.spp < 2^24 */
+    float threshold;    /* relative standard error at which a pixel stops, >= 0 */
+    float floor;        /* added to the mean in the test, > 0: keeps dark pixels from running to max_passes on noise alone */
+} ptmi_adaptive_params;
+typedef struct {
+    int      pass;            /* passes of this accumulation so far */
+    uint64_t active_before;   /* local pixels this pass rendered */
+    uint64_t active_after;    /* still active after its stopping test (0: the accumulation is finished) */
+    uint64_t samples;         /* samples this pass added (active_before * spp) */
+    double   seconds;         /* device time of the pass, stopping test and resolve included */
+    /* the ptmi_stats fields of the pass (rays .. cert_fallback only with config.collect_stats) */
+    double   bounce_kernel_ms;
+    uint64_t bounce_launches, path_visits;
+    uint64_t rays, node_visits, prim_tests, hits, top_node_visits, cert_chain, cert_fallback;
+} ptmi_pass_stats;
+void ptmi_default_adaptive_params(ptmi_adaptive_params*);   /* min_passes 4, max_passes 64, threshold 0.02, floor 0.01 */
+int  ptmi_accum_reset(ptmi_ctx*);
+int  ptmi_accum_pass(ptmi_ctx*, const ptmi_adaptive_params* /* NULL: plain progressive */, ptmi_pass_stats* /* may be NULL */);
+/* samples per local pixel of the current accumulation (0 everywhere before its first pass), local rows x width, local
+ * row-major like ptmi_read_image */
+int  ptmi_read_sample_counts(const ptmi_ctx*, uint32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,8 @@
   python tools/ptmi_render.py --scene tests/golden/scenes/cbox.obj --width 512 --height 512 --spp 64 --out cbox.png
   python tools/ptmi_render.py --scene ... --subdivision 2 --radiosity --sampling-mode 3 --out guided.png
   python tools/ptmi_render.py --scene ... --radiosity --integrator radiosity --out radiosity_view.png
+  python tools/ptmi_render.py --scene ... --spp 8 --passes 16 --out progressive.png          (16 passes of 8 samples)
+  python tools/ptmi_render.py --scene ... --spp 8 --adaptive 0.02 --counts-png counts.png   (passes until every pixel stops)
 """
 import argparse
 import os
@@ -30,6 +32,11 @@ def main():
     ap.add_argument("--point-to-point", action="store_true")
     ap.add_argument("--filter", choices=["none", "bilateral", "gaussian"], default="none", help="Apply Filter & Rebuild CDFs")
     ap.add_argument("--yaw", type=float, default=None); ap.add_argument("--pitch", type=float, default=None); ap.add_argument("--fov", type=float, default=None)
+    ap.add_argument("--passes", type=int, default=0, help="progressive: this many accumulation passes of --spp samples instead of one frame")
+    ap.add_argument("--adaptive", type=float, nargs="?", const=-1.0, default=None, metavar="THRESHOLD",
+                    help="adaptive: passes of --spp samples until every pixel has stopped (relative standard error THRESHOLD; "
+                         "default: the library's); --passes then sets max_passes")
+    ap.add_argument("--counts-png", default=None, help="with --passes / --adaptive: grey map of the samples per pixel (white = most)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -54,8 +61,27 @@ def main():
     r.update_resolution(a.width, a.height)
     r.set_config(spp=a.spp, max_depth=a.max_depth, seed_base=a.seed_base, sampling_mode=a.sampling_mode,
                  mis_bsdf_fraction=a.mis_bsdf_fraction, integrator=1 if a.integrator == "radiosity" else 0)
-    st = r.render_frame()
-    print(f"frame: {a.width}x{a.height} x {a.spp} spp in {st.seconds * 1e3:.2f} ms = {st.samples / st.seconds / 1e6:.1f} Msamples/s")
+    if a.adaptive is not None or a.passes > 0:
+        prm = {}
+        if a.adaptive is not None:
+            if a.adaptive >= 0: prm["threshold"] = a.adaptive
+            if a.passes > 0: prm["max_passes"] = a.passes
+            prm.setdefault("threshold", ptmi.default_adaptive_params().threshold)      # (no keywords would mean plain progressive)
+            passes = r.render_adaptive(**prm)
+        else:
+            r.accum_reset()
+            passes = [r.accum_pass(None) for _ in range(a.passes)]
+        secs = sum(p.seconds for p in passes); samples = sum(p.samples for p in passes)
+        print(f"{len(passes)} passes: {a.width}x{a.height}, {samples / (a.width * a.height):.2f} samples per pixel on average, "
+              f"{secs * 1e3:.2f} ms = {samples / secs / 1e6:.1f} Msamples/s")
+        if a.counts_png:
+            counts = r.sample_counts().astype("float64")
+            grey = (255.0 * counts / max(counts.max(), 1.0)).astype("uint8")
+            ptmi.write_png(a.counts_png, grey[:, :, None].repeat(3, axis=2))
+            print(f"wrote {a.counts_png}")
+    else:
+        st = r.render_frame()
+        print(f"frame: {a.width}x{a.height} x {a.spp} spp in {st.seconds * 1e3:.2f} ms = {st.samples / st.seconds / 1e6:.1f} Msamples/s")
     if a.out:
         rgb, _ = r.read_image()
         ptmi.write_png(a.out, rgb)
