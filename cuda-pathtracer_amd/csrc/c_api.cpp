@@ -34,6 +34,9 @@ int guarded(Fn&& fn) {
     catch (...) { g_last_error = "unknown error"; return PTMI_E_INVALID; }
 }
 void need(bool ok, const char* what) { if (!ok) throw ArgError(what); }
+
+// a call that changes what a frame would show: the accumulation restarts and the feature buffers go stale
+void viewChanged(ApplicationState& app) { accumReset(app); featuresStale(app); }
 f3 v3(const float* p) { return mk3(p[0], p[1], p[2]); }
 
 #define PTMI_HIP(call)                                                                                   \
@@ -89,7 +92,7 @@ int ptmi_load_scene(ptmi_ctx* c, const char* filename, int subdivision_count, in
         PTMI_HIP(hipSetDevice(c->app.device_id));
         c->app.config.convert_quads_to_triangles = convert_quads != 0;
         c->app.radiosity.cleanup();                       // a solution belongs to the scene it was computed for
-        accumReset(c->app);
+        viewChanged(c->app);
         c->app.scene.loadScene(filename, subdivision_count, convert_quads != 0);
     });
 }
@@ -100,7 +103,7 @@ int ptmi_load_scene_arrays(ptmi_ctx* c, int n, const int* type, const float* ver
         need(c != nullptr, "ctx is NULL");
         PTMI_HIP(hipSetDevice(c->app.device_id));
         c->app.radiosity.cleanup();
-        accumReset(c->app);
+        viewChanged(c->app);
         c->app.scene.loadSceneArrays(prims_from_arrays(n, type, verts, normal, bsdf, Le));
     });
 }
@@ -242,7 +245,7 @@ int ptmi_set_radiosity_grids(ptmi_ctx* c, int n_prims, const float* rgb) {
         need(rgb == nullptr || n_prims == (int)c->app.scene.h_primitives.size(), "n_prims does not match the loaded scene");
         PTMI_HIP(hipSetDevice(c->app.device_id));
         c->app.radiosity.grids_are_scene_grids = false;               // the caller's grids replace the solver's
-        accumReset(c->app);
+        viewChanged(c->app);
         c->app.scene.precomputeCDFs(rgb);
     });
 }
@@ -252,7 +255,7 @@ int ptmi_set_radiosity(ptmi_ctx* c, int n_prims, const float* rgb) {
         need(c->app.scene.d_nodes != nullptr, "no scene loaded");
         need(rgb == nullptr || n_prims == (int)c->app.scene.h_primitives.size(), "n_prims does not match the loaded scene");
         PTMI_HIP(hipSetDevice(c->app.device_id));
-        accumReset(c->app);
+        viewChanged(c->app);
         c->app.scene.setRadiosity(rgb);
     });
 }
@@ -272,7 +275,7 @@ int ptmi_run_radiosity_solver(ptmi_ctx* c, const ptmi_radiosity_params* p, ptmi_
         need(prm.filter_sigma_spatial > 0.0f && prm.filter_sigma_range > 0.0f, "filter sigmas must be positive");
         PTMI_HIP(hipSetDevice(c->app.device_id));
         RadiosityState& r = c->app.radiosity;
-        accumReset(c->app);
+        viewChanged(c->app);
         r.num_iterations = prm.num_iterations; r.mc_samples = prm.mc_samples; r.use_monte_carlo = prm.use_monte_carlo != 0;
         RadiosityStats st;
         r.runSolver(c->app.scene, c->app.render.d_jump, prm.enable_filtering != 0, prm.use_bilateral != 0,
@@ -319,7 +322,7 @@ int ptmi_apply_grid_filter(ptmi_ctx* c, int use_bilateral, float sigma_spatial, 
         need(sigma_spatial > 0.0f && sigma_range > 0.0f, "filter sigmas must be positive");
         PTMI_HIP(hipSetDevice(c->app.device_id));
         sync_solver_grids(c);
-        accumReset(c->app);
+        viewChanged(c->app);
         c->app.scene.precomputeCDFsFromFiltered(use_bilateral != 0, sigma_spatial, sigma_range, c->app.render.stream);
     });
 }
@@ -329,7 +332,7 @@ int ptmi_use_raw_cdfs(ptmi_ctx* c) {
         PTMI_HIP(hipSetDevice(c->app.device_id));
         sync_solver_grids(c);
         need(!c->app.scene.h_radiosity_grids.empty(), "the scene has no radiosity grids");
-        accumReset(c->app);
+        viewChanged(c->app);
         c->app.scene.precomputeCDFs(c->app.scene.h_radiosity_grids.data());
     });
 }
@@ -358,7 +361,7 @@ int ptmi_update_resolution(ptmi_ctx* c, int width, int height, const ptmi_tiling
         TileMap tm;
         if (tiling) { tm.n_ranks = tiling->n_ranks; tm.rank = tiling->rank; tm.row_block = tiling->row_block; }
         c->app.render.seed_base = c->app.config.seed_base;
-        accumReset(c->app);
+        viewChanged(c->app);
         c->app.render.updateResolution(width, height, tiling ? &tm : nullptr);
     });
 }
@@ -369,7 +372,7 @@ int ptmi_set_camera(ptmi_ctx* c, const ptmi_camera* cam) {
         AppConfig& cfg = c->app.config;
         cfg.camera_origin = v3(cam->origin); cfg.look_at = v3(cam->lookat); cfg.up = v3(cam->vup);
         cfg.fov = cam->vfov_deg; cfg.orbit = cam->orbit != 0;
-        accumReset(c->app);
+        viewChanged(c->app);
         Sensor& s = c->app.render.h_camera;
         const int w = s.image_width, h = s.image_height; const float aspect = s.aspect;
         s = Sensor(cfg.camera_origin, cfg.look_at, cfg.up, cfg.fov, 1.0f);    // application.h:107-113
@@ -398,7 +401,7 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
         c->app.render.want_chunks = cfg->streams;
         c->app.render.download_image = cfg->download_image != 0;
         a.fast_tree = cfg->fast_tree != 0;
-        accumReset(c->app);
+        viewChanged(c->app);
     });
 }
 
@@ -795,6 +798,47 @@ int ptmi_accum_pass(ptmi_ctx* c, const ptmi_adaptive_params* params, ptmi_pass_s
 }
 int ptmi_read_sample_counts(const ptmi_ctx* c, uint32_t* counts) {
     return guarded([&] { need(c && counts, "NULL argument"); readSampleCounts(c->app, counts); });
+}
+
+// ---- feature buffers and the denoiser ----
+static DenoiseParams denoise_params_from(const ptmi_denoise_params& p) {
+    DenoiseParams d;
+    d.iterations = p.iterations; d.sigma_color = p.sigma_color; d.color_floor = p.color_floor; d.sigma_position = p.sigma_position;
+    d.normal_squarings = p.normal_squarings; d.feature_grid = p.feature_grid; d.demodulate = p.demodulate;
+    return d;
+}
+void ptmi_default_denoise_params(ptmi_denoise_params* p) {
+    if (!p) return;
+    const DenoiseParams d;
+    p->iterations = d.iterations; p->sigma_color = d.sigma_color; p->color_floor = d.color_floor; p->sigma_position = d.sigma_position;
+    p->normal_squarings = d.normal_squarings; p->feature_grid = d.feature_grid; p->demodulate = d.demodulate;
+}
+int ptmi_check_denoise_params(const ptmi_denoise_params* p) {
+    return guarded([&] { need(p != nullptr, "params is NULL"); checkDenoiseParams(denoise_params_from(*p)); });
+}
+int ptmi_render_features(ptmi_ctx* c, int grid) {
+    return guarded([&] { need(c != nullptr, "ctx is NULL"); renderFeatures(c->app, grid); });
+}
+int ptmi_read_features(const ptmi_ctx* c, float* albedo, float* normal, float* position, float* hit_fraction) {
+    return guarded([&] { need(c != nullptr, "ctx is NULL"); readFeatures(c->app, albedo, normal, position, hit_fraction); });
+}
+int ptmi_denoise(ptmi_ctx* c, const ptmi_denoise_params* params) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        ptmi_denoise_params p;
+        ptmi_default_denoise_params(&p);
+        denoise(c->app, denoise_params_from(params ? *params : p));
+    });
+}
+int ptmi_read_denoised(const ptmi_ctx* c, unsigned char* rgb8, float* radiance) {
+    return guarded([&] { need(c != nullptr, "ctx is NULL"); readDenoised(c->app, rgb8, radiance); });
+}
+int ptmi_denoise_timing(const ptmi_ctx* c, double* features_ms, double* denoise_ms) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        if (features_ms) *features_ms = c->app.render.dn.features_ms;
+        if (denoise_ms) *denoise_ms = c->app.render.dn.denoise_ms;
+    });
 }
 
 }  // extern "C"

@@ -205,6 +205,28 @@ void launch_adapt(const PathState& st, const AccumBuffers& ab, const AdaptRule& 
 void launch_resolve_counts(const TileMap& tm, const PathState& st, const unsigned int* passes, int spp, unsigned char* rgb8,
                            float* radiance, unsigned int* counts, hipStream_t s);
 
+// ---- feature buffers and the denoiser (include/ptmi.h: ptmi_render_features, ptmi_denoise) ---------------------------------
+// Per local pixel, local row-major (the order of ptmi_read_image), the means over the g x g first hits of the feature pass.
+struct FeatureBuffers {
+    float4* albedo = nullptr;        // (Kd.xyz, hit fraction)
+    float4* normal = nullptr;        // (stored primitive normal.xyz, 0)
+    float4* position = nullptr;      // (hit point o + t d .xyz, 0)
+};
+void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams& fp, int g, const FeatureBuffers& fb, hipStream_t s);
+// The filter's constants for one run (csrc/denoise.hip; the contract is written out in include/ptmi.h)
+struct DenoiseArgs {
+    int width, height;               // the whole frame (a single rank)
+    int demodulate;                  // 1: filter radiance / albedo (per channel, where the albedo is not 0)
+    int normal_squarings;
+    float color_floor;
+    float sigma_x2;                  // sigma_x * sigma_x (> 0)
+};
+// iterations passes of the edge-avoiding a-trous filter over radiance (3 floats per pixel, local row-major) guided by fb; the
+// filtered radiance -> out_radiance (3 floats per pixel) and its tone map -> out_rgb8.  buf: 2 x width x height float4 of scratch.
+// sigma_c[i]: the colour sigma of iteration i.
+void launch_denoise(const DenoiseArgs& a, const FeatureBuffers& fb, const float* radiance, int iterations, const float* sigma_c,
+                    float4* buf, unsigned char* out_rgb8, float* out_radiance, hipStream_t s);
+
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)
 

@@ -87,15 +87,19 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_init(TileMap tm, PathState
 // ---------------------------------------------------------------------------------------------
 // camera (sensor.h:31-33 + ray.h:9-12) and the per-sample jitter (integrator.h:384-385)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void camera_ray(const FrameParams& fp, const TileMap& tm, int x, int y, Rng& rng, f3& o, f3& d) {
-    const float u = ((float)x + rng_uniform(rng)) / (float)tm.width;
-    const float v = ((float)y + rng_uniform(rng)) / (float)tm.height;
+// get_ray(u, v) of the sensor: the ray through (u, v) of the image plane
+__device__ __forceinline__ void camera_ray_uv(const FrameParams& fp, float u, float v, f3& o, f3& d) {
     const f3 org = mk3(fp.cam_origin[0], fp.cam_origin[1], fp.cam_origin[2]);
     const f3 llc = mk3(fp.cam_llc[0], fp.cam_llc[1], fp.cam_llc[2]);
     const f3 hor = mk3(fp.cam_hor[0], fp.cam_hor[1], fp.cam_hor[2]);
     const f3 ver = mk3(fp.cam_ver[0], fp.cam_ver[1], fp.cam_ver[2]);
     o = org;
     d = unit_vector(llc + u * hor + v * ver - org);
+}
+__device__ __forceinline__ void camera_ray(const FrameParams& fp, const TileMap& tm, int x, int y, Rng& rng, f3& o, f3& d) {
+    const float u = ((float)x + rng_uniform(rng)) / (float)tm.width;
+    const float v = ((float)y + rng_uniform(rng)) / (float)tm.height;
+    camera_ray_uv(fp, u, v, o, d);
 }
 
 __global__ __launch_bounds__(kBlock) void ptmi_frame_begin(TileMap tm, PathState st, FrameParams fp) {
@@ -1397,20 +1401,6 @@ void launch_frame_begin(const TileMap& tm, const PathState& st, const FrameParam
 // ---------------------------------------------------------------------------------------------
 // resolve: color /= spp; Reinhard; gamma 1/2.2; 8-bit (integrator.h:393-407)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void resolve_pixel(const float4& D, float k, size_t out, unsigned char* __restrict__ rgb8,
-                                              float* __restrict__ radiance) {
-    const float c[3] = {D.x * k, D.y * k, D.z * k};
-    const float gamma = 1.0f / 2.2f;
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        if (radiance) radiance[out * 3 + ch] = c[ch];
-        if (rgb8) {
-            const float tm_ = c[ch] / (c[ch] + 1.0f);       // color / (color + 1), component-wise true division
-            const float g = ptmi_powf(tm_, gamma);
-            rgb8[out * 3 + ch] = (unsigned char)(255.99f * fminf(g, 1.0f));
-        }
-    }
-}
 __global__ __launch_bounds__(kBlock) void ptmi_resolve(TileMap tm, PathState st, int spp, unsigned char* __restrict__ rgb8,
                                                        float* __restrict__ radiance, const float4* __restrict__ color_src) {
     const int n = tm.local_rows * tm.width;
@@ -1682,6 +1672,64 @@ void launch_render_radiosity(const DeviceScene& sc, const TileMap& tm, const Pat
     else if (deep) { if (sc.has_quads) PTMI_RAD(TRAVERSAL_STACK, true); else PTMI_RAD(TRAVERSAL_STACK, false); }
     else { if (sc.has_quads) PTMI_RAD(TRAVERSAL_LANE, true); else PTMI_RAD(TRAVERSAL_LANE, false); }
 #undef PTMI_RAD
+}
+
+// ---------------------------------------------------------------------------------------------
+// feature pass (include/ptmi.h: ptmi_render_features): g x g camera rays per local pixel through the stratum centres, first
+// hit by the walk of the Radiosity view (the reference's hit for every ray), no RNG.  One thread per local pixel, local
+// row-major; sums in stratum order (row j of the strata outer, column i inner), then x rcp_rn((float)(g * g)).
+// ---------------------------------------------------------------------------------------------
+template <int MODE, bool HAS_QUADS>
+__global__ __launch_bounds__(kBlock) void ptmi_features(DeviceScene sc, TileMap tm, FrameParams fp, int g, FeatureBuffers fb) {
+    extern __shared__ float4 smem[];
+    int* stack = reinterpret_cast<int*>(smem) + threadIdx.x;
+    const int n = tm.local_rows * tm.width;
+    const int idx = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = idx < n;
+    const int lr = live ? idx / tm.width : 0;
+    const int x = live ? idx - lr * tm.width : 0;
+    const int y = ((lr / tm.row_block) * tm.n_ranks + tm.rank) * tm.row_block + (lr % tm.row_block);
+    const float gf = (float)g;
+    f3 alb = mk3(0.0f, 0.0f, 0.0f), nrm = mk3(0.0f, 0.0f, 0.0f), pos = mk3(0.0f, 0.0f, 0.0f);
+    float hits = 0.0f;
+    LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
+    for (int j = 0; j < g; j++) {
+        for (int i = 0; i < g; i++) {
+            const float u = ((float)x + ((float)i + 0.5f) / gf) / (float)tm.width;
+            const float v = ((float)y + ((float)j + 0.5f) / gf) / (float)tm.height;
+            f3 o, d;
+            camera_ray_uv(fp, u, v, o, d);
+            float t = 0.0f; int k = -1;
+            bool hit;
+            if constexpr (MODE == TRAVERSAL_CERTIFIED) hit = live && certified_closest_hit<HAS_QUADS>(sc, reinterpret_cast<uint2*>(smem) + threadIdx.x, o, d, 1e-4f, t, k);
+            else hit = scene_intersect<MODE, HAS_QUADS, false>(sc.nodes, sc.prims, sc.prim_stride, sc.n_nodes, stack, live, o, d, 1e-4f, FLT_MAX, t, k, cn);
+            if (live && hit) {
+                alb = alb + xyz(sc.mats[3 * k + 1]);
+                nrm = nrm + xyz(sc.mats[3 * k]);
+                pos = pos + (o + t * d);
+                hits = hits + 1.0f;
+            }
+        }
+    }
+    if (!live) return;
+    const float kk = rcp_rn((float)(g * g));
+    fb.albedo[idx] = make_float4(alb.x * kk, alb.y * kk, alb.z * kk, hits * kk);
+    fb.normal[idx] = make_float4(nrm.x * kk, nrm.y * kk, nrm.z * kk, 0.0f);
+    fb.position[idx] = make_float4(pos.x * kk, pos.y * kk, pos.z * kk, 0.0f);
+}
+
+void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams& fp, int g, const FeatureBuffers& fb, hipStream_t s) {
+    const int n = tm.local_rows * tm.width;
+    if (n <= 0) return;
+    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+    const bool deep = sc.traversal == TRAVERSAL_STACK;                                // the walk choice of launch_render_radiosity
+    const bool cert = sc.traversal == TRAVERSAL_CERTIFIED && sc.wnodes && sc.wcert && sc.wanc && sc.wref_slot && (!sc.has_quads || sc.wqprims);
+    const size_t lds = cert ? (size_t)sc.w_depth * kBlock * sizeof(uint2) : deep ? (size_t)sc.stack_entries * kBlock * sizeof(int) : 0;
+#define PTMI_FEAT(M_, Q_) hipLaunchKernelGGL((ptmi_features<M_, Q_>), grid, block, lds, s, sc, tm, fp, g, fb)
+    if (cert) { if (sc.has_quads) PTMI_FEAT(TRAVERSAL_CERTIFIED, true); else PTMI_FEAT(TRAVERSAL_CERTIFIED, false); }
+    else if (deep) { if (sc.has_quads) PTMI_FEAT(TRAVERSAL_STACK, true); else PTMI_FEAT(TRAVERSAL_STACK, false); }
+    else { if (sc.has_quads) PTMI_FEAT(TRAVERSAL_LANE, true); else PTMI_FEAT(TRAVERSAL_LANE, false); }
+#undef PTMI_FEAT
 }
 
 // ---------------------------------------------------------------------------------------------

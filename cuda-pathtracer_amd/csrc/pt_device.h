@@ -119,4 +119,21 @@ __device__ __forceinline__ void build_frame(f3 n, f3& t, f3& b) {               
     b = mk3(c, 1.0f - n.y * n.y * a, -n.y);
 }
 
+// resolve of one pixel (integrator.h:393-407): colour sum x k -> float radiance; Reinhard, gamma 1/2.2, 8 bit -> rgb8 (either
+// output may be nullptr).  The frame and pass resolves (kernels.hip) and the denoiser's tone map (denoise.hip, k = 1) share it.
+__device__ __forceinline__ void resolve_pixel(const float4& D, float k, size_t out, unsigned char* __restrict__ rgb8,
+                                              float* __restrict__ radiance) {
+    const float c[3] = {D.x * k, D.y * k, D.z * k};
+    const float gamma = 1.0f / 2.2f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        if (radiance) radiance[out * 3 + ch] = c[ch];
+        if (rgb8) {
+            const float tm_ = c[ch] / (c[ch] + 1.0f);       // color / (color + 1), component-wise true division
+            const float g = ptmi_powf(tm_, gamma);
+            rgb8[out * 3 + ch] = (unsigned char)(255.99f * fminf(g, 1.0f));
+        }
+    }
+}
+
 }  // namespace ptmi

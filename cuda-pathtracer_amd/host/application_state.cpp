@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <array>
 #include <chrono>
+#include <cmath>
 #include <limits>
 #include <cctype>
 #include <cstring>
@@ -707,6 +708,7 @@ void RenderState::freeBuffers() {
     if (h_image) { (void)hipHostFree(h_image); h_image = nullptr; }
     freeChunks();
     freeAccum();
+    freeDenoise();
     d_state = PathState();
     d_image = nullptr; d_radiance = nullptr; d_stats = nullptr;
     n_local = 0;
@@ -755,6 +757,12 @@ void RenderState::freeAccum() {
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (a.chunk.h_count) (void)hipHostFree(a.chunk.h_count);
     a = Accum();
+}
+
+void RenderState::freeDenoise() {
+    void* ptrs[] = {dn.fb.albedo, dn.fb.normal, dn.fb.position, dn.d_rgb8, dn.d_radiance, dn.d_buf};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    dn = Denoise();
 }
 
 void RenderState::allocateAccum() {
@@ -881,6 +889,16 @@ struct PassRun { AdaptRule rule; int active_after = 0; };
 
 static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pass);
 
+// camera update (application.h:161-163) and the camera fields of the frame's parameters
+static void cameraFrameParams(ApplicationState& g, FrameParams& fp) {
+    RenderState& r = g.render;
+    if (g.config.orbit) r.h_camera.updateCameraOrbit(); else r.h_camera.updateCamera();
+    const CameraFrame cf = r.h_camera.frame();
+    const f3* src[4] = {&cf.origin, &cf.lower_left_corner, &cf.horizontal, &cf.vertical};
+    float* dst[4] = {fp.cam_origin, fp.cam_llc, fp.cam_hor, fp.cam_ver};
+    for (int i = 0; i < 4; i++) { dst[i][0] = src[i]->x; dst[i][1] = src[i]->y; dst[i][2] = src[i]->z; }
+}
+
 void renderFrames(ApplicationState& g, int n_frames, FrameStats* stats) {
     accumReset(g);                                     // a frame starts its sums from zero (ptmi_frame_begin)
     renderRun(g, n_frames, stats, nullptr);
@@ -901,13 +919,8 @@ static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, Pass
     if (g.config.max_depth < 1 || g.config.max_depth > 255) throw ArgError("max_depth must be in [1, 255]");
     PTMI_HIP(hipSetDevice(g.device_id));
 
-    // camera update (application.h:161-163)
-    if (g.config.orbit) r.h_camera.updateCameraOrbit(); else r.h_camera.updateCamera();
-    const CameraFrame cf = r.h_camera.frame();
     FrameParams fp;
-    const f3* src[4] = {&cf.origin, &cf.lower_left_corner, &cf.horizontal, &cf.vertical};
-    float* dst[4] = {fp.cam_origin, fp.cam_llc, fp.cam_hor, fp.cam_ver};
-    for (int i = 0; i < 4; i++) { dst[i][0] = src[i]->x; dst[i][1] = src[i]->y; dst[i][2] = src[i]->z; }
+    cameraFrameParams(g, fp);
     fp.spp = g.config.spp; fp.max_depth = g.config.max_depth;
     fp.sampling_mode = (int)g.config.sampling_mode; fp.mis_bsdf_fraction = g.config.mis_bsdf_fraction;
     PTMI_HIP(hipSetDevice(g.device_id));
@@ -922,6 +935,7 @@ static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, Pass
     // what ptmi_select_frame may resolve: nothing until THIS path-tracing run has completed (a Radiosity frame or a run that
     // threw leaves the colour sums of some earlier run behind, and resolving those would overwrite a valid image)
     r.batch_frames = 1; r.batch_spp = 0;
+    r.dn.image_current = false;                        // what ptmi_denoise may filter: likewise, only a completed path-tracing run
 
     const int n_local = (int)r.n_local;
     // segments per launch: 32 while the device has more waves to run than it holds at once; once the pixels still active fit
@@ -1167,6 +1181,7 @@ static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, Pass
     drain.armed = false;
     if (pass) pass->active_after = active_after;       // (select_frame has nothing to resolve after a pass: batch_spp stays 0)
     else { r.batch_frames = n_frames; r.batch_spp = g.config.spp; }
+    r.dn.image_current = true;
     if (cost_now) { r.cost_valid = true; r.cost_frame++; }
 
     if (stats) {
@@ -1255,6 +1270,131 @@ void readSampleCounts(const ApplicationState& g, uint32_t* counts) {
     if (r.accum.pass == 0 || !r.accum.allocated()) { std::memset(counts, 0, r.n_local * sizeof(uint32_t)); return; }
     PTMI_HIP(hipSetDevice(g.device_id));
     PTMI_HIP(hipMemcpy(counts, r.accum.d_counts, r.n_local * sizeof(uint32_t), hipMemcpyDeviceToHost));
+}
+
+// ------------------------------------------------------------------------------------------------
+// feature buffers and the denoiser (include/ptmi.h: ptmi_render_features, ptmi_denoise)
+// ------------------------------------------------------------------------------------------------
+void featuresStale(ApplicationState& g) {
+    g.render.dn.features_valid = false;
+    g.render.dn.image_current = false;                 // the image shows the scene / view / config as it was before the change
+}
+
+static float elapsedMs(hipEvent_t a, hipEvent_t b) {
+    float ms = 0.0f;
+    PTMI_HIP(hipEventElapsedTime(&ms, a, b));
+    return ms;
+}
+
+void renderFeatures(ApplicationState& g, int grid) {
+    RenderState& r = g.render;
+    RenderState::Denoise& d = r.dn;
+    if (grid < 1 || grid > 4) throw ArgError("renderFeatures: grid must be in [1, 4]");
+    if (!g.scene.d_nodes) throw ArgError("renderFeatures: no scene loaded");
+    if (!r.d_state.A) throw ArgError("renderFeatures: buffers not allocated (call updateResolution first)");
+    PTMI_HIP(hipSetDevice(g.device_id));
+    const size_t n = std::max<size_t>(r.n_local, 1);
+    if (!d.fb.albedo) {
+        try {
+            d.fb.albedo = (float4*)hipMallocSafe(n * sizeof(float4), "features.albedo");
+            d.fb.normal = (float4*)hipMallocSafe(n * sizeof(float4), "features.normal");
+            d.fb.position = (float4*)hipMallocSafe(n * sizeof(float4), "features.position");
+        } catch (...) { r.freeDenoise(); throw; }
+    }
+    d.features_valid = false;
+    FrameParams fp;
+    cameraFrameParams(g, fp);
+    while (g.event_pool.size() < 2) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
+    PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
+    launch_features(g.scene.d_scene, r.tile, fp, grid, d.fb, r.stream);
+    PTMI_HIP(hipGetLastError());
+    PTMI_HIP(hipEventRecord(g.event_pool[1], r.stream));
+    PTMI_HIP(hipStreamSynchronize(r.stream));
+    d.features_ms = elapsedMs(g.event_pool[0], g.event_pool[1]);
+    d.grid = grid;
+    d.features_valid = true;
+}
+
+void readFeatures(const ApplicationState& g, float* albedo, float* normal, float* position, float* hit_fraction) {
+    const RenderState& r = g.render;
+    if (!r.dn.features_valid) throw ArgError("readFeatures: no current feature buffers (ptmi_render_features first)");
+    PTMI_HIP(hipSetDevice(g.device_id));
+    std::vector<float4> h(r.n_local);
+    const float4* src[3] = {r.dn.fb.albedo, r.dn.fb.normal, r.dn.fb.position};
+    float* dst[3] = {albedo, normal, position};
+    for (int k = 0; k < 3; k++) {
+        if (!dst[k] && !(k == 0 && hit_fraction)) continue;
+        if (r.n_local) PTMI_HIP(hipMemcpy(h.data(), src[k], r.n_local * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < r.n_local; i++) {
+            if (dst[k]) { dst[k][3 * i] = h[i].x; dst[k][3 * i + 1] = h[i].y; dst[k][3 * i + 2] = h[i].z; }
+            if (k == 0 && hit_fraction) hit_fraction[i] = h[i].w;
+        }
+    }
+}
+
+void checkDenoiseParams(const DenoiseParams& p) {
+    if (p.iterations < 0 || p.iterations > 10) throw ArgError("denoise: iterations must be in [0, 10]");
+    if (!(p.sigma_color >= 1e-4f && p.sigma_color <= 1e4f)) throw ArgError("denoise: sigma_color must be in [1e-4, 1e4]");
+    if (!(p.color_floor >= 1e-6f && p.color_floor <= 1e4f)) throw ArgError("denoise: color_floor must be in [1e-6, 1e4]");
+    if (!(p.sigma_position <= 0.0f || (p.sigma_position >= 1e-6f && p.sigma_position <= 1e12f)))
+        throw ArgError("denoise: sigma_position must be <= 0 (automatic) or in [1e-6, 1e12]");
+    if (p.normal_squarings < 0 || p.normal_squarings > 10) throw ArgError("denoise: normal_squarings must be in [0, 10]");
+    if (p.feature_grid < 1 || p.feature_grid > 4) throw ArgError("denoise: feature_grid must be in [1, 4]");
+    if (p.demodulate != 0 && p.demodulate != 1) throw ArgError("denoise: demodulate must be 0 or 1");
+}
+
+void denoise(ApplicationState& g, const DenoiseParams& p) {
+    RenderState& r = g.render;
+    RenderState::Denoise& d = r.dn;
+    if (r.tile.n_ranks > 1) throw ArgError("denoise: the context is tiled over more than one rank (the filter needs rows of other ranks)");
+    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError("denoise: the Radiosity integrator's image is not denoised");
+    if (!g.scene.d_nodes || !r.d_state.A || !d.image_current)
+        throw ArgError("denoise: no image rendered yet (none since the last change of scene, camera, resolution or config)");
+    checkDenoiseParams(p);
+    DenoiseArgs a;
+    a.width = r.tile.width; a.height = r.tile.local_rows;
+    a.demodulate = p.demodulate; a.normal_squarings = p.normal_squarings; a.color_floor = p.color_floor;
+    float sigma_x = p.sigma_position;
+    if (sigma_x <= 0.0f) {                                    // 2 % of the diagonal of the root box of the scene's BVH
+        const AABB& b = g.scene.bvh_nodes.at(0).bbox;
+        const float dx = b.max.x - b.min.x, dy = b.max.y - b.min.y, dz = b.max.z - b.min.z;
+        sigma_x = 0.02f * std::sqrt(dx * dx + dy * dy + dz * dz);
+        if (!(sigma_x >= 1e-6f && sigma_x <= 1e12f)) throw ArgError("denoise: the scene's bounding box gives no usable sigma_position; set one");
+    }
+    a.sigma_x2 = sigma_x * sigma_x;
+    float sigma_c[10];
+    for (int i = 0; i < p.iterations; i++) sigma_c[i] = std::ldexp(p.sigma_color, -i);     // sigma_color x 2^-i, exact
+    if (!d.features_valid || d.grid != p.feature_grid) renderFeatures(g, p.feature_grid);
+    PTMI_HIP(hipSetDevice(g.device_id));
+    const size_t n = std::max<size_t>(r.n_local, 1);
+    if (!d.d_rgb8) {
+        try {
+            d.d_rgb8 = (unsigned char*)hipMallocSafe(n * 3, "denoise.rgb8");
+            d.d_radiance = (float*)hipMallocSafe(n * 3 * sizeof(float), "denoise.radiance");
+            d.d_buf = (float4*)hipMallocSafe(2 * n * sizeof(float4), "denoise.buf");
+        } catch (...) {
+            for (void* q : {(void*)d.d_rgb8, (void*)d.d_radiance, (void*)d.d_buf}) if (q) (void)hipFree(q);
+            d.d_rgb8 = nullptr; d.d_radiance = nullptr; d.d_buf = nullptr;
+            throw;
+        }
+    }
+    d.denoised = false;
+    if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));
+    PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
+    launch_denoise(a, d.fb, r.d_radiance, p.iterations, sigma_c, d.d_buf, d.d_rgb8, d.d_radiance, r.stream);
+    PTMI_HIP(hipGetLastError());
+    PTMI_HIP(hipEventRecord(g.event_pool[1], r.stream));
+    PTMI_HIP(hipStreamSynchronize(r.stream));
+    d.denoise_ms = elapsedMs(g.event_pool[0], g.event_pool[1]);
+    d.denoised = true;
+}
+
+void readDenoised(const ApplicationState& g, unsigned char* rgb8, float* radiance) {
+    const RenderState& r = g.render;
+    if (!r.dn.denoised) throw ArgError("readDenoised: nothing denoised yet (ptmi_denoise first)");
+    PTMI_HIP(hipSetDevice(g.device_id));
+    if (rgb8 && r.n_local) PTMI_HIP(hipMemcpy(rgb8, r.dn.d_rgb8, r.n_local * 3, hipMemcpyDeviceToHost));
+    if (radiance && r.n_local) PTMI_HIP(hipMemcpy(radiance, r.dn.d_radiance, r.n_local * 3 * sizeof(float), hipMemcpyDeviceToHost));
 }
 
 }  // namespace ptmi

@@ -212,6 +212,20 @@ struct RenderState {
         Chunk chunk;                                 // d_queue_init is not owned: it points at the pass's queue (nullptr at pass 1)
         bool allocated() const { return d_counts != nullptr; }
     } accum;
+    // Feature buffers of the local pixels (renderFeatures) and the denoiser's outputs and scratch (denoise); allocated at first
+    // use, freed with the other buffers.  Nothing here is read by a frame or a pass.
+    struct Denoise {
+        FeatureBuffers fb;
+        int grid = 0;                                // g of the feature pass the buffers hold
+        bool features_valid = false;                 // false: never computed, or stale (scene, camera, resolution, config changed)
+        bool image_current = false;                  // the image buffers hold a path-tracing frame or pass rendered since the
+                                                     // last such change (what ptmi_denoise may filter)
+        unsigned char* d_rgb8 = nullptr;             // denoised image, local row-major like d_image
+        float* d_radiance = nullptr;
+        float4* d_buf = nullptr;                     // 2 x n_local: the filter's ping-pong buffers
+        bool denoised = false;                       // d_rgb8 / d_radiance hold a result
+        double features_ms = 0.0, denoise_ms = 0.0;  // device time of the last feature pass / filter run
+    } dn;
 
     void allocateBuffers();                         // application_state.h:91-123 (+ render_init)
     void updateResolution(int w, int h, const TileMap* tiling);   // application_state.h:125-129
@@ -220,6 +234,7 @@ struct RenderState {
     void freeChunks();
     void allocateAccum();
     void freeAccum();
+    void freeDenoise();
     ~RenderState() { freeBuffers(); }
 };
 
@@ -298,6 +313,20 @@ struct PassStats {
 void accumReset(ApplicationState& g_state);
 void accumPass(ApplicationState& g_state, const AdaptiveParams* params, PassStats* stats);
 void readSampleCounts(const ApplicationState& g_state, uint32_t* counts);
+
+// Feature buffers and the edge-avoiding a-trous denoiser (include/ptmi.h: ptmi_render_features, ptmi_denoise).
+struct DenoiseParams {
+    int iterations = 5;
+    float sigma_color = 4.0f, color_floor = 2.0f;    // measured: cbox 128^2 at 8 spp
+    float sigma_position = 0.0f;                     // <= 0: 2 % of the scene's bounding-box diagonal
+    int normal_squarings = 7, feature_grid = 2, demodulate = 1;
+};
+void featuresStale(ApplicationState& g_state);       // the triggers that restart an accumulation: features and image are stale
+void renderFeatures(ApplicationState& g_state, int grid);
+void readFeatures(const ApplicationState& g_state, float* albedo, float* normal, float* position, float* hit_fraction);
+void checkDenoiseParams(const DenoiseParams& p);     // throws ArgError for a parameter out of range
+void denoise(ApplicationState& g_state, const DenoiseParams& p);
+void readDenoised(const ApplicationState& g_state, unsigned char* rgb8, float* radiance);
 
 bool packBvhNodes(const std::vector<BVHNode>& bvh_nodes, int top_records, std::vector<float4>& g, int& n_pos, int& n_top, int& top_depth);
 

@@ -31,6 +31,8 @@ EXPORTS = [
     "ptmi_debug_set_fast_tree", "ptmi_debug_intersect_fast", "ptmi_dist_comm_count", "ptmi_host_fast_tree_build", "ptmi_host_fast_tree_intersect", "ptmi_host_fast_tree_stats",
     "ptmi_debug_set_solver_walk", "ptmi_debug_get_traversal",
     "ptmi_default_adaptive_params", "ptmi_accum_reset", "ptmi_accum_pass", "ptmi_read_sample_counts",
+    "ptmi_default_denoise_params", "ptmi_check_denoise_params", "ptmi_render_features", "ptmi_read_features", "ptmi_denoise",
+    "ptmi_read_denoised", "ptmi_denoise_timing",
 ]
 
 
@@ -76,6 +78,11 @@ class PassStats(C.Structure):
                 ("seconds", C.c_double), ("bounce_kernel_ms", C.c_double), ("bounce_launches", C.c_uint64), ("path_visits", C.c_uint64),
                 ("rays", C.c_uint64), ("node_visits", C.c_uint64), ("prim_tests", C.c_uint64), ("hits", C.c_uint64),
                 ("top_node_visits", C.c_uint64), ("cert_chain", C.c_uint64), ("cert_fallback", C.c_uint64)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("color_floor", C.c_float), ("sigma_position", C.c_float),
+                ("normal_squarings", C.c_int), ("feature_grid", C.c_int), ("demodulate", C.c_int)]
 
 
 class PtmiError(RuntimeError):
@@ -169,6 +176,13 @@ def lib():
         L.ptmi_accum_reset.argtypes = [vp]
         L.ptmi_accum_pass.argtypes = [vp, C.POINTER(AdaptiveParams), C.POINTER(PassStats)]
         L.ptmi_read_sample_counts.argtypes = [vp, vp]
+        L.ptmi_default_denoise_params.argtypes = [C.POINTER(DenoiseParams)]; L.ptmi_default_denoise_params.restype = None
+        L.ptmi_check_denoise_params.argtypes = [C.POINTER(DenoiseParams)]
+        L.ptmi_render_features.argtypes = [vp, C.c_int]
+        L.ptmi_read_features.argtypes = [vp, vp, vp, vp, vp]
+        L.ptmi_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
+        L.ptmi_read_denoised.argtypes = [vp, vp, vp]
+        L.ptmi_denoise_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -283,6 +297,17 @@ def default_adaptive_params(**params):
     for k, v in params.items():
         if k not in dict(AdaptiveParams._fields_):
             raise TypeError(f"unknown adaptive parameter {k}")
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def default_denoise_params(**params):
+    """ptmi_default_denoise_params, with any field overridden by keyword (iterations, sigma_color, color_floor, sigma_position,
+    normal_squarings, feature_grid, demodulate)."""
+    p = DenoiseParams(); lib().ptmi_default_denoise_params(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(DenoiseParams._fields_):
+            raise TypeError(f"unknown denoise parameter {k}")
         setattr(p, k, type(getattr(p, k))(v))
     return p
 
@@ -484,6 +509,39 @@ class Renderer:
         counts = np.zeros((len(self.local_rows()), self.width), np.uint32)
         self._ck(self.L.ptmi_read_sample_counts(self.h, counts.ctypes.data))
         return counts
+
+    # --- feature buffers and the denoiser (include/ptmi.h: ptmi_render_features, ptmi_denoise) ---
+    def render_features(self, grid=2):
+        self._ck(self.L.ptmi_render_features(self.h, int(grid)))
+
+    def features(self):
+        """The current feature buffers: albedo, normal, position (local rows, width, 3) and hit_fraction (local rows, width),
+        float32, rows as read_image returns them."""
+        n = len(self.local_rows())
+        out = dict(albedo=np.zeros((n, self.width, 3), np.float32), normal=np.zeros((n, self.width, 3), np.float32),
+                   position=np.zeros((n, self.width, 3), np.float32), hit_fraction=np.zeros((n, self.width), np.float32))
+        self._ck(self.L.ptmi_read_features(self.h, out["albedo"].ctypes.data, out["normal"].ctypes.data, out["position"].ctypes.data,
+                                           out["hit_fraction"].ctypes.data))
+        return out
+
+    def denoise(self, **params):
+        """Denoises the image read_image returns (keyword parameters: fields of DenoiseParams over the defaults); returns the
+        result as (rgb8, radiance), shaped like read_image's."""
+        p = default_denoise_params(**params)
+        self._ck(self.L.ptmi_denoise(self.h, C.byref(p)))
+        return self.read_denoised()
+
+    def read_denoised(self):
+        n = len(self.local_rows())
+        rgb = np.zeros((n, self.width, 3), np.uint8); rad = np.zeros((n, self.width, 3), np.float32)
+        self._ck(self.L.ptmi_read_denoised(self.h, rgb.ctypes.data, rad.ctypes.data))
+        return rgb, rad
+
+    def denoise_timing(self):
+        """(ms of the last feature pass, ms of the last filter run), device time"""
+        a = C.c_double(); b = C.c_double()
+        self._ck(self.L.ptmi_denoise_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def device_image(self):
         a = C.c_void_p(); b = C.c_void_p()

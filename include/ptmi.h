@@ -427,6 +427,71 @@ int  ptmi_accum_pass(ptmi_ctx*, const ptmi_adaptive_params* /* NULL: plain progr
  * row-major like ptmi_read_image */
 int  ptmi_read_sample_counts(const ptmi_ctx*, uint32_t* counts);
 
+/* ---- feature buffers and an edge-avoiding a-trous denoiser (new in this implementation) -----------------------------------
+ * FEATURE PASS.  ptmi_render_features traces g x g camera rays per local pixel (g = grid, 1..4) through the stratum centres
+ * and keeps, per pixel, the means of the first hits' albedo (Kd), stored primitive normal, hit point and hit fraction.  It uses
+ * no RNG (the pixel streams are neither read nor written) and changes no image, sum or accumulation state.  In float32, in
+ * the order written (-ffp-contract=off, correctly rounded division):
+ *     for j = 0 .. g-1 (outer), i = 0 .. g-1 (inner):
+ *         u = ((float)x + ((float)i + 0.5f) / (float)g) / (float)width      x, y: the GLOBAL pixel (row 0 = bottom)
+ *         v = ((float)y + ((float)j + 0.5f) / (float)g) / (float)height
+ *         ray = the camera's get_ray(u, v) of a frame (a frame's camera_ray with the jitter replaced by the stratum centre)
+ *         hit = the reference's closest hit for t > 1e-4 (the walk of the Radiosity view: certified above 64 primitives)
+ *         if hit: A = A + Kd;  N = N + normal;  P = P + (o + t * d);  H = H + 1.0f      (per component; sums start at +0)
+ *     k = rcp_rn((float)(g * g));  albedo = A * k, normal = N * k, position = P * k, hit_fraction = H * k
+ * A miss adds nothing (the same as adding zeros).  The pass works on tiled contexts: every rank computes its own rows.
+ * ptmi_read_features returns the buffers of the last feature pass in local row-major order (that of ptmi_read_image): albedo,
+ * normal and position 3 floats per pixel, hit_fraction 1; any pointer may be NULL.
+ * Features go STALE under the calls that restart an accumulation (see ptmi_accum_pass: scene loads, camera, resolution,
+ * config, radiosity changes); ptmi_read_features then fails until the next ptmi_render_features, and ptmi_denoise recomputes them.
+ *
+ * THE FILTER.  ptmi_denoise filters the radiance that ptmi_read_image would return (the selected frame, or the last
+ * accumulation pass) into buffers of its own; the frame image, colour sums, streams and accumulation state are untouched, so the
+ * next frame, pass or read is bit-identical to one without the denoise.  With iterations = 0 the output is the input (no
+ * demodulation round trip): radiance equal, rgb8 equal to ptmi_read_image's.  Otherwise, float32 in the order written:
+ *   1. c = radiance; with demodulate, per channel: if albedo.ch != 0: c.ch = c.ch / albedo.ch
+ *      lum(c) = 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z
+ *   2. for iteration it = 0 .. iterations-1, stride s = 2^it, sigma_c = sigma_color * 2^-it (exact), for every pixel p, over
+ *      the taps q = p + (di * s, dj * s), dj = -2..2 (outer, rows), di = -2..2 (inner, columns); a q outside the image is skipped:
+ *         h   = H[dj + 2] * H[di + 2]                          H = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *         a   = sigma_c * (min(lum(c_p), lum(c_q)) + color_floor)    (the darker of the two: a firefly or an emitter next to a
+                                                                       dimmer pixel weighs little from either side)
+ *         wc  = 1 / (1 + ((dr*dr + dg*dg) + db*db) / (a * a))          (dr, dg, db) = c_p - c_q
+ *         wn  = max(0, (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z), then wn = wn * wn normal_squarings times
+ *         wx  = 1 / (1 + ((ex*ex + ey*ey) + ez*ez) / (sigma_x * sigma_x))     (ex, ey, ez) = position_p - position_q
+ *         w   = (((h * wc) * wn) * wx);   W = W + w;   S.ch = S.ch + w * c_q.ch         (W, S start at +0, taps in order)
+ *      c'_p = S / W per channel (true division) if W > 0, else c'_p = c_p;  every pixel reads the previous iteration's c.
+ *      sigma_x = sigma_position, or for sigma_position <= 0: 0.02f * sqrtf((dx*dx + dy*dy) + dz*dz) with (dx, dy, dz) = max - min
+ *      of the root box of the scene's BVH (ptmi_scene_get_bvh node 0); sigma_x * sigma_x is computed in float.
+ *   3. with demodulate, per channel: if albedo.ch != 0: c.ch = c.ch * albedo.ch
+ *   4. radiance = c; rgb8 = the frame's tone map of c (c / (c + 1), to the power 1 / 2.2f by ptmi_math.h's powf, 255.99f * min(., 1), truncated).
+ * Features are the current ones for params->feature_grid, recomputed first if stale or of another grid.  A pixel every
+ * feature ray missed has normal 0, so all its taps weigh 0 and it keeps its input.
+ * PTMI_E_INVALID: a context tiled over more than one rank (the filter needs rows of other ranks), the Radiosity integrator, no
+ * image to filter, and parameters out of range or NaN.  "No image" means no path-tracing frame or pass has completed since the
+ * last call that makes features stale (the list above), so the image and its features always show the same scene and view:
+ * after ptmi_update_resolution, ptmi_set_camera, ptmi_set_config, a scene load, ... render first (a Radiosity frame does not
+ * count); ptmi_select_frame keeps the batch's image current. */
+typedef struct {
+    int   iterations;        /* 5; 0 .. 10 */
+    float sigma_color;       /* 4.0; relative colour tolerance of iteration 0, 1e-4 .. 1e4 */
+    float color_floor;       /* 2.0; added to the luminance in the colour weight (radiance units), 1e-6 .. 1e4 */
+    float sigma_position;    /* 0 (<= 0: 2 % of the scene's bounding-box diagonal); else 1e-6 .. 1e12 */
+    int   normal_squarings;  /* 7 (normal weight = max(0, n_p . n_q)^128); 0 .. 10 */
+    int   feature_grid;      /* 2; the g of the feature pass, 1 .. 4 */
+    int   demodulate;        /* 1: filter radiance / albedo; 0: the radiance itself */
+} ptmi_denoise_params;
+void ptmi_default_denoise_params(ptmi_denoise_params*);
+/* the parameter check of ptmi_denoise alone (no context, no device): 0 or PTMI_E_INVALID with the message */
+int  ptmi_check_denoise_params(const ptmi_denoise_params*);
+int  ptmi_render_features(ptmi_ctx*, int grid);
+int  ptmi_read_features(const ptmi_ctx*, float* albedo, float* normal, float* position, float* hit_fraction);
+int  ptmi_denoise(ptmi_ctx*, const ptmi_denoise_params* /* NULL: defaults */);
+/* the last denoise's result, local row-major like ptmi_read_image; either may be NULL */
+int  ptmi_read_denoised(const ptmi_ctx*, unsigned char* rgb8, float* radiance);
+/* device time (hipEvents) of the last feature pass and of the last filter run (feature pass excluded), in ms */
+int  ptmi_denoise_timing(const ptmi_ctx*, double* features_ms, double* denoise_ms);
+
 #ifdef __cplusplus
 }
 #endif

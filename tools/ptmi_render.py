@@ -7,6 +7,8 @@
   python tools/ptmi_render.py --scene ... --radiosity --integrator radiosity --out radiosity_view.png
   python tools/ptmi_render.py --scene ... --spp 8 --passes 16 --out progressive.png          (16 passes of 8 samples)
   python tools/ptmi_render.py --scene ... --spp 8 --adaptive 0.02 --counts-png counts.png   (passes until every pixel stops)
+  python tools/ptmi_render.py --scene ... --spp 8 --denoise --out denoised.png             (a-trous denoiser, 5 iterations)
+  python tools/ptmi_render.py --scene ... --spp 8 --aov-png aov                              (aov_albedo/normal/depth.png)
 """
 import argparse
 import os
@@ -37,6 +39,10 @@ def main():
                     help="adaptive: passes of --spp samples until every pixel has stopped (relative standard error THRESHOLD; "
                          "default: the library's); --passes then sets max_passes")
     ap.add_argument("--counts-png", default=None, help="with --passes / --adaptive: grey map of the samples per pixel (white = most)")
+    ap.add_argument("--denoise", type=int, nargs="?", const=-1, default=None, metavar="ITERATIONS",
+                    help="--out gets the image through the edge-avoiding a-trous denoiser (ITERATIONS, default 5)")
+    ap.add_argument("--aov-png", default=None, metavar="PREFIX", help="write PREFIX_albedo.png, PREFIX_normal.png, PREFIX_depth.png "
+                    "from the feature buffers of the denoiser")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -82,11 +88,35 @@ def main():
     else:
         st = r.render_frame()
         print(f"frame: {a.width}x{a.height} x {a.spp} spp in {st.seconds * 1e3:.2f} ms = {st.samples / st.seconds / 1e6:.1f} Msamples/s")
-    if a.out:
+    if a.denoise is not None:
+        prm = {} if a.denoise < 0 else {"iterations": a.denoise}
+        rgb, _ = r.denoise(**prm)
+        fms, dms = r.denoise_timing()
+        print(f"denoise: features {fms:.3f} ms, filter {dms:.3f} ms")
+    elif a.out:
         rgb, _ = r.read_image()
+    if a.out:
         ptmi.write_png(a.out, rgb)
         print(f"wrote {a.out}")
+    if a.aov_png:
+        write_aovs(r, a.aov_png)
     r.close()
+
+
+def write_aovs(r, prefix):
+    """albedo as is, normal as 0.5 n + 0.5, depth (distance from the camera) as grey, near = white, misses black"""
+    import numpy as np
+    r.render_features(ptmi.default_denoise_params().feature_grid)
+    f = r.features()
+    to8 = lambda x: (255.99 * np.clip(x, 0.0, 1.0)).astype(np.uint8)
+    ptmi.write_png(f"{prefix}_albedo.png", to8(f["albedo"]))
+    ptmi.write_png(f"{prefix}_normal.png", to8(0.5 * f["normal"] + 0.5 * (f["hit_fraction"][..., None] > 0)))
+    hit = f["hit_fraction"] > 0
+    depth = np.linalg.norm(f["position"] - r.camera_frame()[:3], axis=2)
+    near, far = (depth[hit].min(), depth[hit].max()) if hit.any() else (0.0, 1.0)
+    grey = np.where(hit, 1.0 - (depth - near) / max(far - near, 1e-6), 0.0)
+    ptmi.write_png(f"{prefix}_depth.png", to8(grey)[:, :, None].repeat(3, axis=2))
+    print(f"wrote {prefix}_albedo.png, {prefix}_normal.png, {prefix}_depth.png")
 
 
 if __name__ == "__main__":
