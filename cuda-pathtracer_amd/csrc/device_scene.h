@@ -77,6 +77,10 @@ struct DeviceScene {
     int w_cert_debug = 0;              // test hook of the solver's certified walk: 1 every blocked ray takes the ancestor chain, 2 the reference's walk
     const int* wfast_of_ref = nullptr; // reference leaf-order slot -> fast order
     float w_guard = 0.0f;              // the boxes are padded for ray origins with |coordinate| <= w_guard; others take the reference's walk
+    // The certified walk can run on this scene.  SceneState::buildFast sets every w* pointer at once, after all its uploads:
+    // wprims, wref_slot and (scenes with quads) wqprims with wnodes; wcert, wanc and wfast_of_ref together when the ancestor
+    // lists fit; freeFast clears them all.
+    PT_HD bool certified_ready() const { return wnodes && wcert && wanc; }
 };
 // PACKED LAYOUT.  On the 1 M-triangle scene the phased walk is bound by the rate at which L2 misses are served (it runs at
 // the same speed with 2 and with 7 waves per SIMD, with and without half of its node reads moved to LDS): what counts is the

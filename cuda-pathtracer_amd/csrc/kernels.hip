@@ -12,6 +12,9 @@
 //   ptmi_bounce_phased the same work for larger scenes: per-lane stackless walk with wave-scheduled NODE/PRIM/SHADE phases
 //   ptmi_resolve       integrator.h:393-407
 #include "pt_device.h"
+#include "wide_walk.h"
+
+#include <type_traits>
 
 namespace ptmi {
 
@@ -165,7 +168,6 @@ __device__ __forceinline__ void leaf_prim(const float4* __restrict__ prims, int 
 }
 
 // The same for the 36-byte triangle records of the packed layout (v0, e1, e2: three 12-byte loads)
-struct f3p { float x, y, z; };
 __device__ __forceinline__ void leaf_prim_packed(const float* __restrict__ gprims, int k, f3 o, f3 d, float t_lo, float& closest_t, int& slot_hit) {
     const f3p* r = reinterpret_cast<const f3p*>(gprims) + 3 * (size_t)k;
     const f3p v0 = r[0], e1 = r[1], e2 = r[2];
@@ -897,7 +899,7 @@ __global__ __launch_bounds__(kBlock, 8) __attribute__((amdgpu_num_sgpr(80))) voi
 //   (scene.h:50-110) returns exactly the same hit if (1) it reaches k*'s leaf and (2) no second triangle is hit at exactly t*.
 // (1): the reference enters a node when `!(min(t_exit, closest_t) < t_entry)` holds for it and all its ancestors, closest_t being
 // whatever it is at that moment - never below the final t*; the test is monotone in closest_t, so if every ancestor of k*'s leaf
-// (leaf included) passes with closest_t = t* it passes in the reference.  One fetch (the leaf's box, see VERIFY below) shows
+// (leaf included) passes with closest_t = t* it passes in the reference.  One fetch (the leaf's box: csrc/wide_walk.h) shows
 // that for 99.7 % of the hits; the rest evaluate these slab tests themselves (box_hit, the exact walk's arithmetic) from a
 // per-leaf list of ancestor node indices, leaf first, four nodes per step fetched in parallel, until a box holds the hit point
 // with the margin - mostly the parent or grandparent.
@@ -959,9 +961,9 @@ __device__ __forceinline__ void bounce_wide_body(const BounceArgs& a) {
     int segs_left = a.segments;
     int slot_hit = -1, sp = 0;
     float closest_t = FLT_MAX;
-    f3 inv = mk3(wide_inv(p.d.x), wide_inv(p.d.y), wide_inv(p.d.z));
-    uint32_t octinv = wide_octinv(inv);
-    uint32_t g_base = 0u, g_bits = (1u << 8) | (1u << octinv);      // the root: slot 0 of a virtual parent
+    f3 inv;
+    uint32_t octinv, g_base, g_bits;
+    WIDE_WALK_BEGIN(p.d, inv, octinv, g_base, g_bits);
     uint32_t t_base = 0u, t_mask = 0u;
     if (STATS && alive) cn.rays++;
     // where the walk goes when it has run out of nodes and triangles
@@ -972,12 +974,9 @@ __device__ __forceinline__ void bounce_wide_body(const BounceArgs& a) {
         t_base = 0xffffffffu;                                          // first the one-fetch certificate, then (rarely) the chain
         return PH_VERIFY;
     };
-    auto origin_in_range = [&]() { return fmaxf(fabsf(p.o.x), fmaxf(fabsf(p.o.y), fabsf(p.o.z))) <= a.sc.w_guard; };
+    auto origin_in_range = [&]() { return wide_origin_ok(a.sc, p.o); };
     if (CERT && alive && !origin_in_range()) phase = PH_EXACT;
 
-#ifdef PTMI_WALK_CAP
-    int walk_cap_n = 0;
-#endif
     while (true) {
         const int c_node = __popcll(__ballot(phase == PH_NODE));
         const int c_prim = __popcll(__ballot(phase == PH_PRIM));
@@ -991,12 +990,7 @@ __device__ __forceinline__ void bounce_wide_body(const BounceArgs& a) {
                 wt_n[wt_k]++; wt_l[wt_k] += wt_k == 0 ? c_node : wt_k == 1 ? c_prim : c_shade;)
         if (c_node >= c_prim && c_node >= c_shade) {
             if (phase == PH_NODE) {
-                if ((g_bits & 0xffu) == 0u) { sp--; const uint2 e = stack[sp * kBlock]; g_base = e.x; g_bits = e.y; }
-                const int bit = 31 - __clz((int)(g_bits & 0xffu));
-                g_bits ^= 1u << bit;
-                const uint32_t child = (uint32_t)bit ^ octinv;
-                const uint32_t ni = g_base + (uint32_t)__popc((g_bits >> 8) & ((1u << child) - 1u));
-                if (g_bits & 0xffu) { stack[sp * kBlock] = make_uint2(g_base, g_bits); sp++; }
+                WIDE_NEXT_NODE(ni, g_base, g_bits, sp, stack, octinv, {});
                 uint4 q0, q1, q2, q3, q4, q5, q6;
                 if ((int)ni < n_top) {
                     // explicit address spaces: left generic, the two branches are merged into ONE flat_load through a selected pointer
@@ -1042,20 +1036,7 @@ __device__ __forceinline__ void bounce_wide_body(const BounceArgs& a) {
                         const int k = kk[b];
                         if (STATS) cn.prim_tests++;
                         float tt = 0.0f;
-                        bool ok;
-                        if (QUADS && __float_as_int(q0[b].w) != 0) {
-                            // Quad::intersect under an upper bound returns the smaller t of its two halves whenever that is below
-                            // the bound (each half accepts t < closest, the second sees the first's result): quad.h:56-121
-                            const float eps_up = __uint_as_float(__float_as_uint(1e-8f) + 1u);
-                            const float ta = mt_candidate(xyz(q0[b]), xyz(q1[b]), xyz(q2[b]), p.o, p.d, eps_up, t_lo);
-                            const float tb = mt_candidate(xyz(q0[b]), xyz(q2[b]), xyz(q3[b]), p.o, p.d, eps_up, t_lo);
-                            tt = min_raw(ta, tb);
-                            ok = tt < __builtin_inff();
-                        } else {
-                            const f3 v0 = QUADS ? xyz(q0[b]) : mk3(r0[b].x, r0[b].y, r0[b].z), e1 = QUADS ? xyz(q1[b]) : mk3(r1[b].x, r1[b].y, r1[b].z),
-                                     e2 = QUADS ? xyz(q2[b]) : mk3(r2[b].x, r2[b].y, r2[b].z);
-                            ok = mt_hit(v0, e1, e2, p.o, p.d, 1e-8f, t_lo, tt);
-                        }
+                        const bool ok = QUADS ? wide_quad_hit(q0[b], q1[b], q2[b], q3[b], p.o, p.d, t_lo, tt) : wide_tri_hit(r0[b], r1[b], r2[b], p.o, p.d, t_lo, tt);
                         if (ok) {
                             if (tt < closest_t) { closest_t = tt; slot_hit = k; }
                             else if (tt == closest_t && slot_hit >= 0) {           // the reference keeps the hit it visits first (scene.h:89-90)
@@ -1070,59 +1051,21 @@ __device__ __forceinline__ void bounce_wide_body(const BounceArgs& a) {
         } else {
             if (CERT && phase >= PH_VERIFY) {
                 if (phase == PH_VERIFY && t_base == 0xffffffffu) {
-                    // ONE fetch: the box of the hit triangle's leaf in the reference's tree.  Boxes are nested, so if the hit point
-                    // Q = o + t* d lies inside the LEAF's box by eps on every face, it lies inside every ancestor's by at least
-                    // as much - and eps = 2^-20 (|o_a| + big) is more than the reference's slab arithmetic can be off by on any box
-                    // of the scene: t0' = fl(fl(lo - o) fl(1 / d)) is within 3 * 2^-24 |lo - o| / |d| of the true plane distance,
-                    // Q_a' = fl(o_a + fl(t* d_a)) within 2 * 2^-24 (|o_a| + |t* d_a|) of Q_a, |lo_a - o_a| and |t* d_a| <= |o_a| + big.
-                    // Then every entry distance comes out <= t*, every exit distance >= t*, and `!(min(exit, closest_t) < entry)`
-                    // holds whatever closest_t >= t* the reference carries there.  A direction component below 2^-60 (1 / d near
-                    // overflow) or a point within eps of a face goes to the chain of exact slab tests instead.
+                    // ONE fetch: the box of the hit triangle's leaf in the reference's tree (the argument: csrc/wide_walk.h)
                     const float4 lo = a.sc.wcert[kWideCertStride * (size_t)slot_hit], hi = a.sc.wcert[kWideCertStride * (size_t)slot_hit + 1];
                     const f3 q = p.o + closest_t * p.d;
-                    // eps from THIS box's own coordinates M_a = max(|lo_a|, |hi_a|) (round 3 took the scene's largest coordinate: one
-                    // far-away primitive then sent every hit of the scene to the chain).  A point inside the box has |Q_a| <= M_a and
-                    // |t* d_a| <= |o_a| + M_a, so the bounds above sum to <= 11 * 2^-24 (|o_a| + M_a) < eps; and the margin carries to
-                    // every ancestor: a face of an ancestor at X lies |X - F| beyond the leaf's face F, its own arithmetic error
-                    // 2^-22 (|o_a| + |X|) <= 2^-22 (|o_a| + |F| + |X - F|) stays below eps + |X - F|
-                    const float ex = 9.5367431640625e-7f * (fabsf(p.o.x) + fmaxf(fabsf(lo.x), fabsf(hi.x))), ey = 9.5367431640625e-7f * (fabsf(p.o.y) + fmaxf(fabsf(lo.y), fabsf(hi.y))),
-                                ez = 9.5367431640625e-7f * (fabsf(p.o.z) + fmaxf(fabsf(lo.z), fabsf(hi.z)));
-                    const bool inside = q.x - lo.x >= ex && hi.x - q.x >= ex && q.y - lo.y >= ey && hi.y - q.y >= ey && q.z - lo.z >= ez && hi.z - q.z >= ez;
-                    const bool finite_slopes = fabsf(p.d.x) >= 8.673617379884035e-19f && fabsf(p.d.y) >= 8.673617379884035e-19f && fabsf(p.d.z) >= 8.673617379884035e-19f;
+                    const bool inside = CERT_LEAF_INSIDE(p.o, q, lo, hi);
+                    const bool finite_slopes = CERT_SLOPES_OK(p.d, kCertSlope);
                     if (inside && finite_slopes) phase = PH_SHADE;
                     else {
-                        const uint32_t ref = __float_as_uint(lo.w);
-                        g_base = ref >> 5; t_base = ref & 31u;
+                        g_base = cert_first_chunk(lo); t_base = cert_chunks(lo);
                         inv = mk3(rcp_rn(p.d.x), rcp_rn(p.d.y), rcp_rn(p.d.z));       // the reference's 1 / d for its slab tests
                         if (STATS) cn.cert_chain++;
-                        if (t_base == 0u) phase = PH_EXACT;                         // (no list: never built that way; the count below must not wrap)
+                        if (t_base == 0u) phase = PH_EXACT;                         // (no list: fails closed; the count below must not wrap)
                     }
                 } else if (phase == PH_VERIFY) {
-                    const uint4 idx = a.sc.wanc[g_base];
-                    g_base++; t_base--;
-                    const uint32_t ni[4] = {idx.x, idx.y, idx.z, idx.w};
-                    float4 n0[4], n1[4];
-#pragma unroll
-                    for (int c = 0; c < 4; c++) {
-                        const uint32_t j = ni[c] == 0xffffffffu ? 0u : ni[c];      // padding repeats the root
-                        n0[c] = a.sc.nodes[2 * (size_t)j]; n1[c] = a.sc.nodes[2 * (size_t)j + 1];
-                    }
-                    // from the leaf upwards: a box that holds Q with the margin settles all boxes above it (nested) - usually the
-                    // leaf's parent or grandparent; below it every box has to pass the reference's own slab test
-                    const f3 q = p.o + closest_t * p.d;
-                    const float slopes = min3_raw(fabsf(p.d.x), fabsf(p.d.y), fabsf(p.d.z)) - 8.673617379884035e-19f;
-                    bool proven = false, failed = false;
-#pragma unroll
-                    for (int c = 0; c < 4; c++) {
-                        const float ex = 9.5367431640625e-7f * (fabsf(p.o.x) + fmaxf(fabsf(n0[c].x), fabsf(n1[c].x))), ey = 9.5367431640625e-7f * (fabsf(p.o.y) + fmaxf(fabsf(n0[c].y), fabsf(n1[c].y))),
-                                    ez = 9.5367431640625e-7f * (fabsf(p.o.z) + fmaxf(fabsf(n0[c].z), fabsf(n1[c].z)));      // this box's own eps (see the one-fetch step)
-                        const float mx = min3_raw(q.x - n0[c].x - ex, n1[c].x - q.x - ex, slopes);
-                        const float my = min3_raw(q.y - n0[c].y - ey, n1[c].y - q.y - ey, q.z - n0[c].z - ez);
-                        const bool holds = min3_raw(mx, my, n1[c].z - q.z - ez) >= 0.0f;
-                        const bool passes = box_hit(n0[c], n1[c], p.o, inv, t_min, closest_t);
-                        failed = failed || (!proven && !holds && !passes);
-                        proven = proven || holds;
-                    }
+                    // one 4-node chunk of the chain, leaf first, with the reference's own slab test
+                    CERT_CHUNK(proven, failed, a.sc, g_base, (g_base++, t_base--), p.o, p.d, closest_t, kCertSlope, box_hit(n0[c], n1[c], p.o, inv, t_min, closest_t));
                     if (STATS) cn.node_visits += 4;
                     if (failed) phase = PH_EXACT;
                     else if (proven || t_base == 0u) phase = PH_SHADE;
@@ -1142,9 +1085,7 @@ __device__ __forceinline__ void bounce_wide_body(const BounceArgs& a) {
                 segs_left--;
                 if (more && segs_left != 0) {                          // the next segment of this pixel
                     slot_hit = -1; closest_t = FLT_MAX; sp = 0; t_mask = 0u;
-                    inv = mk3(wide_inv(p.d.x), wide_inv(p.d.y), wide_inv(p.d.z));
-                    octinv = wide_octinv(inv);
-                    g_base = 0u; g_bits = (1u << 8) | (1u << octinv);
+                    WIDE_WALK_BEGIN(p.d, inv, octinv, g_base, g_bits);
                     phase = PH_NODE;
                     if (STATS) cn.rays++;
                     if (CERT && !origin_in_range()) phase = PH_EXACT;
@@ -1152,9 +1093,7 @@ __device__ __forceinline__ void bounce_wide_body(const BounceArgs& a) {
                     phase = PH_DONE;
                     if (end_visit(a, n_in, more, slot, p, segs_left)) {            // the lane goes on with the next queued pixel
                         slot_hit = -1; closest_t = FLT_MAX; sp = 0; t_mask = 0u;
-                        inv = mk3(wide_inv(p.d.x), wide_inv(p.d.y), wide_inv(p.d.z));
-                        octinv = wide_octinv(inv);
-                        g_base = 0u; g_bits = (1u << 8) | (1u << octinv);
+                        WIDE_WALK_BEGIN(p.d, inv, octinv, g_base, g_bits);
                         phase = PH_NODE;
                         if (STATS) cn.rays++;
                         if (CERT && !origin_in_range()) phase = PH_EXACT;
@@ -1513,107 +1452,51 @@ void launch_resolve_counts(const TileMap& tm, const PathState& st, const unsigne
     hipLaunchKernelGGL(ptmi_resolve_counts, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, tm, st, passes, spp, rgb8, radiance, counts);
 }
 
-// The proof of the certified walk for ONE hit (bounce_wide_body, VERIFY, in straight-line form): the hit point inside the hit leaf's
-// box of the reference's tree by eps, else the exact slab tests of the leaf's ancestors, leaf first, up to the first box that holds
-// the point with the margin.  false: a box of the chain failed - the reference's own walk has to decide this ray.
-__device__ __forceinline__ bool certified_proof(const DeviceScene& sc, f3 o, f3 d, float t_min, float closest_t, int slot_hit) {
-    const float4 lo = sc.wcert[kWideCertStride * (size_t)slot_hit], hi = sc.wcert[kWideCertStride * (size_t)slot_hit + 1];
-    const f3 q = o + closest_t * d;
-    const float kEps = 9.5367431640625e-7f, kSlope = 8.673617379884035e-19f;
-    const bool slopes = fabsf(d.x) >= kSlope && fabsf(d.y) >= kSlope && fabsf(d.z) >= kSlope;
-    const float ex = kEps * (fabsf(o.x) + fmaxf(fabsf(lo.x), fabsf(hi.x))), ey = kEps * (fabsf(o.y) + fmaxf(fabsf(lo.y), fabsf(hi.y))),
-                ez = kEps * (fabsf(o.z) + fmaxf(fabsf(lo.z), fabsf(hi.z)));
-    const bool inside = q.x - lo.x >= ex && hi.x - q.x >= ex && q.y - lo.y >= ey && hi.y - q.y >= ey && q.z - lo.z >= ez && hi.z - q.z >= ez;
-    if (inside && slopes) return true;
-    const f3 rinv = mk3(rcp_rn(d.x), rcp_rn(d.y), rcp_rn(d.z));            // the reference's 1 / d for its slab tests
-    const uint32_t ref = __float_as_uint(lo.w);
-    uint32_t off = ref >> 5;
-    bool proven = false, failed = false;
-    for (int left = (int)(ref & 31u); left > 0 && !proven && !failed; left--, off++) {
-        const uint4 idx = sc.wanc[off];
-        const uint32_t ni[4] = {idx.x, idx.y, idx.z, idx.w};
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            const uint32_t j = ni[c] == 0xffffffffu ? 0u : ni[c];              // padding repeats the root
-            const float4 n0 = sc.nodes[2 * (size_t)j], n1 = sc.nodes[2 * (size_t)j + 1];
-            const float nx = kEps * (fabsf(o.x) + fmaxf(fabsf(n0.x), fabsf(n1.x))), ny = kEps * (fabsf(o.y) + fmaxf(fabsf(n0.y), fabsf(n1.y))),
-                        nz = kEps * (fabsf(o.z) + fmaxf(fabsf(n0.z), fabsf(n1.z)));
-            const bool holds = slopes && q.x - n0.x >= nx && n1.x - q.x >= nx && q.y - n0.y >= ny && n1.y - q.y >= ny && q.z - n0.z >= nz && n1.z - q.z >= nz;
-            const bool passes = box_hit(n0, n1, o, rinv, t_min, closest_t);
-            failed = failed || (!proven && !holds && !passes);
-            proven = proven || holds;
-        }
-    }
-    return !failed;
-}
-
-// ---------------------------------------------------------------------------------------------
 // The certified closest hit of ONE ray, lane by lane (no phases): the walk and the proof of bounce_wide_body<..., CERT> in
-// straight-line form, for callers that trace a ray at a time (the Radiosity view).  Returns the REFERENCE's hit: its leaf-order
-// slot in ref_slot, so that the caller indexes the reference's per-primitive arrays.  stack: this lane's column of w_depth
-// 8-byte entries in LDS (entry e at stack[e * kBlock]).
-// ---------------------------------------------------------------------------------------------
+// straight-line form (csrc/wide_walk.h), for callers that trace a ray at a time (the Radiosity view, the feature pass).  Returns
+// the REFERENCE's hit: its leaf-order slot in ref_slot, so that the caller indexes the reference's per-primitive arrays.
+// stack: this lane's column of w_depth 8-byte entries in LDS (entry e at stack[e * kBlock]).
 template <bool QUADS>
 __device__ __forceinline__ bool certified_closest_hit(const DeviceScene& sc, uint2* stack, f3 o, f3 d, float t_min, float& t_hit, int& ref_slot) {
     LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
     auto reference_walk = [&]() { return intersect_lane<QUADS, false>(sc.nodes, sc.prims, sc.prim_stride, sc.n_nodes, true, o, d, t_min, FLT_MAX, t_hit, ref_slot, cn); };
-    if (fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z))) > sc.w_guard) return reference_walk();      // the boxes are not padded for this origin
-    const f3 inv = mk3(wide_inv(d.x), wide_inv(d.y), wide_inv(d.z));
-    const uint32_t octinv = wide_octinv(inv);
-    const float t_lo = mt_t_lo(t_min);
+    if (!wide_origin_ok(sc, o)) return reference_walk();
     float closest_t = FLT_MAX;
-    int slot_hit = -1, sp = 0;
     bool tie = false;
-    uint32_t g_base = 0u, g_bits = (1u << 8) | (1u << octinv);
-    while (true) {
-        if ((g_bits & 0xffu) == 0u) {
-            if (sp == 0) break;
-            sp--; const uint2 e = stack[sp * kBlock]; g_base = e.x; g_bits = e.y;
-        }
-        const int bit = 31 - __clz((int)(g_bits & 0xffu));
-        g_bits ^= 1u << bit;
-        const uint32_t child = (uint32_t)bit ^ octinv;
-        const uint32_t ni = g_base + (uint32_t)__popc((g_bits >> 8) & ((1u << child) - 1u));
-        if (g_bits & 0xffu) { stack[sp * kBlock] = make_uint2(g_base, g_bits); sp++; }
-        const uint4* q = sc.wnodes + 8 * (size_t)ni;
-        const WideStep st = wide_node_test(q[0], q[1], q[2], q[3], q[4], q[5], q[6], o, inv, octinv, t_min, closest_t);
-        uint32_t tris = st.tris;
-        while (tris) {
-            const int k = (int)st.tri_base + __ffs((int)tris) - 1;
-            tris &= tris - 1u;
-            float tt = 0.0f;
-            bool ok;
-            if (QUADS && __float_as_int(sc.wqprims[4 * (size_t)k].w) != 0) {               // a quad: the smaller t of its two halves
-                const float4* r = sc.wqprims + 4 * (size_t)k;
-                const float eps_up = __uint_as_float(__float_as_uint(1e-8f) + 1u);
-                tt = min_raw(mt_candidate(xyz(r[0]), xyz(r[1]), xyz(r[2]), o, d, eps_up, t_lo), mt_candidate(xyz(r[0]), xyz(r[2]), xyz(r[3]), o, d, eps_up, t_lo));
-                ok = tt < __builtin_inff();
-            } else if (QUADS) {
-                const float4* r = sc.wqprims + 4 * (size_t)k;
-                ok = mt_hit(xyz(r[0]), xyz(r[1]), xyz(r[2]), o, d, 1e-8f, t_lo, tt);
-            } else {
-                const f3p* r = reinterpret_cast<const f3p*>(sc.wprims) + 3 * (size_t)k;
-                const f3p v0 = r[0], e1 = r[1], e2 = r[2];
-                ok = mt_hit(mk3(v0.x, v0.y, v0.z), mk3(e1.x, e1.y, e1.z), mk3(e2.x, e2.y, e2.z), o, d, 1e-8f, t_lo, tt);
-            }
-            if (ok) {
-                if (tt < closest_t) { closest_t = tt; slot_hit = k; tie = false; }
-                else if (tt == closest_t && slot_hit >= 0) tie = true;             // the reference keeps the hit it visits first: let it decide
-            }
-        }
-        g_base = st.child_base; g_bits = (st.imask << 8) | st.inner;
-    }
+    WideCounts wc = {0, 0};
+    const int slot_hit = wide_closest_hit<QUADS, false>(sc, stack, o, d, t_min, closest_t, tie, wc);
     if (slot_hit < 0) return false;                        // the reference can only accept triangles this walk would have found
-    if (tie || !certified_proof(sc, o, d, t_min, closest_t, slot_hit)) return reference_walk();
+    if (tie) return reference_walk();                      // the reference keeps the hit it visits first: let it decide
+    const float4 lo = sc.wcert[kWideCertStride * (size_t)slot_hit], hi = sc.wcert[kWideCertStride * (size_t)slot_hit + 1];
+    const f3 q = o + closest_t * d;
+    const f3 rinv = mk3(rcp_rn(d.x), rcp_rn(d.y), rcp_rn(d.z));            // the reference's 1 / d for its slab tests
+    const bool proven = (CERT_LEAF_INSIDE(o, q, lo, hi) && CERT_SLOPES_OK(d, kCertSlope)) ||
+                        cert_chain(sc, lo, o, d, closest_t, kCertSlope, [=](const float4& n0, const float4& n1) { return box_hit(n0, n1, o, rinv, t_min, closest_t); });
+    if (!proven) return reference_walk();
     t_hit = closest_t;
     ref_slot = sc.wref_slot[slot_hit];
     return true;
 }
 
+// The first-hit walk of the Radiosity view and the feature pass: MODE TRAVERSAL_CERTIFIED the certified walk (scenes above the
+// sweep's 64 primitives: the 8-wide tree + the proof per hit, else the reference's walk - the reference's hit for every ray);
+// TRAVERSAL_LANE / TRAVERSAL_STACK the reference's walk.  f(integral_constant MODE, integral_constant HAS_QUADS, LDS bytes).
+template <typename F>
+static void first_hit_walk(const DeviceScene& sc, F&& f) {
+    const bool deep = sc.traversal == TRAVERSAL_STACK;                                // per-lane walk from global memory; stack only for deep trees
+    const bool cert = sc.traversal == TRAVERSAL_CERTIFIED && sc.certified_ready();
+    const size_t lds = cert ? (size_t)sc.w_depth * kBlock * sizeof(uint2) : deep ? (size_t)sc.stack_entries * kBlock * sizeof(int) : 0;
+    auto with_quads = [&](auto mode) {
+        if (sc.has_quads) f(mode, std::true_type{}, lds);
+        else f(mode, std::false_type{}, lds);
+    };
+    if (cert) with_quads(std::integral_constant<int, TRAVERSAL_CERTIFIED>{});
+    else if (deep) with_quads(std::integral_constant<int, TRAVERSAL_STACK>{});
+    else with_quads(std::integral_constant<int, TRAVERSAL_LANE>{});
+}
+
 // ---------------------------------------------------------------------------------------------
-// render_radiosity (integrator.h:460-504): a visualisation pass, one thread per pixel, not performance-critical
-// MODE TRAVERSAL_CERTIFIED: the first hit through the certified walk (scenes above the sweep's 64 primitives: the 8-wide tree + the
-// proof per hit, else the reference's walk - the reference's hit for every ray); TRAVERSAL_LANE / TRAVERSAL_STACK: the reference's walk
+// render_radiosity (integrator.h:460-504): a visualisation pass, one thread per pixel, not performance-critical; the walk: first_hit_walk
 // ---------------------------------------------------------------------------------------------
 template <int MODE, bool HAS_QUADS>
 __global__ __launch_bounds__(kBlock) void ptmi_render_radiosity(DeviceScene sc, TileMap tm, PathState st, FrameParams fp,
@@ -1663,15 +1546,10 @@ void launch_render_radiosity(const DeviceScene& sc, const TileMap& tm, const Pat
                              unsigned char* rgb8, float* radiance, hipStream_t s) {
     const int n = tm.local_rows * tm.width;
     if (n <= 0) return;
-    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    const bool deep = sc.traversal == TRAVERSAL_STACK;                                // per-lane walk from global memory; stack only for deep trees
-    const bool cert = sc.traversal == TRAVERSAL_CERTIFIED && sc.wnodes && sc.wcert && sc.wanc && sc.wref_slot && (!sc.has_quads || sc.wqprims);
-    const size_t lds = cert ? (size_t)sc.w_depth * kBlock * sizeof(uint2) : deep ? (size_t)sc.stack_entries * kBlock * sizeof(int) : 0;
-#define PTMI_RAD(M_, Q_) hipLaunchKernelGGL((ptmi_render_radiosity<M_, Q_>), grid, block, lds, s, sc, tm, st, fp, rgb8, radiance)
-    if (cert) { if (sc.has_quads) PTMI_RAD(TRAVERSAL_CERTIFIED, true); else PTMI_RAD(TRAVERSAL_CERTIFIED, false); }
-    else if (deep) { if (sc.has_quads) PTMI_RAD(TRAVERSAL_STACK, true); else PTMI_RAD(TRAVERSAL_STACK, false); }
-    else { if (sc.has_quads) PTMI_RAD(TRAVERSAL_LANE, true); else PTMI_RAD(TRAVERSAL_LANE, false); }
-#undef PTMI_RAD
+    first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
+        hipLaunchKernelGGL((ptmi_render_radiosity<decltype(mode)::value, decltype(quads)::value>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s,
+                           sc, tm, st, fp, rgb8, radiance);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1721,15 +1599,9 @@ __global__ __launch_bounds__(kBlock) void ptmi_features(DeviceScene sc, TileMap 
 void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams& fp, int g, const FeatureBuffers& fb, hipStream_t s) {
     const int n = tm.local_rows * tm.width;
     if (n <= 0) return;
-    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    const bool deep = sc.traversal == TRAVERSAL_STACK;                                // the walk choice of launch_render_radiosity
-    const bool cert = sc.traversal == TRAVERSAL_CERTIFIED && sc.wnodes && sc.wcert && sc.wanc && sc.wref_slot && (!sc.has_quads || sc.wqprims);
-    const size_t lds = cert ? (size_t)sc.w_depth * kBlock * sizeof(uint2) : deep ? (size_t)sc.stack_entries * kBlock * sizeof(int) : 0;
-#define PTMI_FEAT(M_, Q_) hipLaunchKernelGGL((ptmi_features<M_, Q_>), grid, block, lds, s, sc, tm, fp, g, fb)
-    if (cert) { if (sc.has_quads) PTMI_FEAT(TRAVERSAL_CERTIFIED, true); else PTMI_FEAT(TRAVERSAL_CERTIFIED, false); }
-    else if (deep) { if (sc.has_quads) PTMI_FEAT(TRAVERSAL_STACK, true); else PTMI_FEAT(TRAVERSAL_STACK, false); }
-    else { if (sc.has_quads) PTMI_FEAT(TRAVERSAL_LANE, true); else PTMI_FEAT(TRAVERSAL_LANE, false); }
-#undef PTMI_FEAT
+    first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
+        hipLaunchKernelGGL((ptmi_features<decltype(mode)::value, decltype(quads)::value>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, tm, fp, g, fb);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1775,67 +1647,31 @@ void launch_debug_intersect(const DeviceScene& sc, int n, const float* o, const 
 #undef PTMI_DBG
 }
 
-// Closest hit through the fast tree for n rays (test hook): the walk of ptmi_bounce_wide, lane by lane, without the phases
+// Closest hit through the fast tree for n rays (test hook): wide_closest_hit, the walk of the Radiosity view and the features
+template <bool QUADS>
 __global__ __launch_bounds__(kBlock) void ptmi_debug_intersect_wide_k(DeviceScene sc, int n, const float* o, const float* d, float t_min,
                                                                       float t_max, int* hit, int* prim, float* t_out,
                                                                       unsigned long long* counts /* [0] node visits [1] triangle tests */) {
     extern __shared__ float4 smem[];
-    uint2* stack = reinterpret_cast<uint2*>(smem) + threadIdx.x;
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const f3 ro = mk3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
-    const f3 inv = mk3(wide_inv(rd.x), wide_inv(rd.y), wide_inv(rd.z));
-    const uint32_t octinv = wide_octinv(inv);
-    const float t_lo = mt_t_lo(t_min);
     float closest_t = t_max;
-    int slot_hit = -1, sp = 0;
-    uint32_t g_base = 0u, g_bits = (1u << 8) | (1u << octinv);
-    unsigned int nv = 0, pt = 0;
-    while (true) {
-        if ((g_bits & 0xffu) == 0u) {
-            if (sp == 0) break;
-            sp--; const uint2 e = stack[sp * kBlock]; g_base = e.x; g_bits = e.y;
-        }
-        const int bit = 31 - __clz((int)(g_bits & 0xffu));
-        g_bits ^= 1u << bit;
-        const uint32_t child = (uint32_t)bit ^ octinv;
-        const uint32_t ni = g_base + (uint32_t)__popc((g_bits >> 8) & ((1u << child) - 1u));
-        if (g_bits & 0xffu) { stack[sp * kBlock] = make_uint2(g_base, g_bits); sp++; }
-        const uint4* q = sc.wnodes + 8 * (size_t)ni;
-        nv++;
-        const WideStep st = wide_node_test(q[0], q[1], q[2], q[3], q[4], q[5], q[6], ro, inv, octinv, t_min, closest_t);
-        uint32_t tris = st.tris;
-        while (tris) {
-            const int k = (int)st.tri_base + __ffs((int)tris) - 1;
-            tris &= tris - 1u;
-            pt++;
-            const f3p* r = reinterpret_cast<const f3p*>(sc.wprims) + 3 * (size_t)k;
-            const f3p v0 = r[0], e1 = r[1], e2 = r[2];
-            float tt = 0.0f;
-            bool ok;
-            if (sc.wqprims && __float_as_int(sc.wqprims[4 * (size_t)k].w) != 0) {           // a quad: the smaller t of its two halves
-                const float4* q = sc.wqprims + 4 * (size_t)k;
-                const float eps_up = __uint_as_float(__float_as_uint(1e-8f) + 1u);
-                tt = min_raw(mt_candidate(xyz(q[0]), xyz(q[1]), xyz(q[2]), ro, rd, eps_up, t_lo), mt_candidate(xyz(q[0]), xyz(q[2]), xyz(q[3]), ro, rd, eps_up, t_lo));
-                ok = tt < __builtin_inff();
-            } else ok = mt_hit(mk3(v0.x, v0.y, v0.z), mk3(e1.x, e1.y, e1.z), mk3(e2.x, e2.y, e2.z), ro, rd, 1e-8f, t_lo, tt);
-            if (ok) {
-                if (tt < closest_t) { closest_t = tt; slot_hit = k; }
-                else if (tt == closest_t && slot_hit >= 0 && sc.wref_slot[k] < sc.wref_slot[slot_hit]) slot_hit = k;
-            }
-        }
-        g_base = st.child_base; g_bits = (st.imask << 8) | st.inner;
-    }
+    bool tie = false;
+    WideCounts wc = {0, 0};
+    const int slot_hit = wide_closest_hit<QUADS, true>(sc, reinterpret_cast<uint2*>(smem) + threadIdx.x, ro, rd, t_min, closest_t, tie, wc);
     hit[i] = slot_hit >= 0 ? 1 : 0;
     prim[i] = slot_hit >= 0 ? sc.wload_index[slot_hit] : -1;
     t_out[i] = slot_hit >= 0 ? closest_t : 0.0f;
-    if (counts) { atomicAdd(&counts[0], (unsigned long long)nv); atomicAdd(&counts[1], (unsigned long long)pt); }
+    if (counts) { atomicAdd(&counts[0], (unsigned long long)wc.node_visits); atomicAdd(&counts[1], (unsigned long long)wc.prim_tests); }
 }
 void launch_debug_intersect_wide(const DeviceScene& sc, int n, const float* o, const float* d, float t_min, float t_max,
                                  int* hit, int* prim, float* t, unsigned long long* counts, hipStream_t s) {
     if (n <= 0) return;
     const size_t lds = (size_t)sc.w_depth * kBlock * sizeof(uint2);
-    hipLaunchKernelGGL(ptmi_debug_intersect_wide_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, n, o, d, t_min, t_max, hit, prim, t, counts);
+    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+    if (sc.has_quads) hipLaunchKernelGGL(ptmi_debug_intersect_wide_k<true>, grid, block, lds, s, sc, n, o, d, t_min, t_max, hit, prim, t, counts);
+    else hipLaunchKernelGGL(ptmi_debug_intersect_wide_k<false>, grid, block, lds, s, sc, n, o, d, t_min, t_max, hit, prim, t, counts);
 }
 
 __global__ void ptmi_debug_rng_k(const uint32_t* __restrict__ jump, unsigned long long seed_base, int n_pixels,

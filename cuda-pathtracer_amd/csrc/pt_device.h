@@ -109,6 +109,7 @@ __device__ __forceinline__ float mt_t_lo(float t_min) {
 }
 
 __device__ __forceinline__ f3 xyz(const float4& v) { return mk3(v.x, v.y, v.z); }
+struct f3p { float x, y, z; };      // one vector of a 36-byte triangle record (v0, e1, e2), read as a 12-byte load
 
 // Frisvad frame (grid.h:287-297, form_factors.h:93-103, integrator.h:72-82: the same code three times)
 __device__ __forceinline__ void build_frame(f3 n, f3& t, f3& b) {                 // grid.h:287-297

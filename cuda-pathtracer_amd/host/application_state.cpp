@@ -406,6 +406,7 @@ void SceneState::buildFast() {
             path.clear();
             for (int x = i; x >= 0; x = parent[x]) path.push_back(x);
             const size_t first_chunk = anc.size() / 4, chunks = (path.size() + 3) / 4;
+            if (chunks == 0) throw std::logic_error("fast tree: an empty ancestor list");      // the list starts with the leaf itself
             if (chunks > 31 || first_chunk >= (1u << 27)) { fits = false; break; }
             for (size_t k = 0; k < path.size(); k++) anc.push_back((uint32_t)path[k]);      // the leaf first, the root last
             while (anc.size() % 4) anc.push_back(0xffffffffu);
@@ -527,7 +528,7 @@ void RadiosityState::runSolver(SceneState& scene, const uint32_t* d_jump, bool e
                 catch (const ArgError&) { if (!automatic) throw; }
             }
             if (!scene.fastReady()) walk = 0;
-            if (walk == 2 && !(scene.d_scene.wcert && scene.d_scene.wanc)) walk = 0;
+            if (walk == 2 && !scene.d_scene.certified_ready()) walk = 0;
         }
         d.fast_tree = walk;
     }
@@ -685,14 +686,14 @@ void SceneState::chooseTraversal() {
     if (!d_nodes) return;
     if (bvh_depth > 62) d_scene.traversal = TRAVERSAL_STACK;           // the reference's stack-overflow rule can trigger
     else if ((int)h_primitives.size() <= sweep_max_prims) d_scene.traversal = TRAVERSAL_SWEEP;
-    else d_scene.traversal = certified_default && d_scene.wnodes && d_scene.wcert && d_scene.wanc ? TRAVERSAL_CERTIFIED : (d_scene.gnodes ? TRAVERSAL_PACKED : TRAVERSAL_PHASED);
+    else d_scene.traversal = certified_default && d_scene.certified_ready() ? TRAVERSAL_CERTIFIED : (d_scene.gnodes ? TRAVERSAL_PACKED : TRAVERSAL_PHASED);
     // PHASED: measured faster than the segment-synchronous LANE walk from 128 primitives up (LDS-resident or not); PACKED: the
     // phased walk over the packed layout of scenes too large for LDS; LANE stays available through the override
     if (force_traversal >= 0 && !(force_traversal != TRAVERSAL_STACK && bvh_depth > 62)) d_scene.traversal = force_traversal;
     if (d_scene.traversal == TRAVERSAL_SWEEP && !d_scene.lds_resident) d_scene.traversal = TRAVERSAL_LANE;   // the sweep reads through LDS
     if (d_scene.traversal == TRAVERSAL_PACKED && !d_scene.gnodes) d_scene.traversal = TRAVERSAL_PHASED;
     // CERTIFIED needs the fast tree and the ancestor lists (triangle scenes of depth <= 62); otherwise the exact walk it stands for
-    if (d_scene.traversal == TRAVERSAL_CERTIFIED && !(d_scene.wnodes && d_scene.wanc))
+    if (d_scene.traversal == TRAVERSAL_CERTIFIED && !d_scene.certified_ready())
         d_scene.traversal = (int)h_primitives.size() <= sweep_max_prims && d_scene.lds_resident ? TRAVERSAL_SWEEP : (d_scene.gnodes ? TRAVERSAL_PACKED : TRAVERSAL_PHASED);
 }
 
@@ -957,7 +958,7 @@ static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, Pass
         g.scene.buildFast();
     DeviceScene scene = g.scene.d_scene;
     if (g.config.fast_tree && g.scene.fastReady()) scene.traversal = TRAVERSAL_WIDE;
-    if (scene.traversal == TRAVERSAL_CERTIFIED && !(g.scene.fastReady() && scene.wanc)) scene.traversal = scene.gnodes ? TRAVERSAL_PACKED : TRAVERSAL_PHASED;
+    if (scene.traversal == TRAVERSAL_CERTIFIED && !scene.certified_ready()) scene.traversal = scene.gnodes ? TRAVERSAL_PACKED : TRAVERSAL_PHASED;
     const int trav = scene.traversal;
     const bool phased = trav == TRAVERSAL_PHASED || trav == TRAVERSAL_PACKED || trav == TRAVERSAL_WIDE || trav == TRAVERSAL_CERTIFIED;
     // The phased kernels keep their lanes busy across sample boundaries, so a launch boundary buys them only the compaction; with

@@ -140,7 +140,7 @@ for it in range(n_scenes):
         ok = frames[1][0] == R.CERTIFIED and st.cert_chain <= 0.05 * max(st.hits, 1) and st.cert_fallback <= 1e-3 * max(st.hits, 1)
         line += f"; chain / hits {st.cert_chain / max(st.hits, 1):.4f} (bound 0.05), reference's walk / hits {st.cert_fallback / max(st.hits, 1):.2e} (bound 1e-3): {'ok' if ok else 'OVER'}"
         bad += 0 if ok else 1
-    if n <= 3000 and kind <= 3:                  # the pre-pass too
+    if (n <= 3000 and kind <= 3) or kind in (6, 8):      # the pre-pass too (6: degenerate primitives, 8: the far-away outlier)
         sols = []
         for walk in (0, -1):
             R.set_solver_walk(walk, 65); s2 = R.run_radiosity_solver(mc_samples=8, num_iterations=2); sols.append((s2, R.radiosity_solution()))
