@@ -35,8 +35,9 @@ int guarded(Fn&& fn) {
 }
 void need(bool ok, const char* what) { if (!ok) throw ArgError(what); }
 
-// a call that changes what a frame would show: the accumulation restarts and the feature buffers go stale
-void viewChanged(ApplicationState& app) { accumReset(app); featuresStale(app); }
+// a call that changes what a frame would show: the accumulation restarts, the feature buffers go stale and the temporal
+// history empties (ptmi_set_camera keeps the history: reprojecting it into the new view is the temporal step's job)
+void viewChanged(ApplicationState& app) { accumReset(app); featuresStale(app); temporalReset(app); }
 f3 v3(const float* p) { return mk3(p[0], p[1], p[2]); }
 
 #define PTMI_HIP(call)                                                                                   \
@@ -372,7 +373,8 @@ int ptmi_set_camera(ptmi_ctx* c, const ptmi_camera* cam) {
         AppConfig& cfg = c->app.config;
         cfg.camera_origin = v3(cam->origin); cfg.look_at = v3(cam->lookat); cfg.up = v3(cam->vup);
         cfg.fov = cam->vfov_deg; cfg.orbit = cam->orbit != 0;
-        viewChanged(c->app);
+        accumReset(c->app);
+        featuresStale(c->app);
         Sensor& s = c->app.render.h_camera;
         const int w = s.image_width, h = s.image_height; const float aspect = s.aspect;
         s = Sensor(cfg.camera_origin, cfg.look_at, cfg.up, cfg.fov, 1.0f);    // application.h:107-113
@@ -838,6 +840,53 @@ int ptmi_denoise_timing(const ptmi_ctx* c, double* features_ms, double* denoise_
         need(c != nullptr, "ctx is NULL");
         if (features_ms) *features_ms = c->app.render.dn.features_ms;
         if (denoise_ms) *denoise_ms = c->app.render.dn.denoise_ms;
+    });
+}
+
+// ---- temporal accumulation with reprojection ----
+static TemporalParams temporal_params_from(const ptmi_temporal_params& p) {
+    TemporalParams t;
+    t.max_history = p.max_history; t.normal_min = p.normal_min; t.sigma_position = p.sigma_position; t.feature_grid = p.feature_grid;
+    t.sigma_albedo = p.sigma_albedo;
+    return t;
+}
+void ptmi_default_temporal_params(ptmi_temporal_params* p) {
+    if (!p) return;
+    const TemporalParams t;
+    p->max_history = t.max_history; p->normal_min = t.normal_min; p->sigma_position = t.sigma_position; p->feature_grid = t.feature_grid;
+    p->sigma_albedo = t.sigma_albedo;
+}
+int ptmi_check_temporal_params(const ptmi_temporal_params* p) {
+    return guarded([&] { need(p != nullptr, "params is NULL"); checkTemporalParams(temporal_params_from(*p)); });
+}
+int ptmi_temporal_reset(ptmi_ctx* c) {
+    return guarded([&] { need(c != nullptr, "ctx is NULL"); temporalReset(c->app); });
+}
+int ptmi_temporal_accumulate(ptmi_ctx* c, const ptmi_temporal_params* params, ptmi_temporal_stats* stats) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        ptmi_temporal_params p;
+        ptmi_default_temporal_params(&p);
+        TemporalStats st;
+        temporalAccumulate(c->app, temporal_params_from(params ? *params : p), &st);
+        if (stats) {
+            stats->accepted = st.accepted; stats->rejected = st.rejected; stats->missed = st.missed;
+            stats->seconds = st.seconds; stats->features_ms = st.features_ms;
+        }
+    });
+}
+int ptmi_read_temporal(const ptmi_ctx* c, unsigned char* rgb8, float* radiance) {
+    return guarded([&] { need(c != nullptr, "ctx is NULL"); readTemporal(c->app, rgb8, radiance); });
+}
+int ptmi_read_history_counts(const ptmi_ctx* c, float* counts) {
+    return guarded([&] { need(c && counts, "NULL argument"); readHistoryCounts(c->app, counts); });
+}
+int ptmi_denoise_temporal(ptmi_ctx* c, const ptmi_denoise_params* params) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        ptmi_denoise_params p;
+        ptmi_default_denoise_params(&p);
+        denoiseTemporal(c->app, denoise_params_from(params ? *params : p));
     });
 }
 

@@ -231,6 +231,34 @@ struct DenoiseArgs {
 void launch_denoise(const DenoiseArgs& a, const FeatureBuffers& fb, const float* radiance, int iterations, const float* sigma_c,
                     float4* buf, unsigned char* out_rgb8, float* out_radiance, hipStream_t s);
 
+// ---- temporal accumulation with reprojection (include/ptmi.h: ptmi_temporal_accumulate) ------------------------------------
+// The step's constants (csrc/temporal.hip; the contract is written out in include/ptmi.h)
+struct TemporalArgs {
+    int width, height;               // the whole frame (a single rank)
+    int history;                     // 0: the history is empty (every pixel restarts)
+    int still;                       // 1: camera frame and resolution bit-identical to the history's
+    float cam[12];                   // the history's camera frame: origin, lower-left corner, horizontal, vertical
+    float origin[3];                 // the current camera's origin
+    float m;                         // the input's samples per pixel where there are no per-pixel counts (config.spp)
+    float max_history;               // (float)max_history
+    float normal_min;
+    float sigma_x2;                  // sigma_x * sigma_x
+    float sigma_a2;                  // sigma_albedo * sigma_albedo
+};
+// One side of the history's ping-pong, local row-major
+struct TemporalHistory {
+    float4* color = nullptr;         // (colour.xyz, sample count)
+    float4* normal = nullptr;        // (the feature normal .xyz, hit fraction) of the history's view
+    float4* position = nullptr;      // (the feature position .xyz, 0) of the history's view
+    float4* albedo = nullptr;        // (the feature albedo .xyz, hit fraction) of the history's view
+};
+// One step: the current radiance (3 floats per pixel) with its sample counts (counts, or a.m everywhere where counts ==
+// nullptr) and features fb over the history prev -> next; the result -> out_radiance and its tone map
+// -> rgb8; accepted / rejected / missed pixels are added to stats[0..2].
+void launch_temporal(const TemporalArgs& a, const FeatureBuffers& fb, const float* radiance, const unsigned int* counts,
+                     const TemporalHistory& prev, const TemporalHistory& next, unsigned char* rgb8,
+                     float* out_radiance, unsigned long long* stats, hipStream_t s);
+
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)
 

@@ -220,12 +220,27 @@ struct RenderState {
         bool features_valid = false;                 // false: never computed, or stale (scene, camera, resolution, config changed)
         bool image_current = false;                  // the image buffers hold a path-tracing frame or pass rendered since the
                                                      // last such change (what ptmi_denoise may filter)
+        bool image_pass = false;                     // that image is an accumulation pass (samples per pixel: accum.d_counts)
         unsigned char* d_rgb8 = nullptr;             // denoised image, local row-major like d_image
         float* d_radiance = nullptr;
         float4* d_buf = nullptr;                     // 2 x n_local: the filter's ping-pong buffers
         bool denoised = false;                       // d_rgb8 / d_radiance hold a result
         double features_ms = 0.0, denoise_ms = 0.0;  // device time of the last feature pass / filter run
     } dn;
+    // The temporal accumulation's history (temporalAccumulate) and outputs; allocated at first use, freed with the other
+    // buffers.  Nothing here is read by a frame, a pass or ptmi_denoise.
+    struct Temporal {
+        TemporalHistory side[2];                     // the ping-pong: side[cur] is the history
+        int cur = 0;
+        bool valid = false;                          // false: the history is empty
+        float cam[12] = {};                          // the history's camera frame (ptmi_get_camera_frame) and resolution
+        int width = 0, height = 0;
+        int grid = 0;                                // g of the features the history holds
+        unsigned char* d_rgb8 = nullptr;             // the last step's result, local row-major like d_image
+        float* d_radiance = nullptr;
+        unsigned long long* d_stats = nullptr;       // accepted, rejected, missed of the last step
+        bool stepped = false;                        // d_rgb8 / d_radiance hold a result
+    } tp;
 
     void allocateBuffers();                         // application_state.h:91-123 (+ render_init)
     void updateResolution(int w, int h, const TileMap* tiling);   // application_state.h:125-129
@@ -235,6 +250,7 @@ struct RenderState {
     void allocateAccum();
     void freeAccum();
     void freeDenoise();
+    void freeTemporal();
     ~RenderState() { freeBuffers(); }
 };
 
@@ -327,6 +343,25 @@ void readFeatures(const ApplicationState& g_state, float* albedo, float* normal,
 void checkDenoiseParams(const DenoiseParams& p);     // throws ArgError for a parameter out of range
 void denoise(ApplicationState& g_state, const DenoiseParams& p);
 void readDenoised(const ApplicationState& g_state, unsigned char* rgb8, float* radiance);
+
+// Temporal accumulation with reprojection (include/ptmi.h: ptmi_temporal_accumulate).
+struct TemporalParams {
+    int max_history = 32;
+    float normal_min = 0.9f;
+    float sigma_position = 0.0f;                     // <= 0: 1 % of the scene's bounding-box diagonal
+    int feature_grid = 2;
+    float sigma_albedo = 0.1f;
+};
+struct TemporalStats {
+    uint64_t accepted = 0, rejected = 0, missed = 0;
+    double seconds = 0.0, features_ms = 0.0;
+};
+void temporalReset(ApplicationState& g_state);       // empties the history
+void checkTemporalParams(const TemporalParams& p);   // throws ArgError for a parameter out of range
+void temporalAccumulate(ApplicationState& g_state, const TemporalParams& p, TemporalStats* stats);
+void readTemporal(const ApplicationState& g_state, unsigned char* rgb8, float* radiance);
+void readHistoryCounts(const ApplicationState& g_state, float* counts);
+void denoiseTemporal(ApplicationState& g_state, const DenoiseParams& p);
 
 bool packBvhNodes(const std::vector<BVHNode>& bvh_nodes, int top_records, std::vector<float4>& g, int& n_pos, int& n_top, int& top_depth);
 

@@ -33,6 +33,8 @@ EXPORTS = [
     "ptmi_default_adaptive_params", "ptmi_accum_reset", "ptmi_accum_pass", "ptmi_read_sample_counts",
     "ptmi_default_denoise_params", "ptmi_check_denoise_params", "ptmi_render_features", "ptmi_read_features", "ptmi_denoise",
     "ptmi_read_denoised", "ptmi_denoise_timing",
+    "ptmi_default_temporal_params", "ptmi_check_temporal_params", "ptmi_temporal_reset", "ptmi_temporal_accumulate",
+    "ptmi_read_temporal", "ptmi_read_history_counts", "ptmi_denoise_temporal",
 ]
 
 
@@ -83,6 +85,16 @@ class PassStats(C.Structure):
 class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("color_floor", C.c_float), ("sigma_position", C.c_float),
                 ("normal_squarings", C.c_int), ("feature_grid", C.c_int), ("demodulate", C.c_int)]
+
+
+class TemporalParams(C.Structure):
+    _fields_ = [("max_history", C.c_int), ("normal_min", C.c_float), ("sigma_position", C.c_float), ("feature_grid", C.c_int),
+                ("sigma_albedo", C.c_float)]
+
+
+class TemporalStats(C.Structure):
+    _fields_ = [("accepted", C.c_uint64), ("rejected", C.c_uint64), ("missed", C.c_uint64), ("seconds", C.c_double),
+                ("features_ms", C.c_double)]
 
 
 class PtmiError(RuntimeError):
@@ -183,6 +195,13 @@ def lib():
         L.ptmi_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
         L.ptmi_read_denoised.argtypes = [vp, vp, vp]
         L.ptmi_denoise_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.ptmi_default_temporal_params.argtypes = [C.POINTER(TemporalParams)]; L.ptmi_default_temporal_params.restype = None
+        L.ptmi_check_temporal_params.argtypes = [C.POINTER(TemporalParams)]
+        L.ptmi_temporal_reset.argtypes = [vp]
+        L.ptmi_temporal_accumulate.argtypes = [vp, C.POINTER(TemporalParams), C.POINTER(TemporalStats)]
+        L.ptmi_read_temporal.argtypes = [vp, vp, vp]
+        L.ptmi_read_history_counts.argtypes = [vp, vp]
+        L.ptmi_denoise_temporal.argtypes = [vp, C.POINTER(DenoiseParams)]
         _lib = L
     return _lib
 
@@ -308,6 +327,17 @@ def default_denoise_params(**params):
     for k, v in params.items():
         if k not in dict(DenoiseParams._fields_):
             raise TypeError(f"unknown denoise parameter {k}")
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def default_temporal_params(**params):
+    """ptmi_default_temporal_params, with any field overridden by keyword (max_history, normal_min, sigma_position,
+    feature_grid, sigma_albedo)."""
+    p = TemporalParams(); lib().ptmi_default_temporal_params(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(TemporalParams._fields_):
+            raise TypeError(f"unknown temporal parameter {k}")
         setattr(p, k, type(getattr(p, k))(v))
     return p
 
@@ -542,6 +572,39 @@ class Renderer:
         a = C.c_double(); b = C.c_double()
         self._ck(self.L.ptmi_denoise_timing(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # --- temporal accumulation with reprojection (include/ptmi.h: ptmi_temporal_accumulate) ---
+    def temporal_accumulate(self, **params):
+        """Blends the image read_image returns into the history, reprojected from the history's view (keyword parameters:
+        fields of TemporalParams over the defaults); returns (rgb8, radiance, TemporalStats), the images shaped like
+        read_image's."""
+        p = default_temporal_params(**params)
+        st = TemporalStats()
+        self._ck(self.L.ptmi_temporal_accumulate(self.h, C.byref(p), C.byref(st)))
+        rgb, rad = self.read_temporal()
+        return rgb, rad, st
+
+    def temporal_reset(self):
+        self._ck(self.L.ptmi_temporal_reset(self.h))
+
+    def read_temporal(self):
+        n = len(self.local_rows())
+        rgb = np.zeros((n, self.width, 3), np.uint8); rad = np.zeros((n, self.width, 3), np.float32)
+        self._ck(self.L.ptmi_read_temporal(self.h, rgb.ctypes.data, rad.ctypes.data))
+        return rgb, rad
+
+    def history_counts(self):
+        """Samples behind each pixel's history, (local rows, width) float32 (0 while the history is empty)."""
+        counts = np.zeros((len(self.local_rows()), self.width), np.float32)
+        self._ck(self.L.ptmi_read_history_counts(self.h, counts.ctypes.data))
+        return counts
+
+    def denoise_temporal(self, **params):
+        """The a-trous filter over the history's colour, guided by the history's features (keyword parameters: fields of
+        DenoiseParams over the defaults); returns (rgb8, radiance) like denoise."""
+        p = default_denoise_params(**params)
+        self._ck(self.L.ptmi_denoise_temporal(self.h, C.byref(p)))
+        return self.read_denoised()
 
     def device_image(self):
         a = C.c_void_p(); b = C.c_void_p()

@@ -492,6 +492,83 @@ int  ptmi_read_denoised(const ptmi_ctx*, unsigned char* rgb8, float* radiance);
 /* device time (hipEvents) of the last feature pass and of the last filter run (feature pass excluded), in ms */
 int  ptmi_denoise_timing(const ptmi_ctx*, double* features_ms, double* denoise_ms);
 
+/* ---- temporal accumulation with reprojection (new in this implementation) ------------------------------------------------
+ * ptmi_temporal_accumulate blends the current image into a per-pixel HISTORY carried across views: the history of the last
+ * view is reprojected into the current one through the feature buffers, accepted where the geometry agrees, and mixed with
+ * the current image by sample count (the temporal stage of SVGF, Schied et al. 2017).  The BSDF is Lambertian and the scene
+ * static, so a surface point's outgoing radiance does not depend on the view: reprojected history is unbiased except for
+ * what the resampling blurs.  The output can then go through the a-trous filter (ptmi_denoise_temporal).
+ *
+ * INPUTS of a step: the radiance ptmi_read_image would return (it must be current, under ptmi_denoise's rule), its samples
+ * per pixel m (config.spp after a frame or a selected frame; after an accumulation pass the pixel's own count,
+ * ptmi_read_sample_counts), and the features for params->feature_grid (recomputed first if stale or of another grid, as
+ * ptmi_denoise does).  The HISTORY holds per pixel a colour c and a float sample count n, a copy of the features of the
+ * view it was last updated in (albedo, normal, position, hit fraction), and that view's camera frame (the 12 floats of
+ * ptmi_get_camera_frame) and resolution.
+ *
+ * THE STEP, per local pixel p, float32 in the order written (-ffp-contract=off, correctly rounded division);
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, cross(a, b) = (a.y*b.z - a.z*b.y, -(a.x*b.z - a.z*b.x), a.x*b.y - a.y*b.x):
+ *   0. STILL CAMERA: if the history is not empty and the camera frame and resolution are bit-identical to the history's,
+ *      the only tap is p itself with weight 1: h = c_hist(p), n_acc = n_hist(p) (pixels every feature ray missed included);
+ *      go to 5.  With max_history large a still camera gives the per-pixel running mean of its frames.
+ *   1. RESTART if the history is empty or p's hit fraction hf is 0: c = c_cur, n = m (as they are, no blend); go to 6.
+ *   2. x = position / hf, n_c = normal / hf, a_c = albedo / hf (per component, true division: the feature sums count hits only).
+ *   3. (o, llc, hor, ver) = the history's camera frame, o_cur = the current one's origin;  f = llc - o;  nrm = cross(hor, ver);
+ *      d = x - o;  den = dot(d, nrm);  fn = dot(f, nrm);  sp = dot(n_c, o - x);  sc = dot(n_c, o_cur - x);
+ *      unless ((fn > 0 and den > 0) or (fn < 0 and den < 0)) and ((sp > 0 and sc > 0) or (sp < 0 and sc < 0)): no taps
+ *      (restart, as 1) - x must lie in front of the previous camera, and both cameras on the same side of the surface (the
+ *      two sides of a wall are lit differently);
+ *      s = fn / den;  q = s * d - f (per component);  u = dot(q, hor) / dot(hor, hor);  v = dot(q, ver) / dot(ver, ver);
+ *      px = u * (float)width - 0.5f;  py = v * (float)height - 0.5f      (width, height: the history's resolution)
+ *   4. fx = px - floorf(px), fy = py - floorf(py); the taps, in this order, with weights
+ *         (x0, y0): (1 - fx) * (1 - fy);  (x0 + 1, y0): fx * (1 - fy);  (x0, y0 + 1): (1 - fx) * fy;  (x0 + 1, y0 + 1): fx * fy
+ *      with x0 = floorf(px), y0 = floorf(py) (global pixels, row 0 = bottom).  A tap t is skipped if it lies outside the image,
+ *      if its history hit fraction hf_t is 0, if dot(n_c, n_t) >= normal_min does not hold, if dot(e, e) <= sigma_x * sigma_x
+ *      does not hold, or if dot(ea, ea) <= sigma_albedo * sigma_albedo does not hold, where n_t = normal_t / hf_t,
+ *      e = x - position_t / hf_t, ea = a_c - albedo_t / hf_t (the history's features, per component; the albedo test keeps
+ *      an emitter (Kd = 0) and the surface around it from bleeding into each other through the resampling).  Over
+ *      the taps kept, in order, from +0:  W = W + w;  S.ch = S.ch + w * c_t.ch;  Sn = Sn + w * n_t.
+ *      If W > 0.01f:  h = S / W per channel, n_acc = Sn / W;  else restart as in 1.
+ *   5. n' = min(n_acc + m, (float)max_history * m);  alpha = m / n';  c = h + alpha * (c_cur - h) per channel;  n = n'.
+ *   6. radiance = c; rgb8 = the frame's tone map of c (resolve at k = 1, as ptmi_denoise); both to buffers of the step's own
+ *      (ptmi_read_temporal).  Then the history becomes the current view's: c, n, the current features, camera frame, resolution.
+ *   sigma_x = sigma_position, or for sigma_position <= 0: 0.01f * sqrtf((dx*dx + dy*dy) + dz*dz) with (dx, dy, dz) = max - min
+ *   of the root box of the scene's BVH (as ptmi_denoise computes its 2 %).
+ * Stats: accepted = pixels whose history was reused (0 or 5), missed = restarts of pixels with hf = 0, rejected = every other
+ * restart (an empty history included); they add up to the local pixel count.
+ *
+ * STATE.  ptmi_set_camera keeps the history.  Every other call that restarts an accumulation empties it: scene loads,
+ * ptmi_update_resolution, a successful ptmi_set_config, the radiosity setters and solver; so does ptmi_temporal_reset.  A
+ * step writes only buffers of its own: frames, passes, streams, the accumulation, the validity of the feature buffers and
+ * ptmi_denoise's results are what they would be without it (it may recompute the features, as ptmi_denoise does).
+ * ptmi_read_history_counts returns n per local pixel (0 everywhere while the history is empty).
+ * ptmi_denoise_temporal runs ptmi_denoise's filter, unchanged, over the history's colour guided by the history's features
+ * (its view's albedo, normal, position); the result is read with ptmi_read_denoised.
+ * PTMI_E_INVALID: a context tiled over more than one rank (taps cross ranks), the Radiosity integrator, no current image,
+ * parameters out of range or NaN; ptmi_denoise_temporal with an empty history or a feature_grid other than the history's. */
+typedef struct {
+    int   max_history;      /* 32; cap on n in units of the current input's m (alpha >= 1 / max_history); 1 .. 65536 */
+    float normal_min;       /* 0.9; a tap is accepted only if n_c . n_t >= normal_min; -1 .. 1 */
+    float sigma_position;   /* 0 (<= 0: 1 % of the scene's bounding-box diagonal); else 1e-6 .. 1e12 */
+    int   feature_grid;     /* 2; g of the feature pass used for reprojection, 1 .. 4 */
+    float sigma_albedo;     /* 0.1; a tap is accepted only if |a_c - a_t|^2 <= sigma_albedo^2; 0 .. 1e6 */
+} ptmi_temporal_params;
+typedef struct {
+    uint64_t accepted, rejected, missed;   /* local pixels: history reused / restarted / restarted, every feature ray missed */
+    double   seconds;                      /* device time of the step (the feature pass excluded) */
+    double   features_ms;                  /* device time of the feature pass the step ran (0 if none) */
+} ptmi_temporal_stats;
+void ptmi_default_temporal_params(ptmi_temporal_params*);
+/* the parameter check of ptmi_temporal_accumulate alone (no context, no device): 0 or PTMI_E_INVALID with the message */
+int  ptmi_check_temporal_params(const ptmi_temporal_params*);
+int  ptmi_temporal_reset(ptmi_ctx*);
+int  ptmi_temporal_accumulate(ptmi_ctx*, const ptmi_temporal_params* /* NULL: defaults */, ptmi_temporal_stats* /* may be NULL */);
+/* the last step's result, local row-major like ptmi_read_image; either may be NULL */
+int  ptmi_read_temporal(const ptmi_ctx*, unsigned char* rgb8, float* radiance);
+/* the history's sample count n per local pixel, local row-major */
+int  ptmi_read_history_counts(const ptmi_ctx*, float* counts);
+int  ptmi_denoise_temporal(ptmi_ctx*, const ptmi_denoise_params* /* NULL: defaults */);
+
 #ifdef __cplusplus
 }
 #endif

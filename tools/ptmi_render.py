@@ -9,6 +9,8 @@
   python tools/ptmi_render.py --scene ... --spp 8 --adaptive 0.02 --counts-png counts.png   (passes until every pixel stops)
   python tools/ptmi_render.py --scene ... --spp 8 --denoise --out denoised.png             (a-trous denoiser, 5 iterations)
   python tools/ptmi_render.py --scene ... --spp 8 --aov-png aov                              (aov_albedo/normal/depth.png)
+  python tools/ptmi_render.py --scene ... --spp 4 --orbit 16 --yaw-step 2 --temporal --denoise --out-prefix orbit_
+                               (16 views 2 degrees apart, each through the temporal accumulation and the denoiser)
 """
 import argparse
 import os
@@ -43,6 +45,10 @@ def main():
                     help="--out gets the image through the edge-avoiding a-trous denoiser (ITERATIONS, default 5)")
     ap.add_argument("--aov-png", default=None, metavar="PREFIX", help="write PREFIX_albedo.png, PREFIX_normal.png, PREFIX_depth.png "
                     "from the feature buffers of the denoiser")
+    ap.add_argument("--orbit", type=int, default=0, metavar="FRAMES", help="render FRAMES views, --yaw-step degrees apart, one frame each")
+    ap.add_argument("--yaw-step", type=float, default=2.0, metavar="DEG")
+    ap.add_argument("--temporal", action="store_true", help="with --orbit: every view through the temporal accumulation (reprojected history)")
+    ap.add_argument("--out-prefix", default=None, help="with --orbit: write every view to PREFIXnnn.png")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -67,6 +73,10 @@ def main():
     r.update_resolution(a.width, a.height)
     r.set_config(spp=a.spp, max_depth=a.max_depth, seed_base=a.seed_base, sampling_mode=a.sampling_mode,
                  mis_bsdf_fraction=a.mis_bsdf_fraction, integrator=1 if a.integrator == "radiosity" else 0)
+    if a.orbit > 0:
+        orbit(r, a, cam)
+        r.close()
+        return
     if a.adaptive is not None or a.passes > 0:
         prm = {}
         if a.adaptive is not None:
@@ -101,6 +111,33 @@ def main():
     if a.aov_png:
         write_aovs(r, a.aov_png)
     r.close()
+
+
+def orbit(r, a, cam):
+    """--orbit: one frame per view, the camera turned by --yaw-step between views; each view optionally through the temporal
+    accumulation (--temporal) and the denoiser (--denoise: over the history with --temporal, else over the frame)"""
+    prm = {} if a.denoise is None or a.denoise < 0 else {"iterations": a.denoise}
+    yaw0 = cam.yaw_deg
+    for i in range(a.orbit):
+        cam.yaw_deg = yaw0 + i * a.yaw_step
+        r.set_camera(cam)
+        st = r.render_frame()
+        line = f"view {i}: yaw {cam.yaw_deg:.2f}, frame {st.seconds * 1e3:.2f} ms"
+        if a.temporal:
+            rgb, _, ts = r.temporal_accumulate()
+            line += f", temporal {ts.seconds * 1e3:.3f} ms (accepted {ts.accepted}, rejected {ts.rejected}, missed {ts.missed})"
+            if a.denoise is not None:
+                rgb, _ = r.denoise_temporal(**prm)
+        elif a.denoise is not None:
+            rgb, _ = r.denoise(**prm)
+        else:
+            rgb, _ = r.read_image()
+        print(line)
+        if a.out_prefix:
+            ptmi.write_png(f"{a.out_prefix}{i:03d}.png", rgb)
+    if a.out:
+        ptmi.write_png(a.out, rgb)
+        print(f"wrote {a.out}")
 
 
 def write_aovs(r, prefix):
