@@ -772,6 +772,30 @@ int ptmi_debug_cosine_sample(ptmi_ctx* c, int n, const float* normals, const flo
     });
 }
 
+int ptmi_debug_guided_sample(ptmi_ctx* c, int op, int n, int n_recs, const float* recs, const int* rec_idx, const float* normals,
+                             const float* in3, const uint32_t* states, float* out, int* used) {
+    return guarded([&] {
+        need(c && normals && in3 && states && out && used, "NULL argument");
+        need(n > 0, "n must be positive");
+        need(op >= 0 && op <= 5, "op must be in [0, 5]");
+        const bool grid = op >= 1 && op <= 3;
+        if (grid) {
+            need(recs && rec_idx && n_recs > 0, "ops 1-3 need CDF records and their indices");
+            for (int i = 0; i < n; i++) need(rec_idx[i] >= 0 && rec_idx[i] < n_recs, "record index out of range");
+        }
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<float> d_r(grid ? (size_t)n_recs * kCdfDwords : 1), d_n(3 * (size_t)n), d_a(3 * (size_t)n), d_o(6 * (size_t)n);
+        DevBuf<int> d_i(grid ? (size_t)n : 1), d_u(n);
+        DevBuf<uint32_t> d_s(6 * (size_t)n);
+        if (grid) { d_r.upload(recs, (size_t)n_recs * kCdfDwords); d_i.upload(rec_idx, n); }
+        d_n.upload(normals, 3 * (size_t)n); d_a.upload(in3, 3 * (size_t)n); d_s.upload(states, 6 * (size_t)n);
+        launch_debug_guided(n, op, grid ? d_r.p : nullptr, grid ? d_i.p : nullptr, d_n.p, d_a.p, d_s.p, d_o.p, d_u.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d_o.download(out, 6 * (size_t)n); d_u.download(used, n);
+    });
+}
+
 // ---- progressive and adaptive accumulation ----
 void ptmi_default_adaptive_params(ptmi_adaptive_params* p) {
     if (!p) return;

@@ -447,10 +447,14 @@ __device__ __forceinline__ f3 grid_sample(const float* __restrict__ g, f3 normal
     out_pdf = grid_pdf_for_cell(g, theta_idx, phi_idx);
     return world;
 }
+// vector.h:198-203 to the sign of a zero: the reference's dot starts from `T sum = 0`, so three -0 products give +0, where
+// dot() (pt_vec.h) gives -0.  Only here does that sign reach a result - atan2f(+0, -0) is pi, atan2f(+0, +0) is 0 - e.g. for
+// dir == normal == (-0, 0, -1); everywhere else a dot only meets comparisons and fmaxf(., 0).
+__device__ __forceinline__ float dot_from_zero(f3 a, f3 b) { float s = 0.0f; s += a.x * b.x; s += a.y * b.y; s += a.z * b.z; return s; }
 __device__ __forceinline__ float grid_compute_pdf(const float* __restrict__ g, f3 dir, f3 normal) {   // grid.h:200-216, 299-310
     f3 tangent, bitangent;
     build_frame(normal, tangent, bitangent);
-    const float lx = dot(dir, tangent), ly = dot(dir, bitangent), lz = dot(dir, normal);
+    const float lx = dot_from_zero(dir, tangent), ly = dot_from_zero(dir, bitangent), lz = dot(dir, normal);
     const float theta = ptmi_acosf(fminf(fmaxf(lz, -1.0f), 1.0f));
     float phi = ptmi_atan2f(ly, lx);
     if (phi < 0.0f) phi = (float)((double)phi + (double)2.0f * PTMI_PI_D);
@@ -1727,6 +1731,59 @@ __global__ void ptmi_debug_cosine_k(int n, const float* normals, const float* u,
 void launch_debug_cosine(int n, const float* normals, const float* u, const float* v, float* out, hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL(ptmi_debug_cosine_k, dim3((n + 255) / 256), dim3(256), 0, s, n, normals, u, v, out);
+}
+
+// Guided sampling per call (test hook): the bounce kernels' own cosine_hemisphere, grid_sample, grid_compute_pdf, sample_mis,
+// mis_power_heuristic and resolve_pixel on n cases, each drawing from its own XORWOW state (6 words: v0..v4, d).  The tests
+// pass states whose next raw outputs are scripted words and d = 0, so used[i] = d / 362437 counts the draws a call made.
+//   op 0 cosine_hemisphere(normal, u, v), u and v drawn as integrator.h:63-64 draws them   -> out[0..2] direction
+//   op 1 grid_sample(record, normal)                                                      -> direction, out[3] pdf
+//   op 2 grid_compute_pdf(record, dir = in3, normal)                                      -> out[3] pdf
+//   op 3 sample_mis(record, normal, bsdf_prob = in3[0])                                   -> direction, out[3] weight
+//   op 4 mis_power_heuristic(in3[0], in3[1])                                              -> out[3]
+//   op 5 resolve_pixel(colour = in3, k = 1)                                               -> out[0..2] rgb8, out[3..5] radiance
+// recs: records of kCdfDwords words, rec_idx[i] picks case i's (ops 1-3 only; the host checks the indices).  out: 6 per case.
+__global__ __launch_bounds__(kBlock) void ptmi_debug_guided_k(int n, int op, const float* __restrict__ recs, const int* __restrict__ rec_idx,
+                                                              const float* __restrict__ normals, const float* __restrict__ in3,
+                                                              const uint32_t* __restrict__ states, float* __restrict__ out,
+                                                              int* __restrict__ used) {
+    fill_grid_solid_angles();
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* s = states + (size_t)i * 6;
+    Rng rng = {s[0], s[1], s[2], s[3], s[4], s[5]};
+    const f3 nrm = mk3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]);
+    const f3 a = mk3(in3[3 * i], in3[3 * i + 1], in3[3 * i + 2]);
+    const float* g = (op >= 1 && op <= 3) ? recs + (size_t)rec_idx[i] * kCdfDwords : nullptr;
+    float r[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    f3 dir = mk3(0.0f, 0.0f, 0.0f);
+    if (op == 0) {
+        const float u = rng_uniform(rng);
+        const float v = rng_uniform(rng);
+        dir = cosine_hemisphere(nrm, u, v);
+    } else if (op == 1) {
+        dir = grid_sample(g, nrm, rng, r[3]);
+    } else if (op == 2) {
+        r[3] = grid_compute_pdf(g, a, nrm);
+    } else if (op == 3) {
+        dir = sample_mis(g, nrm, rng, r[3], a.x);
+    } else if (op == 4) {
+        r[3] = mis_power_heuristic(a.x, a.y);
+    } else if (op == 5) {
+        unsigned char rgb[3];
+        resolve_pixel(make_float4(a.x, a.y, a.z, 0.0f), 1.0f, 0, rgb, &r[3]);
+        dir = mk3((float)rgb[0], (float)rgb[1], (float)rgb[2]);
+    }
+    r[0] = dir.x; r[1] = dir.y; r[2] = dir.z;
+    for (int c = 0; c < 6; c++) out[(size_t)i * 6 + c] = r[c];
+    used[i] = (int)(rng.d / 362437u);
+}
+
+void launch_debug_guided(int n, int op, const float* recs, const int* rec_idx, const float* normals, const float* in3,
+                         const uint32_t* states, float* out, int* used, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_guided_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n, op, recs, rec_idx, normals, in3,
+                       states, out, used);
 }
 
 }  // namespace ptmi

@@ -22,7 +22,7 @@ EXPORTS = [
     "ptmi_local_rows", "ptmi_local_row_map", "ptmi_render_frame", "ptmi_device_image", "ptmi_read_image",
     "ptmi_copy_image_device", "ptmi_set_radiosity_grids", "ptmi_get_precomputed_cdfs", "ptmi_set_radiosity",
            "ptmi_write_png", "ptmi_apply_grid_filter", "ptmi_use_raw_cdfs", "ptmi_get_filtered_pdfs", "ptmi_default_radiosity_params", "ptmi_run_radiosity_solver", "ptmi_get_radiosity_solution",
-    "ptmi_debug_intersect", "ptmi_debug_rng", "ptmi_debug_cosine_sample", "ptmi_debug_set_traversal", "ptmi_debug_rcp_check",
+    "ptmi_debug_intersect", "ptmi_debug_rng", "ptmi_debug_cosine_sample", "ptmi_debug_guided_sample", "ptmi_debug_set_traversal", "ptmi_debug_rcp_check",
     "ptmi_host_scene_load", "ptmi_host_scene_from_arrays", "ptmi_host_scene_free", "ptmi_host_scene_info",
     "ptmi_host_scene_get_prims", "ptmi_host_scene_get_bvh", "ptmi_host_camera_frame", "ptmi_host_local_row_map",
     "ptmi_host_cdf_record_layout", "ptmi_host_image",
@@ -151,6 +151,7 @@ def lib():
         L.ptmi_debug_intersect.argtypes = [vp, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]
         L.ptmi_debug_rng.argtypes = [vp, C.c_uint64, C.c_int, vp, C.c_int, vp]
         L.ptmi_debug_cosine_sample.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.ptmi_debug_guided_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
         L.ptmi_debug_set_traversal.argtypes = [vp, C.c_int, C.c_int, ip]
         L.ptmi_debug_set_solver_walk.argtypes = [vp, C.c_int, C.c_int]
         L.ptmi_debug_get_traversal.argtypes = [vp, ip]
@@ -758,6 +759,25 @@ class Renderer:
         out = np.zeros_like(normals)
         self._ck(self.L.ptmi_debug_cosine_sample(self.h, len(u), normals.ctypes.data, u.ctypes.data, v.ctypes.data, out.ctypes.data))
         return out
+
+    GUIDED_COSINE, GUIDED_GRID_SAMPLE, GUIDED_GRID_PDF, GUIDED_MIS, GUIDED_MIS_WEIGHT, GUIDED_TONEMAP = range(6)
+
+    def debug_guided_sample(self, op, normals, in3, states, recs=None, rec_idx=None):
+        """ptmi_debug_guided_sample: the bounce kernels' guided-sampling functions on n cases.  normals, in3: (n, 3); states:
+        (n, 6) uint32 XORWOW states; recs: (m, 530) float32 CDF records and rec_idx: (n,) for the grid ops.
+        Returns out (n, 6) float32 and used (n,) int32, the draws each call made."""
+        normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3); n = len(normals)
+        in3 = np.ascontiguousarray(in3, np.float32).reshape(n, 3)
+        states = np.ascontiguousarray(states, np.uint32).reshape(n, 6)
+        out = np.zeros((n, 6), np.float32); used = np.zeros(n, np.int32)
+        if recs is not None:
+            recs = np.ascontiguousarray(recs, np.float32).reshape(-1, 530)
+            rec_idx = np.ascontiguousarray(rec_idx, np.int32).reshape(n)
+        self._ck(self.L.ptmi_debug_guided_sample(self.h, int(op), n, 0 if recs is None else len(recs),
+                                                 None if recs is None else recs.ctypes.data,
+                                                 None if recs is None else rec_idx.ctypes.data, normals.ctypes.data,
+                                                 in3.ctypes.data, states.ctypes.data, out.ctypes.data, used.ctypes.data))
+        return out, used
 
 
 def write_png(path, rgb8):

@@ -10,13 +10,13 @@
  *     is PINNED: tests/test_oracle_vs_ref.py compares this file bit-for-bit
  *     with the reference's own headers compiled from /root/reference by
  *     oracle/Makefile into oracle/_ref/ (g++, no stand-in headers).
- *   - OBJ/MTL loader, integrator(), sampleCosineHemisphere, the render kernel's
- *     tone-map and the cuRAND XORWOW generator cannot be compiled here
- *     (file_manager.h / grid.h include <cuda_runtime.h>, <curand_kernel.h>,
- *     absent from this image; no stand-ins are written).  They are restated
- *     below from the source text and pinned only by the known answers the
- *     survey recorded from the reference (primitive counts, BVH
- *     dump, camera-ray hits).  RNG parity with real cuRAND: UNPINNED.
+ *   - the OBJ/MTL loader (ref_obj_harness.cpp), integrator(), sampleCosineHemisphere,
+ *     Grid::sample / computePDF, MIS, the render kernel's tone-map and
+ *     render_radiosity (ref_integrator_harness.cpp, with a stand-in for the closed
+ *     cuRAND API and the numerics contract's libm) are PINNED the same way
+ *     (tests/test_integrator_vs_ref.py).  RNG parity with real cuRAND: the XORWOW
+ *     step and skip-ahead against rocRAND; the seed scramble and the float
+ *     mapping UNPINNED.
  *
  * All file:line citations are relative to /root/reference/include/.
  * Compile with -ffp-contract=off: every float expression below is written in
@@ -927,11 +927,12 @@ static float mis_power_heuristic(float pdf_a, float pdf_b) {   /* integrator.h:9
     const float a2 = pdf_a * pdf_a, b2 = pdf_b * pdf_b;
     return a2 / (a2 + b2);
 }
-static v3 sample_mis(const ocdf* g, v3 normal, uint32_t rng[6], float* weight, float bsdf_prob) {   /* integrator.h:112-167 */
+static v3 sample_mis(const ocdf* g, v3 normal, uint32_t rng[6], float* weight, float bsdf_prob, int* used_bsdf) {   /* integrator.h:112-167 */
     const float BSDF_PROB = fmaxf(fminf(bsdf_prob, 0.99f), 0.01f);
     const float GRID_PROB = 1.0f - BSDF_PROB;
     const float xi = rng_uniform(rng);
     v3 dir; float pdf_grid, pdf_bsdf, mis_w;
+    *used_bsdf = xi < BSDF_PROB;
     if (xi < BSDF_PROB) {
         const float u = rng_uniform(rng), v = rng_uniform(rng);
         dir = sample_cosine_hemisphere_uv(normal, u, v);
@@ -951,6 +952,57 @@ static v3 sample_mis(const ocdf* g, v3 normal, uint32_t rng[6], float* weight, f
         } else *weight = 0.0f;
     }
     return dir;
+}
+
+/* ------------------------------------------------------------------------ */
+/* per-call hooks over scripted raw words (tests/test_integrator_vs_ref.py)   */
+/* ------------------------------------------------------------------------ */
+/* A XORWOW state whose next n <= 5 raw outputs are words[0..n) (the rest 0), with d = 0.  The i-th draw (i = 1..5) returns
+ * x[4+i] + i * 362437 where x[k+5] = f(x[k+4]) ^ g(x[k]), f(x) = x ^ (x << 4), g(x) = t ^ (t << 1), t = x ^ (x >> 2), and
+ * x[0..4] = v0..v4.  So x[5..9] are given, v4 = g^-1(x[9] ^ f(x[8])) and then vk = g^-1(x[5+k] ^ f(x[4+k])), k = 0..3. */
+static uint32_t inv_xor_shl(uint32_t y, int k) { uint32_t x = y; for (int s = k; s < 32; s += k) x ^= y << s; return x; }
+static uint32_t inv_xor_shr(uint32_t y, int k) { uint32_t x = y; for (int s = k; s < 32; s += k) x ^= y >> s; return x; }
+static uint32_t xw_f(uint32_t x) { return x ^ (x << 4); }
+static uint32_t xw_g_inv(uint32_t y) { return inv_xor_shr(inv_xor_shl(y, 1), 2); }
+void po_xorwow_script(const uint32_t* words, int n, uint32_t st[6]) {
+    uint32_t x[10] = {0};
+    for (int i = 0; i < 5; i++) x[5 + i] = (i < n ? words[i] : 0u) - (uint32_t)(i + 1) * 362437u;
+    x[4] = xw_g_inv(x[9] ^ xw_f(x[8]));
+    for (int k = 0; k < 4; k++) x[k] = xw_g_inv(x[5 + k] ^ xw_f(x[4 + k]));
+    for (int k = 0; k < 5; k++) st[k] = x[k];
+    st[5] = 0u;
+}
+static void scripted_state(const uint32_t* words, int n, uint32_t st[6]) { po_xorwow_script(words, n > 5 ? 5 : n, st); }
+/* draws made so far from a state po_xorwow_script built (d counts them) */
+static int draws_since_script(const uint32_t st[6]) { return (int)(st[5] / 362437u); }
+
+float po_word_to_uniform(uint32_t x) { uint32_t st[6]; scripted_state(&x, 1, st); return rng_uniform(st); }
+int po_sample_cosine_words(const float n[3], const uint32_t* words, int n_words, float out[3]) {
+    uint32_t st[6]; scripted_state(words, n_words, st);
+    const float u = rng_uniform(st), v = rng_uniform(st);                 /* integrator.h:63-64 */
+    v3 d = sample_cosine_hemisphere_uv(V(n[0], n[1], n[2]), u, v);
+    for (int k = 0; k < 3; k++) out[k] = d.e[k];
+    return draws_since_script(st);
+}
+float po_mis_power_heuristic(float a, float b) { return mis_power_heuristic(a, b); }
+/* rec: one PrecomputedCDF record (530 words, po_scene_get_cdfs) */
+int po_grid_sample(const float* rec, const float n[3], const uint32_t* words, int n_words, float out[3], float* out_pdf) {
+    uint32_t st[6]; scripted_state(words, n_words, st);
+    v3 d = grid_sample((const ocdf*)rec, V(n[0], n[1], n[2]), st, out_pdf);
+    for (int k = 0; k < 3; k++) out[k] = d.e[k];
+    return draws_since_script(st);
+}
+float po_grid_pdf(const float* rec, const float dir[3], const float n[3]) {
+    return grid_compute_pdf((const ocdf*)rec, V(dir[0], dir[1], dir[2]), V(n[0], n[1], n[2]));
+}
+int po_sample_mis(const float* rec, const float n[3], float bsdf_prob, const uint32_t* words, int n_words, float out[3],
+                  float* out_weight, int* out_used_bsdf) {
+    uint32_t st[6]; scripted_state(words, n_words, st);
+    float w = 0.0f;
+    v3 d = sample_mis((const ocdf*)rec, V(n[0], n[1], n[2]), st, &w, bsdf_prob, out_used_bsdf);
+    for (int k = 0; k < 3; k++) out[k] = d.e[k];
+    *out_weight = w;
+    return draws_since_script(st);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -986,8 +1038,8 @@ static void integrator(const po_scene* sc, ray_t ray, v3* L, int max_depth, uint
          * branch below falls back to cosine sampling (:258-261) with the same two draws as the BSDF mode */
         const ocdf* g = (mode != SAMPLING_BSDF && sc->cdfs && sc->cdfs[prim].is_valid) ? &sc->cdfs[prim] : NULL;
         if (g && mode == SAMPLING_MIS) {                                         /* :238-241 */
-            float weight = 1.0f;
-            next_dir = sample_mis(g, shading_normal, rng, &weight, sc->mis_bsdf_fraction);
+            float weight = 1.0f; int used_bsdf;
+            next_dir = sample_mis(g, shading_normal, rng, &weight, sc->mis_bsdf_fraction, &used_bsdf);
             throughput = V(throughput.e[0] * weight, throughput.e[1] * weight, throughput.e[2] * weight);
         } else if (g) {                                                          /* :242-257 pure grid sampling */
             float grid_pdf;
@@ -1405,6 +1457,22 @@ int po_scene_apply_grid_filter(po_scene* s, int use_bilateral, float sigma_spati
     return 0;
 }
 
+/* render's tone-map of color / spp (integrator.h:395-407): Reinhard, gamma 1/2.2, 8 bit */
+static void tonemap(v3 color, unsigned char* out) {
+    v3 tm = vdivv(color, vadd(color, V(1.0f, 1.0f, 1.0f)));   /* :396 */
+    const float gamma = 1.0f / 2.2f;
+    for (int c = 0; c < 3; c++) {
+        float g = ptmi_powf(tm.e[c], gamma);
+        out[c] = (unsigned char)(255.99f * fminf(g, 1.0f));
+    }
+}
+void po_tonemap(const float color[3], unsigned char out[3]) { tonemap(V(color[0], color[1], color[2]), out); }
+/* color /= float(spp) (vector.h:90-94: a multiply by the reciprocal taken in binary64) */
+void po_average(const float sum[3], int spp, float out[3]) {
+    const float k = recip_via_double((float)spp);
+    for (int c = 0; c < 3; c++) out[c] = sum[c] * k;
+}
+
 static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 
 int po_render(const po_scene* sc, const po_camera* cam, int width, int height, int spp, int max_depth, int sampling_mode,
@@ -1457,14 +1525,7 @@ int po_render(const po_scene* sc, const po_camera* cam, int width, int height, i
                 color = V(color.e[0] * k, color.e[1] * k, color.e[2] * k);
             }
             if (out_radiance) for (int c = 0; c < 3; c++) out_radiance[(size_t)pixel_index * 3 + c] = color.e[c];
-            if (out_rgb8) {
-                v3 tm = vdivv(color, vadd(color, V(1.0f, 1.0f, 1.0f)));   /* :396 */
-                const float gamma = 1.0f / 2.2f;
-                for (int c = 0; c < 3; c++) {
-                    float g = ptmi_powf(tm.e[c], gamma);
-                    out_rgb8[(size_t)pixel_index * 3 + c] = (unsigned char)(255.99f * fminf(g, 1.0f));
-                }
-            }
+            if (out_rgb8) tonemap(color, &out_rgb8[(size_t)pixel_index * 3]);
         }
         c_rays += cn.rays; c_nodes += cn.node_visits; c_tests += cn.prim_tests; c_hits += cn.hits;
     }

@@ -101,6 +101,20 @@ float po_acosf(float x);
 float po_atan2f(float y, float x);
 void po_sample_cosine_hemisphere(const float n[3], float u, float v, float out[3]);
 
+/* per-call hooks over scripted raw 32-bit words (tests/test_integrator_vs_ref.py): each draws from a XORWOW state whose
+ * next raw outputs are words[0..n_words) (n_words <= 5) and returns the number of draws it made.  rec: one PrecomputedCDF
+ * record, 530 words as po_scene_get_cdfs writes them. */
+void po_xorwow_script(const uint32_t* words, int n_words, uint32_t state[6]);   /* the state itself (d = 0) */
+float po_word_to_uniform(uint32_t x);                                           /* curand_uniform of one raw word */
+int po_sample_cosine_words(const float n[3], const uint32_t* words, int n_words, float out[3]);
+float po_mis_power_heuristic(float pdf_a, float pdf_b);
+int po_grid_sample(const float* rec, const float n[3], const uint32_t* words, int n_words, float out[3], float* out_pdf);
+float po_grid_pdf(const float* rec, const float dir[3], const float n[3]);
+int po_sample_mis(const float* rec, const float n[3], float bsdf_prob, const uint32_t* words, int n_words, float out[3],
+                  float* out_weight, int* out_used_bsdf);
+void po_tonemap(const float color[3], unsigned char out[3]);   /* render's tone-map of color / spp */
+void po_average(const float sum[3], int spp, float out[3]);    /* color /= float(spp) */
+
 /* intersection ------------------------------------------------------------ */
 void po_intersect(const po_scene*, const float o[3], const float d[3], float t_min, float t_max,
                   int use_bvh, po_hit* out);

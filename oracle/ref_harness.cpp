@@ -13,10 +13,10 @@
 //
 // utils/file_manager.h (loadOBJ / loadMTL) is compiled too, in ref_obj_harness.cpp: it needs <cuda_runtime.h>, and
 // NVIDIA's genuine header ships in this image's Triton wheel (oracle/Makefile finds it).
-// What is NOT compilable here: rendering/grid.h (hence integrator.h) and rendering/form_factors.h include
-// <curand_kernel.h> (closed NVIDIA library, nowhere in the image); rendering/grid_filter.h launches kernels with
-// <<< >>> from host wrappers (no g++ can parse it); application_state.h includes GL/glew.h and GLFW.
-// Those are restated in ptmi_oracle.c only.
+// rendering/grid.h and integrator.h are compiled in ref_integrator_harness.cpp, against NVIDIA's genuine <cuda_runtime.h> and
+// a project-written stand-in for the closed <curand_kernel.h> API (oracle/shim/).  What is NOT compilable here:
+// rendering/form_factors.h includes rendering/grid_filter.h, which launches kernels with <<< >>> from host wrappers (no
+// g++ can parse it); application_state.h includes GL/glew.h and GLFW.  Those are restated in ptmi_oracle.c only.
 #include <hip/amd_detail/host_defines.h>
 
 #include <cfloat>

@@ -2,14 +2,15 @@
 
 Provenance: the oracle (oracle/ptmi_oracle.c) is a restatement whose geometry layer is checked bit-for-bit
 against the reference's own headers compiled from /root/reference (tests/test_oracle_vs_ref.py) and whose
-loader/BVH/camera are checked against the known answers in SURVEY.md §8c; the integrator loop and the
-cuRAND XORWOW restatement are NOT pinned by any reference execution (the reference ships no tests or
-fixtures for this path and its integrator.h cannot be compiled here).  These files therefore pin the
-ORACLE (regression) and give the GPU tests a fixture that does not need the oracle library.
+loader/BVH/camera are checked against the known answers in SURVEY.md §8c; the integrator, the guided sampling and
+the tone-map are checked against the reference's own integrator.h / grid.h compiled with a stand-in for the closed
+cuRAND API (tests/test_integrator_vs_ref.py); cuRAND's seed scramble and float mapping stay unpinned.  These files
+pin the ORACLE (regression) and give the GPU tests a fixture that does not need the oracle library.
 
 Run from the repo root:  python tests/golden/make_golden.py
-With --ref-only, only what the compiled reference (oracle/_ref) answers to tests/test_oracle_vs_ref.py and
-tests/test_pbrt_loader.py: golden/ref_geometry.npz and golden/ref_pbrt.npz.
+With --ref-only, only what the compiled reference (oracle/_ref) answers to tests/test_oracle_vs_ref.py,
+tests/test_pbrt_loader.py and tests/test_integrator_vs_ref.py: golden/ref_geometry.npz, golden/ref_pbrt.npz and
+golden/ref_integrator.npz.
 """
 import json
 import os
@@ -24,7 +25,8 @@ from oracle_binding import OracleScene, SCENES, default_camera  # noqa: E402
 if "--ref-only" in sys.argv:
     import subprocess
     sys.exit(subprocess.call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(os.path.dirname(HERE), "test_oracle_vs_ref.py"),
-                             os.path.join(os.path.dirname(HERE), "test_pbrt_loader.py")],
+                             os.path.join(os.path.dirname(HERE), "test_pbrt_loader.py"),
+                             os.path.join(os.path.dirname(HERE), "test_integrator_vs_ref.py")],
                              env=dict(os.environ, PTMI_RECORD_REF_ANSWERS="1")))
 
 CASES = [  # scene, subdivision, convert_quads, W, H, spp, max_depth

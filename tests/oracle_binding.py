@@ -116,6 +116,17 @@ def oracle_lib():
                                 C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.po_radiosity_solve.restype = C.c_int
         L.po_radiosity_solve.argtypes = [C.c_void_p, C.POINTER(RadiosityParams), C.c_int] + [C.c_void_p] * 6
+        vp, f, u32 = C.c_void_p, C.c_float, C.c_uint32
+        L.po_xorwow_script.argtypes = [vp, C.c_int, vp]
+        L.po_xorwow_next_raw.argtypes = [vp, C.c_int, vp]
+        L.po_word_to_uniform.restype = f; L.po_word_to_uniform.argtypes = [u32]
+        L.po_sample_cosine_words.argtypes = [vp, vp, C.c_int, vp]
+        L.po_mis_power_heuristic.restype = f; L.po_mis_power_heuristic.argtypes = [f, f]
+        L.po_grid_sample.argtypes = [vp, vp, vp, C.c_int, vp, vp]
+        L.po_grid_pdf.restype = f; L.po_grid_pdf.argtypes = [vp, vp, vp]
+        L.po_sample_mis.argtypes = [vp, vp, f, vp, C.c_int, vp, vp, vp]
+        L.po_tonemap.argtypes = [vp, vp]; L.po_tonemap.restype = None
+        L.po_average.argtypes = [vp, C.c_int, vp]; L.po_average.restype = None
         L.po_scene_apply_grid_filter.restype = C.c_int
         L.po_scene_apply_grid_filter.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         L.po_form_factor_rows.restype = C.c_int
@@ -480,3 +491,72 @@ def recorded_reference(golden, live):
     yield r
     if record:
         np.savez_compressed(golden, **r.fresh)
+
+
+# ---- the reference's integrator.h + grid.h, compiled (oracle/_ref/libptmi_ref_integrator.so; oracle/ref_integrator_harness.cpp) ----
+REF_INT_SO = os.path.join(os.path.dirname(REF_SO), "libptmi_ref_integrator.so")
+_ref_int = None
+
+
+def ref_int_available():
+    return os.path.exists(REF_INT_SO)
+
+
+def ref_int_lib():
+    global _ref_int
+    if _ref_int is None:
+        L = C.CDLL(REF_INT_SO)
+        vp, f, i = C.c_void_p, C.c_float, C.c_int
+        L.ref_sample_cosine_hemisphere.argtypes = [vp, vp, i, vp]
+        L.ref_mis_power_heuristic.restype = f; L.ref_mis_power_heuristic.argtypes = [f, f]
+        L.ref_grid_sample.argtypes = [vp, vp, vp, i, vp, vp, vp]
+        L.ref_grid_pdf.restype = f; L.ref_grid_pdf.argtypes = [vp, vp, vp]
+        L.ref_sample_mis.argtypes = [vp, vp, f, vp, i, vp, vp, vp]
+        L.ref_int_scene_create.restype = vp; L.ref_int_scene_create.argtypes = [i] + [vp] * 8 + [f]
+        L.ref_int_scene_free.argtypes = [vp]; L.ref_int_scene_free.restype = None
+        L.ref_render.argtypes = [vp, vp, i, i, i, i, i, vp]
+        L.ref_render_radiosity.argtypes = [vp, vp, i, i, i, i, vp]
+        L.ref_radiance.argtypes = [vp, vp, i, i, i, i, i, i, vp]
+        _ref_int = L
+    return _ref_int
+
+
+def _camera13(cam):
+    return np.array(list(cam.origin) + list(cam.lookat) + list(cam.vup) + [cam.vfov_deg, cam.yaw_deg, cam.pitch_deg, float(cam.orbit)],
+                    np.float32)
+
+
+def _opt(a, dtype=np.float32):
+    return None if a is None else np.ascontiguousarray(a, dtype)
+
+
+class RefIntegratorScene:
+    """The reference's Scene (BVHBuilder) with precomputed_cdfs = `cdfs` (n x 530 words, the oracle's records) or, without
+    them, the primitives' raw radiosity grids (initFromRadiosity); per-primitive radiosity for render_radiosity."""
+
+    def __init__(self, types, verts, normal, bsdf, Le, radiosity=None, cdfs=None, rad_grids=None, mis_fraction=0.5):
+        self.L = ref_int_lib()
+        self.keep = [np.ascontiguousarray(types, np.int32)] + [np.ascontiguousarray(a, np.float32) for a in (verts, normal, bsdf, Le)] + \
+                    [_opt(radiosity), _opt(cdfs), _opt(rad_grids)]
+        ptrs = [None if a is None else a.ctypes.data for a in self.keep]
+        self.h = self.L.ref_int_scene_create(len(self.keep[0]), *ptrs, float(mis_fraction))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.ref_int_scene_free(self.h)
+            self.h = None
+
+    def render(self, cam, width, height, spp, mode=0, n_threads=0):
+        rgb = np.zeros((height, width, 3), np.uint8)
+        self.L.ref_render(self.h, _camera13(cam).ctypes.data, width, height, spp, int(mode), n_threads, rgb.ctypes.data)
+        return rgb
+
+    def render_radiosity(self, cam, width, height, spp, n_threads=0):
+        rgb = np.zeros((height, width, 3), np.uint8)
+        self.L.ref_render_radiosity(self.h, _camera13(cam).ctypes.data, width, height, spp, n_threads, rgb.ctypes.data)
+        return rgb
+
+    def radiance(self, cam, width, height, spp, max_depth=5, mode=0, n_threads=0):
+        rad = np.zeros((height, width, 3), np.float32)
+        self.L.ref_radiance(self.h, _camera13(cam).ctypes.data, width, height, spp, max_depth, int(mode), n_threads, rad.ctypes.data)
+        return rad
