@@ -74,7 +74,7 @@ void ptmi_default_config(ptmi_config* c) {
     const AppConfig d;
     c->spp = d.spp; c->max_depth = d.max_depth; c->sampling_mode = (int)d.sampling_mode; c->seed_base = d.seed_base;
     c->segments_per_launch = 0; c->collect_stats = 0; c->wave_tiles = 0; c->streams = 0; c->mis_bsdf_fraction = d.mis_bsdf_fraction; c->integrator = 0;
-    c->download_image = 0; c->fast_tree = 0;
+    c->download_image = 0; c->fast_tree = 0; c->next_event = 0;
 }
 void ptmi_default_tiling(ptmi_tiling* t) { t->n_ranks = 1; t->rank = 0; t->row_block = 8; }
 
@@ -197,6 +197,17 @@ int ptmi_host_scene_get_prims(const ptmi_host_scene* s, int* type, float* verts,
 }
 int ptmi_host_scene_get_bvh(const ptmi_host_scene* s, float* bmin, float* bmax, int* left, int* right, int* count, int* indices) {
     return guarded([&] { need(s != nullptr, "scene is NULL"); scene_get_bvh(s->scene, bmin, bmax, left, right, count, indices); });
+}
+int ptmi_host_emitters(const ptmi_host_scene* s, int* n_emitters, int* prim, float* cdf, float* pdf_area) {
+    return guarded([&] {
+        need(s != nullptr, "scene is NULL");
+        const SceneState& sc = s->scene;
+        const size_t ne = sc.h_emit_prim.size();
+        if (n_emitters) *n_emitters = (int)ne;
+        if (prim) std::memcpy(prim, sc.h_emit_prim.data(), ne * sizeof(int));
+        if (cdf) std::memcpy(cdf, sc.h_emit_cdf.data(), ne * sizeof(float));
+        if (pdf_area) std::memcpy(pdf_area, sc.h_pdf_area.data(), sc.h_pdf_area.size() * sizeof(float));
+    });
 }
 int ptmi_write_png(const char* path, int width, int height, const unsigned char* rgb8) {
     return guarded([&] {
@@ -394,6 +405,12 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
         need(cfg->integrator == 0 || cfg->integrator == 1, "integrator must be 0 (PathTracing) or 1 (Radiosity)");
         need(cfg->segments_per_launch >= 0, "segments_per_launch must be >= 0");
         need(cfg->streams >= 0 && cfg->streams <= RenderState::kMaxChunks, "streams must be 0..4");
+        need(cfg->next_event == 0 || cfg->next_event == 1, "next_event must be 0 or 1");
+        if (cfg->next_event) {
+            need(cfg->integrator == 0, "next_event needs integrator 0 (PathTracing): the Radiosity view traces first hits only");
+            need(cfg->sampling_mode == 0, "next_event needs sampling_mode 0 (BSDF): MIS against the guided modes' grid pdf is not implemented");
+            need(cfg->fast_tree == 0, "next_event needs fast_tree 0: NEE frames always trace the reference's hits");
+        }
         AppConfig& a = c->app.config;                    // every check is above this line: a rejected config changes nothing
         a.spp = cfg->spp; a.max_depth = cfg->max_depth; a.sampling_mode = (SamplingMode)cfg->sampling_mode;
         a.mis_bsdf_fraction = cfg->mis_bsdf_fraction;
@@ -403,6 +420,7 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
         c->app.render.want_chunks = cfg->streams;
         c->app.render.download_image = cfg->download_image != 0;
         a.fast_tree = cfg->fast_tree != 0;
+        a.next_event = cfg->next_event != 0;
         viewChanged(c->app);
     });
 }

@@ -17,14 +17,13 @@
 //                           one workgroup per primitive, one thread per grid cell, contributions added in ascending j
 #include "pt_device.h"
 #include "wide_walk.h"
+#include "prim_sample.h"
 
 namespace ptmi {
 
 namespace {
 
 constexpr int kQueueCap = 2 * kBlock;
-
-struct Geom { f3 v0, v1, v2, v3; int type; float area, ratio; f3 normal, centroid; };
 
 __device__ __forceinline__ Geom load_geom(const float4* __restrict__ geo, int p) {
     const float4 a = geo[6 * p], b = geo[6 * p + 1], c = geo[6 * p + 2], d = geo[6 * p + 3], e = geo[6 * p + 4], f = geo[6 * p + 5];
@@ -33,22 +32,6 @@ __device__ __forceinline__ Geom load_geom(const float4* __restrict__ geo, int p)
     g.type = __float_as_int(a.w); g.area = b.w; g.ratio = c.w;
     g.normal = xyz(e); g.centroid = xyz(f);
     return g;
-}
-
-// primitive.h:153-157
-__device__ __forceinline__ f3 bary_point(f3 a, f3 b, f3 c, float r1, float r2) {
-    const float sqrt_r1 = sqrt_rn(r1);
-    const float u = 1.0f - sqrt_r1;
-    const float v = sqrt_r1 * (1.0f - r2);
-    const float w = sqrt_r1 * r2;
-    return u * a + v * b + w * c;
-}
-// Primitive::sampleUniform (primitive.h:150-191); the quad's area ratio comes precomputed from the host
-template <bool HAS_QUADS>
-__device__ __forceinline__ f3 sample_uniform(const Geom& g, float r1, float r2) {
-    if (!HAS_QUADS || g.type == 0) return bary_point(g.v0, g.v1, g.v2, r1, r2);      // triangle-only scenes: v3 / ratio / type stay out of registers
-    if (r1 < g.ratio) return bary_point(g.v0, g.v1, g.v3, r1 / g.ratio, r2);                     // (v00, v10, v01)
-    return bary_point(g.v1, g.v2, g.v3, (r1 - g.ratio) / (1.0f - g.ratio), r2);                  // (v10, v11, v01)
 }
 
 // direction_to_grid_indices_local (form_factors.h:107-130): theta over [0, pi] -> 16 rows, phi over [0, 2 pi) -> 16 columns

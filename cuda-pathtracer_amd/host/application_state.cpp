@@ -89,6 +89,11 @@ void SceneState::cleanup() {
     if (d_mats) (void)hipFree(d_mats);
     if (d_precomputed_cdfs) (void)hipFree(d_precomputed_cdfs);
     if (d_radiosity) (void)hipFree(d_radiosity);
+    if (d_emit_rec) (void)hipFree(d_emit_rec);
+    if (d_emit_cdf) (void)hipFree(d_emit_cdf);
+    if (d_pdf_area) (void)hipFree(d_pdf_area);
+    d_emit_rec = nullptr; d_emit_cdf = d_pdf_area = nullptr; d_emitters = EmitterTable();
+    h_emit_prim.clear(); h_emit_cdf.clear(); h_pdf_area.clear();
     freePacked();
     freeFast();
     fast_declined = false;
@@ -127,6 +132,7 @@ void SceneState::loadSceneHost(const std::string& filename, int subdivision_coun
     h_primitives.swap(prims);
     scene_file = filename;
     buildBVH();
+    buildEmitters();
 }
 
 void SceneState::loadSceneArraysHost(std::vector<Primitive> prims) {
@@ -135,6 +141,29 @@ void SceneState::loadSceneArraysHost(std::vector<Primitive> prims) {
     h_primitives.swap(prims);
     scene_file = "<arrays>";
     buildBVH();
+    buildEmitters();
+}
+
+// The emitter table of next-event estimation, float32 in the order of include/ptmi.h: w = area * ((Le.x + Le.y) + Le.z), the
+// emitters are the primitives with w > 0 in load order, c_j their running sum from +0, pdf_area = (w / total) / area
+void SceneState::buildEmitters() {
+    const int n = (int)h_primitives.size();
+    h_emit_prim.clear(); h_emit_cdf.clear();
+    h_pdf_area.assign((size_t)n, 0.0f);
+    std::vector<float> w_of;
+    float c = 0.0f;
+    for (int i = 0; i < n; i++) {
+        const Primitive& p = h_primitives[i];
+        const float w = p.area() * ((p.Le.x + p.Le.y) + p.Le.z);
+        if (!(w > 0.0f)) continue;
+        c = c + w;
+        h_emit_prim.push_back(i); h_emit_cdf.push_back(c); w_of.push_back(w);
+    }
+    const float total = h_emit_cdf.empty() ? 0.0f : h_emit_cdf.back();
+    for (size_t j = 0; j < h_emit_prim.size(); j++) {
+        const int i = h_emit_prim[j];
+        h_pdf_area[i] = (w_of[j] / total) / h_primitives[i].area();
+    }
 }
 
 void SceneState::buildBVH() {
@@ -193,6 +222,37 @@ void SceneState::upload() {
     PTMI_HIP(hipMemcpy(d_nodes, nodes.data(), nodes.size() * sizeof(float4), hipMemcpyHostToDevice));
     PTMI_HIP(hipMemcpy(d_prims, prims.data(), prims.size() * sizeof(float4), hipMemcpyHostToDevice));
     PTMI_HIP(hipMemcpy(d_mats, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice));
+
+    // the emitter table (device_scene.h: EmitterTable): records in emitter order, pdf_area by leaf-order slot
+    {
+        const int ne = (int)h_emit_prim.size();
+        std::vector<int> slot_of((size_t)n);
+        for (int k = 0; k < n; k++) slot_of[bvh_indices[k]] = k;
+        std::vector<float4> rec((size_t)kEmitterStride * ne);
+        std::vector<float> pdf_slot((size_t)n, 0.0f);
+        for (int k = 0; k < n; k++) pdf_slot[k] = h_pdf_area[bvh_indices[k]];
+        for (int j = 0; j < ne; j++) {
+            const int i = h_emit_prim[j];
+            const Primitive& p = h_primitives[i];
+            float4* r = &rec[(size_t)kEmitterStride * j];
+            r[0] = make_float4(p.v[0].x, p.v[0].y, p.v[0].z, bits(slot_of[i]));
+            r[1] = make_float4(p.v[1].x, p.v[1].y, p.v[1].z, p.sampleAreaRatio());
+            r[2] = make_float4(p.v[2].x, p.v[2].y, p.v[2].z, bits(p.type == PRIM_QUAD ? 1 : 0));
+            r[3] = make_float4(p.v[3].x, p.v[3].y, p.v[3].z, h_pdf_area[i]);
+            r[4] = make_float4(p.normal.x, p.normal.y, p.normal.z, 0.0f);
+            r[5] = make_float4(p.Le.x, p.Le.y, p.Le.z, 0.0f);
+        }
+        d_pdf_area = (float*)hipMallocSafe((size_t)n * sizeof(float), "d_pdf_area");
+        PTMI_HIP(hipMemcpy(d_pdf_area, pdf_slot.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        if (ne > 0) {
+            d_emit_rec = (float4*)hipMallocSafe(rec.size() * sizeof(float4), "d_emit_rec");
+            d_emit_cdf = (float*)hipMallocSafe((size_t)ne * sizeof(float), "d_emit_cdf");
+            PTMI_HIP(hipMemcpy(d_emit_rec, rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice));
+            PTMI_HIP(hipMemcpy(d_emit_cdf, h_emit_cdf.data(), (size_t)ne * sizeof(float), hipMemcpyHostToDevice));
+        }
+        d_emitters.cdf = d_emit_cdf; d_emitters.rec = d_emit_rec; d_emitters.pdf_area = d_pdf_area;
+        d_emitters.n = ne; d_emitters.total = ne ? h_emit_cdf.back() : 0.0f;
+    }
 
     d_scene.nodes = d_nodes; d_scene.prims = d_prims; d_scene.mats = d_mats;
     d_scene.n_nodes = (int)bvh_nodes.size(); d_scene.n_prims = n;
@@ -1006,7 +1066,10 @@ static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, Pass
     // queued, and the frame needs no launch boundary to re-pack its lanes before the queue has run dry
     // (the sweep of the small LDS-resident scenes does not gain: with refill its waves lose the coherence their shared walk lives on -
     // c2 5 685 Msamples/s in image order, 6 790 in cost order, against 6 717 for its 32-segment launches on the same box)
-    bool refill = (trav == TRAVERSAL_WIDE || trav == TRAVERSAL_CERTIFIED) && g.config.segments_per_launch <= 0 && wave_slots > 0;
+    // next-event estimation (include/ptmi.h: ptmi_config.next_event) replaces the frame-begin / bounce loop below with ONE launch
+    // of ptmi_render_nee on the frame's stream: no chunks, no refill, no launch order by cost
+    const bool nee = g.config.next_event && g.config.current_integrator == IntegratorType::PathTracing;
+    bool refill = (trav == TRAVERSAL_WIDE || trav == TRAVERSAL_CERTIFIED) && g.config.segments_per_launch <= 0 && wave_slots > 0 && !nee;
     const int refill_segments = kRestOfFrameSegments;
     // launch order by last frame's cost (below): in 16 classes, and only while the frame has at most three pixels per lane of the
     // launch - an eighth of the 1 M-triangle frame (1.3 per lane) gains 9 % at 64 spp and 12 % at 2048 spp; the whole frame (10.7
@@ -1020,14 +1083,14 @@ static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, Pass
     // With refill one launch keeps every wave slot busy by itself: a second chunk's kernel only competes with it (an eighth of the
     // 1 M-triangle frame 1 661 -> 1 716 Msamples/s with one chunk, the whole frame 2 600 -> 2 795; three chunks: 1 628 / 2 501).  The
     // automatic choice follows the walk; a forced count (config.streams) stays.
-    if (!pass && r.want_chunks == 0 && g.config.current_integrator == IntegratorType::PathTracing) {
+    if (!pass && !nee && r.want_chunks == 0 && g.config.current_integrator == IntegratorType::PathTracing) {
         const int want = refill ? 1 : (r.n_local >= (size_t)(1 << 18) ? 2 : 1);
         if (want != r.n_chunks) { PTMI_HIP(hipStreamSynchronize(r.stream)); r.setupChunks(want); }
     }
     // a pass runs its queue as one chunk on chunk 0's stream
     if (pass) r.accum.chunk.stream = r.chunk[0].stream;
     RenderState::Chunk* chunks = pass ? &r.accum.chunk : r.chunk;
-    const int n_chunks = pass ? 1 : r.n_chunks;
+    const int n_chunks = nee ? 0 : pass ? 1 : r.n_chunks;
 
     auto event = [&](size_t i) {
         while (g.event_pool.size() <= i) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
@@ -1057,7 +1120,8 @@ static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, Pass
         return;
     }
 
-    if (pass) launch_pass_begin(r.tile, r.d_state, fp, chunks[0].d_queue_init, chunks[0].n, pass->rule.first != 0, s);
+    if (nee) {}                                        // the NEE kernel starts its own camera rays
+    else if (pass) launch_pass_begin(r.tile, r.d_state, fp, chunks[0].d_queue_init, chunks[0].n, pass->rule.first != 0, s);
     else launch_frame_begin(r.tile, r.d_state, fp, s);
 
     // Launch order of a refill frame: the pixels that took the most segments in the last frame first.  A pixel has ONE path in
@@ -1096,6 +1160,17 @@ static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, Pass
     }
     uint64_t launches = 0, visits = 0;
     const size_t first_pair_event = n_ev;
+    if (nee) {                                         // the whole frame, batch or pass in one launch (its events: the one pair)
+        const int n = pass ? chunks[0].n : n_local;
+        const hipEvent_t e0 = stats ? event(n_ev++) : nullptr;
+        if (stats) PTMI_HIP(hipEventRecord(e0, s));
+        launch_render_nee(g.scene.d_scene, g.scene.d_emitters, r.tile, r.d_state, fp, pass ? chunks[0].d_queue_init : nullptr, n,
+                          pass ? pass->rule.first != 0 : true, s);
+        PTMI_HIP(hipGetLastError());
+        const hipEvent_t e1 = stats ? event(n_ev++) : nullptr;
+        if (stats) PTMI_HIP(hipEventRecord(e1, s));
+        launches = n > 0 ? 1 : 0; visits = (uint64_t)n;
+    }
     auto busy = [&] { for (int c = 0; c < n_chunks; c++) if (!run[c].finished || run[c].retired < run[c].issued) return true; return false; };
     while (busy()) {
         for (int c = 0; c < n_chunks; c++) {

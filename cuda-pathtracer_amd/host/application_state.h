@@ -51,6 +51,7 @@ struct AppConfig {                                   // application_state.h:262-
     float mis_bsdf_fraction = 0.5f;                  // application_state.h:292 / scene.h:217
     IntegratorType current_integrator = IntegratorType::PathTracing;   // application_state.h:283
     bool fast_tree = false;                          // new: walk the opt-in 8-wide SAH tree instead of the reference's (csrc/wide_bvh.h)
+    bool next_event = false;                         // new: next-event estimation with MIS (include/ptmi.h: ptmi_config.next_event)
 };
 
 struct SceneState {
@@ -108,6 +109,14 @@ struct SceneState {
     // per-primitive radiosity for the Radiosity integrator (render_radiosity); n_prims*3 floats, load order; nullptr = zero
     float4* d_radiosity = nullptr;
     void setRadiosity(const float* rgb);
+    // next-event estimation: the emitter table (csrc/device_scene.h: EmitterTable), built by both host loaders in load order
+    // (buildEmitters), uploaded with the scene and freed with it
+    std::vector<int> h_emit_prim;                    // load-order index of emitter j
+    std::vector<float> h_emit_cdf;                   // running sum c_j
+    std::vector<float> h_pdf_area;                   // per primitive, load order (0: not an emitter)
+    float4* d_emit_rec = nullptr;
+    float *d_emit_cdf = nullptr, *d_pdf_area = nullptr;
+    EmitterTable d_emitters;
     int sweep_max_prims = 64;                        // scenes up to this many primitives use the wave-uniform sweep
     int force_traversal = -1;                        // test/benchmark override (TraversalMode), -1 = automatic
 
@@ -124,6 +133,7 @@ struct SceneState {
 
 private:
     void buildBVH();                                 // RayTracingManager::buildAccelStructure (ray_tracing_backend.h:81-129)
+    void buildEmitters();                            // the host half of the emitter table
     void upload();                                   // SoA re-layout + H2D
     void freePacked();
 };

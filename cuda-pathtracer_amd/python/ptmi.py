@@ -35,6 +35,7 @@ EXPORTS = [
     "ptmi_read_denoised", "ptmi_denoise_timing",
     "ptmi_default_temporal_params", "ptmi_check_temporal_params", "ptmi_temporal_reset", "ptmi_temporal_accumulate",
     "ptmi_read_temporal", "ptmi_read_history_counts", "ptmi_denoise_temporal",
+    "ptmi_host_emitters",
 ]
 
 
@@ -46,7 +47,7 @@ class Camera(C.Structure):
 class Config(C.Structure):
     _fields_ = [("spp", C.c_int), ("max_depth", C.c_int), ("sampling_mode", C.c_int), ("seed_base", C.c_uint64),
                 ("segments_per_launch", C.c_int), ("collect_stats", C.c_int), ("wave_tiles", C.c_int), ("streams", C.c_int), ("mis_bsdf_fraction", C.c_float), ("integrator", C.c_int),
-                ("download_image", C.c_int), ("fast_tree", C.c_int)]
+                ("download_image", C.c_int), ("fast_tree", C.c_int), ("next_event", C.c_int)]
 
 
 class Tiling(C.Structure):
@@ -162,6 +163,7 @@ def lib():
         L.ptmi_host_scene_info.argtypes = [vp, ip, ip, ip, ip, ip]
         L.ptmi_host_scene_get_prims.argtypes = [vp] * 6
         L.ptmi_host_scene_get_bvh.argtypes = [vp] * 7
+        L.ptmi_host_emitters.argtypes = [vp, ip, vp, vp, vp]
         L.ptmi_host_camera_frame.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, vp]
         L.ptmi_host_local_row_map.argtypes = [C.c_int, C.POINTER(Tiling), ip, vp]
         L.ptmi_write_png.argtypes = [C.c_char_p, C.c_int, C.c_int, vp]
@@ -260,6 +262,16 @@ class HostScene:
         _check(lib().ptmi_host_scene_get_bvh(self.h, bmin.ctypes.data, bmax.ctypes.data, left.ctypes.data, right.ctypes.data,
                                              count.ctypes.data, idx.ctypes.data))
         return dict(bmin=bmin, bmax=bmax, left=left, right=right, count=count, indices=idx)
+
+    def emitters(self):
+        """The emitter table of next-event estimation (include/ptmi.h): load-order index and running sum c_j of every emitter,
+        and pdf_area per primitive (load order, 0 where the primitive is not an emitter)."""
+        n = C.c_int()
+        _check(lib().ptmi_host_emitters(self.h, C.byref(n), None, None, None))
+        prim = np.zeros(n.value, np.int32); cdf = np.zeros(n.value, np.float32)
+        pdf_area = np.zeros(self.info()["n_prims"], np.float32)
+        _check(lib().ptmi_host_emitters(self.h, C.byref(n), prim.ctypes.data, cdf.ctypes.data, pdf_area.ctypes.data))
+        return dict(prim=prim, cdf=cdf, pdf_area=pdf_area)
 
 
     # --- the opt-in fast tree (csrc/wide_bvh.h), host halves ---
@@ -465,7 +477,7 @@ class Renderer:
         self._ck(self.L.ptmi_set_camera(self.h, C.byref(cam)))
 
     def set_config(self, spp=None, max_depth=None, seed_base=None, segments_per_launch=None, collect_stats=None, wave_tiles=None, streams=None,
-                   sampling_mode=None, mis_bsdf_fraction=None, integrator=None, download_image=None, fast_tree=None):
+                   sampling_mode=None, mis_bsdf_fraction=None, integrator=None, download_image=None, fast_tree=None, next_event=None):
         c = self.config
         if spp is not None: c.spp = int(spp)
         if max_depth is not None: c.max_depth = int(max_depth)
@@ -479,6 +491,7 @@ class Renderer:
         if integrator is not None: c.integrator = int(integrator)
         if download_image is not None: c.download_image = int(bool(download_image))
         if fast_tree is not None: c.fast_tree = int(bool(fast_tree))
+        if next_event is not None: c.next_event = int(bool(next_event))
         self._ck(self.L.ptmi_set_config(self.h, C.byref(c)))
 
     def camera_frame(self):

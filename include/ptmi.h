@@ -100,6 +100,12 @@ typedef struct {
                                    * ptmi_run_radiosity_solver reads the switch too: its
                                    * visibility walk (form_factors.h:143-208) then skips the proof as well (n = 8192: 84 -> 71 ms;
                                    * 2 of 67 M form factors differ) */
+    int      next_event;          /* 0 (default): the reference's estimator.  1: next-event estimation with MIS - every path vertex
+                                   * also samples a point on an emitter and traces one shadow ray to it (the contract: "next-event
+                                   * estimation" below).  Needs integrator 0, sampling_mode 0 and fast_tree 0 (ptmi_set_config
+                                   * returns PTMI_E_INVALID otherwise).  segments_per_launch, wave_tiles, streams and collect_stats
+                                   * have no effect on it: the counters stay 0; seconds, samples, bounce_kernel_ms and
+                                   * bounce_launches are filled in */
 } ptmi_config;
 
 /* Framebuffer sharding (new in this implementation; the reference is single-GPU).
@@ -301,6 +307,10 @@ void ptmi_host_scene_free(ptmi_host_scene*);
 int  ptmi_host_scene_info(const ptmi_host_scene*, int* n_prims, int* n_tris, int* n_quads, int* n_bvh_nodes, int* bvh_depth);
 int  ptmi_host_scene_get_prims(const ptmi_host_scene*, int* type, float* verts, float* normal, float* bsdf, float* Le);
 int  ptmi_host_scene_get_bvh(const ptmi_host_scene*, float* bmin, float* bmax, int* left, int* right, int* count, int* indices);
+/* The emitter table of next-event estimation (see "next-event estimation" below) in load order: prim (load-order index of emitter
+ * j) and cdf (c_j) have n_emitters entries each, pdf_area has n_prims (0 for every primitive that is not an emitter).  Any
+ * pointer may be NULL (ask for the count first). */
+int  ptmi_host_emitters(const ptmi_host_scene*, int* n_emitters, int* prim, float* cdf, float* pdf_area);
 /* Sensor after allocateBuffers() + renderFrame()'s camera update for a width x height frame (12 floats). */
 /* "Save PNG" (ui/ui_windows.h:195-210): 8-bit RGB file of a whole frame as ptmi_read_image returns it (row 0 = bottom);
  * rows are flipped on write like stbi_flip_vertically_on_write(1) does. */
@@ -575,6 +585,47 @@ int  ptmi_read_temporal(const ptmi_ctx*, unsigned char* rgb8, float* radiance);
 /* the history's sample count n per local pixel, local row-major */
 int  ptmi_read_history_counts(const ptmi_ctx*, float* counts);
 int  ptmi_denoise_temporal(ptmi_ctx*, const ptmi_denoise_params* /* NULL: defaults */);
+
+/* ---- next-event estimation with multiple importance sampling (new in this implementation) --------------------------------------
+ * ptmi_config.next_event = 1: at every path vertex a point on an emitter is sampled and one shadow ray traced to it, and the power
+ * heuristic combines that sample with the BSDF sample (Veach 1997), so the estimator stays unbiased.  It applies to
+ * ptmi_render_frame, ptmi_render_frames (ptmi_select_frame as usual), ptmi_accum_pass (progressive and adaptive: a pass continues
+ * the pixel's sums) and tiled contexts (streams are keyed by the global pixel); ptmi_denoise, ptmi_temporal_accumulate and
+ * ptmi_gather_frame take the NEE image as they take any other.  Colour sums, the resolve and the tone map are a frame's; a pixel's
+ * RNG stream carries over between frames as it does without NEE.  One launch runs every queued pixel's samples to their end.
+ *
+ * THE EMITTER TABLE (built by both scene loaders, ptmi_host_emitters), float32 in the order written (-ffp-contract=off):
+ *     area_i = Triangle/Quad::area (triangle.h:28, quad.h:31: 0.5f * length(cross(v1 - v0, v2 - v0)) for a triangle,
+ *              0.5f * (length(cross(v10 - v00, v01 - v00)) + length(cross(v11 - v10, v11 - v01))) for a quad)
+ *     w_i    = area_i * ((Le.x + Le.y) + Le.z)
+ *     the emitters are the primitives with w_i > 0, in load order; c_j = c_{j-1} + w_j from c_{-1} = +0; total = c_last
+ *     pdf_area_j = (w_j / total) / area_j; every other primitive has pdf_area = 0
+ *     select(u), u in (0, 1]: the smallest j with u * total <= c_j
+ *
+ * THE ESTIMATOR, per sample.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; c * (a, b, c) and a * b per component; x / PI =
+ * (float)((double)x / M_PI); mis(a, b) = misPowerHeuristic (integrator.h:91-96): 0 if a <= 0, else (a*a) / (a*a + b*b).
+ * The camera ray and its two draws are exactly a frame's; beta = (1, 1, 1), L = (0, 0, 0), p_b_prev = 0.  For depth = 0 ..
+ * max_depth - 1, as integrator.h:189-268 (all draws curand_uniform of the pixel's stream):
+ *   1. the reference's closest hit of (o, d) for t > 1e-4; none: the sample ends.  Primitive k, stored normal n_k, Kd, Le_k,
+ *      p = o + t * d.  If depth >= 1 and pdf_area_k > 0:
+ *          p_l = (pdf_area_k * (t * t)) / fabsf(dot(n_k, d));   w = mis(p_b_prev, p_l);   L = L + (beta * Le_k) * w
+ *      else (depth 0, or not an emitter):  L = L + beta * Le_k
+ *   2. depth > 2: Russian roulette with one draw; beta = beta * Kd; the |beta| < 1e-5 exit - all exactly as the reference.
+ *      sn = dot(d, n_k) < 0 ? n_k : -n_k;  o' = p + 1e-4f * sn   (the reference's spawn point, integrator.h:266)
+ *   3. NEE, if depth + 1 < max_depth and the scene has an emitter.  ALWAYS three draws, u_sel, r1, r2, in this order, whatever
+ *      comes of them:  j = select(u_sel);  y = Primitive::sampleUniform of emitter j with (r1, r2) (primitive.h:150-191);
+ *          v = y - o';  dist2 = dot(v, v);  dist = sqrtf(dist2);  wi = (v.x / dist, v.y / dist, v.z / dist)
+ *          cos_s = dot(sn, wi);  cos_l = fabsf(dot(n_j, wi))        n_j: emitter j's stored normal
+ *      if cos_s > 0 and cos_l > 0, and the reference's closest hit of (o', wi) for t > 1e-4 is emitter j itself (the same walk
+ *      as the path rays):
+ *          p_l = (pdf_area_j * dist2) / cos_l;  p_b = cos_s / PI;  w = (p_b * mis(p_l, p_b)) / p_l;  L = L + (beta * Le_j) * w
+ *   4. two draws u, v; depth = depth + 1; if depth < max_depth:  next = sampleCosineHemisphere(sn, u, v) (integrator.h:62-85),
+ *      p_b_prev = fmaxf(dot(sn, next), 0) / PI,  o = o',  d = unit_vector(next); else the sample ends.
+ * At the end of the sample colour = colour + L (integrator.h:390).
+ * The two MIS weights of an emitter point sum to 1 wherever both strategies can produce it, so every pixel's expected value is
+ * that of the reference's estimator.  This needs the stored normal of an emitter to be its plane normal, up to sign: the .obj
+ * and PBRT loaders guarantee it; for ptmi_load_scene_arrays the caller does.  Without an emitter in the scene NEE draws
+ * nothing and a frame is the reference's frame. */
 
 #ifdef __cplusplus
 }

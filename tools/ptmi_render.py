@@ -49,6 +49,7 @@ def main():
     ap.add_argument("--yaw-step", type=float, default=2.0, metavar="DEG")
     ap.add_argument("--temporal", action="store_true", help="with --orbit: every view through the temporal accumulation (reprojected history)")
     ap.add_argument("--out-prefix", default=None, help="with --orbit: write every view to PREFIXnnn.png")
+    ap.add_argument("--next-event", action="store_true", help="next-event estimation with MIS: sample the emitters at every bounce")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -72,7 +73,7 @@ def main():
     r.set_camera(cam)
     r.update_resolution(a.width, a.height)
     r.set_config(spp=a.spp, max_depth=a.max_depth, seed_base=a.seed_base, sampling_mode=a.sampling_mode,
-                 mis_bsdf_fraction=a.mis_bsdf_fraction, integrator=1 if a.integrator == "radiosity" else 0)
+                 mis_bsdf_fraction=a.mis_bsdf_fraction, integrator=1 if a.integrator == "radiosity" else 0, next_event=a.next_event)
     if a.orbit > 0:
         orbit(r, a, cam)
         r.close()
