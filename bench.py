@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the per-pixel render loop on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c5tile|c4|c5] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c5tile|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one renderFrame(): all spp samples of every pixel of the frame (scene, path state and RNG streams resident
 in HBM; successive steps are successive frames, RNG state carrying over as in the reference, integrator.h:379).
+
+A plain run is lean: set-up (with the counter frames, whose RNG state the timed steps start from), warm-up, the K timed
+steps, --dump-outputs, and the result line with its `config` counters and `roofline` (no runs of their own).  Everything
+else is measured only with --full: the same steps again with the 8-bit image downloaded (value_incl_d2h) and the other
+way (pipelined batch <-> one call per step), the `extra_configs` below and the `cpu_baseline`.
 
 Workloads (BASELINE.json `configs`):
   c2      configs[1]  cbox.obj 1024x1024, 256 spp, max 8 bounces          - the configuration the metric is quoted on (default)
@@ -16,13 +21,15 @@ Workloads (BASELINE.json `configs`):
                       is full (an eighth of the frame is 0.52 M pixels = 8192 waves, about one per wave slot)
   c4      configs[3]  cbox.obj 4096x4096, 512 spp, max 5 bounces, rows tiled over the N GPUs (strong scaling)
   c5      configs[4]  the whole 1 M-triangle frame tiled over the N GPUs (strong scaling)
-N = 1 default: c2 as the headline line + `extra_configs` (c3, c5tile, c5frame), each with its own roofline block.
+N = 1 default: c2 as the headline line; with --full + `extra_configs` (c3, c4, c5tile, c5frame and their variants), each
+with its own roofline block.
 N > 1 default: weak scaling of c2 - the same view and spp at side = round(1024*sqrt(N)), so every GPU owns ~1024^2
 pixels; rows are dealt to ranks in interleaved row blocks (no data-path collective) and ONE RCCL gather at frame end
-(ptmi_gather_frame: ncclSend/ncclRecv behind the C ABI, exact tile sizes, 8-bit image) inside the timed region.
+(ptmi_gather_frame: ncclSend/ncclRecv behind the C ABI, exact tile sizes, 8-bit image) inside the timed region; with
+--full + the strong-scaled `extra_configs` (c4, c5).
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed inside the library on the streams it
-launches on) and `cpu_baseline` (the oracle, timed on the host cores on a bounded sample).
+launches on) and, with --full, `cpu_baseline` (the oracle, timed on the host cores on a bounded sample).
 """
 import argparse
 import json
@@ -338,7 +345,9 @@ def roofline_block(name, cfg, m, exact_workload):
 
 def measure(r, cfg, steps, warmup, run_steps, barrier, segments, reduce_max, pipelined=True):
     """counters frame (untimed, stats build) + warmup + `steps` timed frames of the loaded workload.
-    run_steps(k, stats, pipelined) renders k steps (frames) and returns the list of their ptmi_stats."""
+    run_steps(k, stats, pipelined) renders k steps (frames) and returns the list of their ptmi_stats.
+    The counter frames belong to every run, --full or not: they advance the RNG streams, so the timed frames start from the
+    state they leave."""
     # two counter frames where the timed walk is not the reference's own: (1) the reference's walk (forced: the packed layout) for
     # SURVEY 8(d)'s algorithmic figure, which is defined on the reference's node visits and primitive tests; (2) the walk that is
     # timed (certified / fast tree), for what it really fetches
@@ -389,16 +398,19 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
-    ap.add_argument("--no-extra", action="store_true", help="N = 1, config c2: skip the extra_configs (c3, c5tile, c5frame)")
+    ap.add_argument("--full", action="store_true", help="measure everything, not only the headline: the steps again with the image "
+                    "downloaded and the other way (pipelined batch <-> one call per step), the extra_configs and the cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full, config c2: skip the extra_configs")
     ap.add_argument("--spp", type=int, default=0, help=argparse.SUPPRESS)          # for quick experiments only
     ap.add_argument("--side", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--segments", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--streams", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--no-cpu", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--extra-budget", type=float, default=240.0, help="seconds the extra_configs may take in all; the ones left are recorded as skipped")
+    ap.add_argument("--extra-budget", type=float, default=240.0, help="with --full: seconds the extra_configs may take in all; the ones left "
+                    "are recorded as skipped")
     ap.add_argument("--gather", choices=("rgb8", "radiance", "both"), default="rgb8", help="what the frame-end gather moves (N > 1)")
     ap.add_argument("--pipeline", action="store_true", help="render the K steps as ONE pipelined batch (ptmi_render_frames) instead of one "
-                    "ptmi_render_frame call per step; without it the batch rate is still reported as value_pipelined_batch (N = 1)")
+                    "ptmi_render_frame call per step; without it and with --full the batch rate is still reported as value_pipelined_batch (N = 1)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the image of the last timed step as DIR/rgb8.npy and "
                     "DIR/radiance.npy (float32; a fixed sample of pixels + DIR/pixel_index.npy above 64 MB); N > 1: rank 0's gathered frame")
     # profile pass (tools/profile.sh): exactly `steps` frames of the timing build of the kernel, nothing else on the GPU
@@ -541,9 +553,9 @@ def main():
     value = total_samples / m["elapsed"] / 1e6
 
     # the reference's renderFrame() ends with the D2H of the 8-bit image (application.h:211): same steps again with
-    # config.download_image (pinned host image); reported next to `value`, which leaves results on the device
+    # config.download_image (pinned host image); reported next to `value`, which leaves results on the device (--full)
     value_incl_d2h = value_other = None
-    if world == 1 and not use_dist:
+    if args.full and world == 1 and not use_dist:
         r.set_config(download_image=True)
         run_steps(min(args.warmup, 1), False, pipelined)
         barrier()
@@ -581,8 +593,8 @@ def main():
             out["value_incl_d2h"] = round(value_incl_d2h, 3)
             out["d2h_note"] = "value leaves the frame on the device; value_incl_d2h adds renderFrame()'s 3 B/pixel copy to pinned host memory (application.h:211)"
 
-    # N = 1, headline configuration: the other single-GPU workloads of BASELINE.json, driver-timed in the same run
-    if world == 1 and not use_dist and name == "c2" and not args.no_extra and exact:
+    # N = 1, headline configuration, --full: the other single-GPU workloads of BASELINE.json, driver-timed in the same run
+    if args.full and world == 1 and not use_dist and name == "c2" and not args.no_extra and exact:
         extras = []
         loaded = None
         t_extras = time.perf_counter()
@@ -633,11 +645,11 @@ def main():
         r.set_config(fast_tree=False)
         out["extra_configs"] = extras
 
-    # N > 1, default line: `value` stays the weak-scaled headline configuration; BASELINE's own multi-GPU configurations are
+    # N > 1, default line, --full: `value` stays the weak-scaled headline configuration; BASELINE's own multi-GPU configurations are
     # timed in the same run as STRONG scaling (fixed frame, rows tiled over the N ranks, one RCCL gather per frame): configs[3]
     # (c4, at its full 512 spp) and configs[4] (c5, the 1 M-triangle frame at 64 of its 2048 spp: the default = certified walk,
     # the reference's own tree, and the opt-in fast tree without the certificate; and ONE frame at the full 2048 spp, default walk).  A failure here is recorded in the line and does not cost the headline number.
-    if world > 1 and name == "c2" and not args.no_extra and not args.side and not args.spp:
+    if args.full and world > 1 and name == "c2" and not args.no_extra and not args.side and not args.spp:
         extras = []
         loaded = cfg["scene"]
         t_extras = time.perf_counter()
@@ -677,7 +689,7 @@ def main():
         if rccl:
             out["rccl_ranks"] = r.dist_comm_count()       # what RCCL itself reports for the communicator the gathers ran on (ncclCommCount)
             assert out["rccl_ranks"] == world, f"RCCL sees {out['rccl_ranks']} ranks, the launcher started {world}"
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(cfg, cfg["width"], cfg["height"])
         print(json.dumps(out), flush=True)
     r.close()

@@ -190,7 +190,7 @@ def test_rccl_gather_through_the_c_abi_one_rank_and_placement_kernel():
 def test_bench_line_carries_every_contract_field():
     import json
     root = os.path.dirname(HERE)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--spp", "16"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--spp", "16", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -213,9 +213,32 @@ def test_bench_line_carries_every_contract_field():
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_is_lean(tmp_path):
+    """The default command without --full: the headline line and the dumped image, none of what only --full measures."""
+    import json
+    import numpy as np
+    root = os.path.dirname(HERE)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "Msamples/s" and d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0
+    # value and ms_per_step describe the same timed steps: 1024 x 1024 pixels x 256 spp per step
+    assert abs(d["value"] * d["ms_per_step"] / (1024 * 1024 * 256 / 1e3) - 1.0) < 1e-3
+    for k in ("cpu_baseline", "extra_configs", "value_incl_d2h", "value_pipelined_batch", "value_one_call_per_step"):
+        assert k not in d, k
+    for k in ("rgb8", "radiance"):
+        a = np.load(tmp_path / "out" / f"{k}.npy")
+        assert a.shape == (1024, 1024, 3) and a.dtype == np.float32
+
+
+@pytest.mark.gpu
 def test_bench_launches_its_own_ranks(tmp_path):
-    """`python bench.py --gpus 3` with NO launcher around it (WORLD_SIZE unset), as the driver may run it: bench.py starts the three
-    ranks itself before anything touches a GPU, relays rank 0's line and exits with the worst child's code.  Default N > 1 line:
+    """`python bench.py --gpus 3 --full` with NO launcher around it (WORLD_SIZE unset), as the driver may run it: bench.py starts the three
+    ranks itself before anything touches a GPU, relays rank 0's line and exits with the worst child's code.  The --full N > 1 line:
     weak-scaled c2 as `value` plus the strong-scaled BASELINE configurations (c4; c5 by the default walk and through both trees; shrunk here by the
     rehearsal switch) and the rank count RCCL itself reports.  The ranks share the test box's GPU over tests/mock_rccl.cpp."""
     import json
@@ -224,8 +247,8 @@ def test_bench_launches_its_own_ranks(tmp_path):
     env["PTMI_RCCL_LIB"] = str(tmp_path / "lib" / "librccl.so.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--rehearse-shared-gpu", "--no-cpu"],
-                       env=env, capture_output=True, text=True, timeout=1200)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--rehearse-shared-gpu", "--no-cpu",
+                        "--full"], env=env, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-2500:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 3 and line["scaling"] == "weak" and line["value"] > 0 and line["rccl_ranks"] == 3

@@ -11,7 +11,7 @@ TAG=$1; CFG=${2:-c2}; FRAMES=${3:-1}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 cat /sys/fs/cgroup/cpu.max > $OUT/cpu_max.txt 2>&1 || true
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --config $CFG --steps 3 --warmup 1 --no-cpu --no-extra > $OUT/bench_trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --config $CFG --steps 3 --warmup 1 --full --no-cpu --no-extra > $OUT/bench_trace.log 2>&1
 echo trace-done
 for PASS in "FETCH_SIZE" "WRITE_SIZE" \
             "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY" \
