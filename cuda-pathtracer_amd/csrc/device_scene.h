@@ -260,22 +260,22 @@ void launch_temporal(const TemporalArgs& a, const FeatureBuffers& fb, const floa
                      float* out_radiance, unsigned long long* stats, hipStream_t s);
 
 // ---- next-event estimation (include/ptmi.h: ptmi_config.next_event) ------------------------------------------------------
-// The emitter table of the loaded scene (host: SceneState::buildEmitters / upload).  Emitters are the primitives with
-// w = area * ((Le.x + Le.y) + Le.z) > 0, in load order; nothing is sized for a handful of lights (the 1 M-triangle scene has
-// 65 536).  Kept apart from DeviceScene so that no other kernel's arguments change.
-//   cdf[j]                   running float sum of w over emitters 0..j (binary search of u * total)
+// The emitter table of the loaded scene (host: SceneState::buildEmitters / upload; include/ptmi.h states which primitives are
+// emitters and how cdf and pdf_area are made), in load order; nothing is sized for a handful of lights (the 1 M-triangle scene
+// has 65 536).  Kept apart from DeviceScene so that no other kernel's arguments change.
+//   cdf[j]                   running sum of w over emitters 0..j (binary search of u * total)
 //   rec[kEmitterStride*j+0]  (v0.xyz, bits(leaf-order slot))     the slot: a shadow ray is visible iff its closest hit is it
 //   rec[kEmitterStride*j+1]  (v1.xyz, quad area ratio)          Primitive::sampleAreaRatio (1 for triangles)
 //   rec[kEmitterStride*j+2]  (v2.xyz, bits(type))
 //   rec[kEmitterStride*j+3]  (v3.xyz, pdf_area)                 v3: quads only
-//   rec[kEmitterStride*j+4]  (stored normal.xyz, 0)
+//   rec[kEmitterStride*j+4]  (geometric normal.xyz, 0)
 //   rec[kEmitterStride*j+5]  (Le.xyz, 0)
-//   pdf_area[k]              per LEAF-ORDER slot: (w / total) / area of an emitter, 0 for every other primitive
+//   pdf_area[k]              per LEAF-ORDER slot: (geometric normal.xyz, pdf_area) of an emitter, 0 for every other primitive
 constexpr int kEmitterStride = 6;
 struct EmitterTable {
     const float* cdf = nullptr;
     const float4* rec = nullptr;
-    const float* pdf_area = nullptr;   // n_prims entries, also without emitters
+    const float4* pdf_area = nullptr;  // n_prims entries, also without emitters
     int n = 0;
     float total = 0.0f;
 };

@@ -1672,9 +1672,10 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                 if (!hit) break;                                                          // integrator.h:198-201
                 const f3 nrm = xyz(sc.mats[3 * k]), bsdf = xyz(sc.mats[3 * k + 1]), Le = xyz(sc.mats[3 * k + 2]);
                 const f3 hp = o + t * d;                                                  // triangle.h:90
-                const float pa = depth > 0 ? em.pdf_area[k] : 0.0f;
+                const float4 pe = depth > 0 ? em.pdf_area[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                const float pa = pe.w;
                 if (pa > 0.0f) {                                                          // an emitter found by the BSDF sample
-                    const float p_l = (pa * (t * t)) / fabsf(dot(nrm, d));
+                    const float p_l = (pa * (t * t)) / fabsf(dot(xyz(pe), d));           // the geometric normal: area -> solid angle
                     const float w = mis_power_heuristic(pb_prev, p_l);
                     const f3 c = tp * Le;
                     L = L + mk3(c.x * w, c.y * w, c.z * w);
@@ -1704,9 +1705,9 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                     const float dist = sqrt_rn(dist2);
                     const f3 wi = mk3(v.x / dist, v.y / dist, v.z / dist);
                     const float cos_s = dot(sn, wi);
-                    const float cos_l = fabsf(dot(xyz(a4), wi));
-                    if (cos_s > 0.0f && cos_l > 0.0f) {
-                        const float p_l = (a3.w * dist2) / cos_l;
+                    const float cos_l = fabsf(dot(xyz(a4), wi));                          // a4: the geometric normal
+                    const float p_l = (a3.w * dist2) / cos_l;
+                    if (cos_s > 0.0f && cos_l > 0.0f && p_l > 0.0f && p_l <= FLT_MAX) {   // a p_l of 0 or inf weighs 0 (no NaN)
                         const float p_b = cos_over_pi(cos_s);
                         const float w = (p_b * mis_power_heuristic(p_l, p_b)) / p_l;
                         const f3 c = tp * xyz(rec[5]);

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <limits>
 #include <cctype>
+#include <cfloat>
 #include <cstring>
 #include <map>
 
@@ -92,8 +93,8 @@ void SceneState::cleanup() {
     if (d_emit_rec) (void)hipFree(d_emit_rec);
     if (d_emit_cdf) (void)hipFree(d_emit_cdf);
     if (d_pdf_area) (void)hipFree(d_pdf_area);
-    d_emit_rec = nullptr; d_emit_cdf = d_pdf_area = nullptr; d_emitters = EmitterTable();
-    h_emit_prim.clear(); h_emit_cdf.clear(); h_pdf_area.clear();
+    d_emit_rec = d_pdf_area = nullptr; d_emit_cdf = nullptr; d_emitters = EmitterTable();
+    h_emit_prim.clear(); h_emit_cdf.clear(); h_emit_normal.clear(); h_pdf_area.clear(); h_emit_total = 0.0f;
     freePacked();
     freeFast();
     fast_declined = false;
@@ -144,26 +145,74 @@ void SceneState::loadSceneArraysHost(std::vector<Primitive> prims) {
     buildEmitters();
 }
 
-// The emitter table of next-event estimation, float32 in the order of include/ptmi.h: w = area * ((Le.x + Le.y) + Le.z), the
-// emitters are the primitives with w > 0 in load order, c_j their running sum from +0, pdf_area = (w / total) / area
+// The geometric normal of include/ptmi.h's emitter table: unit_vector(cross(e1, e2)) of the triangle's (v1 - v0, v2 - v0) or the
+// quad's (v10 - v00, v01 - v00)
+static f3 emitterNormal(const Primitive& p) {
+    return unit_vector(cross(p.v[1] - p.v[0], (p.type == PRIM_QUAD ? p.v[3] : p.v[2]) - p.v[0]));
+}
+
+// The emitter table of next-event estimation in the order of include/ptmi.h.  Candidates: a finite geometric normal, a quad only
+// if planar.  Float32: w = area * ((Le.x + Le.y) + Le.z) > 0, running sums c_j from +0 that skip a weight the sum absorbs
+// (c + w == c), pdf_area = (w / total) / area.  Where a weight or the sum overflows float, the same in binary64, normalised to a
+// total of 1, skipping the entries that round to the one before.
 void SceneState::buildEmitters() {
     const int n = (int)h_primitives.size();
-    h_emit_prim.clear(); h_emit_cdf.clear();
+    h_emit_prim.clear(); h_emit_cdf.clear(); h_emit_normal.clear();
     h_pdf_area.assign((size_t)n, 0.0f);
+    h_emit_total = 0.0f;
+    std::vector<int> cand;
+    for (int i = 0; i < n; i++) {
+        const Primitive& p = h_primitives[i];
+        const f3 ng = emitterNormal(p);
+        if (!std::isfinite(ng.x) || !std::isfinite(ng.y) || !std::isfinite(ng.z)) continue;
+        if (p.type == PRIM_QUAD) {                   // the walk splits a quad along v00-v11, sampleUniform along v10-v01
+            const f3 diag = p.v[2] - p.v[0];
+            if (!(fabsf(dot(ng, diag)) <= 1e-4f * length(diag))) continue;
+        }
+        cand.push_back(i);
+    }
     std::vector<float> w_of;
     float c = 0.0f;
-    for (int i = 0; i < n; i++) {
+    bool overflow = false;
+    for (int i : cand) {
         const Primitive& p = h_primitives[i];
         const float w = p.area() * ((p.Le.x + p.Le.y) + p.Le.z);
         if (!(w > 0.0f)) continue;
+        if (!(w <= FLT_MAX) || !(c + w <= FLT_MAX)) { overflow = true; break; }
+        if (!(c + w > c)) continue;                  // absorbed: select() could never return it
         c = c + w;
         h_emit_prim.push_back(i); h_emit_cdf.push_back(c); w_of.push_back(w);
     }
-    const float total = h_emit_cdf.empty() ? 0.0f : h_emit_cdf.back();
-    for (size_t j = 0; j < h_emit_prim.size(); j++) {
-        const int i = h_emit_prim[j];
-        h_pdf_area[i] = (w_of[j] / total) / h_primitives[i].area();
+    if (!overflow) {
+        h_emit_total = c;
+        for (size_t j = 0; j < h_emit_prim.size(); j++) {
+            const int i = h_emit_prim[j];
+            h_pdf_area[i] = (w_of[j] / c) / h_primitives[i].area();
+        }
+    } else {
+        h_emit_prim.clear(); h_emit_cdf.clear();
+        std::vector<int> pos;
+        std::vector<double> wd, cd;
+        double t = 0.0;
+        for (int i : cand) {
+            const Primitive& p = h_primitives[i];
+            const double w = (double)p.area() * (((double)p.Le.x + (double)p.Le.y) + (double)p.Le.z);
+            if (!(w > 0.0) || !std::isfinite(w)) continue;
+            t = t + w;
+            pos.push_back(i); wd.push_back(w); cd.push_back(t);
+        }
+        float prev = 0.0f;
+        for (size_t k = 0; k < pos.size(); k++) {
+            const float cdf = (float)(cd[k] / t);
+            if (!(cdf > prev)) continue;             // absorbed
+            const int i = pos[k];
+            h_pdf_area[i] = (float)((wd[k] / t) / (double)h_primitives[i].area());
+            h_emit_prim.push_back(i); h_emit_cdf.push_back(cdf);
+            prev = cdf;
+        }
+        h_emit_total = h_emit_prim.empty() ? 0.0f : 1.0f;     // the last entry is C / C = 1
     }
+    for (int i : h_emit_prim) h_emit_normal.push_back(emitterNormal(h_primitives[i]));
 }
 
 void SceneState::buildBVH() {
@@ -229,21 +278,22 @@ void SceneState::upload() {
         std::vector<int> slot_of((size_t)n);
         for (int k = 0; k < n; k++) slot_of[bvh_indices[k]] = k;
         std::vector<float4> rec((size_t)kEmitterStride * ne);
-        std::vector<float> pdf_slot((size_t)n, 0.0f);
-        for (int k = 0; k < n; k++) pdf_slot[k] = h_pdf_area[bvh_indices[k]];
+        std::vector<float4> pdf_slot((size_t)n, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
         for (int j = 0; j < ne; j++) {
             const int i = h_emit_prim[j];
             const Primitive& p = h_primitives[i];
+            const f3 ng = h_emit_normal[j];
             float4* r = &rec[(size_t)kEmitterStride * j];
             r[0] = make_float4(p.v[0].x, p.v[0].y, p.v[0].z, bits(slot_of[i]));
             r[1] = make_float4(p.v[1].x, p.v[1].y, p.v[1].z, p.sampleAreaRatio());
             r[2] = make_float4(p.v[2].x, p.v[2].y, p.v[2].z, bits(p.type == PRIM_QUAD ? 1 : 0));
             r[3] = make_float4(p.v[3].x, p.v[3].y, p.v[3].z, h_pdf_area[i]);
-            r[4] = make_float4(p.normal.x, p.normal.y, p.normal.z, 0.0f);
+            r[4] = make_float4(ng.x, ng.y, ng.z, 0.0f);
             r[5] = make_float4(p.Le.x, p.Le.y, p.Le.z, 0.0f);
+            pdf_slot[slot_of[i]] = make_float4(ng.x, ng.y, ng.z, h_pdf_area[i]);
         }
-        d_pdf_area = (float*)hipMallocSafe((size_t)n * sizeof(float), "d_pdf_area");
-        PTMI_HIP(hipMemcpy(d_pdf_area, pdf_slot.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        d_pdf_area = (float4*)hipMallocSafe((size_t)n * sizeof(float4), "d_pdf_area");
+        PTMI_HIP(hipMemcpy(d_pdf_area, pdf_slot.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
         if (ne > 0) {
             d_emit_rec = (float4*)hipMallocSafe(rec.size() * sizeof(float4), "d_emit_rec");
             d_emit_cdf = (float*)hipMallocSafe((size_t)ne * sizeof(float), "d_emit_cdf");
@@ -251,7 +301,7 @@ void SceneState::upload() {
             PTMI_HIP(hipMemcpy(d_emit_cdf, h_emit_cdf.data(), (size_t)ne * sizeof(float), hipMemcpyHostToDevice));
         }
         d_emitters.cdf = d_emit_cdf; d_emitters.rec = d_emit_rec; d_emitters.pdf_area = d_pdf_area;
-        d_emitters.n = ne; d_emitters.total = ne ? h_emit_cdf.back() : 0.0f;
+        d_emitters.n = ne; d_emitters.total = h_emit_total;
     }
 
     d_scene.nodes = d_nodes; d_scene.prims = d_prims; d_scene.mats = d_mats;

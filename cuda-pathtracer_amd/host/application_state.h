@@ -113,9 +113,11 @@ struct SceneState {
     // (buildEmitters), uploaded with the scene and freed with it
     std::vector<int> h_emit_prim;                    // load-order index of emitter j
     std::vector<float> h_emit_cdf;                   // running sum c_j
+    float h_emit_total = 0.0f;                       // c_last (1 where the table was built in binary64)
+    std::vector<f3> h_emit_normal;                   // geometric normal of emitter j
     std::vector<float> h_pdf_area;                   // per primitive, load order (0: not an emitter)
-    float4* d_emit_rec = nullptr;
-    float *d_emit_cdf = nullptr, *d_pdf_area = nullptr;
+    float4 *d_emit_rec = nullptr, *d_pdf_area = nullptr;
+    float* d_emit_cdf = nullptr;
     EmitterTable d_emitters;
     int sweep_max_prims = 64;                        // scenes up to this many primitives use the wave-uniform sweep
     int force_traversal = -1;                        // test/benchmark override (TraversalMode), -1 = automatic

@@ -594,12 +594,22 @@ int  ptmi_denoise_temporal(ptmi_ctx*, const ptmi_denoise_params* /* NULL: defaul
  * ptmi_gather_frame take the NEE image as they take any other.  Colour sums, the resolve and the tone map are a frame's; a pixel's
  * RNG stream carries over between frames as it does without NEE.  One launch runs every queued pixel's samples to their end.
  *
- * THE EMITTER TABLE (built by both scene loaders, ptmi_host_emitters), float32 in the order written (-ffp-contract=off):
+ * THE EMITTER TABLE (built by both scene loaders, ptmi_host_emitters), in the order written (-ffp-contract=off):
  *     area_i = Triangle/Quad::area (triangle.h:28, quad.h:31: 0.5f * length(cross(v1 - v0, v2 - v0)) for a triangle,
- *              0.5f * (length(cross(v10 - v00, v01 - v00)) + length(cross(v11 - v10, v11 - v01))) for a quad)
- *     w_i    = area_i * ((Le.x + Le.y) + Le.z)
- *     the emitters are the primitives with w_i > 0, in load order; c_j = c_{j-1} + w_j from c_{-1} = +0; total = c_last
- *     pdf_area_j = (w_j / total) / area_j; every other primitive has pdf_area = 0
+ *              0.5f * (length(cross(v10 - v00, v01 - v00)) + length(cross(v11 - v10, v11 - v01))) for a quad), float32
+ *     ng_i   = unit_vector(cross(v1 - v0, v2 - v0)) for a triangle, unit_vector(cross(v10 - v00, v01 - v00)) for a quad, float32
+ *              (vector.h:205-218): the GEOMETRIC normal, whatever the stored normal is
+ *     the candidates are the primitives with a finite ng_i, in load order; a quad only if it is planar,
+ *              fabsf(dot(ng_i, v11 - v00)) <= 1e-4f * length(v11 - v00) (the walk splits a quad along v00-v11, sampleUniform
+ *              along v10-v01: only for a planar quad do both cover one surface)
+ *     w_i    = area_i * ((Le.x + Le.y) + Le.z), float32
+ *     the emitters are the candidates with w_i > 0 whose weight the running sum does not absorb: c_j = c_{j-1} + w_j from
+ *              c_{-1} = +0, and a candidate with c + w == c (select() could never return it) is skipped; total = c_last;
+ *              pdf_area_j = (w_j / total) / area_j; every other primitive has pdf_area = 0
+ *     OVERFLOW: if some candidate's w_i > FLT_MAX or c + w_i > FLT_MAX, the table is built in binary64 instead:
+ *              W_i = (double)area_i * (((double)Le.x + Le.y) + Le.z) over the candidates with 0 < W_i < inf, C_k their running
+ *              sum from 0, T = C_last; c_j = (float)(C_k / T), skipping a candidate whose c rounds to the one before;
+ *              pdf_area_j = (float)((W_j / T) / area_j); total = 1.  Le up to FLT_MAX keeps a finite table.
  *     select(u), u in (0, 1]: the smallest j with u * total <= c_j
  *
  * THE ESTIMATOR, per sample.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; c * (a, b, c) and a * b per component; x / PI =
@@ -608,24 +618,26 @@ int  ptmi_denoise_temporal(ptmi_ctx*, const ptmi_denoise_params* /* NULL: defaul
  * max_depth - 1, as integrator.h:189-268 (all draws curand_uniform of the pixel's stream):
  *   1. the reference's closest hit of (o, d) for t > 1e-4; none: the sample ends.  Primitive k, stored normal n_k, Kd, Le_k,
  *      p = o + t * d.  If depth >= 1 and pdf_area_k > 0:
- *          p_l = (pdf_area_k * (t * t)) / fabsf(dot(n_k, d));   w = mis(p_b_prev, p_l);   L = L + (beta * Le_k) * w
+ *          p_l = (pdf_area_k * (t * t)) / fabsf(dot(ng_k, d));   w = mis(p_b_prev, p_l);   L = L + (beta * Le_k) * w
  *      else (depth 0, or not an emitter):  L = L + beta * Le_k
  *   2. depth > 2: Russian roulette with one draw; beta = beta * Kd; the |beta| < 1e-5 exit - all exactly as the reference.
  *      sn = dot(d, n_k) < 0 ? n_k : -n_k;  o' = p + 1e-4f * sn   (the reference's spawn point, integrator.h:266)
  *   3. NEE, if depth + 1 < max_depth and the scene has an emitter.  ALWAYS three draws, u_sel, r1, r2, in this order, whatever
  *      comes of them:  j = select(u_sel);  y = Primitive::sampleUniform of emitter j with (r1, r2) (primitive.h:150-191);
  *          v = y - o';  dist2 = dot(v, v);  dist = sqrtf(dist2);  wi = (v.x / dist, v.y / dist, v.z / dist)
- *          cos_s = dot(sn, wi);  cos_l = fabsf(dot(n_j, wi))        n_j: emitter j's stored normal
- *      if cos_s > 0 and cos_l > 0, and the reference's closest hit of (o', wi) for t > 1e-4 is emitter j itself (the same walk
- *      as the path rays):
- *          p_l = (pdf_area_j * dist2) / cos_l;  p_b = cos_s / PI;  w = (p_b * mis(p_l, p_b)) / p_l;  L = L + (beta * Le_j) * w
+ *          cos_s = dot(sn, wi);  cos_l = fabsf(dot(ng_j, wi));  p_l = (pdf_area_j * dist2) / cos_l     ng_j: the table's
+ *      if cos_s > 0, cos_l > 0 and 0 < p_l <= FLT_MAX (a p_l of 0 or inf weighs 0), and the reference's closest hit of (o', wi)
+ *      for t > 1e-4 is emitter j itself (the same walk as the path rays):
+ *          p_b = cos_s / PI;  w = (p_b * mis(p_l, p_b)) / p_l;  L = L + (beta * Le_j) * w
  *   4. two draws u, v; depth = depth + 1; if depth < max_depth:  next = sampleCosineHemisphere(sn, u, v) (integrator.h:62-85),
  *      p_b_prev = fmaxf(dot(sn, next), 0) / PI,  o = o',  d = unit_vector(next); else the sample ends.
  * At the end of the sample colour = colour + L (integrator.h:390).
  * The two MIS weights of an emitter point sum to 1 wherever both strategies can produce it, so every pixel's expected value is
- * that of the reference's estimator.  This needs the stored normal of an emitter to be its plane normal, up to sign: the .obj
- * and PBRT loaders guarantee it; for ptmi_load_scene_arrays the caller does.  Without an emitter in the scene NEE draws
- * nothing and a frame is the reference's frame. */
+ * that of the reference's estimator.  Both pdfs convert area to solid angle with the geometric normal ng, so this holds for any
+ * stored normal (the loaders store a corner's vn or N, smooth normals included); the stored normal keeps its role on the
+ * shading side (sn, the cosine lobe), as in the reference.  A primitive that is no emitter (a non-planar quad, an absorbed
+ * weight) is found by BSDF samples alone, with weight 1.  Without an emitter in the scene NEE draws nothing and a frame is the
+ * reference's frame. */
 
 #ifdef __cplusplus
 }

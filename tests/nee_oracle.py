@@ -48,23 +48,79 @@ def areas(oscene):
     return out
 
 
-def emitter_table(oscene):
-    """The emitter table of the header: (prim, cdf, pdf_area), float32 in the order written"""
-    le = oscene.prims()["Le"]
+def geometric_normals(oscene):
+    """ng of every primitive, load order: unit_vector(cross(e1, e2)) of the triangle's (v1 - v0, v2 - v0), the quad's
+    (v10 - v00, v01 - v00), float32 as pt_vec.h (NaN or 0 where the edges are degenerate)"""
+    p = oscene.prims()
+    v = p["verts"]
+    e1 = v[:, 1] - v[:, 0]
+    e2 = np.where((p["type"] == 1)[:, None], v[:, 3], v[:, 2]) - v[:, 0]
+    with np.errstate(all="ignore"):
+        c = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], -(e1[:, 0] * e2[:, 2] - e1[:, 2] * e2[:, 0]),
+                      e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1).astype(f32)
+        ln = np.sqrt((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]).astype(f32)
+        k = (f32(1.0) / ln).astype(f32)
+        return (c * k[:, None]).astype(f32)
+
+
+def planar(verts, ng):
+    """a quad is an emitter only if |dot(ng, v11 - v00)| <= 1e-4f * length(v11 - v00), float32"""
+    dg = (verts[2] - verts[0]).astype(f32)
+    with np.errstate(all="ignore"):
+        return bool(abs(_dot(ng, dg)) <= f32(f32(1e-4) * f32(np.sqrt(_dot(dg, dg)))))
+
+
+def emitter_table(oscene, with_total=False):
+    """The emitter table of the header: (prim, cdf, pdf_area), in the order written.  Float32 running sums over the candidates
+    that skip an absorbed weight, pdf_area = (w / total) / area; where a weight or the sum overflows float, the same in binary64,
+    cdf = (float)(C_j / total) skipping entries that round to the one before (total 1).  with_total: also the total."""
+    p = oscene.prims()
+    le = p["Le"]
     area = areas(oscene)
+    ng = geometric_normals(oscene)
+    cand = [i for i in range(oscene.n_prims)
+            if np.isfinite(ng[i]).all() and not (p["type"][i] == 1 and not planar(p["verts"][i], ng[i]))]
     prim, cdf, ws = [], [], []
-    c = f32(0.0)
-    for i in range(oscene.n_prims):
-        w = f32(area[i] * f32(f32(le[i, 0] + le[i, 1]) + le[i, 2]))
-        if not w > 0:
-            continue
-        c = f32(c + w)
-        prim.append(i); cdf.append(c); ws.append(w)
     pdf_area = np.zeros(oscene.n_prims, f32)
-    total = cdf[-1] if cdf else f32(0.0)
-    for j, i in enumerate(prim):
-        pdf_area[i] = f32(f32(ws[j] / total) / area[i])
-    return np.array(prim, np.int32), np.array(cdf, f32), pdf_area
+    c = f32(0.0)
+    overflow = False
+    with np.errstate(all="ignore"):
+        for i in cand:
+            w = f32(area[i] * f32(f32(le[i, 0] + le[i, 1]) + le[i, 2]))
+            if not w > 0:
+                continue
+            if not (w <= FLT_MAX and f32(c + w) <= FLT_MAX):
+                overflow = True
+                break
+            if not f32(c + w) > c:
+                continue
+            c = f32(c + w)
+            prim.append(i); cdf.append(c); ws.append(w)
+    if not overflow:
+        total = c
+        for j, i in enumerate(prim):
+            pdf_area[i] = f32(f32(ws[j] / total) / area[i])
+    else:
+        prim, cdf = [], []
+        pos, wd, cd = [], [], []
+        t = 0.0
+        for i in cand:
+            w = float(area[i]) * ((float(le[i, 0]) + float(le[i, 1])) + float(le[i, 2]))
+            if not (w > 0 and np.isfinite(w)):
+                continue
+            t = t + w
+            pos.append(i); wd.append(w); cd.append(t)
+        prev = f32(0.0)
+        for i, w, ci in zip(pos, wd, cd):
+            cj = f32(ci / t)
+            if not cj > prev:
+                continue
+            pdf_area[i] = f32((w / t) / float(area[i]))
+            prim.append(i); cdf.append(cj)
+            prev = cj
+        total = f32(1.0) if prim else f32(0.0)
+    out = (np.array(prim, np.int32), np.array(cdf, f32), pdf_area)
+    return out + (total,) if with_total else out
 
 
 def _dot(a, b):
@@ -88,8 +144,8 @@ class NeeRenderer:
         L = lib()
         self.s, self.w, self.h = oscene, width, height
         self.prims = oscene.prims()
-        self.prim, self.cdf, self.pdf_area = emitter_table(oscene)
-        self.total = self.cdf[-1] if len(self.cdf) else f32(0.0)
+        self.prim, self.cdf, self.pdf_area, self.total = emitter_table(oscene, with_total=True)
+        self.ng = geometric_normals(oscene)
         self.cf = CameraFrame()
         L.po_camera_frame_setup(C.byref(cam), width, height, C.byref(self.cf))
         self.rng = np.zeros((height * width, 6), np.uint32)
@@ -122,7 +178,7 @@ class NeeRenderer:
             t = f32(h.t); p = np.array(h.p, f32)
             pa = self.pdf_area[k] if depth > 0 else f32(0.0)
             if pa > 0:
-                p_l = f32(f32(pa * f32(t * t)) / abs(_dot(n_k, d)))
+                p_l = f32(f32(pa * f32(t * t)) / abs(_dot(self.ng[k], d)))
                 w = f32(L.po_mis_power_heuristic(pb_prev, p_l))
                 Lr = Lr + (tp * Le) * w
             else:
@@ -148,11 +204,12 @@ class NeeRenderer:
                 dist = f32(np.sqrt(dist2))
                 wi = vv / dist
                 cos_s = _dot(sn, wi)
-                cos_l = abs(_dot(self.prims["normal"][i].astype(f32), wi))
-                if cos_s > 0 and cos_l > 0:
+                cos_l = abs(_dot(self.ng[i], wi))
+                with np.errstate(all="ignore"):
+                    p_l = f32(f32(self.pdf_area[i] * dist2) / cos_l)
+                if cos_s > 0 and cos_l > 0 and 0 < p_l <= FLT_MAX:
                     hs = self._intersect(o2, wi)
                     if hs.hit and hs.prim == i:
-                        p_l = f32(f32(self.pdf_area[i] * dist2) / cos_l)
                         p_b = _over_pi(cos_s)
                         w = f32(f32(p_b * f32(L.po_mis_power_heuristic(p_l, p_b))) / p_l)
                         Lr = Lr + (tp * self.prims["Le"][i].astype(f32)) * w

@@ -84,6 +84,69 @@ def test_frames_match_the_restatement(R, which, w, h, spp, depth):
     assert rad.max() > 0
 
 
+@pytest.mark.parametrize("name,walk", [("deep", "STACK"), ("deep_quads", "STACK"), ("quads_many", "CERTIFIED"),
+                                       ("declined", None), ("emitters_4k", "CERTIFIED"), ("tilted", None), ("warped", None)])
+def test_furnace_frames_match_the_restatement(R, name, walk):
+    """The walks the Cornell scenes do not reach (tests/furnace.py): the stack walk with triangles and quads, the certified walk
+    with quads, the reference's tree where the 8-wide builder declines, > 1000 emitters; tilted stored normals and a non-planar
+    emitter quad (the geometric normal, the table's planarity rule)"""
+    import furnace as FN
+    w, h, spp, depth = 12, 10, 2, 5
+    arrays = FN.variant(name).arrays()
+    R.load_scene_arrays(*arrays)
+    o = OracleScene.from_arrays(*arrays)
+    R.set_camera(ptmi.default_camera())
+    R.update_resolution(w, h)
+    R.set_config(spp=spp, max_depth=depth, sampling_mode=0, integrator=0, fast_tree=False, next_event=True)
+    if walk:
+        assert R.traversal() == getattr(R, walk)
+    else:
+        assert R.traversal() not in (R.STACK, R.CERTIFIED)
+    if name == "emitters_4k":
+        assert len(ptmi.HostScene.from_arrays(*arrays).emitters()["prim"]) >= 1000
+    ref = NeeRenderer(o, default_camera(), w, h)
+    for frame in range(2):
+        R.render_frame()
+        rgb, rad = R.read_image()
+        ergb, erad = ref.frame(spp, depth)
+        assert np.array_equal(bits(rad), bits(erad)), (name, frame, int((bits(rad) != bits(erad)).sum()))
+        assert np.array_equal(rgb, ergb)
+    assert rad.max() > 0
+
+
+def test_without_emitters_the_frame_is_the_references(R):
+    """Le whose channels sum to 0 is no emitter (w = 0) but still shines: NEE draws nothing and both frames are the reference's"""
+    types, verts, normal, bsdf, Le = soup()
+    Le[0::2] = (2.0, -1.0, -1.0); Le[1::2] = (0.5, 0.5, -1.0)
+    arrays = (types, verts, normal, bsdf, Le)
+    R.load_scene_arrays(*arrays)
+    o = OracleScene.from_arrays(*arrays)
+    assert len(ptmi.HostScene.from_arrays(*arrays).emitters()["prim"]) == 0
+    w, h, spp, depth = 16, 12, 3, 5
+    R.set_camera(ptmi.default_camera())
+    R.update_resolution(w, h)
+    R.set_config(spp=spp, max_depth=depth, sampling_mode=0, integrator=0, fast_tree=False, next_event=True)
+    ref = NeeRenderer(o, default_camera(), w, h)
+    frames = []
+    for frame in range(2):
+        R.render_frame()
+        rgb, rad = R.read_image()
+        ergb, erad = ref.frame(spp, depth)
+        assert np.array_equal(bits(rad), bits(erad)), frame
+        assert np.array_equal(rgb, ergb)
+        frames.append((rgb, rad))
+    orgb, orad, _ = o.render(default_camera(), w, h, spp, max_depth=depth)
+    assert np.array_equal(bits(frames[0][1]), bits(orad)) and np.array_equal(frames[0][0], orgb)
+    R.update_resolution(w, h)                              # freshly seeded streams: the reference's estimator, two frames
+    R.set_config(next_event=False)
+    for frame in range(2):
+        R.render_frame()
+        rgb, rad = R.read_image()
+        assert np.array_equal(bits(rad), bits(frames[frame][1])), frame
+        assert np.array_equal(rgb, frames[frame][0])
+    assert np.abs(frames[1][1]).max() > 0
+
+
 def test_nee_changes_the_estimate_and_off_is_the_reference(R):
     o = setup(R, "cbox", 16, 12, 4, 5, next_event=False)
     R.render_frame()

@@ -78,6 +78,34 @@ def test_zero_area_single_channel_and_uneven_power():
     assert np.all(np.diff(got["cdf"]) > 0)
 
 
+def test_the_table_ignores_stored_normals_and_leaves_out_what_select_cannot_use():
+    """The table depends on the geometry and Le alone (the stored normal plays no part); a non-planar quad and an emitter whose
+    weight the running sum absorbs are no emitters"""
+    types, verts, normal, bsdf, Le = soup(40, [(i, (1.0, 2.0, 3.0)) for i in range(0, 40, 3)], 7)
+    tilted = normal.copy(); tilted[:, 0] += 0.5
+    tilted /= np.linalg.norm(tilted, axis=1, keepdims=True)
+    a = check(ptmi.HostScene.from_arrays(types, verts, normal, bsdf, Le), OracleScene.from_arrays(types, verts, normal, bsdf, Le))
+    b = check(ptmi.HostScene.from_arrays(types, verts, tilted, bsdf, Le), OracleScene.from_arrays(types, verts, tilted, bsdf, Le))
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert np.all(np.diff(a["cdf"]) > 0)
+    # quads: 0 planar, 1 bent out of its plane by 1e-3 of its diagonal (no emitter), 2 bent by 1e-5 (an emitter)
+    types = np.ones(3, np.int32)
+    verts = np.zeros((3, 4, 3), np.float32)
+    for i in range(3):
+        verts[i] = [(0, 0, 2 * i), (1, 0, 2 * i), (1, 1, 2 * i), (0, 1, 2 * i)]
+    verts[1, 2, 2] += 1e-3 * np.sqrt(2.0); verts[2, 2, 2] += 1e-5 * np.sqrt(2.0)
+    nq = np.tile(np.float32([[0, 0, 1]]), (3, 1))
+    Le = np.ones((3, 3), np.float32); Le[0] = 1e9                          # quad 2's weight is absorbed behind quad 0's
+    args = (types, verts, nq, np.full((3, 3), 0.5, np.float32), Le)
+    got = check(ptmi.HostScene.from_arrays(*args), OracleScene.from_arrays(*args))
+    assert got["prim"].tolist() == [0] and got["pdf_area"][1] == 0 and got["pdf_area"][2] == 0
+    Le[0] = 1.0
+    args = (types, verts, nq, np.full((3, 3), 0.5, np.float32), Le)
+    got = check(ptmi.HostScene.from_arrays(*args), OracleScene.from_arrays(*args))
+    assert got["prim"].tolist() == [0, 2]
+
+
 def test_count_alone_and_null_scene():
     hs = ptmi.HostScene.load(os.path.join(SCENES, "cbox.obj"))
     n = C.c_int(-1)
