@@ -1,0 +1,73 @@
+// bounce_sync.hip — ptmi_bounce, the segment-synchronous bounce kernel (scenes up to 64 primitives, and the deep-tree fallback).
+// Compile with -ffp-contract=off (kernels.hip).
+#include "bounce.h"
+
+namespace ptmi {
+
+// ---- ptmi_bounce: segment-synchronous form (SWEEP and STACK walks) ------------------------------------------------
+// Every wave traces one ray segment per lane, then shades, K times.  LDS: [nodes | prims | mats] when LDS_GEOM (always
+// for SWEEP), then the traversal stacks (STACK only).
+// amdgpu_num_sgpr(80): with <= 80 SGPRs eight 256-thread workgroups fit a CU instead of six
+// (MI355X_MICROARCH.md, residency rule); measured +2.4 %, no spills.
+// GUIDED instantiations would take ~100 VGPRs (4 waves per SIMD); capped at 80 (6 waves, 68 bytes of spills): grid
+// sampling +13 %, MIS +9 % on the benchmark frame (5 waves +8 %, 7 the same as 6, 8 waves +10 % / +3 %).
+template <int MODE, bool LDS_GEOM, bool HAS_QUADS, bool STATS, bool GUIDED, bool BATCH>
+__device__ __forceinline__ void bounce_body(const BounceArgs& a) {
+    extern __shared__ float4 smem[];
+    static_assert(MODE != TRAVERSAL_SWEEP || LDS_GEOM, "the sweep reads the scene through LDS broadcasts");
+    const int n_in = a.count_in ? *a.count_in : a.n_in;
+    if ((int)(blockIdx.x * kBlock) >= n_in) return;      // grid was sized from a stale (larger) count: nothing to do
+    const int idx = blockIdx.x * kBlock + threadIdx.x;
+    const bool active = idx < n_in;
+    const float4 *nodes, *prims, *mats;
+    float4* lds = stage_scene<LDS_GEOM>(a.sc, smem, nodes, prims, mats);
+    int* stack = reinterpret_cast<int*>(lds) + threadIdx.x;
+    if (GUIDED) fill_grid_solid_angles();
+
+    const int slot = active ? (a.queue_in ? a.queue_in[idx] : idx) : 0;
+    bool alive = active;
+    PathRegs p = {};
+    if (active) load_path(a.st, a.tm, slot, p);
+    LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
+
+    for (int seg = 0; seg < a.segments; seg++) {
+        if (!__any(alive)) break;
+        // the whole wave enters the traversal together (finished lanes ride along masked): required by SWEEP
+        float t = 0.0f; int k = -1;
+        if (STATS && alive) cn.rays++;
+        const bool hit = scene_intersect<MODE, HAS_QUADS, STATS>(nodes, prims, a.sc.prim_stride, a.sc.n_nodes, stack, alive,
+                                                               p.o, p.d, 1e-4f, FLT_MAX, t, k, cn);
+        if (alive) alive = shade_step<STATS, GUIDED, false, BATCH>(a.fp, a.tm, MatSource{mats, nullptr, nullptr}, a.sc.cdfs, p, hit, t, k, cn, slot);
+    }
+
+    if (active) store_path(a.st, slot, p);
+    finish_launch<STATS>(a, alive, slot, cn);
+}
+template <int MODE, bool LDS_GEOM, bool HAS_QUADS, bool STATS, bool GUIDED, bool BATCH>
+__global__ __launch_bounds__(kBlock, GUIDED ? 6 : (BATCH && MODE == TRAVERSAL_SWEEP ? 8 : 1)) __attribute__((amdgpu_num_sgpr(80))) void ptmi_bounce(BounceArgs a) {
+    bounce_body<MODE, LDS_GEOM, HAS_QUADS, STATS, GUIDED, BATCH>(a);
+    publish_count(a);
+}
+
+// SWEEP exists only with the scene in LDS; LANE and STACK in both forms
+BounceKernel select_bounce_sync(const BounceArgs& a) {
+    const auto pick = [&](auto mode, auto geom) {
+        return with_bool(a.sc.has_quads, [&](auto quads) {
+            return with_bool(a.stats != nullptr, [&](auto stats) {
+                return with_bool(is_guided(a), [&](auto guided) {
+                    return with_bool(a.fp.n_frames > 1, [&](auto batch) -> BounceKernel {
+                        return ptmi_bounce<decltype(mode)::value, decltype(geom)::value, decltype(quads)::value, decltype(stats)::value,
+                                           decltype(guided)::value, decltype(batch)::value>;
+                    });
+                });
+            });
+        });
+    };
+    switch (a.sc.traversal) {
+        case TRAVERSAL_SWEEP: return pick(std::integral_constant<int, TRAVERSAL_SWEEP>{}, std::true_type{});
+        case TRAVERSAL_LANE: return with_bool(a.sc.lds_resident, [&](auto geom) { return pick(std::integral_constant<int, TRAVERSAL_LANE>{}, geom); });
+        default: return with_bool(a.sc.lds_resident, [&](auto geom) { return pick(std::integral_constant<int, TRAVERSAL_STACK>{}, geom); });
+    }
+}
+
+}  // namespace ptmi

@@ -1,0 +1,184 @@
+// debug_hooks.hip — the test hooks: the render kernels' own device functions (traversal.h, shading.h), one call per case.
+// Compile with -ffp-contract=off (kernels.hip).
+#include "shading.h"
+
+namespace ptmi {
+
+// ---------------------------------------------------------------------------------------------
+// test hooks
+// ---------------------------------------------------------------------------------------------
+template <int MODE, bool HAS_QUADS>
+__global__ __launch_bounds__(kBlock) void ptmi_debug_intersect_k(DeviceScene sc, int n, const float* o, const float* d, float t_min,
+                                                                 float t_max, int* hit, int* prim, float* t_out, float* p_out, float* n_out) {
+    extern __shared__ float4 smem[];
+    int* stack = reinterpret_cast<int*>(smem) + threadIdx.x;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = i < n;
+    const int j = live ? i : 0;
+    const f3 ro = mk3(o[3 * j], o[3 * j + 1], o[3 * j + 2]), rd = mk3(d[3 * j], d[3 * j + 1], d[3 * j + 2]);
+    LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
+    float t = 0.0f; int k = -1;
+    const bool h = scene_intersect<MODE, HAS_QUADS, false>(sc.nodes, sc.prims, sc.prim_stride, sc.n_nodes, stack, live, ro, rd, t_min, t_max, t, k, cn);
+    if (!live) return;
+    hit[i] = h ? 1 : 0;
+    prim[i] = h ? __float_as_int(sc.mats[3 * k].w) : -1;
+    t_out[i] = h ? t : 0.0f;
+    const f3 p = h ? ro + t * rd : mk3(0, 0, 0);
+    const f3 nn = h ? xyz(sc.mats[3 * k]) : mk3(0, 0, 0);
+    p_out[3 * i] = p.x; p_out[3 * i + 1] = p.y; p_out[3 * i + 2] = p.z;
+    n_out[3 * i] = nn.x; n_out[3 * i + 1] = nn.y; n_out[3 * i + 2] = nn.z;
+}
+
+void launch_debug_intersect(const DeviceScene& sc, int n, const float* o, const float* d, float t_min, float t_max,
+                            int* hit, int* prim, float* t, float* p, float* nrm, hipStream_t s) {
+    if (n <= 0) return;
+    const size_t lds = (size_t)sc.stack_entries * kBlock * sizeof(int);
+    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+    const int walk = sc.traversal == TRAVERSAL_PHASED || sc.traversal == TRAVERSAL_PACKED || sc.traversal == TRAVERSAL_CERTIFIED ? TRAVERSAL_LANE : sc.traversal;   // the phased kernels walk like LANE
+    const auto launch = [&](auto mode) {
+        with_bool(sc.has_quads, [&](auto quads) {
+            hipLaunchKernelGGL((ptmi_debug_intersect_k<decltype(mode)::value, decltype(quads)::value>), grid, block, lds, s, sc, n, o, d, t_min, t_max, hit, prim, t, p, nrm);
+        });
+    };
+    if (walk == TRAVERSAL_SWEEP) launch(std::integral_constant<int, TRAVERSAL_SWEEP>{});
+    else if (walk == TRAVERSAL_LANE) launch(std::integral_constant<int, TRAVERSAL_LANE>{});
+    else launch(std::integral_constant<int, TRAVERSAL_STACK>{});
+}
+
+// Closest hit through the fast tree for n rays (test hook): wide_closest_hit, the walk of the Radiosity view and the features
+template <bool QUADS>
+__global__ __launch_bounds__(kBlock) void ptmi_debug_intersect_wide_k(DeviceScene sc, int n, const float* o, const float* d, float t_min,
+                                                                      float t_max, int* hit, int* prim, float* t_out,
+                                                                      unsigned long long* counts /* [0] node visits [1] triangle tests */) {
+    extern __shared__ float4 smem[];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const f3 ro = mk3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+    float closest_t = t_max;
+    bool tie = false;
+    WideCounts wc = {0, 0};
+    const int slot_hit = wide_closest_hit<QUADS, true>(sc, reinterpret_cast<uint2*>(smem) + threadIdx.x, ro, rd, t_min, closest_t, tie, wc);
+    hit[i] = slot_hit >= 0 ? 1 : 0;
+    prim[i] = slot_hit >= 0 ? sc.wload_index[slot_hit] : -1;
+    t_out[i] = slot_hit >= 0 ? closest_t : 0.0f;
+    if (counts) { atomicAdd(&counts[0], (unsigned long long)wc.node_visits); atomicAdd(&counts[1], (unsigned long long)wc.prim_tests); }
+}
+void launch_debug_intersect_wide(const DeviceScene& sc, int n, const float* o, const float* d, float t_min, float t_max,
+                                 int* hit, int* prim, float* t, unsigned long long* counts, hipStream_t s) {
+    if (n <= 0) return;
+    const size_t lds = (size_t)sc.w_depth * kBlock * sizeof(uint2);
+    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+    with_bool(sc.has_quads, [&](auto quads) {
+        hipLaunchKernelGGL(ptmi_debug_intersect_wide_k<decltype(quads)::value>, grid, block, lds, s, sc, n, o, d, t_min, t_max, hit, prim, t, counts);
+    });
+}
+
+__global__ void ptmi_debug_rng_k(const uint32_t* __restrict__ jump, unsigned long long seed_base, int n_pixels,
+                                 const int* pixels, int count, float* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    const unsigned int pix = (unsigned int)pixels[i];
+    const unsigned long long seed = seed_base + (unsigned long long)pix;
+    const uint32_t s0 = ((uint32_t)seed) ^ 0xaad26b49u, s1 = (uint32_t)(seed >> 32) ^ 0xf7dcefddu;
+    const uint32_t t0 = 1099087573u * s0, t1 = 2591861531u * s1;
+    uint32_t v[5] = {123456789u + t0, 362436069u ^ t0, 521288629u + t1, 88675123u ^ t1, 5783321u + t0};
+    for (int k = 0; k < 32; k++) {
+        if (!((pix >> k) & 1u)) continue;
+        uint32_t r[5] = {0, 0, 0, 0, 0};
+        for (int w = 0; w < 5; w++)
+            for (int b = 0; b < 32; b++)
+                if ((v[w] >> b) & 1u) for (int c = 0; c < 5; c++) r[c] ^= jump[(k * 160 + w * 32 + b) * 5 + c];
+        for (int w = 0; w < 5; w++) v[w] = r[w];
+    }
+    Rng rng = {v[0], v[1], v[2], v[3], v[4], 6615241u + t1 + t0};
+    for (int c = 0; c < count; c++) out[(size_t)i * count + c] = rng_uniform(rng);
+}
+
+void launch_debug_rng(const uint32_t* d_jump, uint64_t seed_base, int n_pixels, const int* pixels, int count, float* out, hipStream_t s) {
+    if (n_pixels <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_rng_k, dim3((n_pixels + 63) / 64), dim3(64), 0, s, d_jump, (unsigned long long)seed_base,
+                       n_pixels, pixels, count, out);
+}
+
+// exhaustive check of rcp_exact_normal against the IEEE quotient over a range of bit patterns
+__global__ void ptmi_debug_rcp_k(unsigned int first, unsigned long long count, unsigned long long* out /* [0]=mismatches [1]=first bad bits+1 */) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    unsigned long long bad = 0, first_bad = ~0ull;
+    for (unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < count; i += stride) {
+        const unsigned int bits = first + (unsigned int)i;
+        const float a = __uint_as_float(bits);
+        const float want = 1.0f / a, got = rcp_exact_normal(a);
+        if (__float_as_uint(want) != __float_as_uint(got) && !(want != want && got != got)) { bad++; if (first_bad == ~0ull) first_bad = bits; }
+    }
+    if (bad) { atomicAdd(&out[0], bad); atomicMin(&out[1], first_bad); }
+}
+void launch_debug_rcp(unsigned int first, unsigned long long count, unsigned long long* d_out, hipStream_t s) {
+    hipLaunchKernelGGL(ptmi_debug_rcp_k, dim3(4096), dim3(256), 0, s, first, count, d_out);
+}
+
+__global__ void ptmi_debug_cosine_k(int n, const float* normals, const float* u, const float* v, float* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 r = cosine_hemisphere(mk3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]), u[i], v[i]);
+    out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+}
+
+void launch_debug_cosine(int n, const float* normals, const float* u, const float* v, float* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_cosine_k, dim3((n + 255) / 256), dim3(256), 0, s, n, normals, u, v, out);
+}
+
+// Guided sampling per call (test hook): the bounce kernels' own cosine_hemisphere, grid_sample, grid_compute_pdf, sample_mis,
+// mis_power_heuristic and resolve_pixel on n cases, each drawing from its own XORWOW state (6 words: v0..v4, d).  The tests
+// pass states whose next raw outputs are scripted words and d = 0, so used[i] = d / 362437 counts the draws a call made.
+//   op 0 cosine_hemisphere(normal, u, v), u and v drawn as integrator.h:63-64 draws them   -> out[0..2] direction
+//   op 1 grid_sample(record, normal)                                                      -> direction, out[3] pdf
+//   op 2 grid_compute_pdf(record, dir = in3, normal)                                      -> out[3] pdf
+//   op 3 sample_mis(record, normal, bsdf_prob = in3[0])                                   -> direction, out[3] weight
+//   op 4 mis_power_heuristic(in3[0], in3[1])                                              -> out[3]
+//   op 5 resolve_pixel(colour = in3, k = 1)                                               -> out[0..2] rgb8, out[3..5] radiance
+// recs: records of kCdfDwords words, rec_idx[i] picks case i's (ops 1-3 only; the host checks the indices).  out: 6 per case.
+__global__ __launch_bounds__(kBlock) void ptmi_debug_guided_k(int n, int op, const float* __restrict__ recs, const int* __restrict__ rec_idx,
+                                                              const float* __restrict__ normals, const float* __restrict__ in3,
+                                                              const uint32_t* __restrict__ states, float* __restrict__ out,
+                                                              int* __restrict__ used) {
+    fill_grid_solid_angles();
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* s = states + (size_t)i * 6;
+    Rng rng = {s[0], s[1], s[2], s[3], s[4], s[5]};
+    const f3 nrm = mk3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]);
+    const f3 a = mk3(in3[3 * i], in3[3 * i + 1], in3[3 * i + 2]);
+    const float* g = (op >= 1 && op <= 3) ? recs + (size_t)rec_idx[i] * kCdfDwords : nullptr;
+    float r[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    f3 dir = mk3(0.0f, 0.0f, 0.0f);
+    if (op == 0) {
+        const float u = rng_uniform(rng);
+        const float v = rng_uniform(rng);
+        dir = cosine_hemisphere(nrm, u, v);
+    } else if (op == 1) {
+        dir = grid_sample(g, nrm, rng, r[3]);
+    } else if (op == 2) {
+        r[3] = grid_compute_pdf(g, a, nrm);
+    } else if (op == 3) {
+        dir = sample_mis(g, nrm, rng, r[3], a.x);
+    } else if (op == 4) {
+        r[3] = mis_power_heuristic(a.x, a.y);
+    } else if (op == 5) {
+        unsigned char rgb[3];
+        resolve_pixel(make_float4(a.x, a.y, a.z, 0.0f), 1.0f, 0, rgb, &r[3]);
+        dir = mk3((float)rgb[0], (float)rgb[1], (float)rgb[2]);
+    }
+    r[0] = dir.x; r[1] = dir.y; r[2] = dir.z;
+    for (int c = 0; c < 6; c++) out[(size_t)i * 6 + c] = r[c];
+    used[i] = (int)(rng.d / 362437u);
+}
+
+void launch_debug_guided(int n, int op, const float* recs, const int* rec_idx, const float* normals, const float* in3,
+                         const uint32_t* states, float* out, int* used, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_guided_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n, op, recs, rec_idx, normals, in3,
+                       states, out, used);
+}
+
+}  // namespace ptmi

@@ -68,7 +68,7 @@ struct DeviceScene {
     const float4* wmtab = nullptr;     // distinct (Kd, Ke) pairs, 2 float4 per row
     const int* wload_index = nullptr;  // fast order -> load-order primitive index
     const int* wref_slot = nullptr;    // fast order -> reference leaf-order slot (equal-t hits keep the smaller one, scene.h:89-90)
-    // TRAVERSAL_CERTIFIED: what the VERIFY phase and the fallback read (kernels.hip: bounce_wide_body, CERT)
+    // TRAVERSAL_CERTIFIED: what the VERIFY phase and the fallback read (bounce_wide.hip: ptmi_bounce_wide, CERT)
     const uint4* wanc = nullptr;       // per reference leaf: its ancestors' pre-order node indices (leaf included), 4 per chunk, 0xffffffff pads
     const float4* wqprims = nullptr;   // scenes with quads: 64-byte records (v0 | type, e1, e2, e3) in the fast tree's order instead of wprims
     const float4* wcert = nullptr;     // kWideCertStride float4 per fast-order triangle, one 64-byte line per hit: (leaf box min, bits(first chunk << 5 |
@@ -144,7 +144,7 @@ struct StatCounters { unsigned long long rays, node_visits, prim_tests, hits, to
 constexpr int kBlock = 256;
 constexpr int kXorwowJumpWords = 32 * 160 * 5;   // 32 matrices T^(2^67 * 2^k), 160 rows of 5 words
 
-// ---- launchers (kernels.hip) ------------------------------------------------
+// ---- launchers (kernels.hip; the Radiosity view, the features and NEE: first_hit.hip; the hooks: debug_hooks.hip) ------------------------------------------------
 // render_init (integrator.h:274-280): seeds every local pixel's stream and clears its state.
 void launch_render_init(const TileMap& tm, const PathState& st, const uint32_t* d_jump, uint64_t seed_base, hipStream_t s);
 // First camera ray of the frame for every local pixel (sample 0 of the spp loop, integrator.h:383-387).

@@ -1,0 +1,254 @@
+// first_hit.hip — the kernels that trace one ray at a time to its first hit (traversal.h: first_hit): the Radiosity view, the
+// feature pass and next-event estimation.  Compile with -ffp-contract=off (kernels.hip).
+#include "shading.h"
+#include "prim_sample.h"
+
+namespace ptmi {
+
+// The first-hit walk of the Radiosity view and the feature pass: MODE TRAVERSAL_CERTIFIED the certified walk (scenes above the
+// sweep's 64 primitives: the 8-wide tree + the proof per hit, else the reference's walk - the reference's hit for every ray);
+// TRAVERSAL_LANE / TRAVERSAL_STACK the reference's walk.  f(integral_constant MODE, integral_constant HAS_QUADS, LDS bytes).
+template <typename F>
+static void first_hit_walk(const DeviceScene& sc, F&& f) {
+    const bool deep = sc.traversal == TRAVERSAL_STACK;                                // per-lane walk from global memory; stack only for deep trees
+    const bool cert = sc.traversal == TRAVERSAL_CERTIFIED && sc.certified_ready();
+    const size_t lds = cert ? (size_t)sc.w_depth * kBlock * sizeof(uint2) : deep ? (size_t)sc.stack_entries * kBlock * sizeof(int) : 0;
+    auto with_quads = [&](auto mode) { with_bool(sc.has_quads, [&](auto quads) { f(mode, quads, lds); }); };
+    if (cert) with_quads(std::integral_constant<int, TRAVERSAL_CERTIFIED>{});
+    else if (deep) with_quads(std::integral_constant<int, TRAVERSAL_STACK>{});
+    else with_quads(std::integral_constant<int, TRAVERSAL_LANE>{});
+}
+
+// ---------------------------------------------------------------------------------------------
+// render_radiosity (integrator.h:460-504): a visualisation pass, one thread per pixel, not performance-critical; the walk: first_hit_walk
+// ---------------------------------------------------------------------------------------------
+template <int MODE, bool HAS_QUADS>
+__global__ __launch_bounds__(kBlock) void ptmi_render_radiosity(DeviceScene sc, TileMap tm, PathState st, FrameParams fp,
+                                                                unsigned char* __restrict__ rgb8, float* __restrict__ radiance) {
+    extern __shared__ float4 smem[];
+    const int n = tm.local_rows * tm.width;
+    const int slot = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = slot < n;
+    int x = 0, y = 0;
+    Rng rng = {0, 0, 0, 0, 0, 0};
+    if (live) {
+        global_pixel(tm, slot, x, y);
+        const uint4 e = st.E[slot]; const uint2 f = st.F[slot];
+        rng = Rng{e.x, e.y, e.z, e.w, f.x, f.y};                                      // curandState local_rng = rand_state[pixel_index]
+    }
+    f3 color = mk3(0.0f, 0.0f, 0.0f);
+    LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
+    for (int s = 0; s < fp.spp; s++) {
+        f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
+        if (live) camera_ray(fp, tm, x, y, rng, o, d);
+        float t = 0.0f; int k = -1;
+        const bool hit = first_hit<MODE, HAS_QUADS>(sc, smem, live, o, d, 1e-4f, t, k, cn);
+        if (live && hit) {
+            color = color + xyz(sc.mats[3 * k + 2]);                                  // color += si.Le
+            color = color + (sc.radiosity ? xyz(sc.radiosity[k]) : mk3(0.0f, 0.0f, 0.0f));   // color += prim->getRadiosity()
+        }
+    }
+    if (!live) return;
+    const float kk = rcp_rn((float)fp.spp);
+    const float c[3] = {color.x * kk, color.y * kk, color.z * kk};
+    int ox, olr;
+    slot_to_local(tm, slot, ox, olr);
+    const size_t out = (size_t)olr * (size_t)tm.width + (size_t)ox;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        if (radiance) radiance[out * 3 + ch] = c[ch];
+        if (rgb8) rgb8[out * 3 + ch] = (unsigned char)(255.99f * sqrt_rn(fminf(c[ch], 1.0f)));
+    }
+    st.E[slot] = make_uint4(rng.v0, rng.v1, rng.v2, rng.v3);                          // rand_state[pixel_index] = local_rng
+    st.F[slot] = make_uint2(rng.v4, rng.d);
+}
+
+void launch_render_radiosity(const DeviceScene& sc, const TileMap& tm, const PathState& st, const FrameParams& fp,
+                             unsigned char* rgb8, float* radiance, hipStream_t s) {
+    const int n = tm.local_rows * tm.width;
+    if (n <= 0) return;
+    first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
+        hipLaunchKernelGGL((ptmi_render_radiosity<decltype(mode)::value, decltype(quads)::value>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s,
+                           sc, tm, st, fp, rgb8, radiance);
+    });
+}
+
+// ---------------------------------------------------------------------------------------------
+// feature pass (include/ptmi.h: ptmi_render_features): g x g camera rays per local pixel through the stratum centres, first
+// hit by the walk of the Radiosity view (the reference's hit for every ray), no RNG.  One thread per local pixel, local
+// row-major; sums in stratum order (row j of the strata outer, column i inner), then x rcp_rn((float)(g * g)).
+// ---------------------------------------------------------------------------------------------
+template <int MODE, bool HAS_QUADS>
+__global__ __launch_bounds__(kBlock) void ptmi_features(DeviceScene sc, TileMap tm, FrameParams fp, int g, FeatureBuffers fb) {
+    extern __shared__ float4 smem[];
+    const int n = tm.local_rows * tm.width;
+    const int idx = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = idx < n;
+    const int lr = live ? idx / tm.width : 0;
+    const int x = live ? idx - lr * tm.width : 0;
+    const int y = ((lr / tm.row_block) * tm.n_ranks + tm.rank) * tm.row_block + (lr % tm.row_block);
+    const float gf = (float)g;
+    f3 alb = mk3(0.0f, 0.0f, 0.0f), nrm = mk3(0.0f, 0.0f, 0.0f), pos = mk3(0.0f, 0.0f, 0.0f);
+    float hits = 0.0f;
+    LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
+    for (int j = 0; j < g; j++) {
+        for (int i = 0; i < g; i++) {
+            const float u = ((float)x + ((float)i + 0.5f) / gf) / (float)tm.width;
+            const float v = ((float)y + ((float)j + 0.5f) / gf) / (float)tm.height;
+            f3 o, d;
+            camera_ray_uv(fp, u, v, o, d);
+            float t = 0.0f; int k = -1;
+            const bool hit = first_hit<MODE, HAS_QUADS>(sc, smem, live, o, d, 1e-4f, t, k, cn);
+            if (live && hit) {
+                alb = alb + xyz(sc.mats[3 * k + 1]);
+                nrm = nrm + xyz(sc.mats[3 * k]);
+                pos = pos + (o + t * d);
+                hits = hits + 1.0f;
+            }
+        }
+    }
+    if (!live) return;
+    const float kk = rcp_rn((float)(g * g));
+    fb.albedo[idx] = make_float4(alb.x * kk, alb.y * kk, alb.z * kk, hits * kk);
+    fb.normal[idx] = make_float4(nrm.x * kk, nrm.y * kk, nrm.z * kk, 0.0f);
+    fb.position[idx] = make_float4(pos.x * kk, pos.y * kk, pos.z * kk, 0.0f);
+}
+
+void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams& fp, int g, const FeatureBuffers& fb, hipStream_t s) {
+    const int n = tm.local_rows * tm.width;
+    if (n <= 0) return;
+    first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
+        hipLaunchKernelGGL((ptmi_features<decltype(mode)::value, decltype(quads)::value>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, tm, fp, g, fb);
+    });
+}
+
+// ---------------------------------------------------------------------------------------------
+// next-event estimation with MIS (include/ptmi.h: ptmi_config.next_event; the contract, float for float, is written there).
+// One lane per queued pixel runs n_frames x spp samples to their end, so a pixel's sums are added in sample order.  Path rays
+// and shadow rays go through ONE call site of first_hit_walk's walk (the reference's hit for every ray): a lane alternates
+// between its path ray and the shadow ray of the vertex it has just shaded, whose contribution is computed before the walk
+// and added if the walk's closest hit is the sampled emitter.  Every RNG draw of a vertex - Russian roulette, u_sel, r1, r2,
+// u, v - is made before its shadow ray is traced, in the contract's order, so visibility never moves a draw.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int emitter_select(const EmitterTable& em, float u) {
+    const float target = u * em.total;                       // u in (0, 1]: target <= total = cdf[n - 1]
+    int lo = 0, hi = em.n - 1;
+    while (lo < hi) {                                        // smallest j with target <= cdf[j]
+        const int mid = (lo + hi) >> 1;
+        if (target <= em.cdf[mid]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+// cos / M_PI of the reference's pdf_bsdf (integrator.h:128): a binary64 quotient rounded to float
+__device__ __forceinline__ float cos_over_pi(float c) { return (float)((double)c / PTMI_PI_D); }
+
+template <int MODE, bool HAS_QUADS>
+__global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, EmitterTable em, TileMap tm, PathState st, FrameParams fp,
+                                                          const int* __restrict__ queue, int n, int first) {
+    extern __shared__ float4 smem[];
+    const int idx = blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= n) return;                                    // the walks are per lane: no barrier below
+    const int slot = queue ? queue[idx] : idx;
+    int x, y;
+    global_pixel(tm, slot, x, y);
+    const uint4 e = st.E[slot]; const uint2 f = st.F[slot];
+    Rng rng = {e.x, e.y, e.z, e.w, f.x, f.y};
+    f3 color = first ? mk3(0.0f, 0.0f, 0.0f) : xyz(st.D[slot]);
+    LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
+    for (int frame = 0; frame < fp.n_frames; frame++) {
+        if (frame > 0) {                                     // frame batch: bank the previous frame's sum, as shade_step does
+            fp.frame_color[(unsigned int)(frame - 1) * (unsigned int)fp.n_local + (unsigned int)slot] = make_float4(color.x, color.y, color.z, 0.0f);
+            color = mk3(0.0f, 0.0f, 0.0f);
+        }
+        for (int s = 0; s < fp.spp; s++) {
+            f3 o, d;
+            camera_ray(fp, tm, x, y, rng, o, d);
+            f3 tp = mk3(1.0f, 1.0f, 1.0f), L = mk3(0.0f, 0.0f, 0.0f);
+            float pb_prev = 0.0f;                            // pdf of the cosine sample that made the current path ray
+            int depth = 0;
+            bool shadow = false;                             // the next walk is the shadow ray (so, sd) of the last vertex
+            f3 so = o, sd = d, contrib = mk3(0.0f, 0.0f, 0.0f);
+            int s_slot = -1;
+            while (true) {
+                const f3 ro = shadow ? so : o, rd = shadow ? sd : d;
+                float t = 0.0f; int k = -1;
+                const bool hit = first_hit<MODE, HAS_QUADS>(sc, smem, true, ro, rd, 1e-4f, t, k, cn);
+                if (shadow) {                                // visible iff the closest hit is the sampled emitter
+                    if (hit && k == s_slot) L = L + contrib;
+                    shadow = false;
+                    continue;
+                }
+                if (!hit) break;                                                          // integrator.h:198-201
+                const f3 nrm = xyz(sc.mats[3 * k]), bsdf = xyz(sc.mats[3 * k + 1]), Le = xyz(sc.mats[3 * k + 2]);
+                const f3 hp = o + t * d;                                                  // triangle.h:90
+                const float4 pe = depth > 0 ? em.pdf_area[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                const float pa = pe.w;
+                if (pa > 0.0f) {                                                          // an emitter found by the BSDF sample
+                    const float p_l = (pa * (t * t)) / fabsf(dot(xyz(pe), d));           // the geometric normal: area -> solid angle
+                    const float w = mis_power_heuristic(pb_prev, p_l);
+                    const f3 c = tp * Le;
+                    L = L + mk3(c.x * w, c.y * w, c.z * w);
+                } else L = L + tp * Le;                                                   // integrator.h:204
+                if (depth > 2) {                                                          // integrator.h:207-212
+                    const float max_tp = fmaxf(tp.x, fmaxf(tp.y, tp.z));
+                    const float rr_prob = fminf(max_tp, 0.95f);
+                    if (rng_uniform(rng) > rr_prob) break;
+                    tp = div_scalar(tp, rr_prob);
+                }
+                tp = tp * bsdf;                                                           // integrator.h:215
+                if (length(tp) < 1e-5f) break;                                            // integrator.h:218
+                const f3 sn = dot(d, nrm) < 0 ? nrm : -nrm;                               // integrator.h:221-222
+                const f3 o2 = hp + 1e-4f * sn;                                            // integrator.h:266
+                if (depth + 1 < fp.max_depth && em.n > 0) {                               // NEE: three draws whatever comes of them
+                    const float u_sel = rng_uniform(rng);
+                    const float r1 = rng_uniform(rng);
+                    const float r2 = rng_uniform(rng);
+                    const float4* rec = em.rec + (size_t)kEmitterStride * (size_t)emitter_select(em, u_sel);
+                    const float4 a0 = rec[0], a1 = rec[1], a2 = rec[2], a3 = rec[3], a4 = rec[4];
+                    Geom g;
+                    g.v0 = xyz(a0); g.v1 = xyz(a1); g.v2 = xyz(a2); g.v3 = xyz(a3);
+                    g.type = __float_as_int(a2.w); g.ratio = a1.w;
+                    const f3 yv = sample_uniform<HAS_QUADS>(g, r1, r2);
+                    const f3 v = yv - o2;
+                    const float dist2 = dot(v, v);
+                    const float dist = sqrt_rn(dist2);
+                    const f3 wi = mk3(v.x / dist, v.y / dist, v.z / dist);
+                    const float cos_s = dot(sn, wi);
+                    const float cos_l = fabsf(dot(xyz(a4), wi));                          // a4: the geometric normal
+                    const float p_l = (a3.w * dist2) / cos_l;
+                    if (cos_s > 0.0f && cos_l > 0.0f && p_l > 0.0f && p_l <= FLT_MAX) {   // a p_l of 0 or inf weighs 0 (no NaN)
+                        const float p_b = cos_over_pi(cos_s);
+                        const float w = (p_b * mis_power_heuristic(p_l, p_b)) / p_l;
+                        const f3 c = tp * xyz(rec[5]);
+                        contrib = mk3(c.x * w, c.y * w, c.z * w);
+                        so = o2; sd = wi; s_slot = __float_as_int(a0.w);
+                        shadow = true;
+                    }
+                }
+                const float u = rng_uniform(rng);                                         // integrator.h:63-64
+                const float vv = rng_uniform(rng);
+                depth++;
+                if (depth >= fp.max_depth) break;                                         // (no shadow ray pending: NEE needs depth + 1 < max_depth)
+                const f3 next = cosine_hemisphere(sn, u, vv);                             // integrator.h:230
+                pb_prev = cos_over_pi(fmaxf(dot(sn, next), 0.0f));
+                o = o2;
+                d = unit_vector(next);
+            }
+            color = color + L;                                                            // integrator.h:390
+        }
+    }
+    st.D[slot] = make_float4(color.x, color.y, color.z, __uint_as_float(0u));
+    st.E[slot] = make_uint4(rng.v0, rng.v1, rng.v2, rng.v3);
+    st.F[slot] = make_uint2(rng.v4, rng.d);
+}
+
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const TileMap& tm, const PathState& st, const FrameParams& fp,
+                       const int* queue, int n, bool first, hipStream_t s) {
+    if (n <= 0) return;
+    first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
+        hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s,
+                           sc, em, tm, st, fp, queue, n, first ? 1 : 0);
+    });
+}
+
+}  // namespace ptmi

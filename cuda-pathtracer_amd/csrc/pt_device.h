@@ -1,4 +1,4 @@
-// pt_device.h — device helpers shared by the render kernels (kernels.hip) and the radiosity pre-pass (radiosity.hip).
+// pt_device.h — device helpers shared by the render kernels (kernels.hip and the files it lists) and the radiosity pre-pass (radiosity.hip).
 // Compile with -ffp-contract=off (see include/ptmi_math.h, pt_vec.h).
 #pragma once
 #include "device_scene.h"

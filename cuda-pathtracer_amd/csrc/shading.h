@@ -1,0 +1,294 @@
+// shading.h — what a render kernel does between two walks, each defined once: slot <-> pixel, the camera ray, the per-lane path
+// registers, the reference's sampling functions (cosine hemisphere, grid, MIS) and shade_step, one iteration of integrator()'s
+// depth loop.  Everything is __forceinline__ into the calling kernel.
+#pragma once
+#include "pt_device.h"
+#include "traversal.h"
+
+namespace ptmi {
+
+// slot -> (x, local row).  With tile8 a wave's 64 consecutive slots are an 8x8 pixel tile instead of a 64x1 strip:
+// its camera rays span a smaller solid angle and its bounce rays start closer together, so the wave-synchronous
+// sweep visits a smaller union of nodes and primitives.  Pure scheduling: results are keyed by the pixel.
+__device__ __forceinline__ void slot_to_local(const TileMap& tm, int slot, int& x, int& lr) {
+    if (tm.tile8) {
+        const int tile = slot >> 6, in = slot & 63;
+        const int tiles_per_row = tm.width >> 3;
+        const int ty = tile / tiles_per_row, tx = tile - ty * tiles_per_row;
+        lr = (ty << 3) + (in >> 3);
+        x = (tx << 3) + (in & 7);
+    } else {
+        lr = slot / tm.width;
+        x = slot - lr * tm.width;
+    }
+}
+__device__ __forceinline__ int global_pixel(const TileMap& tm, int slot, int& x, int& y) {
+    int lr;
+    slot_to_local(tm, slot, x, lr);
+    y = ((lr / tm.row_block) * tm.n_ranks + tm.rank) * tm.row_block + (lr % tm.row_block);
+    return y * tm.width + x;
+}
+
+// ---------------------------------------------------------------------------------------------
+// camera (sensor.h:31-33 + ray.h:9-12) and the per-sample jitter (integrator.h:384-385)
+// ---------------------------------------------------------------------------------------------
+// get_ray(u, v) of the sensor: the ray through (u, v) of the image plane
+__device__ __forceinline__ void camera_ray_uv(const FrameParams& fp, float u, float v, f3& o, f3& d) {
+    const f3 org = mk3(fp.cam_origin[0], fp.cam_origin[1], fp.cam_origin[2]);
+    const f3 llc = mk3(fp.cam_llc[0], fp.cam_llc[1], fp.cam_llc[2]);
+    const f3 hor = mk3(fp.cam_hor[0], fp.cam_hor[1], fp.cam_hor[2]);
+    const f3 ver = mk3(fp.cam_ver[0], fp.cam_ver[1], fp.cam_ver[2]);
+    o = org;
+    d = unit_vector(llc + u * hor + v * ver - org);
+}
+__device__ __forceinline__ void camera_ray(const FrameParams& fp, const TileMap& tm, int x, int y, Rng& rng, f3& o, f3& d) {
+    const float u = ((float)x + rng_uniform(rng)) / (float)tm.width;
+    const float v = ((float)y + rng_uniform(rng)) / (float)tm.height;
+    camera_ray_uv(fp, u, v, o, d);
+}
+
+// sampleCosineHemisphere (integrator.h:62-85) with the two uniforms already drawn
+__device__ __forceinline__ f3 cosine_hemisphere(f3 n, float u, float v) {
+    const float r = sqrt_rn(u);
+    const float phi = (float)((double)2.0f * PTMI_PI_D * (double)v);      // 2.0f * M_PI * v with a double M_PI
+    float sphi, cphi;
+    ptmi_sincosf(phi, &sphi, &cphi);
+    const float x = r * cphi;
+    const float y = r * sphi;
+    const float z = sqrt_rn(fmaxf(0.0f, 1.0f - u));
+    f3 tangent, bitangent;
+    if (n.z < -0.9999999f) {
+        tangent = mk3(0.0f, -1.0f, 0.0f);
+        bitangent = mk3(-1.0f, 0.0f, 0.0f);
+    } else {
+        const float a = rcp_rn(1.0f + n.z);
+        const float b = -n.x * n.y * a;
+        tangent = mk3(1.0f - n.x * n.x * a, b, -n.x);
+        bitangent = mk3(b, 1.0f - n.y * n.y * a, -n.y);
+    }
+    return unit_vector(x * tangent + y * bitangent + z * n);
+}
+
+// Per-lane path registers (the 88-byte HBM record, unpacked).
+struct PathRegs {
+    f3 o, d, tp, L, color;
+    Rng rng;
+    unsigned int sample_idx;
+    int depth, px, py;
+};
+
+__device__ __forceinline__ void load_path(const PathState& st, const TileMap& tm, int slot, PathRegs& p) {
+    const float4 A = st.A[slot], B = st.B[slot], C = st.C[slot], D = st.D[slot];
+    const uint4 E = st.E[slot]; const uint2 F = st.F[slot];
+    p.o = xyz(A); p.d = xyz(B); p.L = xyz(C); p.color = xyz(D);
+    p.tp = mk3(A.w, B.w, C.w);
+    const unsigned int meta = __float_as_uint(D.w);
+    p.sample_idx = meta >> 8; p.depth = (int)(meta & 0xffu);
+    p.rng = Rng{E.x, E.y, E.z, E.w, F.x, F.y};
+    global_pixel(tm, slot, p.px, p.py);
+}
+__device__ __forceinline__ void store_path(const PathState& st, int slot, const PathRegs& p) {
+    st.A[slot] = make_float4(p.o.x, p.o.y, p.o.z, p.tp.x);
+    st.B[slot] = make_float4(p.d.x, p.d.y, p.d.z, p.tp.y);
+    st.C[slot] = make_float4(p.L.x, p.L.y, p.L.z, p.tp.z);
+    st.D[slot] = make_float4(p.color.x, p.color.y, p.color.z, __uint_as_float((p.sample_idx << 8) | (unsigned int)p.depth));
+    st.E[slot] = make_uint4(p.rng.v0, p.rng.v1, p.rng.v2, p.rng.v3);
+    st.F[slot] = make_uint2(p.rng.v4, p.rng.d);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Guided sampling: Grid over a PrecomputedCDF record (rendering/grid.h), MIS (integrator.h:91-167)
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int linear_search_cdf(const float* __restrict__ cdf, int size, float xi) {   // grid.h:233-240
+    xi = fminf(fmaxf(xi, 0.0f), 0.999999f);
+    int r = size - 1;
+    for (int i = size - 1; i >= 0; i--) if (xi < cdf[i]) r = i;      // first i with xi < cdf[i]
+    return r;
+}
+// The cell's solid angle (grid.h:248-252) depends on theta_idx only: the eight values fmaxf(solid_angle, 1e-6f) are
+// evaluated once per workgroup (fill_grid_solid_angles, same expressions) instead of one binary64 sincos per bounce.
+__shared__ float g_grid_solid_angle[8];
+__device__ __forceinline__ void fill_grid_solid_angles() {     // call from block-uniform code, before the first shade_step
+    if (threadIdx.x < 8) {
+        const int theta_idx = threadIdx.x;
+        const float theta_center = (float)((double)(((float)theta_idx + 0.5f) * 0.125f) * (PTMI_PI_D * 0.5f));
+        float st, ct;
+        ptmi_sincosf(theta_center, &st, &ct);
+        const float sin_theta = fmaxf(st, 0.01f);
+        const float solid_angle = (float)(((double)sin_theta * ((PTMI_PI_D * 0.5f) / 8)) * (2.0f * PTMI_PI_D / 16));
+        g_grid_solid_angle[theta_idx] = fmaxf(solid_angle, 1e-6f);
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ float grid_pdf_for_cell(const float* __restrict__ g, int theta_idx, int phi_idx) {   // grid.h:242-253
+    const float cell_value = g[kCdfPdf + theta_idx * 16 + phi_idx];
+    if (cell_value < 1e-8f) return 1e-6f;
+    const float cell_prob = cell_value / fmaxf(g[kCdfTotal], 1e-6f);
+    return cell_prob / g_grid_solid_angle[theta_idx];
+}
+__device__ __forceinline__ f3 grid_sample(const float* __restrict__ g, f3 normal, Rng& rng, float& out_pdf) {   // grid.h:141-188
+    const float xi1 = rng_uniform(rng);
+    const float xi2 = rng_uniform(rng);
+    const int theta_idx = linear_search_cdf(g + kCdfMarginal, 8, xi1);
+    const int phi_idx = linear_search_cdf(g + kCdfRowCdfs + theta_idx * 16, 16, xi2);
+    const float jitter_theta = rng_uniform(rng);
+    const float jitter_phi = rng_uniform(rng);
+    float theta = (float)((double)(((float)theta_idx + jitter_theta) * 0.125f) * (PTMI_PI_D * 0.5f));
+    theta = fminf(theta, (float)(PTMI_PI_D * 0.5f - (double)0.01f));
+    const float phi = (float)((double)((((float)phi_idx + jitter_phi) * 0.0625f) * 2.0f) * PTMI_PI_D);
+    float sin_t, cos_t, sin_p, cos_p;
+    ptmi_sincosf(theta, &sin_t, &cos_t);
+    ptmi_sincosf(phi, &sin_p, &cos_p);
+    f3 tangent, bitangent;
+    build_frame(normal, tangent, bitangent);
+    const f3 world = unit_vector((sin_t * cos_p) * tangent + (sin_t * sin_p) * bitangent + cos_t * normal);
+    out_pdf = grid_pdf_for_cell(g, theta_idx, phi_idx);
+    return world;
+}
+// vector.h:198-203 to the sign of a zero: the reference's dot starts from `T sum = 0`, so three -0 products give +0, where
+// dot() (pt_vec.h) gives -0.  Only here does that sign reach a result - atan2f(+0, -0) is pi, atan2f(+0, +0) is 0 - e.g. for
+// dir == normal == (-0, 0, -1); everywhere else a dot only meets comparisons and fmaxf(., 0).
+__device__ __forceinline__ float dot_from_zero(f3 a, f3 b) { float s = 0.0f; s += a.x * b.x; s += a.y * b.y; s += a.z * b.z; return s; }
+__device__ __forceinline__ float grid_compute_pdf(const float* __restrict__ g, f3 dir, f3 normal) {   // grid.h:200-216, 299-310
+    f3 tangent, bitangent;
+    build_frame(normal, tangent, bitangent);
+    const float lx = dot_from_zero(dir, tangent), ly = dot_from_zero(dir, bitangent), lz = dot(dir, normal);
+    const float theta = ptmi_acosf(fminf(fmaxf(lz, -1.0f), 1.0f));
+    float phi = ptmi_atan2f(ly, lx);
+    if (phi < 0.0f) phi = (float)((double)phi + (double)2.0f * PTMI_PI_D);
+    if ((double)theta > PTMI_PI_D * 0.5f) return 0.0f;
+    int theta_idx = (int)(((double)theta * ((double)2.0f / PTMI_PI_D)) * 8);
+    int phi_idx = (int)(((double)phi * ((double)0.5f / PTMI_PI_D)) * 16);
+    theta_idx = max(0, min(theta_idx, 7));
+    phi_idx = max(0, min(phi_idx, 15));
+    return grid_pdf_for_cell(g, theta_idx, phi_idx);
+}
+__device__ __forceinline__ float mis_power_heuristic(float pdf_a, float pdf_b) {   // integrator.h:91-96
+    if (pdf_a <= 0.0f) return 0.0f;
+    const float a2 = pdf_a * pdf_a, b2 = pdf_b * pdf_b;
+    return a2 / (a2 + b2);
+}
+__device__ __forceinline__ f3 sample_mis(const float* __restrict__ g, f3 normal, Rng& rng, float& weight, float bsdf_prob) {   // integrator.h:112-167
+    const float BSDF_PROB = fmaxf(fminf(bsdf_prob, 0.99f), 0.01f);
+    const float GRID_PROB = 1.0f - BSDF_PROB;
+    const float xi = rng_uniform(rng);
+    f3 dir;
+    if (xi < BSDF_PROB) {
+        const float u = rng_uniform(rng), v = rng_uniform(rng);
+        dir = cosine_hemisphere(normal, u, v);
+        const float cos_theta = fmaxf(dot(dir, normal), 0.0f);
+        const float pdf_bsdf = (float)((double)cos_theta / PTMI_PI_D);
+        const float pdf_grid = grid_compute_pdf(g, dir, normal);
+        const float mis_w = mis_power_heuristic(pdf_bsdf, pdf_grid);
+        weight = (pdf_bsdf > 1e-6f) ? mis_w / BSDF_PROB : 0.0f;
+    } else {
+        float pdf_grid;
+        dir = grid_sample(g, normal, rng, pdf_grid);
+        const float cos_theta = fmaxf(dot(dir, normal), 0.0f);
+        const float pdf_bsdf = (float)((double)cos_theta / PTMI_PI_D);
+        const float mis_w = mis_power_heuristic(pdf_grid, pdf_bsdf);
+        if (pdf_grid > 1e-6f && cos_theta > 0.0f) {
+            const float w = (float)((double)(mis_w * cos_theta) / ((PTMI_PI_D * (double)pdf_grid) * (double)GRID_PROB));
+            weight = fminf(w, 10.0f);
+        } else weight = 0.0f;
+    }
+    return dir;
+}
+
+// One iteration of integrator()'s depth loop after the intersection (integrator.h:198-266), plus the end of the
+// sample and the head of the next spp iteration (integrator.h:383-390) when the path ends.
+// Returns true while the pixel still has a ray to trace; false once all spp samples are done.
+// GUIDED: the grid / MIS branches of integrator.h:232-263 are compiled in (sampling_mode != SAMPLING_BSDF with CDF
+// records present); the plain BSDF instantiation carries none of that code.
+// Material record of leaf-order slot k: plain layout mats[3k..3k+2], packed layout (normal, table row) + (Kd, Ke) table.
+struct MatSource { const float4* mats; const float4* mtab; const int* load_index; int stride = 1; };      // PACKED: entry k at mats[k * stride]
+template <bool PACKED>
+__device__ __forceinline__ void fetch_material(const MatSource& ms, int k, f3& n, f3& bsdf, f3& Le, int& row) {
+    if (PACKED) {
+        const float4 m = ms.mats[(size_t)k * ms.stride];
+        n = xyz(m); row = __float_as_int(m.w);
+        bsdf = xyz(ms.mtab[2 * row]); Le = xyz(ms.mtab[2 * row + 1]);
+    } else {
+        const float4 m = ms.mats[3 * k];
+        n = xyz(m); row = __float_as_int(m.w);                                    // here: the load-order primitive index
+        bsdf = xyz(ms.mats[3 * k + 1]); Le = xyz(ms.mats[3 * k + 2]);
+    }
+}
+template <bool STATS, bool GUIDED, bool PACKED = false, bool BATCH = false>
+__device__ __forceinline__ bool shade_step(const FrameParams& fp, const TileMap& tm, const MatSource& ms, const float* cdfs, PathRegs& p,
+                                           bool hit, float t, int k, LaneCounters& cn, int slot) {
+    bool end_sample = !hit;                                                       // integrator.h:198-201
+    if (hit) {
+        if (STATS) cn.hits++;
+        f3 n, bsdf, Le; int row;
+        fetch_material<PACKED>(ms, k, n, bsdf, Le, row);
+        const f3 hp = p.o + t * p.d;                                              // triangle.h:90
+        p.L = p.L + p.tp * Le;                                                    // integrator.h:204
+        if (p.depth > 2) {                                                        // integrator.h:207-212
+            const float max_tp = fmaxf(p.tp.x, fmaxf(p.tp.y, p.tp.z));
+            const float rr_prob = fminf(max_tp, 0.95f);
+            if (rng_uniform(p.rng) > rr_prob) end_sample = true;
+            else p.tp = div_scalar(p.tp, rr_prob);
+        }
+        if (!end_sample) {
+            p.tp = p.tp * bsdf;                                                   // integrator.h:215
+            if (length(p.tp) < 1e-5f) end_sample = true;                          // integrator.h:218
+            else {
+                const f3 sn = dot(p.d, n) < 0 ? n : -n;                           // integrator.h:221-222
+                // initGridFromPrimitive (integrator.h:31-57): the primitive's precomputed record, if it is valid
+                const float* g = nullptr;
+                if (GUIDED) {
+                    const float* rec = cdfs + (size_t)(PACKED ? ms.load_index[k] : row) * kCdfDwords;
+                    if (__float_as_int(rec[kCdfValid]) != 0) g = rec;
+                }
+                if (GUIDED && g) {
+                    f3 next;
+                    float weight = 1.0f;
+                    if (fp.sampling_mode == 3) {                                  // SAMPLING_MIS, integrator.h:238-241
+                        next = sample_mis(g, sn, p.rng, weight, fp.mis_bsdf_fraction);
+                    } else {                                                      // pure grid sampling, integrator.h:242-257
+                        float grid_pdf;
+                        next = grid_sample(g, sn, p.rng, grid_pdf);
+                        const float cos_theta = fmaxf(dot(next, sn), 0.0f);
+                        weight = (float)((double)cos_theta / (PTMI_PI_D * (double)fmaxf(grid_pdf, 1e-6f)));
+                        weight = fminf(fmaxf(weight, 0.0f), 10.0f);
+                    }
+                    p.tp = mk3(p.tp.x * weight, p.tp.y * weight, p.tp.z * weight);
+                    p.depth++;
+                    if (p.depth < fp.max_depth) {
+                        p.o = hp + 1e-4f * sn;                                    // integrator.h:266
+                        p.d = unit_vector(next);
+                    } else end_sample = true;
+                } else {                                                          // BSDF mode, or the cosine fallback :258-261
+                    const float u = rng_uniform(p.rng);                           // integrator.h:63-64
+                    const float v = rng_uniform(p.rng);
+                    p.depth++;
+                    if (p.depth < fp.max_depth) {
+                        const f3 next = cosine_hemisphere(sn, u, v);              // integrator.h:230
+                        p.o = hp + 1e-4f * sn;                                    // integrator.h:266
+                        p.d = unit_vector(next);                                  // Ray ctor normalises again
+                    } else end_sample = true;                                     // loop bound; the draws above are still consumed
+                }
+            }
+        }
+    }
+    if (end_sample) {
+        p.color = p.color + p.L;                                                  // integrator.h:390
+        p.sample_idx++;
+        if (!BATCH) {
+            if (p.sample_idx >= (unsigned int)fp.spp) return false;
+        } else if ((p.sample_idx & fp.sample_mask) >= (unsigned int)fp.spp) {     // the spp loop of this frame is through
+            const unsigned int frame = p.sample_idx >> 16;
+            if (frame + 1u >= (unsigned int)fp.n_frames) return false;
+            // frame batch: bank this frame's colour sum and go straight on with the next frame's first sample
+            fp.frame_color[frame * (unsigned int)fp.n_local + (unsigned int)slot] = make_float4(p.color.x, p.color.y, p.color.z, 0.0f);   // < 2^31 (host check)
+            p.sample_idx = (frame + 1u) << 16;
+            p.color = mk3(0.0f, 0.0f, 0.0f);
+        }
+        camera_ray(fp, tm, p.px, p.py, p.rng, p.o, p.d);                          // next iteration of the spp loop
+        p.tp = mk3(1.0f, 1.0f, 1.0f); p.L = mk3(0.0f, 0.0f, 0.0f); p.depth = 0;
+    }
+    return true;
+}
+
+}  // namespace ptmi

@@ -12,22 +12,23 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(_HERE)
 ROOT = os.path.dirname(PKG)
 
-# everything that reaches build/kernels.o (csrc/kernels.hip and what it includes) + the flags it is compiled with
-KERNEL_SOURCES = [
-    os.path.join(PKG, "csrc", "kernels.hip"), os.path.join(PKG, "csrc", "pt_device.h"), os.path.join(PKG, "csrc", "pt_vec.h"),
-    os.path.join(PKG, "csrc", "device_scene.h"), os.path.join(PKG, "csrc", "wide_bvh.h"), os.path.join(ROOT, "include", "ptmi_math.h"),
-    os.path.join(PKG, "Makefile"),
+def _csrc(*names):
+    return [os.path.join(PKG, "csrc", n) for n in names]
+
+
+# what both kernel sets include + the flags they are compiled with
+_SHARED_SOURCES = _csrc("pt_device.h", "pt_vec.h", "device_scene.h", "wide_bvh.h", "wide_walk.h", "prim_sample.h") + [
+    os.path.join(ROOT, "include", "ptmi_math.h"), os.path.join(PKG, "Makefile")]
+# everything that reaches the render kernels' objects (the Makefile's RENDER_HIP and what those files include)
+KERNEL_SOURCES = _csrc("kernels.hip", "bounce_sync.hip", "bounce_phased.hip", "bounce_wide.hip", "first_hit.hip", "debug_hooks.hip",
+                       "traversal.h", "shading.h", "bounce.h") + _SHARED_SOURCES + [
     # the host loop that decides how the kernels are launched (chunks, run-ahead, segments per launch)
     os.path.join(PKG, "host", "application_state.cpp"),
     # the builder of the opt-in fast tree: the tree's shape decides what ptmi_bounce_wide fetches
     os.path.join(PKG, "host", "wide_bvh.cpp"),
 ]
-# everything that reaches build/radiosity.o (the radiosity pre-pass kernels) + its flags + the host code that launches them
-SOLVER_SOURCES = [
-    os.path.join(PKG, "csrc", "radiosity.hip"), os.path.join(PKG, "csrc", "pt_device.h"), os.path.join(PKG, "csrc", "pt_vec.h"),
-    os.path.join(PKG, "csrc", "device_scene.h"), os.path.join(PKG, "csrc", "wide_bvh.h"), os.path.join(ROOT, "include", "ptmi_math.h"),
-    os.path.join(PKG, "Makefile"), os.path.join(PKG, "host", "application_state.cpp"),
-]
+# everything that reaches build/radiosity.o (the radiosity pre-pass kernels) + the host code that launches them
+SOLVER_SOURCES = _csrc("radiosity.hip") + _SHARED_SOURCES + [os.path.join(PKG, "host", "application_state.cpp")]
 
 
 def _sha(paths):

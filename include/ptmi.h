@@ -380,7 +380,7 @@ int ptmi_debug_rng(ptmi_ctx*, uint64_t seed_base, int n_pixels, const int* pixel
 int ptmi_debug_rcp_check(ptmi_ctx*, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad_bits);
 /* sampleCosineHemisphere (integrator.h:62-85) with explicit (u, v). */
 int ptmi_debug_cosine_sample(ptmi_ctx*, int n, const float* normals, const float* u, const float* v, float* out_dirs);
-/* Guided sampling per call, through the bounce kernels' own device functions (kernels.hip: ptmi_debug_guided_k).  Case i
+/* Guided sampling per call, through the bounce kernels' own device functions (debug_hooks.hip: ptmi_debug_guided_k).  Case i
  * draws from XORWOW state states[6i..6i+6) (v0..v4, d); used[i] = draws made, counted from d = 0.  op: 0 sampleCosineHemisphere,
  * 1 Grid::sample, 2 Grid::computePDF (dir = in3), 3 sampleMIS (bsdf_prob = in3[0]), 4 misPowerHeuristic(in3[0], in3[1]),
  * 5 render's tone-map of colour in3.  Ops 1-3 read record rec_idx[i] of the n_recs PrecomputedCDF records (530 words each).

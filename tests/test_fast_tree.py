@@ -304,7 +304,7 @@ def render_vs_oracle(R, o, W, H, spp, depth, cam=None):
 
 @pytest.mark.gpu
 def test_certified_walk_is_exact_and_the_default_of_large_triangle_scenes(R):
-    """TRAVERSAL_CERTIFIED (kernels.hip: bounce_wide_body, CERT): the fast tree's hit + a proof per ray that the reference's walk
+    """TRAVERSAL_CERTIFIED (bounce_wide.hip: ptmi_bounce_wide, CERT): the fast tree's hit + a proof per ray that the reference's walk
     returns the same one, else the reference's walk for that ray.  65 536 triangles (more than the 8 192 nodes from which the
     packed layout is built): the automatic choice must be the certified walk and the frame the oracle's, bit for bit; the share
     of hits that needed the ancestor chain and of rays that were walked again is printed."""

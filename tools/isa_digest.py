@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Per-kernel instruction streams and resource metadata of a source tree's .hip files, to show that moving code between files
+changed no kernel.  No GPU needed.
+
+  python tools/isa_digest.py dump cuda-pathtracer_amd a.json      # compiles every csrc/*.hip for the device only, disassembles
+  python tools/isa_digest.py diff parent.json a.json [--skip SUBSTRING]   # --skip: kernels expected to change; their metadata is listed
+
+dump: every .hip is compiled with the Makefile's flags + --cuda-device-only, unbundled, and for each kernel the disassembly
+(comments stripped, trailing padding ignored) and the AMDGPU metadata note (registers, scratch, LDS, kernarg size) are recorded.
+diff: kernel names missing / new / duplicated, and every kernel whose text or metadata differs.
+"""
+import concurrent.futures
+import hashlib
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+import yaml
+
+ROCM = os.environ.get("ROCM", "/opt/rocm")
+LLVM = os.path.join(ROCM, "llvm", "bin")
+ARCH = os.environ.get("ARCH", "gfx950")
+META = [".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
+        ".group_segment_fixed_size", ".kernarg_segment_size", ".max_flat_workgroup_size", ".wavefront_size"]
+PAD = re.compile(r"^(s_nop 0|s_code_end|\.\.\.)$")
+
+
+def makefile_flags(pkg):
+    with open(os.path.join(pkg, "Makefile")) as f:
+        return re.search(r"^COMMON\s*=\s*(.*)$", f.read(), re.M).group(1).split()
+
+
+def one_file(pkg, src, tmp, flags):
+    base = os.path.join(tmp, os.path.basename(src))
+    subprocess.run([os.path.join(ROCM, "bin", "hipcc"), "--offload-arch=" + ARCH, *flags, "--cuda-device-only", "-c", src, "-o", base + ".o"],
+                   check=True, cwd=pkg)
+    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--" + ARCH,
+                    "--input=" + base + ".o", "--output=" + base + ".co", "--unbundle"], check=True)
+    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", base + ".co"], capture_output=True, text=True, check=True).stdout
+    doc = yaml.safe_load(notes[notes.index("---"):notes.rindex("...")])
+    kernels = {k[".name"]: {m: k.get(m) for m in META} for k in doc.get("amdhsa.kernels", [])}
+    dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", "--no-leading-addr", base + ".co"],
+                         capture_output=True, text=True, check=True).stdout
+    out, name, lines = [], None, []
+
+    def close():
+        if name in kernels:
+            while lines and PAD.match(lines[-1]):
+                lines.pop()
+            out.append({"name": name, "file": os.path.basename(src), "meta": kernels[name], "n": len(lines),
+                        "sha": hashlib.sha256("\n".join(lines).encode()).hexdigest()})
+    for ln in dis.split("\n"):
+        m = re.match(r"^<(.*)>:$", ln.strip())
+        if m:
+            close()
+            name, lines = m.group(1), []
+        elif name:
+            ln = ln.split("//")[0].strip()
+            if ln:
+                lines.append(ln)
+    close()
+    assert len(out) == len(kernels), (src, len(out), len(kernels))
+    return out
+
+
+def dump(pkg, dest, extra):
+    pkg = os.path.abspath(pkg)
+    flags = makefile_flags(pkg) + extra
+    srcs = sorted(os.path.join(pkg, "csrc", f) for f in os.listdir(os.path.join(pkg, "csrc")) if f.endswith(".hip"))
+    with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(int(os.environ.get("JOBS", "4"))) as ex:
+        res = [k for r in ex.map(lambda s: one_file(pkg, s, tmp, flags), srcs) for k in r]
+    with open(dest, "w") as f:
+        json.dump(res, f, indent=0)
+    print("%d kernels in %d files -> %s" % (len(res), len(srcs), dest))
+
+
+def diff(a, b, skip):
+    A, B = json.load(open(a)), json.load(open(b))
+    bad = 0
+    for tag, L in (("parent", A), ("new", B)):
+        names = [k["name"] for k in L]
+        for n in sorted(set(n for n in names if names.count(n) > 1)):
+            print("DUPLICATE in %s: %s" % (tag, n)); bad += 1
+    da, db = {k["name"]: k for k in A}, {k["name"]: k for k in B}
+    for n in sorted(set(da) - set(db)):
+        print("MISSING: %s" % n); bad += 1
+    for n in sorted(set(db) - set(da)):
+        print("NEW: %s" % n); bad += 1
+    same = skipped = 0
+    for n in sorted(set(da) & set(db)):
+        if skip and skip in n:
+            skipped += 1
+            ma, mb = da[n]["meta"], db[n]["meta"]
+            print("CHANGED %s\n    %s" % (n, "  ".join("%s %s->%s" % (m[1:], ma[m], mb[m]) for m in META if ma[m] != mb[m]) or "(metadata equal)"))
+            continue
+        if da[n]["sha"] != db[n]["sha"] or da[n]["meta"] != db[n]["meta"]:
+            print("DIFFERS: %s (%s -> %s)  text %s  meta %s" % (n, da[n]["file"], db[n]["file"], da[n]["sha"] == db[n]["sha"], da[n]["meta"] == db[n]["meta"])); bad += 1
+        else:
+            same += 1
+    print("parent %d kernels, new %d; identical %d, skipped %d, defects %d" % (len(A), len(B), same, skipped, bad))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) >= 4 and sys.argv[1] == "dump":
+        dump(sys.argv[2], sys.argv[3], sys.argv[4:])
+    elif len(sys.argv) >= 4 and sys.argv[1] == "diff":
+        sys.exit(diff(sys.argv[2], sys.argv[3], sys.argv[5] if len(sys.argv) > 5 and sys.argv[4] == "--skip" else None))
+    else:
+        sys.exit(__doc__)
