@@ -814,6 +814,37 @@ int ptmi_debug_guided_sample(ptmi_ctx* c, int op, int n, int n_recs, const float
     });
 }
 
+int ptmi_debug_math(ptmi_ctx* c, int op, int n, const float* a, const float* b, double* out) {
+    return guarded([&] {
+        need(c && a && b && out, "NULL argument");
+        need(n > 0, "n must be positive");
+        need(op >= 0 && op < PTMI_MATH_OPS, "unknown op");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<float> d_a(n), d_b(n);
+        DevBuf<double> d_o(2 * (size_t)n);
+        d_a.upload(a, n); d_b.upload(b, n);
+        launch_debug_math(n, op, d_a.p, d_b.p, d_o.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d_o.download(out, 2 * (size_t)n);
+    });
+}
+
+int ptmi_debug_grid_index(ptmi_ctx* c, int n, const float* dirs, const float* normals, int* out) {
+    return guarded([&] {
+        need(c && dirs && normals && out, "NULL argument");
+        need(n > 0, "n must be positive");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<float> d_d(3 * (size_t)n), d_n(3 * (size_t)n);
+        DevBuf<int> d_o(n);
+        d_d.upload(dirs, 3 * (size_t)n); d_n.upload(normals, 3 * (size_t)n);
+        launch_debug_grid_index(n, d_d.p, d_n.p, d_o.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d_o.download(out, n);
+    });
+}
+
 // ---- progressive and adaptive accumulation ----
 void ptmi_default_adaptive_params(ptmi_adaptive_params* p) {
     if (!p) return;

@@ -1,6 +1,7 @@
 // debug_hooks.hip — the test hooks: the render kernels' own device functions (traversal.h, shading.h), one call per case.
 // Compile with -ffp-contract=off (kernels.hip).
 #include "shading.h"
+#include "../../include/ptmi.h"      // PTMI_MATH_*
 
 namespace ptmi {
 
@@ -179,6 +180,51 @@ void launch_debug_guided(int n, int op, const float* recs, const int* rec_idx, c
     if (n <= 0) return;
     hipLaunchKernelGGL(ptmi_debug_guided_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n, op, recs, rec_idx, normals, in3,
                        states, out, used);
+}
+
+// The numerics contract per call (test hook): include/ptmi_math.h's device build and the IEEE primitives the kernels rely on,
+// one operation on n cases (a[i], b[i]); two doubles per case, float and int results promoted (exact).  op: PTMI_MATH_*.
+__global__ void ptmi_debug_math_k(int n, int op, const float* __restrict__ a_in, const float* __restrict__ b_in, double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float a = a_in[i], b = b_in[i];
+    double r0 = 0.0, r1 = 0.0;
+    float f0 = 0.0f, f1 = 0.0f;
+    switch (op) {
+        case PTMI_MATH_SINCOS_D: ptmi_sincos_d((double)a, &r0, &r1); break;
+        case PTMI_MATH_TAN_D:    r0 = ptmi_tan_d((double)a); break;
+        case PTMI_MATH_LOG_D:    r0 = ptmi_log_d((double)a); break;
+        case PTMI_MATH_EXP_D:    r0 = ptmi_exp_d((double)a); break;
+        case PTMI_MATH_ATAN2_D:  r0 = ptmi_atan2_d((double)a, (double)b); break;
+        case PTMI_MATH_SINCOSF:  ptmi_sincosf(a, &f0, &f1); r0 = (double)f0; r1 = (double)f1; break;
+        case PTMI_MATH_POWF:     r0 = (double)ptmi_powf(a, b); break;
+        case PTMI_MATH_EXPF:     r0 = (double)ptmi_expf(a); break;
+        case PTMI_MATH_ATAN2F:   r0 = (double)ptmi_atan2f(a, b); break;
+        case PTMI_MATH_ACOSF:    r0 = (double)ptmi_acosf(a); break;
+        case PTMI_MATH_DIV:      r0 = (double)(a / b); break;
+        case PTMI_MATH_RCP:      r0 = (double)rcp_rn(a); break;
+        case PTMI_MATH_SQRT:     r0 = (double)sqrt_rn(a); break;
+        case PTMI_MATH_ROUND:    r0 = (double)(float)((double)a * (double)b); break;
+        case PTMI_MATH_TRUNC:    r0 = (double)(int)a; r1 = (double)(int)(double)a; break;
+        default: break;
+    }
+    out[2 * (size_t)i] = r0; out[2 * (size_t)i + 1] = r1;
+}
+void launch_debug_math(int n, int op, const float* a, const float* b, double* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_math_k, dim3((n + 255) / 256), dim3(256), 0, s, n, op, a, b, out);
+}
+
+// direction_to_grid_index_local (pt_device.h), the form-factor kernel's binning, on n (direction, normal) pairs
+__global__ void ptmi_debug_grid_index_k(int n, const float* __restrict__ dirs, const float* __restrict__ normals, int* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = direction_to_grid_index_local(mk3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]),
+                                           mk3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]));
+}
+void launch_debug_grid_index(int n, const float* dirs, const float* normals, int* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_grid_index_k, dim3((n + 255) / 256), dim3(256), 0, s, n, dirs, normals, out);
 }
 
 }  // namespace ptmi

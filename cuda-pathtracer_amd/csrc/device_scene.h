@@ -341,5 +341,7 @@ void launch_debug_rcp(unsigned int first_bits, unsigned long long count, unsigne
 void launch_debug_cosine(int n, const float* normals, const float* u, const float* v, float* out, hipStream_t s);
 void launch_debug_guided(int n, int op, const float* recs, const int* rec_idx, const float* normals, const float* in3,
                          const uint32_t* states, float* out, int* used, hipStream_t s);
+void launch_debug_math(int n, int op, const float* a, const float* b, double* out /* 2n */, hipStream_t s);
+void launch_debug_grid_index(int n, const float* dirs, const float* normals, int* out, hipStream_t s);
 
 }  // namespace ptmi

@@ -120,6 +120,29 @@ __device__ __forceinline__ void build_frame(f3 n, f3& t, f3& b) {               
     b = mk3(c, 1.0f - n.y * n.y * a, -n.y);
 }
 
+// vector.h:198-203 to the sign of a zero: the reference's dot starts from `T sum = 0`, so three -0 products give +0, where
+// dot() (pt_vec.h) gives -0.  Only where a local direction goes into atan2f does that sign reach a result - atan2f(+0, -0) is pi,
+// atan2f(+0, +0) is 0, atan2f(-0, -1) is -pi - i.e. in grid_compute_pdf (shading.h) and direction_to_grid_index_local below, e.g.
+// for dir == -normal == (-1, 0, 0); everywhere else a dot only meets comparisons and fmaxf(., 0).
+__device__ __forceinline__ float dot_from_zero(f3 a, f3 b) { float s = 0.0f; s += a.x * b.x; s += a.y * b.y; s += a.z * b.z; return s; }
+
+// direction_to_grid_indices_local (form_factors.h:107-130): theta over [0, pi] -> 16 rows, phi over [0, 2 pi) -> 16 columns.
+// The form-factor kernel (radiosity.hip) bins with it; here so that the test hook (debug_hooks.hip) calls the same function.
+__device__ __forceinline__ int direction_to_grid_index_local(f3 world_dir, f3 normal) {
+    f3 tangent, bitangent;
+    build_frame(normal, tangent, bitangent);
+    const float lx = dot_from_zero(world_dir, tangent), ly = dot_from_zero(world_dir, bitangent), lz = dot(world_dir, normal);
+    const float r = sqrt_rn(lx * lx + ly * ly + lz * lz);
+    const float theta = (r > 0.0f) ? ptmi_acosf(fminf(lz / r, 1.0f)) : 0.0f;
+    float phi = ptmi_atan2f(ly, lx);
+    if (phi < 0.0f) phi = (float)((double)phi + (double)2.0f * PTMI_PI_D);
+    int grid_theta = (int)fminf((float)(((double)theta / PTMI_PI_D) * kGridRes), (float)(kGridRes - 1));
+    int grid_phi = (int)fminf((float)(((double)phi / ((double)2.0f * PTMI_PI_D)) * kGridRes), (float)(kGridRes - 1));
+    grid_theta = max(0, min(grid_theta, kGridRes - 1));
+    grid_phi = max(0, min(grid_phi, kGridRes - 1));
+    return grid_theta * kGridRes + grid_phi;
+}
+
 // resolve of one pixel (integrator.h:393-407): colour sum x k -> float radiance; Reinhard, gamma 1/2.2, 8 bit -> rgb8 (either
 // output may be nullptr).  The frame and pass resolves (kernels.hip) and the denoiser's tone map (denoise.hip, k = 1) share it.
 __device__ __forceinline__ void resolve_pixel(const float4& D, float k, size_t out, unsigned char* __restrict__ rgb8,

@@ -34,22 +34,6 @@ __device__ __forceinline__ Geom load_geom(const float4* __restrict__ geo, int p)
     return g;
 }
 
-// direction_to_grid_indices_local (form_factors.h:107-130): theta over [0, pi] -> 16 rows, phi over [0, 2 pi) -> 16 columns
-__device__ __forceinline__ int direction_to_grid_index_local(f3 world_dir, f3 normal) {
-    f3 tangent, bitangent;
-    build_frame(normal, tangent, bitangent);
-    const float lx = dot(world_dir, tangent), ly = dot(world_dir, bitangent), lz = dot(world_dir, normal);
-    const float r = sqrt_rn(lx * lx + ly * ly + lz * lz);
-    const float theta = (r > 0.0f) ? ptmi_acosf(fminf(lz / r, 1.0f)) : 0.0f;
-    float phi = ptmi_atan2f(ly, lx);
-    if (phi < 0.0f) phi = (float)((double)phi + (double)2.0f * PTMI_PI_D);
-    int grid_theta = (int)fminf((float)(((double)theta / PTMI_PI_D) * kGridRes), (float)(kGridRes - 1));
-    int grid_phi = (int)fminf((float)(((double)phi / ((double)2.0f * PTMI_PI_D)) * kGridRes), (float)(kGridRes - 1));
-    grid_theta = max(0, min(grid_theta, kGridRes - 1));
-    grid_phi = max(0, min(grid_phi, kGridRes - 1));
-    return grid_theta * kGridRes + grid_phi;
-}
-
 // Primitive::intersect(r, 1e-5f, max_dist) as a yes/no question: triangle.h:82 accepts t <= t_max, quad.h:78,110
 // only t < t_max (closest_t starts at t_max)
 template <bool HAS_QUADS>

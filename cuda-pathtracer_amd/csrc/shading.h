@@ -145,10 +145,6 @@ __device__ __forceinline__ f3 grid_sample(const float* __restrict__ g, f3 normal
     out_pdf = grid_pdf_for_cell(g, theta_idx, phi_idx);
     return world;
 }
-// vector.h:198-203 to the sign of a zero: the reference's dot starts from `T sum = 0`, so three -0 products give +0, where
-// dot() (pt_vec.h) gives -0.  Only here does that sign reach a result - atan2f(+0, -0) is pi, atan2f(+0, +0) is 0 - e.g. for
-// dir == normal == (-0, 0, -1); everywhere else a dot only meets comparisons and fmaxf(., 0).
-__device__ __forceinline__ float dot_from_zero(f3 a, f3 b) { float s = 0.0f; s += a.x * b.x; s += a.y * b.y; s += a.z * b.z; return s; }
 __device__ __forceinline__ float grid_compute_pdf(const float* __restrict__ g, f3 dir, f3 normal) {   // grid.h:200-216, 299-310
     f3 tangent, bitangent;
     build_frame(normal, tangent, bitangent);

@@ -36,6 +36,7 @@ EXPORTS = [
     "ptmi_default_temporal_params", "ptmi_check_temporal_params", "ptmi_temporal_reset", "ptmi_temporal_accumulate",
     "ptmi_read_temporal", "ptmi_read_history_counts", "ptmi_denoise_temporal",
     "ptmi_host_emitters",
+    "ptmi_debug_math", "ptmi_debug_grid_index",
 ]
 
 
@@ -153,6 +154,8 @@ def lib():
         L.ptmi_debug_rng.argtypes = [vp, C.c_uint64, C.c_int, vp, C.c_int, vp]
         L.ptmi_debug_cosine_sample.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.ptmi_debug_guided_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+        L.ptmi_debug_math.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+        L.ptmi_debug_grid_index.argtypes = [vp, C.c_int, vp, vp, vp]
         L.ptmi_debug_set_traversal.argtypes = [vp, C.c_int, C.c_int, ip]
         L.ptmi_debug_set_solver_walk.argtypes = [vp, C.c_int, C.c_int]
         L.ptmi_debug_get_traversal.argtypes = [vp, ip]
@@ -791,6 +794,26 @@ class Renderer:
                                                  None if recs is None else rec_idx.ctypes.data, normals.ctypes.data,
                                                  in3.ctypes.data, states.ctypes.data, out.ctypes.data, used.ctypes.data))
         return out, used
+
+    (MATH_SINCOS_D, MATH_TAN_D, MATH_LOG_D, MATH_EXP_D, MATH_ATAN2_D, MATH_SINCOSF, MATH_POWF, MATH_EXPF, MATH_ATAN2F, MATH_ACOSF,
+     MATH_DIV, MATH_RCP, MATH_SQRT, MATH_ROUND, MATH_TRUNC) = range(15)
+
+    def debug_math(self, op, a, b=None):
+        """ptmi_debug_math: operation `op` (MATH_*) of the kernels' build of include/ptmi_math.h on the float32 cases (a[i], b[i]).
+        Returns (n, 2) float64; float and int results are promoted, which is exact."""
+        a = np.ascontiguousarray(a, np.float32).reshape(-1); n = len(a)
+        b = np.zeros(n, np.float32) if b is None else np.ascontiguousarray(b, np.float32).reshape(n)
+        out = np.zeros((n, 2), np.float64)
+        self._ck(self.L.ptmi_debug_math(self.h, int(op), n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
+        return out
+
+    def debug_grid_index(self, dirs, normals):
+        """ptmi_debug_grid_index: the form-factor kernel's direction_to_grid_index_local on (n, 3) directions and normals."""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3); n = len(dirs)
+        normals = np.ascontiguousarray(normals, np.float32).reshape(n, 3)
+        out = np.zeros(n, np.int32)
+        self._ck(self.L.ptmi_debug_grid_index(self.h, n, dirs.ctypes.data, normals.ctypes.data, out.ctypes.data))
+        return out
 
 
 def write_png(path, rgb8):

@@ -387,6 +387,32 @@ int ptmi_debug_cosine_sample(ptmi_ctx*, int n, const float* normals, const float
  * out: 6 floats per case - direction (op 5: the three 8-bit values), then pdf / weight / heuristic (op 5: radiance). */
 int ptmi_debug_guided_sample(ptmi_ctx*, int op, int n, int n_recs, const float* recs, const int* rec_idx, const float* normals,
                              const float* in3, const uint32_t* states, float* out /* n*6 */, int* used /* n */);
+/* The numerics contract per call: the gfx950 build of include/ptmi_math.h and the IEEE primitives the kernels rely on (debug_hooks.hip:
+ * ptmi_debug_math_k, built with the bounce kernels' flags).  One operation on n cases (a[i], b[i]); out holds two doubles per case,
+ * float and int results promoted to double (exact), the second 0 where an operation has one result.  oracle/ptmi_oracle.c's
+ * po_math_batch is the host build of the same operations under the same numbers. */
+enum {
+    PTMI_MATH_SINCOS_D = 0,   /* ptmi_sincos_d of (double)a           -> sin, cos */
+    PTMI_MATH_TAN_D    = 1,   /* ptmi_tan_d of (double)a */
+    PTMI_MATH_LOG_D    = 2,   /* ptmi_log_d of (double)a */
+    PTMI_MATH_EXP_D    = 3,   /* ptmi_exp_d of (double)a */
+    PTMI_MATH_ATAN2_D  = 4,   /* ptmi_atan2_d of (double)a, (double)b  a = y, b = x */
+    PTMI_MATH_SINCOSF  = 5,   /* ptmi_sincosf of a                     -> sin, cos */
+    PTMI_MATH_POWF     = 6,   /* ptmi_powf of a, b */
+    PTMI_MATH_EXPF     = 7,   /* ptmi_expf of a */
+    PTMI_MATH_ATAN2F   = 8,   /* ptmi_atan2f of a, b                   a = y, b = x */
+    PTMI_MATH_ACOSF    = 9,   /* ptmi_acosf of a */
+    PTMI_MATH_DIV      = 10,  /* a / b in binary32 */
+    PTMI_MATH_RCP      = 11,  /* rcp_rn(a) = 1.0f / a */
+    PTMI_MATH_SQRT     = 12,  /* sqrt_rn(a) */
+    PTMI_MATH_ROUND    = 13,  /* (float)((double)a * (double)b): the product is exact, so this is the one rounding to binary32 */
+    PTMI_MATH_TRUNC    = 14,  /* (int)a, (int)(double)a; |a| < 2^31 (outside it the conversion is undefined in C) */
+    PTMI_MATH_OPS      = 15
+};
+int ptmi_debug_math(ptmi_ctx*, int op, int n, const float* a, const float* b, double* out /* n*2 */);
+/* direction_to_grid_index_local (form_factors.h:107-130), the function the form-factor kernel bins with, on n (direction, normal)
+ * pairs as given: out[i] = theta row * 16 + phi column.  oracle: po_direction_to_grid_index. */
+int ptmi_debug_grid_index(ptmi_ctx*, int n, const float* dirs, const float* normals, int* out /* n */);
 
 /* ---- progressive and adaptive accumulation (new in this implementation) -------------------------------------------------
  * A frame is an independent estimate of config.spp samples per pixel.  An ACCUMULATION instead goes on from pass to pass:

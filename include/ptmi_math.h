@@ -39,7 +39,9 @@
 PTMI_HD uint64_t ptmi_d2u(double x) { uint64_t u; __builtin_memcpy(&u, &x, 8); return u; }
 PTMI_HD double ptmi_u2d(uint64_t u) { double x; __builtin_memcpy(&x, &u, 8); return x; }
 
-/* floor(x + 0.5) for |x| < 2^31 without calling libm. */
+/* floor(x + 0.5) without calling libm.  DOMAIN: |x + 0.5| < 2^31 and x not NaN.  Outside it the conversion (int)y is undefined
+ * in C, and the builds do differ: x86 gives INT_MIN, the gfx950 conversion saturates and turns NaN into 0.  Every caller keeps
+ * its argument inside (ptmi_sincos_d: |x| <~ 1e5, ptmi_exp_d: |x| <= 700). */
 PTMI_HD int ptmi_round_half_up(double x) {
     double y = x + 0.5;
     int k = (int)y;          /* truncation toward zero */
@@ -47,7 +49,10 @@ PTMI_HD int ptmi_round_half_up(double x) {
     return k;
 }
 
-/* sin and cos of x (radians) in binary64, |x| <~ 1e5.
+/* sin and cos of x (radians) in binary64.  DOMAIN: finite x, |x| <~ 1e5 (beyond it the two-term reduction loses accuracy, and
+ * from |x| >= 2^31 * pi/2, for +-inf and for NaN the quadrant k comes from an undefined conversion - see ptmi_round_half_up - so
+ * ptmi_sincos_d, ptmi_sincosf and ptmi_tan_d then differ between the oracle and the kernels).  No caller passes such an
+ * argument: the angles are theta, phi of a grid cell, 2 pi u of a uniform u and the camera's field of view.
  * Cody-Waite reduction by pi/2 with a 33-bit head so k*head is exact. */
 PTMI_HD void ptmi_sincos_d(double x, double* s_out, double* c_out) {
     const double INV_PIO2 = 6.36619772367581382433e-01;
@@ -141,10 +146,14 @@ PTMI_HD double ptmi_exp_d(double x) {
     return p * scale;
 }
 
-/* powf(x, y) replacement for the gamma step (integrator.h:397-400): x in [0,1]. */
+/* powf(x, y) replacement for the gamma step (integrator.h:397-400): x in [0,1].
+ * y == 0.5 takes the IEEE square root (binary64, rounded once more to binary32: innocuous, 53 >= 2 * 24 + 2): through exp(y log x)
+ * the square root of the last float below every odd power of two - 2^k (1 - 2^-25 - 2^-51..), 2^-27 ulp under a rounding
+ * boundary - came out one ulp high.  The gamma step's y is 1 / 2.2f; it does not take this branch. */
 PTMI_HD float ptmi_powf(float x, float y) {
     if (x != x) return x;
     if (!(x > 0.0f)) return 0.0f;
+    if (y == 0.5f) return (float)__builtin_sqrt((double)x);
     double l = ptmi_log_d((double)x);
     return (float)ptmi_exp_d((double)y * l);
 }

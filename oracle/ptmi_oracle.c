@@ -708,6 +708,34 @@ float po_powf(float x, float y) { return ptmi_powf(x, y); }
 float po_acosf(float x) { return ptmi_acosf(x); }
 float po_expf(float x) { return ptmi_expf(x); }
 float po_atan2f(float y, float x) { return ptmi_atan2f(y, x); }
+/* The host build of ptmi_debug_math (include/ptmi.h: the same op numbers, PTMI_MATH_*): one operation of the contract on n cases
+ * (a[i], b[i]), two doubles per case, float and int results promoted (exact). */
+void po_math_batch(int op, int n, const float* a_in, const float* b_in, double* out) {
+    for (int i = 0; i < n; i++) {
+        const float a = a_in[i], b = b_in[i];
+        double r0 = 0.0, r1 = 0.0;
+        float f0 = 0.0f, f1 = 0.0f;
+        switch (op) {
+            case 0:  ptmi_sincos_d((double)a, &r0, &r1); break;
+            case 1:  r0 = ptmi_tan_d((double)a); break;
+            case 2:  r0 = ptmi_log_d((double)a); break;
+            case 3:  r0 = ptmi_exp_d((double)a); break;
+            case 4:  r0 = ptmi_atan2_d((double)a, (double)b); break;
+            case 5:  ptmi_sincosf(a, &f0, &f1); r0 = (double)f0; r1 = (double)f1; break;
+            case 6:  r0 = (double)ptmi_powf(a, b); break;
+            case 7:  r0 = (double)ptmi_expf(a); break;
+            case 8:  r0 = (double)ptmi_atan2f(a, b); break;
+            case 9:  r0 = (double)ptmi_acosf(a); break;
+            case 10: r0 = (double)(a / b); break;
+            case 11: r0 = (double)(1.0f / a); break;
+            case 12: r0 = (double)sqrtf(a); break;
+            case 13: r0 = (double)(float)((double)a * (double)b); break;
+            case 14: r0 = (double)(int)a; r1 = (double)(int)(double)a; break;
+            default: break;
+        }
+        out[2 * (size_t)i] = r0; out[2 * (size_t)i + 1] = r1;
+    }
+}
 
 /* ------------------------------------------------------------------------ */
 /* triangle.h:64-96, quad.h:49-132, primitive.h:83-90                        */

@@ -99,6 +99,7 @@ void po_sincosf(float x, float* s, float* c);
 float po_powf(float x, float y);
 float po_acosf(float x);
 float po_atan2f(float y, float x);
+void po_math_batch(int op, int n, const float* a, const float* b, double* out /* n*2 */);   /* ops: PTMI_MATH_* of include/ptmi.h */
 void po_sample_cosine_hemisphere(const float n[3], float u, float v, float out[3]);
 
 /* per-call hooks over scripted raw 32-bit words (tests/test_integrator_vs_ref.py): each draws from a XORWOW state whose

@@ -111,6 +111,7 @@ def oracle_lib():
         L.po_acosf.restype = C.c_float; L.po_acosf.argtypes = [C.c_float]
         L.po_expf.restype = C.c_float; L.po_expf.argtypes = [C.c_float]
         L.po_atan2f.restype = C.c_float; L.po_atan2f.argtypes = [C.c_float, C.c_float]
+        L.po_math_batch.restype = None; L.po_math_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.po_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                 C.c_void_p, C.c_void_p, C.POINTER(Stats)]
@@ -299,6 +300,16 @@ def camera_ray(cf, u, v):
     o = np.zeros(3, np.float32); d = np.zeros(3, np.float32)
     oracle_lib().po_camera_ray(C.byref(cf), u, v, o.ctypes.data, d.ctypes.data)
     return o, d
+
+
+def math_batch(op, a, b=None):
+    """po_math_batch: operation `op` (ptmi.Renderer.MATH_* numbers) of the host build of include/ptmi_math.h on the float32 cases
+    (a[i], b[i]).  Returns (n, 2) float64, as Renderer.debug_math does for the device build."""
+    a = np.ascontiguousarray(a, np.float32).reshape(-1); n = len(a)
+    b = np.zeros(n, np.float32) if b is None else np.ascontiguousarray(b, np.float32).reshape(n)
+    out = np.zeros((n, 2), np.float64)
+    oracle_lib().po_math_batch(int(op), n, a.ctypes.data, b.ctypes.data, out.ctypes.data)
+    return out
 
 
 def rng_stream(seed, subsequence, n):
