@@ -40,12 +40,6 @@ void need(bool ok, const char* what) { if (!ok) throw ArgError(what); }
 void viewChanged(ApplicationState& app) { accumReset(app); featuresStale(app); temporalReset(app); }
 f3 v3(const float* p) { return mk3(p[0], p[1], p[2]); }
 
-#define PTMI_HIP(call)                                                                                   \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) throw HipError(e_, std::string(#call) + ": " + hipGetErrorString(e_));     \
-    } while (0)
-
 template <class T>
 struct DevBuf {
     T* p = nullptr;

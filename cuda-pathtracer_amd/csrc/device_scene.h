@@ -288,7 +288,7 @@ void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const Tile
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)
 
-// ---- radiosity pre-pass (radiosity.hip) ----------------------------------------------------------------
+// ---- radiosity pre-pass (radiosity.hip, form_factors.hip) ----------------------------------------------------------------
 // Load-order geometry the form-factor kernels sample (the traversal keeps using the leaf-order prims above):
 //   geo[6*p+0] = (v0 | v00, bits(type))      geo[6*p+3] = (-  | v01, 0)
 //   geo[6*p+1] = (v1 | v10, area)            geo[6*p+4] = (normal, 0)

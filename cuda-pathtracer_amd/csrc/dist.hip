@@ -23,12 +23,6 @@
 
 namespace ptmi {
 
-#define PTMI_HIP(call)                                                                                   \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) throw HipError(e_, std::string(#call) + ": " + hipGetErrorString(e_));     \
-    } while (0)
-
 namespace {
 struct Rccl {
     void* handle = nullptr;

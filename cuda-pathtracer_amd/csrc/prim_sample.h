@@ -1,5 +1,5 @@
 // prim_sample.h — Primitive::sampleUniform (primitive.h:150-191) on the device, stated once for its two callers: the radiosity
-// pre-pass's form factors (radiosity.hip) and the emitter samples of next-event estimation (first_hit.hip: ptmi_render_nee).
+// pre-pass's form factors (form_factors.hip) and the emitter samples of next-event estimation (first_hit.hip: ptmi_render_nee).
 // Compile with -ffp-contract=off (see include/ptmi_math.h, pt_vec.h).
 #pragma once
 #include "pt_vec.h"
@@ -7,7 +7,7 @@
 namespace ptmi {
 namespace {
 
-// A primitive as the samplers see it: the radiosity pre-pass's load-order geometry (radiosity.hip: load_geom) and the
+// A primitive as the samplers see it: the radiosity pre-pass's load-order geometry (form_factors.hip: load_geom) and the
 // emitter records of next-event estimation (first_hit.hip: ptmi_render_nee).  Quads: v0..v3 = v00, v10, v11, v01.
 struct Geom { f3 v0, v1, v2, v3; int type; float area, ratio; f3 normal, centroid; };
 

@@ -1,4 +1,4 @@
-// pt_device.h — device helpers shared by the render kernels (kernels.hip and the files it lists) and the radiosity pre-pass (radiosity.hip).
+// pt_device.h — device helpers shared by the render kernels (kernels.hip and the files it lists) and the radiosity pre-pass (radiosity.hip and the files it lists).
 // Compile with -ffp-contract=off (see include/ptmi_math.h, pt_vec.h).
 #pragma once
 #include "device_scene.h"
@@ -6,9 +6,18 @@
 
 #include <float.h>
 
+#include <type_traits>
+
 #include "../../include/ptmi_math.h"
 
 namespace ptmi {
+
+// Host side, the one idiom that turns a runtime flag into a template argument: f is a generic lambda and gets std::true_type or
+// std::false_type (a walk is passed the same way, as a std::integral_constant<int, walk>).
+template <typename F>
+static decltype(auto) with_bool(bool b, F&& f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // ---------------------------------------------------------------------------------------------
 // RNG: cuRAND XORWOW restated (third-party algorithm; see oracle/ptmi_oracle.c header for status)
@@ -127,7 +136,7 @@ __device__ __forceinline__ void build_frame(f3 n, f3& t, f3& b) {               
 __device__ __forceinline__ float dot_from_zero(f3 a, f3 b) { float s = 0.0f; s += a.x * b.x; s += a.y * b.y; s += a.z * b.z; return s; }
 
 // direction_to_grid_indices_local (form_factors.h:107-130): theta over [0, pi] -> 16 rows, phi over [0, 2 pi) -> 16 columns.
-// The form-factor kernel (radiosity.hip) bins with it; here so that the test hook (debug_hooks.hip) calls the same function.
+// The form-factor kernel (form_factors.hip) and ptmi_radiosity_grid (radiosity.hip) bin with it; here so that the test hook (debug_hooks.hip) calls the same function.
 __device__ __forceinline__ int direction_to_grid_index_local(f3 world_dir, f3 normal) {
     f3 tangent, bitangent;
     build_frame(normal, tangent, bitangent);

@@ -5,16 +5,7 @@
 #include "pt_device.h"
 #include "wide_walk.h"
 
-#include <type_traits>
-
 namespace ptmi {
-
-// Host side, the one idiom that turns a runtime flag into a template argument: f is a generic lambda and gets std::true_type or
-// std::false_type (a walk is passed the same way, as a std::integral_constant<int, TRAVERSAL_...>).
-template <typename F>
-static decltype(auto) with_bool(bool b, F&& f) {
-    return b ? f(std::true_type{}) : f(std::false_type{});
-}
 
 struct LaneCounters { unsigned int rays, node_visits, prim_tests, hits, top_visits, cert_chain, cert_fallback; };
 

@@ -1,7 +1,7 @@
 // wide_walk.h — the device side of the walks over the 8-wide fast tree (csrc/wide_bvh.h) and of the certified walk's proof
 // (DESIGN.md §4.9), each stated once.  ptmi_bounce_wide (bounce_wide.hip) runs these steps in phases; the Radiosity view, the
-// feature pass and the test hook run wide_closest_hit; the solver (radiosity.hip) runs its any-hit walk over WIDE_NEXT_NODE
-// and proves its hits with cert_chain.
+// feature pass and the test hook run wide_closest_hit; the solver (anyhit.h) runs its any-hit walk over WIDE_NEXT_NODE
+// and proves its hits with the chain in its own spelling (certified_blocked).
 //
 // The steps that ptmi_bounce_wide runs in place are macros that expand to exactly the statements the kernel had before they
 // were shared (GNU statement expressions where a value comes out).  As __forceinline__ functions they change the register

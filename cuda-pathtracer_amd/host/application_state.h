@@ -31,6 +31,13 @@ struct IoError : std::runtime_error { using std::runtime_error::runtime_error; }
 struct ArgError : std::runtime_error { using std::runtime_error::runtime_error; };
 struct DistError : std::runtime_error { using std::runtime_error::runtime_error; };   // RCCL missing or an nccl* call failed
 
+// a HIP call that throws HipError on failure
+#define PTMI_HIP(call)                                                                                   \
+    do {                                                                                                 \
+        hipError_t e_ = (call);                                                                          \
+        if (e_ != hipSuccess) throw HipError(e_, std::string(#call) + ": " + hipGetErrorString(e_));     \
+    } while (0)
+
 // cudaMallocSafe (utils/cuda_utils.h:54-60): throws on failure
 void* hipMallocSafe(size_t bytes, const char* name);
 

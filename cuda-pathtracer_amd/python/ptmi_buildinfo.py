@@ -27,8 +27,8 @@ KERNEL_SOURCES = _csrc("kernels.hip", "bounce_sync.hip", "bounce_phased.hip", "b
     # the builder of the opt-in fast tree: the tree's shape decides what ptmi_bounce_wide fetches
     os.path.join(PKG, "host", "wide_bvh.cpp"),
 ]
-# everything that reaches build/radiosity.o (the radiosity pre-pass kernels) + the host code that launches them
-SOLVER_SOURCES = _csrc("radiosity.hip") + _SHARED_SOURCES + [os.path.join(PKG, "host", "application_state.cpp")]
+# everything that reaches build/radiosity.o and build/form_factors.o (the radiosity pre-pass kernels) + the host code that launches them
+SOLVER_SOURCES = _csrc("radiosity.hip", "form_factors.hip", "anyhit.h") + _SHARED_SOURCES + [os.path.join(PKG, "host", "radiosity_state.cpp")]
 
 
 def _sha(paths):
@@ -61,7 +61,7 @@ def stamps():
 
 
 def profile_is_current(profile, solver=False):
-    """(current?, which stamp matched).  solver: the profile describes the radiosity pre-pass kernels (csrc/radiosity.hip)"""
+    """(current?, which stamp matched).  solver: the profile describes the radiosity pre-pass kernels (csrc/radiosity.hip, csrc/form_factors.hip)"""
     if profile.get("lib_sha256") and profile.get("lib_sha256") == lib_sha256():
         return True, "lib"
     if solver:

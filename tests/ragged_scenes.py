@@ -143,3 +143,48 @@ def oracle_case(case):
         if isinstance(a, np.ndarray):
             a.setflags(write=False)
     return o, sol, cd
+
+
+# ---- every form-factor kernel once (test_gpu_every_form_factor_kernel_is_the_oracles) ----------------------------------------
+def deep_chain(mixed):
+    """tests/test_radiosity_solver.py's 60-primitive chain whose tree is deeper than 31 levels (x falls by 2.2 per primitive from
+    2^40), facing each other in turn; mixed: every fourth primitive is the quad over the same base edge"""
+    n = 60
+    x = (2.0 ** 40 * 2.2 ** (-np.arange(n, dtype=np.float64))).astype(F)
+    verts = np.zeros((n, 4, 3), F)
+    types = np.zeros(n, np.int32)
+    for i in range(n):
+        z = F(i) * F(0.01)
+        verts[i, 0] = [x[i], -0.004, z]; verts[i, 1] = [x[i], 0.004, z]; verts[i, 2] = [x[i], 0.0, z + F(0.008)]
+        if mixed and i % 4 == 3:
+            types[i] = 1
+            verts[i, 2] = [x[i], 0.004, z + F(0.008)]; verts[i, 3] = [x[i], -0.004, z + F(0.008)]
+    nr = np.tile(np.array([[1, 0, 0]], F), (n, 1)); nr[::2] = [-1, 0, 0]
+    return types, verts, nr, np.full((n, 3), 0.5, F), np.ones((n, 3), F)
+
+
+FF_SCENES = {"tri68": lambda: random_scene(68, False), "mixed68": lambda: random_scene(68, True),
+             "deep_tri": lambda: deep_chain(False), "deep_mixed": lambda: deep_chain(True)}
+# Monte-Carlo with and without the kernel's own radiosity grid (RAD0: num_iterations == 0); point-to-point launches one kernel
+# whatever num_iterations is
+FF_MODES = {"mc_it0": dict(mc_samples=6, num_iterations=0), "mc_it1": dict(mc_samples=6, num_iterations=1),
+            "p2p_it1": dict(use_monte_carlo=False, num_iterations=1)}
+# (scene, walk asked for, mode): 2 primitive mixes x 3 walks x 3 modes + the deep tree (walk 0 only) x 2 mixes x 3 modes = the 24
+# instantiations of ptmi_form_factors that launch_form_factors can reach
+FF_KERNEL_CASES = [(sc, w, m) for sc in ("tri68", "mixed68") for w in (0, 1, 2) for m in FF_MODES] + \
+                  [(sc, 0, m) for sc in ("deep_tri", "deep_mixed") for m in FF_MODES]
+
+
+@functools.lru_cache(maxsize=None)
+def ff_scene(name):
+    return FF_SCENES[name]()
+
+
+@functools.lru_cache(maxsize=None)
+def ff_oracle(name, mode):
+    """the oracle's solution of a scene of FF_SCENES in a mode of FF_MODES - shared, read-only"""
+    sol = OracleScene.from_arrays(*ff_scene(name)).radiosity_solve(**FF_MODES[mode])
+    for a in sol.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return sol

@@ -252,7 +252,7 @@ def test_radiosity_solver_through_the_fast_tree(R, sub):
 @pytest.mark.gpu
 def test_radiosity_solver_certified_walk_is_the_references(R):
     """The solver's default visibility walk from 256 triangles up: the fast tree + a proof per blocked ray that the reference's
-    any-hit walk (form_factors.h:143-208) is blocked too (radiosity.hip: certified_blocked).  The whole form-factor matrix must
+    any-hit walk (form_factors.h:143-208) is blocked too (anyhit.h: certified_blocked).  The whole form-factor matrix must
     equal the one the reference's own walk gives - 2048 primitives Monte-Carlo and point-to-point (centroid rays between the
     box's walls are axis-parallel: the proof's first stage does not apply, the chain of exact slab tests decides), and with
     every blocked ray forced through the chain (3) and through the reference's walk (4)."""

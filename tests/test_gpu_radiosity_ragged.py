@@ -1,4 +1,4 @@
-"""The radiosity solver's kernels (csrc/radiosity.hip) at the sizes where they change their code path, against the oracle bit
+"""The radiosity solver's kernels (csrc/radiosity.hip, csrc/form_factors.hip) at the sizes where they change their code path, against the oracle bit
 for bit.  The kernels choose by n: the tiled Jacobi kernel iff n % 4 == 0 and n >= 64 (256-column tiles, groups of 8 rows,
 a zeroed diagonal entry per row, a slower loop for tiles that hold a non-finite unshot value), the lane-per-row kernel
 otherwise (1024-entry LDS chunks, dead lanes in the last workgroup), ptmi_radiosity_grid in 2048-entry chunks, the
@@ -130,6 +130,19 @@ def test_binary64_step_agrees_with_the_oracle(case):
     assert_within_step_bound(sol["radiosity"], sol["unshot"], sol["form_factors"], bsdf, Le, case)
 
 
+@pytest.mark.parametrize("scene", list(rs.FF_SCENES))
+def test_oracle_form_factor_kernel_scenes_are_not_trivial(scene):
+    """the scenes of test_gpu_every_form_factor_kernel_is_the_oracles: positive form factors in every mode, and a radiosity grid
+    that is not all zero where only the Monte-Carlo kernel writes it (num_iterations = 0) - a dropped RAD0 would pass otherwise"""
+    assert len(rs.FF_KERNEL_CASES) == len(set(rs.FF_KERNEL_CASES)) == 24
+    types = rs.ff_scene(scene)[0]
+    assert bool((types == 1).any()) == (scene in ("mixed68", "deep_mixed")) and (types == 0).any()
+    for mode in rs.FF_MODES:
+        sol = rs.ff_oracle(scene, mode)
+        assert (sol["form_factors"] > 0).any() and sol["rays"] > 0, (scene, mode)
+    assert rs.ff_oracle(scene, "mc_it0")["radiosity_grid"].any() and rs.ff_oracle(scene, "mc_it0")["grid"].any()
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # GPU
 # ------------------------------------------------------------------------------------------------------------------
@@ -247,3 +260,38 @@ def test_gpu_kernels_selected_by_environment(tmp_path, setting):
         compare_solution(got, exp, f"{setting} {case}")
         assert int(got["rays"]) == exp["rays"] and int(got["pairs"]) == rs.CASES[case][0] ** 2
         assert (got["cdfs"].view(np.uint32) == cdfs.view(np.uint32)).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene,walk,mode", rs.FF_KERNEL_CASES)
+def test_gpu_every_form_factor_kernel_is_the_oracles(R, scene, walk, mode):
+    """launch_form_factors turns (Monte-Carlo, quads, deep tree, num_iterations == 0, walk) into one of 24 instantiations of
+    ptmi_form_factors; the other tests launch a few of them.  Each once, at the smallest scenes that reach it: the reference's
+    walk (0), the opt-in fast tree (1: fast_tree) and the certified walk (2: asked for by name from 65 primitives up) on 68
+    triangles and on 68 mixed primitives; a tree deeper than 31 levels, where every request ends at walk 0.  Everything is the
+    oracle's bit for bit, except the radiosity grid of num_iterations = 0, which the reference itself sums with unordered
+    float atomics: 2e-5 relative, as in test_gpu_solver_zero_iterations."""
+    exp = rs.ff_oracle(scene, mode)
+    deep = scene.startswith("deep")
+    try:
+        R.load_scene_arrays(*rs.ff_scene(scene))
+        assert (R.scene_info()["bvh_depth"] > 31) == deep
+        if walk == 1: R.set_config(fast_tree=True)
+        if walk == 2 or deep: R.set_solver_walk(2, 65 if not deep else 1)
+        st = R.run_radiosity_solver(**rs.FF_MODES[mode])
+        got = R.radiosity_solution()
+    finally:
+        R.set_solver_walk(-1)
+        R.set_config(fast_tree=False)
+    what = f"{scene} walk {walk} {mode}"
+    assert st.walk == walk, what
+    for k in ("form_factors", "radiosity", "unshot", "grid"):
+        bad = differing(got[k], exp[k])
+        assert not bad.any(), f"{what}: {k} differs in {int(bad.sum())} entries"
+    assert st.rays == exp["rays"], what
+    if mode == "mc_it0":
+        err = np.abs(got["radiosity_grid"].astype(np.float64) - exp["radiosity_grid"])
+        print(f"{what}: radiosity grid max error {err.max():.3e}, largest value {np.abs(exp['radiosity_grid']).max():.3e}")
+        assert np.allclose(got["radiosity_grid"], exp["radiosity_grid"], rtol=2e-5, atol=1e-7), what
+    else:
+        assert not differing(got["radiosity_grid"], exp["radiosity_grid"]).any(), f"{what}: radiosity_grid"

@@ -2,7 +2,7 @@
    --fast : the visibility walk through the opt-in fast tree, no certificate;  --walk 0 : the reference's own walk, --walk 2 : certified
            (default: automatic = certified from 256 triangles up)
    --check-profile FILE : only check that FILE (profiles/rNN_pmc_radiosity.json) was taken from the solver kernels that are built
-                          now (stamps of ptmi_buildinfo: the library, or the sources compiled into build/radiosity.o); exit 1 if not"""
+                          now (stamps of ptmi_buildinfo: the library, or the sources compiled into build/radiosity.o and build/form_factors.o); exit 1 if not"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
