@@ -405,6 +405,11 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
             need(cfg->sampling_mode == 0, "next_event needs sampling_mode 0 (BSDF): MIS against the guided modes' grid pdf is not implemented");
             need(cfg->fast_tree == 0, "next_event needs fast_tree 0: NEE frames always trace the reference's hits");
         }
+        if (c->app.env.present()) {
+            need(cfg->integrator == 0, "an environment is set: it needs integrator 0 (PathTracing): the Radiosity view traces first hits only");
+            need(cfg->sampling_mode == 0, "an environment is set: it needs sampling_mode 0 (BSDF): the guided modes do not look the environment up");
+            need(cfg->fast_tree == 0, "an environment is set: it needs fast_tree 0: environment frames always trace the reference's hits");
+        }
         AppConfig& a = c->app.config;                    // every check is above this line: a rejected config changes nothing
         a.spp = cfg->spp; a.max_depth = cfg->max_depth; a.sampling_mode = (SamplingMode)cfg->sampling_mode;
         a.mis_bsdf_fraction = cfg->mis_bsdf_fraction;
@@ -416,6 +421,55 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
         a.fast_tree = cfg->fast_tree != 0;
         a.next_event = cfg->next_event != 0;
         viewChanged(c->app);
+    });
+}
+
+void ptmi_default_env_params(ptmi_env_params* p) {
+    if (!p) return;
+    const EnvParams d;
+    p->scale = d.scale; p->rotation_deg = d.rotation_deg; p->select_fraction = d.select_fraction;
+}
+static EnvParams env_params(const ptmi_env_params* p) {
+    EnvParams e;
+    if (p) { e.scale = p->scale; e.rotation_deg = p->rotation_deg; e.select_fraction = p->select_fraction; }
+    return e;
+}
+int ptmi_check_env_params(const ptmi_env_params* p) {
+    return guarded([&] { need(p != nullptr, "NULL argument"); checkEnvParams(env_params(p)); });
+}
+int ptmi_set_environment(ptmi_ctx* c, int width, int height, const float* rgb, const ptmi_env_params* p) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        if (rgb) {
+            const AppConfig& a = c->app.config;
+            need(a.current_integrator == IntegratorType::PathTracing, "environment: the config has integrator 1 (Radiosity), which traces first hits only");
+            need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "environment: the config has a guided sampling_mode, which does not look the environment up");
+            need(!a.fast_tree, "environment: the config has fast_tree 1; environment frames always trace the reference's hits");
+            c->app.env.set(width, height, rgb, env_params(p));       // every check is done before anything changes
+        } else c->app.env.drop();
+        viewChanged(c->app);                                         // other light: the temporal history holds another image
+    });
+}
+int ptmi_environment_info(const ptmi_ctx* c, int* width, int* height, float* total) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        const EnvState& e = c->app.env;
+        if (width) *width = e.present() ? e.h.width : 0;
+        if (height) *height = e.present() ? e.h.height : 0;
+        if (total) *total = e.present() ? e.h.total : 0.0f;
+    });
+}
+int ptmi_host_env_table(int width, int height, const float* rgb, const ptmi_env_params* p, float* z, float* marginal_cdf, float* row_cdf,
+                        float* texel, float* total) {
+    return guarded([&] {
+        EnvHostTable t;
+        buildEnvTable(width, height, rgb, env_params(p), t);
+        if (z) std::memcpy(z, t.z.data(), t.z.size() * sizeof(float));
+        if (marginal_cdf) std::memcpy(marginal_cdf, t.marginal.data(), t.marginal.size() * sizeof(float));
+        if (row_cdf) std::memcpy(row_cdf, t.row_cdf.data(), t.row_cdf.size() * sizeof(float));
+        if (texel) std::memcpy(texel, t.texel.data(), t.texel.size() * sizeof(float));
+        if (total) *total = t.total;
     });
 }
 

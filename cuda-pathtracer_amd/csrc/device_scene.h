@@ -282,8 +282,29 @@ struct EmitterTable {
 // The NEE frame / pass: one lane per queued pixel (queue nullptr: all local pixels, n of them) runs fp.n_frames x spp samples
 // of the estimator of include/ptmi.h to their end; frame k < n_frames - 1 is banked in fp.frame_color, the last colour sum
 // stays in D.  first: the sums start from zero (a frame, pass 1), else they go on from D (later passes).
-void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const TileMap& tm, const PathState& st, const FrameParams& fp,
-                       const int* queue, int n, bool first, hipStream_t s);
+// ---- environment lighting (include/ptmi.h: ptmi_set_environment) ----------------------------------------------------------
+// The sampling table of the context's lat-long map (host/environment.cpp builds it, RenderState::Env owns the device copy).
+// All of it stays in global memory: a vertex makes at most two binary searches and one texel read against a whole BVH walk,
+// and first_hit_walk fixes the scene's LDS size.  texel == nullptr: no environment.
+//   z[r]                 h + 1 row boundaries in cos(theta), z[0] = 1 ... z[h] = -1; row r covers z[r + 1] < d.y <= z[r]
+//   marginal[r]          float CDF over the rows (ends at exactly 1; all zero for a map of total 0)
+//   row_cdf[r * w + j]   float CDF over the columns of row r (all zero for a row of weight 0)
+//   texel[r * w + j]     (scaled radiance.xyz, pdf per solid angle of the two searches picking this texel)
+struct EnvTable {
+    const float* z = nullptr;
+    const float* marginal = nullptr;
+    const float* row_cdf = nullptr;
+    const float4* texel = nullptr;
+    int w = 0, h = 0;
+    float rot = 0.0f;                  // rotation_deg / 360.0f: the turn of column 0 from +x towards +z
+    float q = 0.0f;                    // the EFFECTIVE probability that a vertex's light sample goes to the environment
+    int next_event = 0;                // ptmi_config.next_event of the run
+    int sampled = 0;                   // next_event and total > 0: a vertex draws five numbers and selects by q
+};
+// fp.n_frames x spp samples per queued pixel.  env.texel == nullptr: the NEE kernel exactly as it was (next_event = 1); else
+// the ENV instantiation, which runs either estimator (env.next_event) and looks the map up where a path ray misses.
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const TileMap& tm, const PathState& st,
+                       const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s);
 
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)

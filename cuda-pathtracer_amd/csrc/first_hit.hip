@@ -142,8 +142,39 @@ __device__ __forceinline__ int emitter_select(const EmitterTable& em, float u) {
 // cos / M_PI of the reference's pdf_bsdf (integrator.h:128): a binary64 quotient rounded to float
 __device__ __forceinline__ float cos_over_pi(float c) { return (float)((double)c / PTMI_PI_D); }
 
-template <int MODE, bool HAS_QUADS>
-__global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, EmitterTable em, TileMap tm, PathState st, FrameParams fp,
+// ---------------------------------------------------------------------------------------------
+// environment lighting (include/ptmi.h: "environment lighting"; the table: device_scene.h EnvTable).  The searches return the
+// smallest index whose entry satisfies the test, as the contract writes them; every load is per lane from global memory.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int cdf_search(const float* __restrict__ cdf, int n, float u) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {                                        // smallest i with u <= cdf[i] (cdf[n - 1] = 1 >= u)
+        const int mid = (lo + hi) >> 1;
+        if (u <= cdf[mid]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+__device__ __forceinline__ int env_row(const EnvTable& ev, float y) {
+    int lo = 0, hi = ev.h - 1;
+    while (lo < hi) {                                        // smallest r with z[r + 1] < y; none (y = -1): h - 1
+        const int mid = (lo + hi) >> 1;
+        if (ev.z[mid + 1] < y) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+// the texel a direction looks up: the nearest one, radiance is piecewise constant
+__device__ __forceinline__ int env_texel(const EnvTable& ev, const f3& d) {
+    const int r = env_row(ev, fminf(fmaxf(d.y, -1.0f), 1.0f));
+    const float phi = ptmi_atan2f(d.z, d.x);
+    const float s = (float)((double)phi / (2.0 * PTMI_PI_D));
+    float t = s - ev.rot;
+    t = t - floorf(t);
+    const int j = min((int)(t * (float)ev.w), ev.w - 1);
+    return r * ev.w + j;
+}
+
+template <int MODE, bool HAS_QUADS, bool ENV>
+__global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, EmitterTable em, EnvTable ev, TileMap tm, PathState st, FrameParams fp,
                                                           const int* __restrict__ queue, int n, int first) {
     extern __shared__ float4 smem[];
     const int idx = blockIdx.x * kBlock + threadIdx.x;
@@ -155,6 +186,10 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     Rng rng = {e.x, e.y, e.z, e.w, f.x, f.y};
     f3 color = first ? mk3(0.0f, 0.0f, 0.0f) : xyz(st.D[slot]);
     LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
+    // wave-uniform switches of the ENV instantiation; without ENV they fold to today's kernel
+    const bool nee_on = ENV ? ev.next_event != 0 : true;     // light samples and MIS weights at all
+    const bool env_on = ENV ? ev.sampled != 0 : false;       // the environment is one of the lights: five draws, selection by q
+    const float q = ENV ? ev.q : 0.0f, omq = 1.0f - q;
     for (int frame = 0; frame < fp.n_frames; frame++) {
         if (frame > 0) {                                     // frame batch: bank the previous frame's sum, as shade_step does
             fp.frame_color[(unsigned int)(frame - 1) * (unsigned int)fp.n_local + (unsigned int)slot] = make_float4(color.x, color.y, color.z, 0.0f);
@@ -168,23 +203,34 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
             int depth = 0;
             bool shadow = false;                             // the next walk is the shadow ray (so, sd) of the last vertex
             f3 so = o, sd = d, contrib = mk3(0.0f, 0.0f, 0.0f);
-            int s_slot = -1;
+            int s_slot = -1;                                 // the sampled emitter's slot; -1: the environment (visible iff nothing is hit)
             while (true) {
                 const f3 ro = shadow ? so : o, rd = shadow ? sd : d;
                 float t = 0.0f; int k = -1;
                 const bool hit = first_hit<MODE, HAS_QUADS>(sc, smem, true, ro, rd, 1e-4f, t, k, cn);
                 if (shadow) {                                // visible iff the closest hit is the sampled emitter
-                    if (hit && k == s_slot) L = L + contrib;
+                    if (ENV && s_slot < 0 ? !hit : (hit && k == s_slot)) L = L + contrib;
                     shadow = false;
                     continue;
                 }
-                if (!hit) break;                                                          // integrator.h:198-201
+                if (!hit) {                                                               // integrator.h:198-201
+                    if constexpr (ENV) {                                                  // the path ray leaves the scene: E(d)
+                        const float4 te = ev.texel[env_texel(ev, d)];
+                        const f3 c = tp * xyz(te);
+                        if (env_on && depth > 0) {
+                            const float w = mis_power_heuristic(pb_prev, q * te.w);
+                            L = L + mk3(c.x * w, c.y * w, c.z * w);
+                        } else L = L + c;
+                    }
+                    break;
+                }
                 const f3 nrm = xyz(sc.mats[3 * k]), bsdf = xyz(sc.mats[3 * k + 1]), Le = xyz(sc.mats[3 * k + 2]);
                 const f3 hp = o + t * d;                                                  // triangle.h:90
-                const float4 pe = depth > 0 ? em.pdf_area[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                const float4 pe = depth > 0 && nee_on ? em.pdf_area[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 const float pa = pe.w;
                 if (pa > 0.0f) {                                                          // an emitter found by the BSDF sample
-                    const float p_l = (pa * (t * t)) / fabsf(dot(xyz(pe), d));           // the geometric normal: area -> solid angle
+                    float p_l = (pa * (t * t)) / fabsf(dot(xyz(pe), d));                 // the geometric normal: area -> solid angle
+                    if (env_on) p_l = omq * p_l;
                     const float w = mis_power_heuristic(pb_prev, p_l);
                     const f3 c = tp * Le;
                     L = L + mk3(c.x * w, c.y * w, c.z * w);
@@ -199,30 +245,61 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                 if (length(tp) < 1e-5f) break;                                            // integrator.h:218
                 const f3 sn = dot(d, nrm) < 0 ? nrm : -nrm;                               // integrator.h:221-222
                 const f3 o2 = hp + 1e-4f * sn;                                            // integrator.h:266
-                if (depth + 1 < fp.max_depth && em.n > 0) {                               // NEE: three draws whatever comes of them
-                    const float u_sel = rng_uniform(rng);
+                if (nee_on && depth + 1 < fp.max_depth && (em.n > 0 || env_on)) {         // NEE: three draws (five with an environment) whatever comes of them
+                    float u_sel = rng_uniform(rng);
                     const float r1 = rng_uniform(rng);
                     const float r2 = rng_uniform(rng);
-                    const float4* rec = em.rec + (size_t)kEmitterStride * (size_t)emitter_select(em, u_sel);
-                    const float4 a0 = rec[0], a1 = rec[1], a2 = rec[2], a3 = rec[3], a4 = rec[4];
-                    Geom g;
-                    g.v0 = xyz(a0); g.v1 = xyz(a1); g.v2 = xyz(a2); g.v3 = xyz(a3);
-                    g.type = __float_as_int(a2.w); g.ratio = a1.w;
-                    const f3 yv = sample_uniform<HAS_QUADS>(g, r1, r2);
-                    const f3 v = yv - o2;
-                    const float dist2 = dot(v, v);
-                    const float dist = sqrt_rn(dist2);
-                    const f3 wi = mk3(v.x / dist, v.y / dist, v.z / dist);
-                    const float cos_s = dot(sn, wi);
-                    const float cos_l = fabsf(dot(xyz(a4), wi));                          // a4: the geometric normal
-                    const float p_l = (a3.w * dist2) / cos_l;
-                    if (cos_s > 0.0f && cos_l > 0.0f && p_l > 0.0f && p_l <= FLT_MAX) {   // a p_l of 0 or inf weighs 0 (no NaN)
-                        const float p_b = cos_over_pi(cos_s);
-                        const float w = (p_b * mis_power_heuristic(p_l, p_b)) / p_l;
-                        const f3 c = tp * xyz(rec[5]);
-                        contrib = mk3(c.x * w, c.y * w, c.z * w);
-                        so = o2; sd = wi; s_slot = __float_as_int(a0.w);
-                        shadow = true;
+                    bool to_env = false;
+                    if (env_on) {
+                        const float r3 = rng_uniform(rng);
+                        const float r4 = rng_uniform(rng);
+                        to_env = u_sel <= q;
+                        if (to_env) {
+                            const int r = cdf_search(ev.marginal, ev.h, r1);
+                            const int j = cdf_search(ev.row_cdf + (size_t)r * (size_t)ev.w, ev.w, r2);
+                            const float z0 = ev.z[r], z1 = ev.z[r + 1];
+                            const float ct = z1 + r3 * (z0 - z1);
+                            const float sth = sqrt_rn(fmaxf(0.0f, 1.0f - ct * ct));
+                            const float a = ((float)j + r4) / (float)ev.w + ev.rot;
+                            float sphi, cphi;
+                            ptmi_sincosf((float)((2.0 * PTMI_PI_D) * (double)a), &sphi, &cphi);
+                            const f3 wi = mk3(sth * cphi, ct, sth * sphi);
+                            const float4 te = ev.texel[r * ev.w + j];
+                            const float cos_s = dot(sn, wi);
+                            const float p_e = q * te.w;
+                            if (cos_s > 0.0f && p_e > 0.0f && p_e <= FLT_MAX) {
+                                const float p_b = cos_over_pi(cos_s);
+                                const float w = (p_b * mis_power_heuristic(p_e, p_b)) / p_e;
+                                const f3 c = tp * xyz(te);
+                                contrib = mk3(c.x * w, c.y * w, c.z * w);
+                                so = o2; sd = wi; s_slot = -1;
+                                shadow = true;
+                            }
+                        } else u_sel = (u_sel - q) / omq;
+                    }
+                    if (!to_env) {
+                        const float4* rec = em.rec + (size_t)kEmitterStride * (size_t)emitter_select(em, u_sel);
+                        const float4 a0 = rec[0], a1 = rec[1], a2 = rec[2], a3 = rec[3], a4 = rec[4];
+                        Geom g;
+                        g.v0 = xyz(a0); g.v1 = xyz(a1); g.v2 = xyz(a2); g.v3 = xyz(a3);
+                        g.type = __float_as_int(a2.w); g.ratio = a1.w;
+                        const f3 yv = sample_uniform<HAS_QUADS>(g, r1, r2);
+                        const f3 v = yv - o2;
+                        const float dist2 = dot(v, v);
+                        const float dist = sqrt_rn(dist2);
+                        const f3 wi = mk3(v.x / dist, v.y / dist, v.z / dist);
+                        const float cos_s = dot(sn, wi);
+                        const float cos_l = fabsf(dot(xyz(a4), wi));                      // a4: the geometric normal
+                        float p_l = (a3.w * dist2) / cos_l;
+                        if (env_on) p_l = omq * p_l;
+                        if (cos_s > 0.0f && cos_l > 0.0f && p_l > 0.0f && p_l <= FLT_MAX) {   // a p_l of 0 or inf weighs 0 (no NaN)
+                            const float p_b = cos_over_pi(cos_s);
+                            const float w = (p_b * mis_power_heuristic(p_l, p_b)) / p_l;
+                            const f3 c = tp * xyz(rec[5]);
+                            contrib = mk3(c.x * w, c.y * w, c.z * w);
+                            so = o2; sd = wi; s_slot = __float_as_int(a0.w);
+                            shadow = true;
+                        }
                     }
                 }
                 const float u = rng_uniform(rng);                                         // integrator.h:63-64
@@ -242,12 +319,14 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     st.F[slot] = make_uint2(rng.v4, rng.d);
 }
 
-void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const TileMap& tm, const PathState& st, const FrameParams& fp,
-                       const int* queue, int n, bool first, hipStream_t s) {
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const TileMap& tm, const PathState& st,
+                       const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s) {
     if (n <= 0) return;
     first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
-        hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s,
-                           sc, em, tm, st, fp, queue, n, first ? 1 : 0);
+        with_bool(env.texel != nullptr, [&](auto with_env) {
+            hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value>),
+                               dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, tm, st, fp, queue, n, first ? 1 : 0);
+        });
     });
 }
 

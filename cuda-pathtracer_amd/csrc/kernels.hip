@@ -14,7 +14,8 @@
 //   bounce_phased.hip  ptmi_bounce_phased the same work for larger scenes: per-lane stackless walk with wave-scheduled NODE/PRIM/SHADE phases
 //   bounce_wide.hip    ptmi_bounce_wide   the phased scheduling over the opt-in 8-wide tree, plain or certified
 //   first_hit.hip      the Radiosity view, the feature pass, and
-//                      ptmi_render_nee    opt-in next-event estimation with MIS (include/ptmi.h): one lane runs a pixel's samples to their end
+//                      ptmi_render_nee    opt-in next-event estimation with MIS (include/ptmi.h): one lane runs a pixel's samples to their end;
+//                                         its ENV instantiation renders every frame of a context with an environment (ptmi_set_environment)
 //   debug_hooks.hip    the test hooks
 #include "bounce.h"
 

@@ -819,6 +819,7 @@ ApplicationState::~ApplicationState() {
     dist.finalize();
     for (hipEvent_t ev : event_pool) (void)hipEventDestroy(ev);
     scene.cleanup();
+    env.drop();
     render.freeBuffers();
     if (render.d_jump) (void)hipFree(render.d_jump);
     if (render.stream) (void)hipStreamDestroy(render.stream);
@@ -847,6 +848,51 @@ struct PassRun { AdaptRule rule; int active_after = 0; };
 }  // namespace
 
 static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pass);
+
+// ---- environment lighting (include/ptmi.h: ptmi_set_environment) ----------------------------------------------------------
+void EnvState::set(int width, int height, const float* rgb, const EnvParams& p) {
+    EnvHostTable t;
+    buildEnvTable(width, height, rgb, p, t);           // throws ArgError: nothing has changed yet
+    const size_t n = (size_t)width * (size_t)height;
+    float* nz = (float*)hipMallocSafe(t.z.size() * sizeof(float), "d_env_z");
+    float* nm = nullptr; float* nc = nullptr; float4* nt = nullptr;
+    try {
+        nm = (float*)hipMallocSafe(t.marginal.size() * sizeof(float), "d_env_marginal");
+        nc = (float*)hipMallocSafe(n * sizeof(float), "d_env_row_cdf");
+        nt = (float4*)hipMallocSafe(n * sizeof(float4), "d_env_texel");
+        PTMI_HIP(hipMemcpy(nz, t.z.data(), t.z.size() * sizeof(float), hipMemcpyHostToDevice));
+        PTMI_HIP(hipMemcpy(nm, t.marginal.data(), t.marginal.size() * sizeof(float), hipMemcpyHostToDevice));
+        PTMI_HIP(hipMemcpy(nc, t.row_cdf.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        PTMI_HIP(hipMemcpy(nt, t.texel.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    } catch (...) {
+        (void)hipFree(nz); if (nm) (void)hipFree(nm); if (nc) (void)hipFree(nc); if (nt) (void)hipFree(nt);
+        throw;
+    }
+    drop();
+    d_z = nz; d_marginal = nm; d_row_cdf = nc; d_texel = nt;
+    params = p;
+    h = std::move(t);
+}
+
+void EnvState::drop() {
+    if (d_z) (void)hipFree(d_z);
+    if (d_marginal) (void)hipFree(d_marginal);
+    if (d_row_cdf) (void)hipFree(d_row_cdf);
+    if (d_texel) (void)hipFree(d_texel);
+    d_z = d_marginal = d_row_cdf = nullptr; d_texel = nullptr;
+    h = EnvHostTable(); params = EnvParams();
+}
+
+EnvTable EnvState::table(bool next_event, int n_emitters) const {
+    EnvTable e;
+    if (!present()) return e;
+    e.z = d_z; e.marginal = d_marginal; e.row_cdf = d_row_cdf; e.texel = d_texel;
+    e.w = h.width; e.h = h.height; e.rot = h.rot_turns;
+    e.next_event = next_event ? 1 : 0;
+    e.sampled = next_event && h.total > 0.0f ? 1 : 0;
+    e.q = n_emitters == 0 ? 1.0f : params.select_fraction;     // (total == 0: not sampled, q is not read)
+    return e;
+}
 
 // camera update (application.h:161-163) and the camera fields of the frame's parameters
 static void cameraFrameParams(ApplicationState& g, FrameParams& fp) {
@@ -958,7 +1004,9 @@ static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, Pass
     // c2 5 685 Msamples/s in image order, 6 790 in cost order, against 6 717 for its 32-segment launches on the same box)
     // next-event estimation (include/ptmi.h: ptmi_config.next_event) replaces the frame-begin / bounce loop below with ONE launch
     // of ptmi_render_nee on the frame's stream: no chunks, no refill, no launch order by cost
-    const bool nee = g.config.next_event && g.config.current_integrator == IntegratorType::PathTracing;
+    // a context with an environment (ptmi_set_environment) takes the same route for both values of next_event: the per-lane kernel
+    // is the one that looks the map up where a path ray misses
+    const bool nee = (g.config.next_event || g.env.present()) && g.config.current_integrator == IntegratorType::PathTracing;
     bool refill = (trav == TRAVERSAL_WIDE || trav == TRAVERSAL_CERTIFIED) && g.config.segments_per_launch <= 0 && wave_slots > 0 && !nee;
     const int refill_segments = kRestOfFrameSegments;
     // launch order by last frame's cost (below): in 16 classes, and only while the frame has at most three pixels per lane of the
@@ -1054,7 +1102,8 @@ static void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, Pass
         const int n = pass ? chunks[0].n : n_local;
         const hipEvent_t e0 = stats ? event(n_ev++) : nullptr;
         if (stats) PTMI_HIP(hipEventRecord(e0, s));
-        launch_render_nee(g.scene.d_scene, g.scene.d_emitters, r.tile, r.d_state, fp, pass ? chunks[0].d_queue_init : nullptr, n,
+        launch_render_nee(g.scene.d_scene, g.scene.d_emitters, g.env.table(g.config.next_event, g.scene.d_emitters.n), r.tile, r.d_state, fp,
+                          pass ? chunks[0].d_queue_init : nullptr, n,
                           pass ? pass->rule.first != 0 : true, s);
         PTMI_HIP(hipGetLastError());
         const hipEvent_t e1 = stats ? event(n_ev++) : nullptr;

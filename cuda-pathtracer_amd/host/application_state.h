@@ -16,6 +16,7 @@
 
 #include "../csrc/device_scene.h"
 #include "bvh.h"
+#include "environment.h"
 #include "file_manager.h"
 #include "pbrt_loader.h"
 #include "sensor.h"
@@ -308,6 +309,21 @@ void distUniqueId(void* out128);                     // ncclGetUniqueId
 void debugPlaceTiles(int width, int height, int n_ranks, int row_block, const unsigned char* h_tiles_rgb, const float* h_tiles_rad,
                      unsigned char* out_rgb, float* out_rad, hipStream_t s);
 
+// The environment light of a context (include/ptmi.h: ptmi_set_environment): the host table and its device copy.  It belongs
+// to the context, like the camera: scene loads keep it.
+struct EnvState {
+    EnvParams params;
+    EnvHostTable h;
+    float *d_z = nullptr, *d_marginal = nullptr, *d_row_cdf = nullptr;
+    float4* d_texel = nullptr;
+    bool present() const { return d_texel != nullptr; }
+    void set(int width, int height, const float* rgb, const EnvParams& p);   // builds, then replaces the device copy; throws before anything changes
+    void drop();
+    // the kernel's view for one run: q and the estimator's switches follow the config and the loaded scene's emitter count
+    EnvTable table(bool next_event, int n_emitters) const;
+    ~EnvState() { drop(); }
+};
+
 struct FrameStats {
     double seconds = 0, bounce_kernel_ms = 0;
     uint64_t bounce_launches = 0, path_visits = 0, samples = 0, rays = 0, node_visits = 0, prim_tests = 0, hits = 0, top_node_visits = 0,
@@ -322,6 +338,7 @@ struct ApplicationState {
     RadiosityState radiosity;
     DistState dist;
     AppConfig config;
+    EnvState env;
     std::vector<uint32_t> h_jump;                    // 32 x 160 x 5 words
     std::vector<hipEvent_t> event_pool;
 

@@ -37,6 +37,7 @@ EXPORTS = [
     "ptmi_read_temporal", "ptmi_read_history_counts", "ptmi_denoise_temporal",
     "ptmi_host_emitters",
     "ptmi_debug_math", "ptmi_debug_grid_index",
+    "ptmi_default_env_params", "ptmi_check_env_params", "ptmi_set_environment", "ptmi_environment_info", "ptmi_host_env_table",
 ]
 
 
@@ -97,6 +98,10 @@ class TemporalParams(C.Structure):
 class TemporalStats(C.Structure):
     _fields_ = [("accepted", C.c_uint64), ("rejected", C.c_uint64), ("missed", C.c_uint64), ("seconds", C.c_double),
                 ("features_ms", C.c_double)]
+
+
+class EnvParams(C.Structure):
+    _fields_ = [("scale", C.c_float), ("rotation_deg", C.c_float), ("select_fraction", C.c_float)]
 
 
 class PtmiError(RuntimeError):
@@ -208,6 +213,11 @@ def lib():
         L.ptmi_read_temporal.argtypes = [vp, vp, vp]
         L.ptmi_read_history_counts.argtypes = [vp, vp]
         L.ptmi_denoise_temporal.argtypes = [vp, C.POINTER(DenoiseParams)]
+        L.ptmi_default_env_params.argtypes = [C.POINTER(EnvParams)]; L.ptmi_default_env_params.restype = None
+        L.ptmi_check_env_params.argtypes = [C.POINTER(EnvParams)]
+        L.ptmi_set_environment.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(EnvParams)]
+        L.ptmi_environment_info.argtypes = [vp, ip, ip, C.POINTER(C.c_float)]
+        L.ptmi_host_env_table.argtypes = [C.c_int, C.c_int, vp, C.POINTER(EnvParams), vp, vp, vp, vp, C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -358,6 +368,36 @@ def default_temporal_params(**params):
     return p
 
 
+def default_env_params(**params):
+    """ptmi_default_env_params, with any field overridden by keyword (scale, rotation_deg, select_fraction)."""
+    p = EnvParams(); lib().ptmi_default_env_params(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(EnvParams._fields_):
+            raise TypeError(f"unknown environment parameter {k}")
+        setattr(p, k, float(v))
+    return p
+
+
+def _env_map(rgb):
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("an environment map is (height, width, 3), row 0 at +y")
+    return rgb
+
+
+def host_env_table(rgb, **params):
+    """The sampling table of an environment map (include/ptmi.h: "environment lighting"), host only: z (h + 1), marginal_cdf
+    (h), row_cdf (h, w), texel (h, w, 4: scaled rgb and the pdf per solid angle) and total."""
+    rgb = _env_map(rgb)
+    h, w = rgb.shape[:2]
+    p = default_env_params(**params)
+    z = np.zeros(h + 1, np.float32); m = np.zeros(h, np.float32); c = np.zeros((h, w), np.float32)
+    t = np.zeros((h, w, 4), np.float32); total = C.c_float()
+    _check(lib().ptmi_host_env_table(w, h, rgb.ctypes.data, C.byref(p), z.ctypes.data, m.ctypes.data, c.ctypes.data, t.ctypes.data,
+                                     C.byref(total)))
+    return dict(z=z, marginal_cdf=m, row_cdf=c, texel=t, total=np.float32(total.value))
+
+
 class Renderer:
     """One ApplicationState bound to one GPU."""
 
@@ -496,6 +536,23 @@ class Renderer:
         if fast_tree is not None: c.fast_tree = int(bool(fast_tree))
         if next_event is not None: c.next_event = int(bool(next_event))
         self._ck(self.L.ptmi_set_config(self.h, C.byref(c)))
+
+    def set_environment(self, rgb, **params):
+        """The context's environment light: rgb (height, width, 3) float32, row 0 at +y, or None to drop it; keywords scale,
+        rotation_deg, select_fraction (include/ptmi.h: ptmi_env_params).  It stays through scene loads."""
+        if rgb is None:
+            self._ck(self.L.ptmi_set_environment(self.h, 0, 0, None, None))
+            return
+        rgb = _env_map(rgb)
+        p = default_env_params(**params)
+        self._ck(self.L.ptmi_set_environment(self.h, rgb.shape[1], rgb.shape[0], rgb.ctypes.data, C.byref(p)))
+
+    def environment_info(self):
+        w, h, t = C.c_int(), C.c_int(), C.c_float()
+        self._ck(self.L.ptmi_environment_info(self.h, C.byref(w), C.byref(h), C.byref(t)))
+        return dict(width=w.value, height=h.value, total=np.float32(t.value))
+
+    host_env_table = staticmethod(host_env_table)
 
     def camera_frame(self):
         out = np.zeros(12, np.float32)

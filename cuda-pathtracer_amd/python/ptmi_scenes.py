@@ -46,3 +46,26 @@ def tessellated_cornell(prims, cells_u=256, cells_v=128, seed=1, amplitude=1e-3)
     v4 = np.zeros((len(tri), 4, 3), F); v4[:, :3] = tri
     return dict(type=np.zeros(len(tri), np.int32), verts=v4, normal=np.concatenate(out_n).astype(F),
                 bsdf=np.concatenate(out_b).astype(F), Le=np.concatenate(out_e).astype(F))
+
+
+def sky(width, height, sun_dir=(0.35, 0.75, 0.55), sun_radiance=(400.0, 380.0, 340.0), sun_texels=1,
+        zenith=(0.25, 0.45, 0.9), horizon=(0.8, 0.85, 0.9), ground=(0.12, 0.11, 0.1)):
+    """A procedural environment map for Renderer.set_environment: (height, width, 3) float32, row 0 at +y.  Rows are the bands
+    cos(pi r / height) .. cos(pi (r + 1) / height) of the direction's y, columns divide the angle from +x towards +z evenly
+    (include/ptmi.h: "environment lighting").  The upper rows blend horizon -> zenith by the band centre's height, the lower rows
+    are `ground`, and the texel that holds sun_dir (and its sun_texels - 1 right-hand neighbours) has sun_radiance ADDED: a
+    small bright region that cosine sampling rarely finds and next-event estimation samples directly."""
+    width, height = int(width), int(height)
+    z = np.cos(np.pi * np.arange(height + 1) / height)
+    mid = 0.5 * (z[:-1] + z[1:])
+    t = np.clip(mid, 0.0, 1.0)[:, None]
+    rows = np.where(mid[:, None] > 0, (1.0 - t) * np.asarray(horizon, np.float64) + t * np.asarray(zenith, np.float64),
+                    np.asarray(ground, np.float64))
+    env = np.repeat(rows[:, None, :], width, axis=1)
+    d = np.asarray(sun_dir, np.float64)
+    d = d / np.linalg.norm(d)
+    r = int(np.clip(np.searchsorted(-z, -d[1], side="left") - 1, 0, height - 1))
+    j = int(np.floor((np.arctan2(d[2], d[0]) / (2.0 * np.pi)) % 1.0 * width)) % width
+    for k in range(max(int(sun_texels), 0)):
+        env[r, (j + k) % width] += np.asarray(sun_radiance, np.float64)
+    return env.astype(np.float32)

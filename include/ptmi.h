@@ -425,7 +425,7 @@ int ptmi_debug_grid_index(ptmi_ctx*, int n, const float* dirs, const float* norm
  * Streams are not re-seeded: an accumulation starts wherever the streams stand, as a frame does (after
  * ptmi_update_resolution: freshly seeded).  The accumulation is RESET - the next pass is pass 1 and starts from zero sums - by
  * ptmi_accum_reset and by every call that changes what a frame would show: ptmi_set_camera, a successful ptmi_set_config,
- * ptmi_update_resolution, the scene loads, ptmi_set_radiosity_grids, ptmi_set_radiosity, ptmi_apply_grid_filter,
+ * a successful ptmi_set_environment, ptmi_update_resolution, the scene loads, ptmi_set_radiosity_grids, ptmi_set_radiosity, ptmi_apply_grid_filter,
  * ptmi_use_raw_cdfs, ptmi_run_radiosity_solver, and ptmi_render_frame / ptmi_render_frames (which behave exactly as before).
  * PTMI_E_INVALID: the Radiosity integrator (config.integrator = 1), ptmi_select_frame after a pass, parameters out of range
  * or NaN, a pass after the accumulation has finished (no pixel active) or reached params->max_passes, and a pass that would
@@ -486,7 +486,7 @@ int  ptmi_read_sample_counts(const ptmi_ctx*, uint32_t* counts);
  * ptmi_read_features returns the buffers of the last feature pass in local row-major order (that of ptmi_read_image): albedo,
  * normal and position 3 floats per pixel, hit_fraction 1; any pointer may be NULL.
  * Features go STALE under the calls that restart an accumulation (see ptmi_accum_pass: scene loads, camera, resolution,
- * config, radiosity changes); ptmi_read_features then fails until the next ptmi_render_features, and ptmi_denoise recomputes them.
+ * config, environment, radiosity changes); ptmi_read_features then fails until the next ptmi_render_features, and ptmi_denoise recomputes them.
  *
  * THE FILTER.  ptmi_denoise filters the radiance that ptmi_read_image would return (the selected frame, or the last
  * accumulation pass) into buffers of its own; the frame image, colour sums, streams and accumulation state are untouched, so the
@@ -581,7 +581,8 @@ int  ptmi_denoise_timing(const ptmi_ctx*, double* features_ms, double* denoise_m
  * restart (an empty history included); they add up to the local pixel count.
  *
  * STATE.  ptmi_set_camera keeps the history.  Every other call that restarts an accumulation empties it: scene loads,
- * ptmi_update_resolution, a successful ptmi_set_config, the radiosity setters and solver; so does ptmi_temporal_reset.  A
+ * ptmi_update_resolution, a successful ptmi_set_config, a successful ptmi_set_environment (the light changes, not the view: there
+ * is nothing to reproject), the radiosity setters and solver; so does ptmi_temporal_reset.  A
  * step writes only buffers of its own: frames, passes, streams, the accumulation, the validity of the feature buffers and
  * ptmi_denoise's results are what they would be without it (it may recompute the features, as ptmi_denoise does).
  * ptmi_read_history_counts returns n per local pixel (0 everywhere while the history is empty).
@@ -664,6 +665,91 @@ int  ptmi_denoise_temporal(ptmi_ctx*, const ptmi_denoise_params* /* NULL: defaul
  * shading side (sn, the cosine lobe), as in the reference.  A primitive that is no emitter (a non-planar quad, an absorbed
  * weight) is found by BSDF samples alone, with weight 1.  Without an emitter in the scene NEE draws nothing and a frame is the
  * reference's frame. */
+
+/* ---- environment lighting: an importance-sampled lat-long radiance map (new in this implementation) -----------------------------
+ * Without an environment a ray that leaves the geometry ends its sample and adds nothing.  ptmi_set_environment gives the
+ * context a radiance map over all directions: a path ray that misses looks it up, and with ptmi_config.next_event = 1 the map is
+ * also a light that every vertex can sample, combined with the BSDF sample by the power heuristic as the emitters are.  The map
+ * belongs to the context, like the camera: it survives scene loads.  Frames, batches, passes (progressive and adaptive), tiled
+ * contexts, ptmi_denoise, ptmi_temporal_accumulate and ptmi_gather_frame work as they do without one; a context with an
+ * environment renders both values of next_event through the per-lane kernel of next-event estimation, so segments_per_launch,
+ * wave_tiles, streams and collect_stats have no effect on it (see ptmi_config.next_event).  Without an environment nothing in
+ * the library behaves differently.
+ *
+ * ptmi_set_environment: rgb holds height * width * 3 floats, row 0 at +y, rows top to bottom; NULL drops the environment
+ * (width, height and the parameters are then ignored).  A successful call restarts an accumulation, makes features stale and
+ * empties the temporal history.  PTMI_E_INVALID, with nothing changed: width or height < 1, width * height > 2^25, a texel
+ * that is negative, NaN or infinite before or after the scale, a total power that overflows float, parameters out of range
+ * (scale finite and >= 0, rotation_deg in [-360, 360], select_fraction in [0, 1]), and a current config with integrator = 1,
+ * sampling_mode != 0 or fast_tree = 1; ptmi_set_config rejects those three while an environment is set (the restrictions of
+ * next_event, for the same reasons).  ptmi_environment_info: 0 x 0 and total 0 without one.
+ *
+ * THE MAP, w x h texels.  Rows are bands of equal cos(theta) boundaries, columns divide phi evenly; y is up:
+ *     z_r     = (float)cos(pi r / h): the cosine ptmi_sincos_d gives for (PTMI_PI_D * (double)r) / (double)h, r = 0 .. h;
+ *               z_0 = 1, z_h = -1 exactly
+ *     rot     = rotation_deg / 360.0f (float): column 0 starts at the angle 2 pi rot from +x towards +z
+ *     E_rj    = rgb * scale per channel (float)
+ *     Omega_r = ((2.0 * PTMI_PI_D) / (double)w) * ((double)z_r - (double)z_{r+1})          the solid angle of a texel of row r
+ * THE LOOKUP texel(d) of a direction d, float32 in the order written (nearest texel: radiance is piecewise constant, so the
+ * sampling density below is exactly proportional to what is looked up):
+ *     y = fminf(fmaxf(d.y, -1), 1);   r = the smallest r in 0 .. h-1 with z_{r+1} < y, or h - 1 if there is none (y = -1)
+ *     phi = atan2f(d.z, d.x);  s = (float)((double)phi / (2.0 * PTMI_PI_D));  t = s - rot;  t = t - floorf(t)
+ *     j = min((int)(t * (float)w), w - 1)                     (atan2f, sincosf here and below: ptmi_math.h's ptmi_atan2f, ptmi_sincosf)
+ * THE TABLE (ptmi_host_env_table; built on the host at every ptmi_set_environment and uploaded), binary64 unless it says float:
+ *     W_rj = Omega_r * (((double)E.x + (double)E.y) + (double)E.z)                         (the emitter table's channel sum)
+ *     R_rj = R_r,j-1 + W_rj from 0 (row running sums), T_r = R_r,w-1;  M_r = M_{r-1} + T_r from 0,  total = (float)M_{h-1}
+ *     c_rj = (float)(R_rj / T_r) if T_r > 0, else 0;   m_r = (float)(M_r / M_{h-1}) if M_{h-1} > 0, else 0
+ *            (float CDFs that end at exactly 1; a row or a map of weight 0 keeps zeros and can never be selected)
+ *     P_rj = ((double)m_r - (double)m_{r-1}) * ((double)c_rj - (double)c_r,j-1)            m_{-1} = c_r,-1 = 0
+ *     pdf_rj = (float)(P_rj / Omega_r) if P_rj > 0, else 0
+ * P_rj is the probability with which the two searches below pick texel (r, j) - differences of the STORED floats - so pdf is
+ * the sampler's density per solid angle whatever rounding the CDFs took.  A texel or row whose CDF step rounds to nothing has
+ * pdf 0: it is found by BSDF samples alone, with weight 1 (the emitter table's rule for absorbed weights).  total == 0 (an
+ * all-black map, scale = 0): the environment is never sampled and no draw is made for it.
+ * texel (ptmi_host_env_table): h * w * 4 floats (E.x, E.y, E.z, pdf); z: h + 1; marginal_cdf: h; row_cdf: h * w.
+ *
+ * THE ESTIMATOR is that of "next-event estimation" above (with next_event = 0: the reference's, integrator.h:189-268, with its
+ * draws) with these changes; beta, L, p_b_prev, sn, o', mis, x / PI and dot as written there.
+ *   1'. the closest-hit walk of (o, d) finds nothing:  (E, pdf) = texel(d);  the sample ends after
+ *          next_event = 1, total > 0 and depth >= 1:   w = mis(p_b_prev, q * pdf);   L = L + (beta * E) * w
+ *          else:                                       L = L + beta * E          (beta = (1, 1, 1) at depth 0: the background)
+ *       next_event = 0 changes nothing else, so an all-zero map gives the bits of a frame without a map.
+ *   With next_event = 1 and total > 0 ("the environment is sampled"; otherwise steps 1 and 3 are exactly those above and a frame
+ *   with an all-zero map is bit-identical to the NEE frame without one):
+ *       q = 1 if the scene has no emitter, else select_fraction
+ *   1.  an emitter found at depth >= 1 weighs  w = mis(p_b_prev, (1.0f - q) * p_l)
+ *   3'. if depth + 1 < max_depth: ALWAYS five draws u_sel, r1, r2, r3, r4, in this order, whatever comes of them.
+ *       If u_sel <= q, the environment:
+ *          r = the smallest row with r1 <= m_r;   j = the smallest column with r2 <= c_rj
+ *          ct = z_{r+1} + r3 * (z_r - z_{r+1});   st = sqrtf(fmaxf(0, 1 - ct * ct))
+ *          a = ((float)j + r4) / (float)w + rot;  (sp, cp) = sincosf((float)((2.0 * PTMI_PI_D) * (double)a))
+ *          wi = (st * cp, ct, st * sp);   (E, pdf) = texel (r, j) itself, no second lookup
+ *          cos_s = dot(sn, wi);  p_e = q * pdf
+ *          if cos_s > 0, 0 < p_e <= FLT_MAX, and the reference's closest-hit walk of (o', wi) for t > 1e-4 finds nothing:
+ *              p_b = cos_s / PI;  w = (p_b * mis(p_e, p_b)) / p_e;  L = L + (beta * E) * w
+ *       else the emitter table, step 3 above with u' = (u_sel - q) / (1.0f - q) in place of u_sel and
+ *          p_l' = (1.0f - q) * p_l in place of p_l, in the test 0 < p_l' <= FLT_MAX and in the weight.
+ *       A strategy whose selection probability is 0 is never drawn (u_sel is in (0, 1]) and weighs nothing: mis(a, 0) = 1.
+ * The two MIS weights of a direction sum to 1 wherever both strategies can produce it - a missed direction by the BSDF sample
+ * (density p_b) and by the environment sample (q * pdf), an emitter point by the BSDF sample and by the emitter sample
+ * ((1 - q) * p_l) - so every pixel's expected value is that of the estimator without next_event.  A sampled direction looks up
+ * its own texel except where rounding puts it on a texel boundary; its E and pdf are the sampled texel's either way. */
+typedef struct {
+    float scale;            /* 1: every texel is multiplied by it on upload (float), >= 0, finite */
+    float rotation_deg;     /* 0: the map turned about +y, [-360, 360] */
+    float select_fraction;  /* 0.5: with next_event, the probability q that a vertex's light sample goes to the
+                               environment and not to the emitter table; in [0, 1] */
+} ptmi_env_params;
+void ptmi_default_env_params(ptmi_env_params*);
+/* the parameter check of ptmi_set_environment alone (no context, no device): 0 or PTMI_E_INVALID with the message */
+int  ptmi_check_env_params(const ptmi_env_params*);
+int  ptmi_set_environment(ptmi_ctx*, int width, int height, const float* rgb /* h*w*3, row 0 = +y; NULL drops it */,
+                          const ptmi_env_params* /* NULL: defaults */);
+int  ptmi_environment_info(const ptmi_ctx*, int* width, int* height, float* total);   /* 0 x 0 without one */
+/* host-only: the sampling table of a map, for inspection and CPU tests (any output pointer may be NULL) */
+int  ptmi_host_env_table(int width, int height, const float* rgb, const ptmi_env_params* /* NULL: defaults */,
+                         float* z /* h+1 */, float* marginal_cdf /* h */, float* row_cdf /* h*w */,
+                         float* texel /* h*w*4: scaled rgb, pdf per solid angle */, float* total);
 
 #ifdef __cplusplus
 }

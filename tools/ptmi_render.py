@@ -11,6 +11,8 @@
   python tools/ptmi_render.py --scene ... --spp 8 --aov-png aov                              (aov_albedo/normal/depth.png)
   python tools/ptmi_render.py --scene ... --spp 4 --orbit 16 --yaw-step 2 --temporal --denoise --out-prefix orbit_
                                (16 views 2 degrees apart, each through the temporal accumulation and the denoiser)
+  python tools/ptmi_render.py --scene ... --sky --next-event --out sky.png                    (procedural sky with a sun)
+  python tools/ptmi_render.py --scene ... --env map.npy --env-rotation 90 --out lit.png      ((h, w, 3) float radiance, row 0 up)
 """
 import argparse
 import os
@@ -50,6 +52,10 @@ def main():
     ap.add_argument("--temporal", action="store_true", help="with --orbit: every view through the temporal accumulation (reprojected history)")
     ap.add_argument("--out-prefix", default=None, help="with --orbit: write every view to PREFIXnnn.png")
     ap.add_argument("--next-event", action="store_true", help="next-event estimation with MIS: sample the emitters at every bounce")
+    ap.add_argument("--env", default=None, metavar="FILE.npy", help="environment light: a (height, width, 3) float lat-long radiance map, row 0 at +y")
+    ap.add_argument("--sky", action="store_true", help="environment light: the procedural sky of ptmi_scenes.sky (gradient + sun)")
+    ap.add_argument("--env-scale", type=float, default=1.0); ap.add_argument("--env-rotation", type=float, default=0.0, metavar="DEG")
+    ap.add_argument("--env-fraction", type=float, default=0.5, help="with --next-event: share of the light samples that go to the environment")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -74,6 +80,18 @@ def main():
     r.update_resolution(a.width, a.height)
     r.set_config(spp=a.spp, max_depth=a.max_depth, seed_base=a.seed_base, sampling_mode=a.sampling_mode,
                  mis_bsdf_fraction=a.mis_bsdf_fraction, integrator=1 if a.integrator == "radiosity" else 0, next_event=a.next_event)
+    if a.env or a.sky:
+        if a.env and a.sky:
+            ap.error("--env and --sky exclude each other")
+        if a.sky:
+            import ptmi_scenes
+            env = ptmi_scenes.sky(64, 32)
+        else:
+            import numpy as np
+            env = np.load(a.env)
+        r.set_environment(env, scale=a.env_scale, rotation_deg=a.env_rotation, select_fraction=a.env_fraction)
+        ei = r.environment_info()
+        print(f"environment: {ei['width']}x{ei['height']}, total power {ei['total']:.4g}")
     if a.orbit > 0:
         orbit(r, a, cam)
         r.close()
