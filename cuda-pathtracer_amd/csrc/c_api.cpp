@@ -40,6 +40,14 @@ void need(bool ok, const char* what) { if (!ok) throw ArgError(what); }
 void viewChanged(ApplicationState& app) { accumReset(app); featuresStale(app); temporalReset(app); }
 f3 v3(const float* p) { return mk3(p[0], p[1], p[2]); }
 
+// FrameStats -> the C structs that carry its fields (ptmi_stats, ptmi_pass_stats)
+template <class Dst>
+void copy_frame_stats(const FrameStats& fs, Dst& d) {
+    d.seconds = fs.seconds; d.bounce_kernel_ms = fs.bounce_kernel_ms; d.bounce_launches = fs.bounce_launches; d.path_visits = fs.path_visits;
+    d.samples = fs.samples; d.rays = fs.rays; d.node_visits = fs.node_visits; d.prim_tests = fs.prim_tests; d.hits = fs.hits;
+    d.top_node_visits = fs.top_node_visits; d.cert_chain = fs.cert_chain; d.cert_fallback = fs.cert_fallback;
+}
+
 template <class T>
 struct DevBuf {
     T* p = nullptr;
@@ -500,12 +508,7 @@ int ptmi_render_frame(ptmi_ctx* c, ptmi_stats* stats) {
         need(c != nullptr, "ctx is NULL");
         FrameStats fs;
         renderFrame(c->app, stats ? &fs : nullptr);
-        if (stats) {
-            stats->seconds = fs.seconds; stats->bounce_kernel_ms = fs.bounce_kernel_ms; stats->bounce_launches = fs.bounce_launches; stats->path_visits = fs.path_visits;
-            stats->samples = fs.samples; stats->rays = fs.rays; stats->node_visits = fs.node_visits;
-            stats->prim_tests = fs.prim_tests; stats->hits = fs.hits; stats->top_node_visits = fs.top_node_visits;
-            stats->cert_chain = fs.cert_chain; stats->cert_fallback = fs.cert_fallback;
-        }
+        if (stats) copy_frame_stats(fs, *stats);
     });
 }
 
@@ -514,12 +517,7 @@ int ptmi_render_frames(ptmi_ctx* c, int n_frames, ptmi_stats* stats) {
         need(c != nullptr, "ctx is NULL");
         FrameStats fs;
         renderFrames(c->app, n_frames, stats ? &fs : nullptr);
-        if (stats) {
-            stats->seconds = fs.seconds; stats->bounce_kernel_ms = fs.bounce_kernel_ms; stats->bounce_launches = fs.bounce_launches; stats->path_visits = fs.path_visits;
-            stats->samples = fs.samples; stats->rays = fs.rays; stats->node_visits = fs.node_visits;
-            stats->prim_tests = fs.prim_tests; stats->hits = fs.hits; stats->top_node_visits = fs.top_node_visits;
-            stats->cert_chain = fs.cert_chain; stats->cert_fallback = fs.cert_fallback;
-        }
+        if (stats) copy_frame_stats(fs, *stats);
     });
 }
 int ptmi_select_frame(ptmi_ctx* c, int frame) {
@@ -910,12 +908,8 @@ int ptmi_accum_pass(ptmi_ctx* c, const ptmi_adaptive_params* params, ptmi_pass_s
         PassStats ps;
         accumPass(c->app, params ? &prm : nullptr, stats ? &ps : nullptr);
         if (stats) {
-            const FrameStats& fs = ps.frame;
             stats->pass = ps.pass; stats->active_before = ps.active_before; stats->active_after = ps.active_after;
-            stats->samples = fs.samples; stats->seconds = fs.seconds; stats->bounce_kernel_ms = fs.bounce_kernel_ms;
-            stats->bounce_launches = fs.bounce_launches; stats->path_visits = fs.path_visits; stats->rays = fs.rays;
-            stats->node_visits = fs.node_visits; stats->prim_tests = fs.prim_tests; stats->hits = fs.hits;
-            stats->top_node_visits = fs.top_node_visits; stats->cert_chain = fs.cert_chain; stats->cert_fallback = fs.cert_fallback;
+            copy_frame_stats(ps.frame, *stats);
         }
     });
 }

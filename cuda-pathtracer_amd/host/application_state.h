@@ -39,6 +39,12 @@ struct DistError : std::runtime_error { using std::runtime_error::runtime_error;
         if (e_ != hipSuccess) throw HipError(e_, std::string(#call) + ": " + hipGetErrorString(e_));     \
     } while (0)
 
+inline float elapsedMs(hipEvent_t a, hipEvent_t b) {
+    float ms = 0.0f;
+    PTMI_HIP(hipEventElapsedTime(&ms, a, b));
+    return ms;
+}
+
 // cudaMallocSafe (utils/cuda_utils.h:54-60): throws on failure
 void* hipMallocSafe(size_t bytes, const char* name);
 
@@ -201,6 +207,9 @@ struct RenderState {
         int *d_queue_init = nullptr, *d_queue[2] = {nullptr, nullptr}, *d_count = nullptr;
         int* h_count = nullptr;                      // pinned + coherent, kCountRing entries
         int* d_hcount = nullptr;                     // the same memory as the device addresses it (count publishing)
+        bool owns_init_queue = false;                // false: d_queue_init points into somebody else's memory (a pass's queue)
+        void allocate(size_t capacity, bool own_init_queue);   // queues of `capacity` entries + the count ring; the stream is the context's
+        void release();
     } chunk[kMaxChunks];
     int n_chunks = 1;
     int want_chunks = 0;                             // 0 = automatic, else forced (scheduling knob)
@@ -406,5 +415,8 @@ std::vector<uint32_t> buildXorwowJumpMatrices();
 
 std::vector<int> localRowMap(const TileMap& tm);
 int countLocalRows(int height, int n_ranks, int rank, int row_block);
+
+// camera update (application.h:161-163) and the camera fields of a frame's parameters (render_state.cpp; frames and feature passes)
+void cameraFrameParams(ApplicationState& g_state, FrameParams& fp);
 
 }  // namespace ptmi

@@ -1,0 +1,268 @@
+// post_process.cpp — what runs on a finished image: feature buffers, the a-trous denoiser, temporal accumulation
+#include "application_state.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace ptmi {
+
+// ------------------------------------------------------------------------------------------------
+// feature buffers and the denoiser (include/ptmi.h: ptmi_render_features, ptmi_denoise)
+// ------------------------------------------------------------------------------------------------
+void featuresStale(ApplicationState& g) {
+    g.render.dn.features_valid = false;
+    g.render.dn.image_current = false;                 // the image shows the scene / view / config as it was before the change
+}
+
+void renderFeatures(ApplicationState& g, int grid) {
+    RenderState& r = g.render;
+    RenderState::Denoise& d = r.dn;
+    if (grid < 1 || grid > 4) throw ArgError("renderFeatures: grid must be in [1, 4]");
+    if (!g.scene.d_nodes) throw ArgError("renderFeatures: no scene loaded");
+    if (!r.d_state.A) throw ArgError("renderFeatures: buffers not allocated (call updateResolution first)");
+    PTMI_HIP(hipSetDevice(g.device_id));
+    const size_t n = std::max<size_t>(r.n_local, 1);
+    if (!d.fb.albedo) {
+        try {
+            d.fb.albedo = (float4*)hipMallocSafe(n * sizeof(float4), "features.albedo");
+            d.fb.normal = (float4*)hipMallocSafe(n * sizeof(float4), "features.normal");
+            d.fb.position = (float4*)hipMallocSafe(n * sizeof(float4), "features.position");
+        } catch (...) { r.freeDenoise(); throw; }
+    }
+    d.features_valid = false;
+    FrameParams fp;
+    cameraFrameParams(g, fp);
+    while (g.event_pool.size() < 2) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
+    PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
+    launch_features(g.scene.d_scene, r.tile, fp, grid, d.fb, r.stream);
+    PTMI_HIP(hipGetLastError());
+    PTMI_HIP(hipEventRecord(g.event_pool[1], r.stream));
+    PTMI_HIP(hipStreamSynchronize(r.stream));
+    d.features_ms = elapsedMs(g.event_pool[0], g.event_pool[1]);
+    d.grid = grid;
+    d.features_valid = true;
+}
+
+void readFeatures(const ApplicationState& g, float* albedo, float* normal, float* position, float* hit_fraction) {
+    const RenderState& r = g.render;
+    if (!r.dn.features_valid) throw ArgError("readFeatures: no current feature buffers (ptmi_render_features first)");
+    PTMI_HIP(hipSetDevice(g.device_id));
+    std::vector<float4> h(r.n_local);
+    const float4* src[3] = {r.dn.fb.albedo, r.dn.fb.normal, r.dn.fb.position};
+    float* dst[3] = {albedo, normal, position};
+    for (int k = 0; k < 3; k++) {
+        if (!dst[k] && !(k == 0 && hit_fraction)) continue;
+        if (r.n_local) PTMI_HIP(hipMemcpy(h.data(), src[k], r.n_local * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < r.n_local; i++) {
+            if (dst[k]) { dst[k][3 * i] = h[i].x; dst[k][3 * i + 1] = h[i].y; dst[k][3 * i + 2] = h[i].z; }
+            if (k == 0 && hit_fraction) hit_fraction[i] = h[i].w;
+        }
+    }
+}
+
+void checkDenoiseParams(const DenoiseParams& p) {
+    if (p.iterations < 0 || p.iterations > 10) throw ArgError("denoise: iterations must be in [0, 10]");
+    if (!(p.sigma_color >= 1e-4f && p.sigma_color <= 1e4f)) throw ArgError("denoise: sigma_color must be in [1e-4, 1e4]");
+    if (!(p.color_floor >= 1e-6f && p.color_floor <= 1e4f)) throw ArgError("denoise: color_floor must be in [1e-6, 1e4]");
+    if (!(p.sigma_position <= 0.0f || (p.sigma_position >= 1e-6f && p.sigma_position <= 1e12f)))
+        throw ArgError("denoise: sigma_position must be <= 0 (automatic) or in [1e-6, 1e12]");
+    if (p.normal_squarings < 0 || p.normal_squarings > 10) throw ArgError("denoise: normal_squarings must be in [0, 10]");
+    if (p.feature_grid < 1 || p.feature_grid > 4) throw ArgError("denoise: feature_grid must be in [1, 4]");
+    if (p.demodulate != 0 && p.demodulate != 1) throw ArgError("denoise: demodulate must be 0 or 1");
+}
+
+// sigma_x of the denoiser and of the temporal step for sigma_position <= 0: fraction x the diagonal of the root box of the
+// scene's BVH, in float
+static float autoSigmaPosition(const ApplicationState& g, float fraction, const char* who) {
+    const AABB& b = g.scene.bvh_nodes.at(0).bbox;
+    const float dx = b.max.x - b.min.x, dy = b.max.y - b.min.y, dz = b.max.z - b.min.z;
+    const float sigma_x = fraction * std::sqrt(dx * dx + dy * dy + dz * dz);
+    if (!(sigma_x >= 1e-6f && sigma_x <= 1e12f)) throw ArgError(std::string(who) + ": the scene's bounding box gives no usable sigma_position; set one");
+    return sigma_x;
+}
+
+// the filter's constants for p (parameters checked first); sigma_c[i]: the colour sigma of iteration i
+static DenoiseArgs denoiseArgs(const ApplicationState& g, const DenoiseParams& p, float* sigma_c) {
+    const RenderState& r = g.render;
+    checkDenoiseParams(p);
+    DenoiseArgs a;
+    a.width = r.tile.width; a.height = r.tile.local_rows;
+    a.demodulate = p.demodulate; a.normal_squarings = p.normal_squarings; a.color_floor = p.color_floor;
+    const float sigma_x = p.sigma_position > 0.0f ? p.sigma_position : autoSigmaPosition(g, 0.02f, "denoise");   // 2 %
+    a.sigma_x2 = sigma_x * sigma_x;
+    for (int i = 0; i < p.iterations; i++) sigma_c[i] = std::ldexp(p.sigma_color, -i);     // sigma_color x 2^-i, exact
+    return a;
+}
+
+// the filter over radiance guided by fb into the denoiser's outputs (what ptmi_read_denoised returns)
+static void denoiseRun(ApplicationState& g, const DenoiseArgs& a, int iterations, const float* sigma_c, const FeatureBuffers& fb,
+                       const float* radiance) {
+    RenderState& r = g.render;
+    RenderState::Denoise& d = r.dn;
+    PTMI_HIP(hipSetDevice(g.device_id));
+    const size_t n = std::max<size_t>(r.n_local, 1);
+    if (!d.d_rgb8) {
+        try {
+            d.d_rgb8 = (unsigned char*)hipMallocSafe(n * 3, "denoise.rgb8");
+            d.d_radiance = (float*)hipMallocSafe(n * 3 * sizeof(float), "denoise.radiance");
+            d.d_buf = (float4*)hipMallocSafe(2 * n * sizeof(float4), "denoise.buf");
+        } catch (...) {
+            for (void* q : {(void*)d.d_rgb8, (void*)d.d_radiance, (void*)d.d_buf}) if (q) (void)hipFree(q);
+            d.d_rgb8 = nullptr; d.d_radiance = nullptr; d.d_buf = nullptr;
+            throw;
+        }
+    }
+    while (g.event_pool.size() < 2) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
+    d.denoised = false;
+    if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));
+    PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
+    launch_denoise(a, fb, radiance, iterations, sigma_c, d.d_buf, d.d_rgb8, d.d_radiance, r.stream);
+    PTMI_HIP(hipGetLastError());
+    PTMI_HIP(hipEventRecord(g.event_pool[1], r.stream));
+    PTMI_HIP(hipStreamSynchronize(r.stream));
+    d.denoise_ms = elapsedMs(g.event_pool[0], g.event_pool[1]);
+    d.denoised = true;
+}
+
+void denoise(ApplicationState& g, const DenoiseParams& p) {
+    RenderState& r = g.render;
+    RenderState::Denoise& d = r.dn;
+    if (r.tile.n_ranks > 1) throw ArgError("denoise: the context is tiled over more than one rank (the filter needs rows of other ranks)");
+    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError("denoise: the Radiosity integrator's image is not denoised");
+    if (!g.scene.d_nodes || !r.d_state.A || !d.image_current)
+        throw ArgError("denoise: no image rendered yet (none since the last change of scene, camera, resolution or config)");
+    float sigma_c[10];
+    const DenoiseArgs a = denoiseArgs(g, p, sigma_c);
+    if (!d.features_valid || d.grid != p.feature_grid) renderFeatures(g, p.feature_grid);
+    denoiseRun(g, a, p.iterations, sigma_c, d.fb, r.d_radiance);
+}
+
+void readDenoised(const ApplicationState& g, unsigned char* rgb8, float* radiance) {
+    const RenderState& r = g.render;
+    if (!r.dn.denoised) throw ArgError("readDenoised: nothing denoised yet (ptmi_denoise first)");
+    PTMI_HIP(hipSetDevice(g.device_id));
+    if (rgb8 && r.n_local) PTMI_HIP(hipMemcpy(rgb8, r.dn.d_rgb8, r.n_local * 3, hipMemcpyDeviceToHost));
+    if (radiance && r.n_local) PTMI_HIP(hipMemcpy(radiance, r.dn.d_radiance, r.n_local * 3 * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+// ------------------------------------------------------------------------------------------------
+// temporal accumulation with reprojection (include/ptmi.h: ptmi_temporal_accumulate)
+// ------------------------------------------------------------------------------------------------
+void temporalReset(ApplicationState& g) { g.render.tp.valid = false; }
+
+void checkTemporalParams(const TemporalParams& p) {
+    if (p.max_history < 1 || p.max_history > 65536) throw ArgError("temporal: max_history must be in [1, 65536]");
+    if (!(p.normal_min >= -1.0f && p.normal_min <= 1.0f)) throw ArgError("temporal: normal_min must be in [-1, 1]");
+    if (!(p.sigma_position <= 0.0f || (p.sigma_position >= 1e-6f && p.sigma_position <= 1e12f)))
+        throw ArgError("temporal: sigma_position must be <= 0 (automatic) or in [1e-6, 1e12]");
+    if (p.feature_grid < 1 || p.feature_grid > 4) throw ArgError("temporal: feature_grid must be in [1, 4]");
+    if (!(p.sigma_albedo >= 0.0f && p.sigma_albedo <= 1e6f)) throw ArgError("temporal: sigma_albedo must be in [0, 1e6]");
+}
+
+// the camera frame the next frame would use (ptmi_get_camera_frame): origin, lower-left corner, horizontal, vertical
+static void viewFrame(const ApplicationState& g, float* out12) {
+    Sensor s = g.render.h_camera;
+    if (g.config.orbit) s.updateCameraOrbit(); else s.updateCamera();
+    const CameraFrame f = s.frame();
+    const f3 v[4] = {f.origin, f.lower_left_corner, f.horizontal, f.vertical};
+    for (int i = 0; i < 4; i++) { out12[3 * i] = v[i].x; out12[3 * i + 1] = v[i].y; out12[3 * i + 2] = v[i].z; }
+}
+
+void temporalAccumulate(ApplicationState& g, const TemporalParams& p, TemporalStats* stats) {
+    RenderState& r = g.render;
+    RenderState::Temporal& t = r.tp;
+    RenderState::Denoise& d = r.dn;
+    if (r.tile.n_ranks > 1) throw ArgError("temporal: the context is tiled over more than one rank (taps cross ranks)");
+    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError("temporal: the Radiosity integrator's image is not accumulated");
+    if (!g.scene.d_nodes || !r.d_state.A || !d.image_current)
+        throw ArgError("temporal: no image rendered yet (none since the last change of scene, camera, resolution or config)");
+    checkTemporalParams(p);
+    TemporalArgs a;
+    a.width = r.tile.width; a.height = r.tile.local_rows;
+    const float sigma_x = p.sigma_position > 0.0f ? p.sigma_position : autoSigmaPosition(g, 0.01f, "temporal");     // 1 %
+    a.sigma_x2 = sigma_x * sigma_x;
+    a.sigma_a2 = p.sigma_albedo * p.sigma_albedo;
+    a.normal_min = p.normal_min;
+    a.max_history = (float)p.max_history;
+    a.m = (float)g.config.spp;
+    const unsigned int* counts = d.image_pass ? r.accum.d_counts : nullptr;     // a pass: every pixel's own count
+    float cam[12];
+    viewFrame(g, cam);
+    double features_ms = 0.0;
+    if (!d.features_valid || d.grid != p.feature_grid) { renderFeatures(g, p.feature_grid); features_ms = d.features_ms; }
+    PTMI_HIP(hipSetDevice(g.device_id));
+    const size_t n = std::max<size_t>(r.n_local, 1);
+    if (!t.d_rgb8) {
+        try {
+            for (TemporalHistory& h : t.side) {
+                h.color = (float4*)hipMallocSafe(n * sizeof(float4), "temporal.color");
+                h.normal = (float4*)hipMallocSafe(n * sizeof(float4), "temporal.normal");
+                h.position = (float4*)hipMallocSafe(n * sizeof(float4), "temporal.position");
+                h.albedo = (float4*)hipMallocSafe(n * sizeof(float4), "temporal.albedo");
+            }
+            t.d_radiance = (float*)hipMallocSafe(n * 3 * sizeof(float), "temporal.radiance");
+            t.d_stats = (unsigned long long*)hipMallocSafe(3 * sizeof(unsigned long long), "temporal.stats");
+            t.d_rgb8 = (unsigned char*)hipMallocSafe(n * 3, "temporal.rgb8");
+        } catch (...) { r.freeTemporal(); throw; }
+    }
+    a.history = t.valid ? 1 : 0;
+    a.still = t.valid && std::memcmp(cam, t.cam, sizeof cam) == 0 && t.width == a.width && t.height == a.height ? 1 : 0;
+    std::memcpy(a.cam, t.cam, sizeof a.cam);
+    std::memcpy(a.origin, cam, sizeof a.origin);
+    while (g.event_pool.size() < 2) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
+    const int next = t.cur ^ 1;
+    unsigned long long h_stats[3] = {0, 0, 0};
+    t.stepped = false;
+    PTMI_HIP(hipMemsetAsync(t.d_stats, 0, sizeof h_stats, r.stream));
+    if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));
+    PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
+    launch_temporal(a, d.fb, r.d_radiance, counts, t.side[t.cur], t.side[next], t.d_rgb8, t.d_radiance, t.d_stats, r.stream);
+    PTMI_HIP(hipGetLastError());
+    PTMI_HIP(hipEventRecord(g.event_pool[1], r.stream));
+    PTMI_HIP(hipMemcpyAsync(h_stats, t.d_stats, sizeof h_stats, hipMemcpyDeviceToHost, r.stream));
+    PTMI_HIP(hipStreamSynchronize(r.stream));
+    t.cur = next;
+    t.valid = true;
+    std::memcpy(t.cam, cam, sizeof cam);
+    t.width = a.width; t.height = a.height;
+    t.grid = p.feature_grid;
+    t.stepped = true;
+    if (stats) {
+        stats->accepted = h_stats[0]; stats->rejected = h_stats[1]; stats->missed = h_stats[2];
+        stats->seconds = elapsedMs(g.event_pool[0], g.event_pool[1]) * 1e-3;
+        stats->features_ms = features_ms;
+    }
+}
+
+void readTemporal(const ApplicationState& g, unsigned char* rgb8, float* radiance) {
+    const RenderState& r = g.render;
+    if (!r.tp.stepped) throw ArgError("readTemporal: no temporal step yet (ptmi_temporal_accumulate first)");
+    PTMI_HIP(hipSetDevice(g.device_id));
+    if (rgb8 && r.n_local) PTMI_HIP(hipMemcpy(rgb8, r.tp.d_rgb8, r.n_local * 3, hipMemcpyDeviceToHost));
+    if (radiance && r.n_local) PTMI_HIP(hipMemcpy(radiance, r.tp.d_radiance, r.n_local * 3 * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+void readHistoryCounts(const ApplicationState& g, float* counts) {
+    const RenderState& r = g.render;
+    if (!r.d_state.A) throw ArgError("readHistoryCounts: buffers not allocated");
+    if (!r.tp.valid) { std::fill(counts, counts + r.n_local, 0.0f); return; }
+    PTMI_HIP(hipSetDevice(g.device_id));
+    std::vector<float4> h(r.n_local);
+    if (r.n_local) PTMI_HIP(hipMemcpy(h.data(), r.tp.side[r.tp.cur].color, r.n_local * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < r.n_local; i++) counts[i] = h[i].w;
+}
+
+void denoiseTemporal(ApplicationState& g, const DenoiseParams& p) {
+    RenderState& r = g.render;
+    const RenderState::Temporal& t = r.tp;
+    if (!t.valid) throw ArgError("denoise_temporal: the history is empty (ptmi_temporal_accumulate first)");
+    float sigma_c[10];
+    const DenoiseArgs a = denoiseArgs(g, p, sigma_c);
+    if (p.feature_grid != t.grid) throw ArgError("denoise_temporal: feature_grid differs from the history's");
+    FeatureBuffers fb;
+    fb.albedo = t.side[t.cur].albedo; fb.normal = t.side[t.cur].normal; fb.position = t.side[t.cur].position;
+    denoiseRun(g, a, p.iterations, sigma_c, fb, t.d_radiance);        // the last step's radiance is the history's colour
+}
+
+}  // namespace ptmi

@@ -337,6 +337,22 @@ def test_result_independent_of_stream_chunks(R):
     assert out[0][2].path_visits == out[1][2].path_visits
     orgb, orad, _ = OracleScene.load(os.path.join(SCENES, "cbox.obj")).render(default_camera(), 200, 120, 5)
     assert_same_image(out[1][0], out[1][1], orgb, orad, "2 streams")
+    # the certified walk's refill launch, alone and shared between three forced chunks (each launch takes its chunk's share of the
+    # wave slots); the kernels' event pairs lie inside the frame's interval on each stream, and there is at least one
+    R.load_scene(os.path.join(SCENES, "cbox.obj"), 2)
+    assert R.set_traversal(-1) == ptmi.Renderer.CERTIFIED
+    out = []
+    for streams in (1, 3):
+        R.set_config(spp=3, max_depth=5, streams=streams, segments_per_launch=0, collect_stats=True)
+        R.update_resolution(96, 64)
+        st = R.render_frame()
+        out.append(R.read_image() + (st,))
+        assert 0 < st.bounce_kernel_ms <= 1e3 * st.seconds * streams, (streams, st.bounce_kernel_ms, st.seconds)
+    assert (bits(out[0][1]) == bits(out[1][1])).all() and (out[0][0] == out[1][0]).all()
+    assert (out[0][2].rays, out[0][2].path_visits) == (out[1][2].rays, out[1][2].path_visits)
+    orgb, orad, _ = OracleScene.load(os.path.join(SCENES, "cbox.obj"), 2).render(default_camera(), 96, 64, 3, max_depth=5)
+    for k, streams in enumerate((1, 3)):
+        assert_same_image(out[k][0], out[k][1], orgb, orad, f"refill, {streams} streams")
     R.set_config(streams=0, segments_per_launch=0, collect_stats=False)
 
 
@@ -474,15 +490,17 @@ def test_tile_union_is_the_single_gpu_frame(R):
     R.update_resolution(W, H)
     R.render_frame()
     rgb1, rad1 = R.read_image()
-    for n_ranks, rb in ((2, 8), (3, 4), (8, 8), (4, 1)):
+    for n_ranks, rb in ((2, 8), (3, 4), (8, 8), (4, 1), (16, 8)):      # (16, 8): ranks 8 - 15 have no rows
         rgb = np.zeros_like(rgb1); rad = np.full_like(rad1, -1)
         for rank in range(n_ranks):
             R.update_resolution(W, H, n_ranks=n_ranks, rank=rank, row_block=rb)
-            R.render_frame()
+            st = R.render_frame()
             rows = R.local_rows()
             a, b = R.read_image()
             if len(rows):
                 rgb[rows] = a; rad[rows] = b
+            else:
+                assert (st.samples, st.bounce_launches) == (0, 0), (n_ranks, rb, rank)
         assert (bits(rad) == bits(rad1)).all() and (rgb == rgb1).all(), (n_ranks, rb)
 
 
