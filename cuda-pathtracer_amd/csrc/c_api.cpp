@@ -418,6 +418,11 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
             need(cfg->sampling_mode == 0, "an environment is set: it needs sampling_mode 0 (BSDF): the guided modes do not look the environment up");
             need(cfg->fast_tree == 0, "an environment is set: it needs fast_tree 0: environment frames always trace the reference's hits");
         }
+        if (c->app.scene.hasSpecular()) {
+            need(cfg->integrator == 0, "specular surfaces are set: they need integrator 0 (PathTracing): the Radiosity view traces first hits only");
+            need(cfg->sampling_mode == 0, "specular surfaces are set: they need sampling_mode 0 (BSDF): the guided modes sample a diffuse lobe at every vertex");
+            need(cfg->fast_tree == 0, "specular surfaces are set: they need fast_tree 0: specular frames always trace the reference's hits");
+        }
         AppConfig& a = c->app.config;                    // every check is above this line: a rejected config changes nothing
         a.spp = cfg->spp; a.max_depth = cfg->max_depth; a.sampling_mode = (SamplingMode)cfg->sampling_mode;
         a.mis_bsdf_fraction = cfg->mis_bsdf_fraction;
@@ -478,6 +483,38 @@ int ptmi_host_env_table(int width, int height, const float* rgb, const ptmi_env_
         if (row_cdf) std::memcpy(row_cdf, t.row_cdf.data(), t.row_cdf.size() * sizeof(float));
         if (texel) std::memcpy(texel, t.texel.data(), t.texel.size() * sizeof(float));
         if (total) *total = t.total;
+    });
+}
+
+int ptmi_check_surfaces(int n_prims, const int* kind, const float* ior) {
+    return guarded([&] { checkSurfaces(n_prims, kind, ior); });
+}
+int ptmi_set_surfaces(ptmi_ctx* c, int n_prims, const int* kind, const float* ior) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        need(c->app.scene.d_nodes != nullptr, "no scene loaded");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        if (kind) {
+            need(n_prims == (int)c->app.scene.h_primitives.size(), "n_prims does not match the loaded scene");
+            checkSurfaces(n_prims, kind, ior);
+            bool specular = false;
+            for (int i = 0; i < n_prims; i++) specular = specular || kind[i] != kSurfaceDiffuse;
+            if (specular) {
+                const AppConfig& a = c->app.config;
+                need(a.current_integrator == IntegratorType::PathTracing, "surfaces: the config has integrator 1 (Radiosity), which traces first hits only");
+                need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "surfaces: the config has a guided sampling_mode, which samples a diffuse lobe at every vertex");
+                need(!a.fast_tree, "surfaces: the config has fast_tree 1; specular frames always trace the reference's hits");
+            }
+        }
+        c->app.scene.setSurfaces(kind, ior);                         // every check is done before anything changes
+        viewChanged(c->app);                                         // other materials: the temporal history holds another image
+    });
+}
+int ptmi_surfaces_info(const ptmi_ctx* c, int* n_mirror, int* n_glass) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        if (n_mirror) *n_mirror = c->app.scene.n_mirror;
+        if (n_glass) *n_glass = c->app.scene.n_glass;
     });
 }
 

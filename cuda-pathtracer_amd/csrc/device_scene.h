@@ -298,13 +298,21 @@ struct EnvTable {
     int w = 0, h = 0;
     float rot = 0.0f;                  // rotation_deg / 360.0f: the turn of column 0 from +x towards +z
     float q = 0.0f;                    // the EFFECTIVE probability that a vertex's light sample goes to the environment
-    int next_event = 0;                // ptmi_config.next_event of the run
     int sampled = 0;                   // next_event and total > 0: a vertex draws five numbers and selects by q
 };
-// fp.n_frames x spp samples per queued pixel.  env.texel == nullptr: the NEE kernel exactly as it was (next_event = 1); else
-// the ENV instantiation, which runs either estimator (env.next_event) and looks the map up where a path ray misses.
-void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const TileMap& tm, const PathState& st,
-                       const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s);
+// ---- specular surfaces (include/ptmi.h: ptmi_set_surfaces) -----------------------------------------------------------------
+// One record per LEAF-ORDER slot, the order of mats and EmitterTable::pdf_area (SceneState::setSurfaces permutes the caller's
+// load-order table): (bits(kind), ior), kind PTMI_SURFACE_*.  An array of its own: the bounce kernels stage mats into LDS and
+// the packed layouts copy it, and none of them may change.  rec == nullptr: every surface is diffuse (no table, or all kinds 0).
+struct SurfaceTable {
+    const float2* rec = nullptr;
+};
+// fp.n_frames x spp samples per queued pixel.  env.texel == nullptr and surf.rec == nullptr: the NEE kernel exactly as it was;
+// that instantiation IGNORES next_event (the host routes a frame here only when it is set, and the switch folds to true).  Else
+// the ENV and / or SPEC instantiation, which reads next_event and runs either estimator, looks the map up where a path ray
+// misses and continues a path through mirror and glass.
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, bool next_event,
+                       const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s);
 
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)

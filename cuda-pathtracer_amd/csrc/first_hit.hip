@@ -173,9 +173,12 @@ __device__ __forceinline__ int env_texel(const EnvTable& ev, const f3& d) {
     return r * ev.w + j;
 }
 
-template <int MODE, bool HAS_QUADS, bool ENV>
-__global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, EmitterTable em, EnvTable ev, TileMap tm, PathState st, FrameParams fp,
-                                                          const int* __restrict__ queue, int n, int first) {
+// specular surfaces (include/ptmi.h: "specular surfaces"; the table: device_scene.h SurfaceTable).  SPEC: the context has a table
+// with a mirror or glass primitive; a vertex on one makes no light sample and no cosine sample and goes on along the reflected or
+// refracted direction, and what the next path ray finds (an emitter, the environment) counts in full.
+template <int MODE, bool HAS_QUADS, bool ENV, bool SPEC>
+__global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, EmitterTable em, EnvTable ev, SurfaceTable sf, TileMap tm, PathState st, FrameParams fp,
+                                                          const int* __restrict__ queue, int n, int first, int next_event) {
     extern __shared__ float4 smem[];
     const int idx = blockIdx.x * kBlock + threadIdx.x;
     if (idx >= n) return;                                    // the walks are per lane: no barrier below
@@ -186,8 +189,8 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     Rng rng = {e.x, e.y, e.z, e.w, f.x, f.y};
     f3 color = first ? mk3(0.0f, 0.0f, 0.0f) : xyz(st.D[slot]);
     LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
-    // wave-uniform switches of the ENV instantiation; without ENV they fold to today's kernel
-    const bool nee_on = ENV ? ev.next_event != 0 : true;     // light samples and MIS weights at all
+    // wave-uniform switches of the ENV and SPEC instantiations; without either they fold to the NEE kernel
+    const bool nee_on = ENV || SPEC ? next_event != 0 : true;   // light samples and MIS weights at all
     const bool env_on = ENV ? ev.sampled != 0 : false;       // the environment is one of the lights: five draws, selection by q
     const float q = ENV ? ev.q : 0.0f, omq = 1.0f - q;
     for (int frame = 0; frame < fp.n_frames; frame++) {
@@ -200,6 +203,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
             camera_ray(fp, tm, x, y, rng, o, d);
             f3 tp = mk3(1.0f, 1.0f, 1.0f), L = mk3(0.0f, 0.0f, 0.0f);
             float pb_prev = 0.0f;                            // pdf of the cosine sample that made the current path ray
+            bool spec_prev = false;                          // SPEC: a mirror or glass vertex made the current path ray: no MIS weight
             int depth = 0;
             bool shadow = false;                             // the next walk is the shadow ray (so, sd) of the last vertex
             f3 so = o, sd = d, contrib = mk3(0.0f, 0.0f, 0.0f);
@@ -217,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                     if constexpr (ENV) {                                                  // the path ray leaves the scene: E(d)
                         const float4 te = ev.texel[env_texel(ev, d)];
                         const f3 c = tp * xyz(te);
-                        if (env_on && depth > 0) {
+                        if (env_on && depth > 0 && !(SPEC && spec_prev)) {
                             const float w = mis_power_heuristic(pb_prev, q * te.w);
                             L = L + mk3(c.x * w, c.y * w, c.z * w);
                         } else L = L + c;
@@ -226,7 +230,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                 }
                 const f3 nrm = xyz(sc.mats[3 * k]), bsdf = xyz(sc.mats[3 * k + 1]), Le = xyz(sc.mats[3 * k + 2]);
                 const f3 hp = o + t * d;                                                  // triangle.h:90
-                const float4 pe = depth > 0 && nee_on ? em.pdf_area[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                const float4 pe = depth > 0 && nee_on && !(SPEC && spec_prev) ? em.pdf_area[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 const float pa = pe.w;
                 if (pa > 0.0f) {                                                          // an emitter found by the BSDF sample
                     float p_l = (pa * (t * t)) / fabsf(dot(xyz(pe), d));                 // the geometric normal: area -> solid angle
@@ -245,6 +249,39 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                 if (length(tp) < 1e-5f) break;                                            // integrator.h:218
                 const f3 sn = dot(d, nrm) < 0 ? nrm : -nrm;                               // integrator.h:221-222
                 const f3 o2 = hp + 1e-4f * sn;                                            // integrator.h:266
+                if constexpr (SPEC) {
+                    const float2 sr = sf.rec[k];
+                    const int kind = __float_as_int(sr.x);
+                    if (kind != 0) {                                                      // no light sample, no cosine sample
+                        const f3 un = unit_vector(sn);
+                        const float dn = dot(d, un);
+                        bool reflect = true;
+                        float eta = 1.0f, ci = 1.0f, ct = 1.0f;
+                        if (kind == 2) {                                                  // glass: one draw whatever comes of it
+                            const float u = rng_uniform(rng);
+                            eta = dot(d, nrm) < 0 ? 1.0f / sr.y : sr.y;                   // n_i / n_t: the stored normal points out of the body
+                            ci = fminf(1.0f, -dn);
+                            const float s2 = (eta * eta) * fmaxf(0.0f, 1.0f - ci * ci);
+                            if (!(s2 >= 1.0f) || eta == 1.0f) {                           // else total internal reflection
+                                ct = eta == 1.0f ? ci : sqrt_rn(1.0f - s2);               // ior 1 is no interface: F = 0 and next = d, exactly
+                                const float rs = (eta * ci - ct) / (eta * ci + ct);
+                                const float rp = (ci - eta * ct) / (ci + eta * ct);
+                                const float fr = 0.5f * (rs * rs + rp * rp);
+                                reflect = u <= fr;
+                            }
+                        }
+                        depth++;
+                        if (depth >= fp.max_depth) break;
+                        const f3 next = reflect ? d - (2.0f * dn) * un : eta * d + (eta * ci - ct) * un;
+                        const float len2 = dot(next, next);
+                        if (!(len2 > 0.0f && len2 <= FLT_MAX)) break;                     // no walk starts with a NaN direction
+                        o = reflect ? o2 : hp - 1e-4f * sn;
+                        d = unit_vector(next);
+                        spec_prev = true;
+                        continue;
+                    }
+                    spec_prev = false;
+                }
                 if (nee_on && depth + 1 < fp.max_depth && (em.n > 0 || env_on)) {         // NEE: three draws (five with an environment) whatever comes of them
                     float u_sel = rng_uniform(rng);
                     const float r1 = rng_uniform(rng);
@@ -319,13 +356,16 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     st.F[slot] = make_uint2(rng.v4, rng.d);
 }
 
-void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const TileMap& tm, const PathState& st,
-                       const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s) {
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, bool next_event,
+                       const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s) {
     if (n <= 0) return;
     first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
         with_bool(env.texel != nullptr, [&](auto with_env) {
-            hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value>),
-                               dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, tm, st, fp, queue, n, first ? 1 : 0);
+            with_bool(surf.rec != nullptr, [&](auto with_spec) {
+                hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value, decltype(with_spec)::value>),
+                                   dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, surf, tm, st, fp, queue, n, first ? 1 : 0,
+                                   next_event ? 1 : 0);
+            });
         });
     });
 }

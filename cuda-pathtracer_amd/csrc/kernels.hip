@@ -15,7 +15,8 @@
 //   bounce_wide.hip    ptmi_bounce_wide   the phased scheduling over the opt-in 8-wide tree, plain or certified
 //   first_hit.hip      the Radiosity view, the feature pass, and
 //                      ptmi_render_nee    opt-in next-event estimation with MIS (include/ptmi.h): one lane runs a pixel's samples to their end;
-//                                         its ENV instantiation renders every frame of a context with an environment (ptmi_set_environment)
+//                                         its ENV instantiation renders every frame of a context with an environment (ptmi_set_environment),
+//                                         its SPEC instantiation every frame of a scene with a mirror or glass primitive (ptmi_set_surfaces)
 //   debug_hooks.hip    the test hooks
 #include "bounce.h"
 

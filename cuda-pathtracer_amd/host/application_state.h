@@ -17,6 +17,7 @@
 #include "../csrc/device_scene.h"
 #include "bvh.h"
 #include "environment.h"
+#include "surfaces.h"
 #include "file_manager.h"
 #include "pbrt_loader.h"
 #include "sensor.h"
@@ -133,6 +134,14 @@ struct SceneState {
     float4 *d_emit_rec = nullptr, *d_pdf_area = nullptr;
     float* d_emit_cdf = nullptr;
     EmitterTable d_emitters;
+    // specular surfaces (include/ptmi.h: ptmi_set_surfaces): the caller's load-order table by leaf-order slot (csrc/device_scene.h:
+    // SurfaceTable).  It indexes primitives, so it goes with the scene (cleanup).  A table whose kinds are all 0 is kept as no
+    // table: d_surfaces stays nullptr and a frame takes the route it takes without one.
+    int n_mirror = 0, n_glass = 0;
+    float2* d_surfaces = nullptr;
+    bool hasSpecular() const { return d_surfaces != nullptr; }
+    void setSurfaces(const int* kind, const float* ior);   // checked by the caller (checkSurfaces); kind nullptr drops the table
+    SurfaceTable surfaceTable() const { SurfaceTable t; t.rec = d_surfaces; return t; }
     int sweep_max_prims = 64;                        // scenes up to this many primitives use the wave-uniform sweep
     int force_traversal = -1;                        // test/benchmark override (TraversalMode), -1 = automatic
 

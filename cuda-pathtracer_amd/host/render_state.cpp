@@ -291,7 +291,6 @@ EnvTable EnvState::table(bool next_event, int n_emitters) const {
     if (!present()) return e;
     e.z = d_z; e.marginal = d_marginal; e.row_cdf = d_row_cdf; e.texel = d_texel;
     e.w = h.width; e.h = h.height; e.rot = h.rot_turns;
-    e.next_event = next_event ? 1 : 0;
     e.sampled = next_event && h.total > 0.0f ? 1 : 0;
     e.q = n_emitters == 0 ? 1.0f : params.select_fraction;     // (total == 0: not sampled, q is not read)
     return e;

@@ -38,6 +38,7 @@ EXPORTS = [
     "ptmi_host_emitters",
     "ptmi_debug_math", "ptmi_debug_grid_index",
     "ptmi_default_env_params", "ptmi_check_env_params", "ptmi_set_environment", "ptmi_environment_info", "ptmi_host_env_table",
+    "ptmi_check_surfaces", "ptmi_set_surfaces", "ptmi_surfaces_info",
 ]
 
 
@@ -218,6 +219,9 @@ def lib():
         L.ptmi_set_environment.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(EnvParams)]
         L.ptmi_environment_info.argtypes = [vp, ip, ip, C.POINTER(C.c_float)]
         L.ptmi_host_env_table.argtypes = [C.c_int, C.c_int, vp, C.POINTER(EnvParams), vp, vp, vp, vp, C.POINTER(C.c_float)]
+        L.ptmi_check_surfaces.argtypes = [C.c_int, vp, vp]
+        L.ptmi_set_surfaces.argtypes = [vp, C.c_int, vp, vp]
+        L.ptmi_surfaces_info.argtypes = [vp, ip, ip]
         _lib = L
     return _lib
 
@@ -398,6 +402,22 @@ def host_env_table(rgb, **params):
     return dict(z=z, marginal_cdf=m, row_cdf=c, texel=t, total=np.float32(total.value))
 
 
+SURFACE_DIFFUSE, SURFACE_MIRROR, SURFACE_GLASS = 0, 1, 2      # PTMI_SURFACE_*
+
+
+def _surface_table(kind, ior):
+    kind = np.ascontiguousarray(kind, np.int32).reshape(-1)
+    if ior is not None:
+        ior = np.ascontiguousarray(np.broadcast_to(np.asarray(ior, np.float32), kind.shape))
+    return kind, ior
+
+
+def check_surfaces(kind, ior=None):
+    """ptmi_check_surfaces: raises PtmiError for a table ptmi_set_surfaces would reject on its own account (host only)."""
+    kind, ior = _surface_table(kind, ior)
+    _check(lib().ptmi_check_surfaces(len(kind), kind.ctypes.data, None if ior is None else ior.ctypes.data))
+
+
 class Renderer:
     """One ApplicationState bound to one GPU."""
 
@@ -553,6 +573,20 @@ class Renderer:
         return dict(width=w.value, height=h.value, total=np.float32(t.value))
 
     host_env_table = staticmethod(host_env_table)
+
+    def set_surfaces(self, kind, ior=None):
+        """Mirror and glass (include/ptmi.h: "specular surfaces"): kind (n_prims,) of SURFACE_DIFFUSE / _MIRROR / _GLASS in load
+        order, or None to drop the table; ior a scalar or (n_prims,), None: 1.5 everywhere.  A scene load drops the table."""
+        if kind is None:
+            self._ck(self.L.ptmi_set_surfaces(self.h, 0, None, None))
+            return
+        kind, ior = _surface_table(kind, ior)
+        self._ck(self.L.ptmi_set_surfaces(self.h, len(kind), kind.ctypes.data, None if ior is None else ior.ctypes.data))
+
+    def surfaces_info(self):
+        m, g = C.c_int(), C.c_int()
+        self._ck(self.L.ptmi_surfaces_info(self.h, C.byref(m), C.byref(g)))
+        return dict(n_mirror=m.value, n_glass=g.value)
 
     def camera_frame(self):
         out = np.zeros(12, np.float32)

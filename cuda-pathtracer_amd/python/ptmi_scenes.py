@@ -69,3 +69,49 @@ def sky(width, height, sun_dir=(0.35, 0.75, 0.55), sun_radiance=(400.0, 380.0, 3
     for k in range(max(int(sun_texels), 0)):
         env[r, (j + k) % width] += np.asarray(sun_radiance, np.float64)
     return env.astype(np.float32)
+
+
+def cornell_blocks(prims):
+    """The kind array for Renderer.set_surfaces that makes the Cornell box's short block a mirror (1) and its tall block glass
+    (2).  prims: dict(type, verts, normal, bsdf, Le) of the loaded scene (Renderer.scene_prims(), HostScene.prims()), subdivided
+    or not, triangles or quads.  The blocks are found from the geometry: primitives that share a corner form a body; a block is
+    a body that emits nothing and keeps clear of the scene's bounding box in x and z (walls, floor, ceiling and back wall reach
+    it); the lower of the two is the short one."""
+    types = np.asarray(prims["type"]); le = np.asarray(prims["Le"])
+    # corners are joined where their float32 coordinates are EQUAL (+ 0.0 makes -0.0 and 0.0 one key): the loaders copy a shared
+    # vertex bit for bit and subdivision takes the midpoint of the same two corners on both sides of an edge.  A scene whose
+    # corners merely lie close together would fall apart into single primitives, and the call would say so (ValueError).
+    verts = np.asarray(prims["verts"], np.float32) + np.float32(0.0)
+    n = len(types)
+    corners = [verts[i, :4 if types[i] == 1 else 3] for i in range(n)]
+    parent = list(range(n))
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+    seen = {}
+    for i in range(n):
+        for c in corners[i]:
+            j = seen.setdefault(c.tobytes(), i)
+            parent[find(i)] = find(j)
+    allv = np.concatenate(corners)
+    lo, hi = allv.min(0), allv.max(0)
+    margin = 1e-3 * (hi - lo)
+    bodies = {}
+    for i in range(n):
+        bodies.setdefault(find(i), []).append(i)
+    blocks = []
+    for members in bodies.values():
+        v = np.concatenate([corners[i] for i in members])
+        inside = all((v[:, a] > lo[a] + margin[a]).all() and (v[:, a] < hi[a] - margin[a]).all() for a in (0, 2))
+        if inside and not le[members].any():
+            blocks.append((float(v[:, 1].max()), members))
+    if len(blocks) != 2:
+        raise ValueError(f"cornell_blocks: expected two blocks, found {len(blocks)} candidate bodies")
+    blocks.sort(key=lambda b: b[0])
+    kind = np.zeros(n, np.int32)
+    kind[blocks[0][1]] = 1
+    kind[blocks[1][1]] = 2
+    return kind

@@ -751,6 +751,69 @@ int  ptmi_host_env_table(int width, int height, const float* rgb, const ptmi_env
                          float* z /* h+1 */, float* marginal_cdf /* h */, float* row_cdf /* h*w */,
                          float* texel /* h*w*4: scaled rgb, pdf per solid angle */, float* total);
 
+/* ---- specular surfaces: mirror and glass (new in this implementation) ----------------------------------------------------------
+ * Every surface the loaders produce is Lambertian.  ptmi_set_surfaces gives the loaded scene a table with one kind per
+ * primitive, in load order as ptmi_set_radiosity: diffuse (today's surface), a perfect mirror, or smooth glass with an index of
+ * refraction.  The primitive's bsdf colour is the specular tint: Kr of a mirror, and on glass it tints reflection and
+ * transmission alike.  Le is added as on any surface.  The table indexes primitives, so a scene load drops it (the environment,
+ * which belongs to the context, survives one).  A table whose kinds are all 0 is no table: the context takes exactly the route
+ * it takes without one.  A context whose table has a specular primitive renders both values of next_event through the per-lane
+ * kernel of next-event estimation, as a context with an environment does (so segments_per_launch, wave_tiles, streams and
+ * collect_stats have no effect on it); frames, batches, passes (progressive and adaptive), tiled contexts, ptmi_denoise,
+ * ptmi_temporal_accumulate and ptmi_gather_frame work as they do without one.
+ * ptmi_run_radiosity_solver, the Radiosity view (integrator = 1) and ptmi_render_features IGNORE the table: the solver and the
+ * view treat every primitive as the diffuse surface its bsdf describes, and the feature pass keeps reporting bsdf as albedo.
+ *
+ * ptmi_set_surfaces: kind NULL drops the table (n_prims and ior are then ignored); ior NULL means 1.5 for every primitive.  A
+ * successful call restarts an accumulation, makes features stale and empties the temporal history.  PTMI_E_INVALID, with nothing
+ * changed: no scene loaded, n_prims != ptmi_scene_info's count, a kind outside 0 .. 2, an ior that is NaN, infinite or outside
+ * [1, 8] (every entry is checked; it is READ for glass only), and - for a table with a specular primitive - a current config with
+ * integrator = 1, sampling_mode != 0 or fast_tree = 1; ptmi_set_config rejects those three while such a table is set (the
+ * restrictions of an environment, for the same reasons).  ptmi_check_surfaces makes the checks that need no context (n_prims >= 1,
+ * kind not NULL, the kinds, the iors).  ptmi_surfaces_info: the table's mirror and glass primitives, 0 and 0 without a table.
+ *
+ * THE ESTIMATOR is that of "next-event estimation" and "environment lighting" above (with next_event = 0: the reference's, with
+ * its draws), float32 in the order written, sqrtf correctly rounded and / the IEEE quotient; beta, L, p_b_prev, sn, o', dot, mis
+ * as written there; kind_k and ior_k are primitive k's entries.  A sample carries one more flag, spec_prev = false at the camera.
+ *   1.  An emitter found while spec_prev is set counts in full, as at depth 0: L = L + beta * Le_k, no MIS weight (no light
+ *       sample could have produced it).  1'. likewise: a path ray that leaves the scene while spec_prev is set adds beta * E.
+ *   2.  Russian roulette, beta = beta * bsdf_k, the |beta| < 1e-5 exit, sn and o' are unchanged: a specular vertex is a vertex.
+ *   A vertex with kind_k = 0 then goes on with steps 3 (3') and 4 exactly as above, draw for draw, and sets spec_prev = false.
+ *   A vertex with kind_k != 0 makes none of the draws of step 3 (3') and traces no shadow ray, makes neither draw of step 4, and:
+ *       un = unit_vector(sn)                 (stored normals may be tilted against the geometry and need not have unit length)
+ *       dn = dot(d, un)
+ *       mirror (kind 1), no draw:            reflect
+ *       glass (kind 2), ALWAYS one draw u, made here, whatever comes of it:
+ *           eta = dot(d, n_k) < 0 ? 1.0f / ior_k : ior_k       the ratio n_i / n_t; the stored normal points out of the body
+ *           ci = fminf(1, -dn);   s2 = (eta * eta) * fmaxf(0, 1 - ci * ci)
+ *           if s2 >= 1 and eta != 1: reflect (total internal reflection); else
+ *               ct = eta == 1 ? ci : sqrtf(1 - s2)      (ior 1 is no interface: rs = rp = F = 0 and next = d + 0 * un, so d
+ *                                                         exactly at every angle; 1 - s2 would form ci^2 as 1 - (1 - ci * ci)
+ *                                                         and lose it near grazing incidence, where s2 even rounds to 1;
+ *                                                         at ci = 0 F is 0 / 0, u <= F is false: refract, next = d)
+ *               rs = (eta * ci - ct) / (eta * ci + ct);   rp = (ci - eta * ct) / (ci + eta * ct)
+ *               F = 0.5f * (rs * rs + rp * rp)
+ *               if u <= F: reflect; else refract
+ *       depth = depth + 1; if depth >= max_depth the sample ends (after the draw, as step 4 ends it after its two)
+ *       reflect:   next = d - (2 * dn) * un,                 o = o' = p + 1e-4f * sn
+ *       refract:   next = eta * d + (eta * ci - ct) * un,    o = p - 1e-4f * sn
+ *       len2 = dot(next, next): unless len2 > 0 and len2 <= FLT_MAX the sample ends here, before anything is traced (a zero or
+ *       non-finite stored normal: no walk is ever started with a NaN direction)
+ *       d = unit_vector(next);  spec_prev = true;  p_b_prev keeps its value (it is not read while spec_prev is set)
+ * Choosing reflection with probability F and transmission with 1 - F cancels the Fresnel factor, so beta takes only the tint.
+ * Transmitted radiance is NOT scaled by eta^2 (the change of solid angle across the interface).  That is exact whenever the
+ * camera and every light are outside closed glass bodies - each path then crosses as often inwards as outwards and the factors
+ * cancel - and it is what this estimator assumes.  A light sample is never aimed through glass or at a mirror's image: light that
+ * reaches a diffuse surface through a specular one is found by BSDF sampling alone, for both values of next_event, and both
+ * count vertices alike, so their expected values are equal. */
+#define PTMI_SURFACE_DIFFUSE 0
+#define PTMI_SURFACE_MIRROR  1
+#define PTMI_SURFACE_GLASS   2
+/* host only, no context: 0 or PTMI_E_INVALID with the message */
+int  ptmi_check_surfaces(int n_prims, const int* kind, const float* ior /* NULL: none to check */);
+int  ptmi_set_surfaces(ptmi_ctx*, int n_prims, const int* kind /* NULL drops the table */, const float* ior /* NULL: 1.5 everywhere */);
+int  ptmi_surfaces_info(const ptmi_ctx*, int* n_mirror, int* n_glass);   /* 0, 0 without a table */
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,10 +4,15 @@ changed no kernel.  No GPU needed.
 
   python tools/isa_digest.py dump cuda-pathtracer_amd a.json      # compiles every csrc/*.hip for the device only, disassembles
   python tools/isa_digest.py diff parent.json a.json [--skip SUBSTRING]   # --skip: kernels expected to change; their metadata is listed
+  python tools/isa_digest.py siblings parent.json a.json SUBSTRING        # a kernel template that gained trailing bool parameters
 
 dump: every .hip is compiled with the Makefile's flags + --cuda-device-only, unbundled, and for each kernel the disassembly
 (comments stripped, trailing padding ignored) and the AMDGPU metadata note (registers, scratch, LDS, kernarg size) are recorded.
-diff: kernel names missing / new / duplicated, and every kernel whose text or metadata differs.
+diff: kernel names missing / new / duplicated, and every kernel whose text or metadata differs.  Kernels whose name holds the
+--skip substring are left out of all three counts when their names changed (a new template parameter renames every instantiation).
+siblings: for the kernels whose name holds SUBSTRING, pairs each new instantiation whose added trailing template arguments are all
+false with the parent's instantiation of the same leading arguments and compares registers, spills, scratch and LDS; lists the
+resources of every new instantiation; three result lines.
 """
 import concurrent.futures
 import hashlib
@@ -85,10 +90,19 @@ def diff(a, b, skip):
         for n in sorted(set(n for n in names if names.count(n) > 1)):
             print("DUPLICATE in %s: %s" % (tag, n)); bad += 1
     da, db = {k["name"]: k for k in A}, {k["name"]: k for k in B}
+    renamed = 0
     for n in sorted(set(da) - set(db)):
+        if skip and skip in n:
+            renamed += 1
+            continue
         print("MISSING: %s" % n); bad += 1
     for n in sorted(set(db) - set(da)):
+        if skip and skip in n:
+            renamed += 1
+            continue
         print("NEW: %s" % n); bad += 1
+    if renamed:
+        print("%d names with '%s' exist on one side only (see `siblings`)" % (renamed, skip))
     same = skipped = 0
     for n in sorted(set(da) & set(db)):
         if skip and skip in n:
@@ -104,10 +118,49 @@ def diff(a, b, skip):
     return 1 if bad else 0
 
 
+RESOURCES = [".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
+             ".group_segment_fixed_size"]
+
+
+def template_args(name):
+    """the literal template arguments (Li<n>E, Lb<n>E) of a mangled kernel name, in order"""
+    return tuple(int(v) for v in re.findall(r"L[ib](\d+)E", name.split("Ev")[0]))
+
+
+def siblings(a, b, sub):
+    A = {template_args(k["name"]): k for k in json.load(open(a)) if sub in k["name"]}
+    B = {template_args(k["name"]): k for k in json.load(open(b)) if sub in k["name"]}
+    n_lead = len(next(iter(A)))
+    paired = differ = heavy = 0
+    for args in sorted(B):
+        m = B[args]["meta"]
+        line = "%s<%s>: %s, %d instructions" % (sub, ", ".join(map(str, args)), "  ".join("%s %s" % (r[1:], m[r]) for r in RESOURCES), B[args]["n"])
+        if not any(args[n_lead:]):
+            p = A.get(args[:n_lead])
+            if p is None:
+                line += "  | NO PARENT"; differ += 1
+            else:
+                paired += 1
+                same = all(p["meta"][r] == m[r] for r in RESOURCES)
+                differ += 0 if same else 1
+                line += "  | parent: %s, %d instructions" % ("same resources" if same else "  ".join("%s %s" % (r[1:], p["meta"][r]) for r in RESOURCES if p["meta"][r] != m[r]), p["n"])
+        if m[".private_segment_fixed_size"] or m[".vgpr_spill_count"]:
+            heavy += 1
+        print(line)
+    spills = [k["meta"][".sgpr_spill_count"] for k in B.values()]
+    pspills = [k["meta"][".sgpr_spill_count"] for k in A.values()]
+    print("%s: parent %d instantiations, new %d; %d with the added parameters false, %d of them differ from the parent's resources" % (sub, len(A), len(B), paired, differ))
+    print("%s: %d of %d new instantiations use scratch or spill VGPRs" % (sub, heavy, len(B)))
+    print("%s: SGPRs parked in VGPR lanes (sgpr_spill_count): parent %d - %d, new %d - %d" % (sub, min(pspills), max(pspills), min(spills), max(spills)))
+    return 1 if differ or heavy or len(A) != paired else 0
+
+
 if __name__ == "__main__":
     if len(sys.argv) >= 4 and sys.argv[1] == "dump":
         dump(sys.argv[2], sys.argv[3], sys.argv[4:])
     elif len(sys.argv) >= 4 and sys.argv[1] == "diff":
         sys.exit(diff(sys.argv[2], sys.argv[3], sys.argv[5] if len(sys.argv) > 5 and sys.argv[4] == "--skip" else None))
+    elif len(sys.argv) == 5 and sys.argv[1] == "siblings":
+        sys.exit(siblings(sys.argv[2], sys.argv[3], sys.argv[4]))
     else:
         sys.exit(__doc__)

@@ -13,6 +13,8 @@
                                (16 views 2 degrees apart, each through the temporal accumulation and the denoiser)
   python tools/ptmi_render.py --scene ... --sky --next-event --out sky.png                    (procedural sky with a sun)
   python tools/ptmi_render.py --scene ... --env map.npy --env-rotation 90 --out lit.png      ((h, w, 3) float radiance, row 0 up)
+  python tools/ptmi_render.py --scene ... --mirror 12-21 --glass 22-31 --ior 1.5 --max-depth 8 --out blocks.png
+                               (load-order primitive indices: cbox.obj's short block a mirror, its tall block glass)
 """
 import argparse
 import os
@@ -21,6 +23,17 @@ import time
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cuda-pathtracer_amd", "python"))
 import ptmi  # noqa: E402
+
+
+def index_list(text):
+    """'12-23,30' -> [12, ..., 23, 30]; ValueError names the item that is no index and no ascending range"""
+    out = []
+    for part in text.split(","):
+        lo, dash, hi = part.strip().partition("-")
+        if not lo.isdigit() or (dash and not hi.isdigit()) or (dash and int(hi) < int(lo)):
+            raise ValueError(f"'{part.strip()}' is neither an index nor a range such as 12-23")
+        out.extend(range(int(lo), int(hi if dash else lo) + 1))
+    return out
 
 
 def main():
@@ -56,6 +69,8 @@ def main():
     ap.add_argument("--sky", action="store_true", help="environment light: the procedural sky of ptmi_scenes.sky (gradient + sun)")
     ap.add_argument("--env-scale", type=float, default=1.0); ap.add_argument("--env-rotation", type=float, default=0.0, metavar="DEG")
     ap.add_argument("--env-fraction", type=float, default=0.5, help="with --next-event: share of the light samples that go to the environment")
+    ap.add_argument("--mirror", default=None, metavar="LIST", help="specular surfaces: load-order primitive indices and ranges, e.g. 12-23,30")
+    ap.add_argument("--glass", default=None, metavar="LIST"); ap.add_argument("--ior", type=float, default=1.5, help="index of refraction of --glass")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -92,6 +107,20 @@ def main():
         r.set_environment(env, scale=a.env_scale, rotation_deg=a.env_rotation, select_fraction=a.env_fraction)
         ei = r.environment_info()
         print(f"environment: {ei['width']}x{ei['height']}, total power {ei['total']:.4g}")
+    if a.mirror or a.glass:
+        import numpy as np
+        kind = np.zeros(info["n_prims"], np.int32)
+        for text, value in ((a.mirror, ptmi.SURFACE_MIRROR), (a.glass, ptmi.SURFACE_GLASS)):
+            try:
+                idx = index_list(text) if text else []
+            except ValueError as e:
+                ap.error(f"--mirror / --glass: {e}")
+            if idx and not (0 <= min(idx) and max(idx) < len(kind)):
+                ap.error(f"--mirror / --glass: the scene has primitives 0 .. {len(kind) - 1}")
+            kind[idx] = value
+        r.set_surfaces(kind, a.ior)
+        si = r.surfaces_info()
+        print(f"surfaces: {si['n_mirror']} mirror, {si['n_glass']} glass primitives, ior {a.ior}")
     if a.orbit > 0:
         orbit(r, a, cam)
         r.close()
