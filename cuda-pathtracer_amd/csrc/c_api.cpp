@@ -489,25 +489,40 @@ int ptmi_host_env_table(int width, int height, const float* rgb, const ptmi_env_
 int ptmi_check_surfaces(int n_prims, const int* kind, const float* ior) {
     return guarded([&] { checkSurfaces(n_prims, kind, ior); });
 }
-int ptmi_set_surfaces(ptmi_ctx* c, int n_prims, const int* kind, const float* ior) {
-    return guarded([&] {
-        need(c != nullptr, "ctx is NULL");
-        need(c->app.scene.d_nodes != nullptr, "no scene loaded");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        if (kind) {
-            need(n_prims == (int)c->app.scene.h_primitives.size(), "n_prims does not match the loaded scene");
-            checkSurfaces(n_prims, kind, ior);
-            bool specular = false;
-            for (int i = 0; i < n_prims; i++) specular = specular || kind[i] != kSurfaceDiffuse;
-            if (specular) {
-                const AppConfig& a = c->app.config;
-                need(a.current_integrator == IntegratorType::PathTracing, "surfaces: the config has integrator 1 (Radiosity), which traces first hits only");
-                need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "surfaces: the config has a guided sampling_mode, which samples a diffuse lobe at every vertex");
-                need(!a.fast_tree, "surfaces: the config has fast_tree 1; specular frames always trace the reference's hits");
-            }
+// ptmi_set_surfaces (rough_api false: kinds 0 .. 2, no roughness) and ptmi_set_surfaces_rough
+static void setSurfacesChecked(ptmi_ctx* c, int n_prims, const int* kind, const float* ior, const float* roughness, bool rough_api) {
+    need(c != nullptr, "ctx is NULL");
+    need(c->app.scene.d_nodes != nullptr, "no scene loaded");
+    PTMI_HIP(hipSetDevice(c->app.device_id));
+    if (kind) {
+        need(n_prims == (int)c->app.scene.h_primitives.size(), "n_prims does not match the loaded scene");
+        if (rough_api) checkSurfacesRough(n_prims, kind, ior, roughness);
+        else checkSurfaces(n_prims, kind, ior);
+        bool specular = false;
+        for (int i = 0; i < n_prims; i++) specular = specular || kind[i] != kSurfaceDiffuse;
+        if (specular) {
+            const AppConfig& a = c->app.config;
+            need(a.current_integrator == IntegratorType::PathTracing, "surfaces: the config has integrator 1 (Radiosity), which traces first hits only");
+            need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "surfaces: the config has a guided sampling_mode, which samples a diffuse lobe at every vertex");
+            need(!a.fast_tree, "surfaces: the config has fast_tree 1; specular frames always trace the reference's hits");
         }
-        c->app.scene.setSurfaces(kind, ior);                         // every check is done before anything changes
-        viewChanged(c->app);                                         // other materials: the temporal history holds another image
+    }
+    c->app.scene.setSurfaces(kind, ior, roughness);              // every check is done before anything changes
+    viewChanged(c->app);                                         // other materials: the temporal history holds another image
+}
+int ptmi_set_surfaces(ptmi_ctx* c, int n_prims, const int* kind, const float* ior) {
+    return guarded([&] { setSurfacesChecked(c, n_prims, kind, ior, nullptr, false); });
+}
+int ptmi_check_surfaces_rough(int n_prims, const int* kind, const float* ior, const float* roughness) {
+    return guarded([&] { checkSurfacesRough(n_prims, kind, ior, roughness); });
+}
+int ptmi_set_surfaces_rough(ptmi_ctx* c, int n_prims, const int* kind, const float* ior, const float* roughness) {
+    return guarded([&] { setSurfacesChecked(c, n_prims, kind, ior, roughness, true); });
+}
+int ptmi_surface_counts(const ptmi_ctx* c, int counts[4]) {
+    return guarded([&] {
+        need(c != nullptr && counts != nullptr, "NULL argument");
+        for (int i = 0; i < 4; i++) counts[i] = c->app.scene.surface_counts[i];
     });
 }
 int ptmi_surfaces_info(const ptmi_ctx* c, int* n_mirror, int* n_glass) {

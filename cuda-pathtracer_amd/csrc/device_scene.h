@@ -302,7 +302,7 @@ struct EnvTable {
 };
 // ---- specular surfaces (include/ptmi.h: ptmi_set_surfaces) -----------------------------------------------------------------
 // One record per LEAF-ORDER slot, the order of mats and EmitterTable::pdf_area (SceneState::setSurfaces permutes the caller's
-// load-order table): (bits(kind), ior), kind PTMI_SURFACE_*.  An array of its own: the bounce kernels stage mats into LDS and
+// load-order table): (bits(kind), param), kind PTMI_SURFACE_*, param the ior of glass and the alpha of rough metal.  An array of its own: the bounce kernels stage mats into LDS and
 // the packed layouts copy it, and none of them may change.  rec == nullptr: every surface is diffuse (no table, or all kinds 0).
 struct SurfaceTable {
     const float2* rec = nullptr;
@@ -310,8 +310,9 @@ struct SurfaceTable {
 // fp.n_frames x spp samples per queued pixel.  env.texel == nullptr and surf.rec == nullptr: the NEE kernel exactly as it was;
 // that instantiation IGNORES next_event (the host routes a frame here only when it is set, and the switch folds to true).  Else
 // the ENV and / or SPEC instantiation, which reads next_event and runs either estimator, looks the map up where a path ray
-// misses and continues a path through mirror and glass.
-void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, bool next_event,
+// misses and continues a path through mirror and glass.  rough: the table holds a rough-metal record (SURF = 2; else the
+// delta kinds' SURF = 1, which never reads a kind 3).
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, bool rough, bool next_event,
                        const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s);
 
 size_t bounce_lds_bytes(const DeviceScene& sc);

@@ -2,6 +2,7 @@
 // feature pass and next-event estimation.  Compile with -ffp-contract=off (kernels.hip).
 #include "shading.h"
 #include "prim_sample.h"
+#include "rough.h"
 
 namespace ptmi {
 
@@ -173,13 +174,34 @@ __device__ __forceinline__ int env_texel(const EnvTable& ev, const f3& d) {
     return r * ev.w + j;
 }
 
+// the weight (f * cos * mis(p, p_b)) / p of a light sample of density p towards wi, f * cos without the colour: the cosine lobe,
+// or the GGX lobe of a rough vertex; false: the sample contributes nothing
+template <int SURF>
+__device__ __forceinline__ bool light_weight(bool rough, const RoughVertex& rv, const f3& wi, float cos_s, float p, float& w) {
+    if constexpr (SURF == 2) {
+        if (rough) {
+            float g, p_b;
+            if (!rough_eval(rv, wi, g, p_b)) return false;
+            w = (g * mis_power_heuristic(p, p_b)) / p;
+            return true;
+        }
+    }
+    const float p_b = cos_over_pi(cos_s);
+    w = (p_b * mis_power_heuristic(p, p_b)) / p;
+    return true;
+}
+
 // specular surfaces (include/ptmi.h: "specular surfaces"; the table: device_scene.h SurfaceTable).  SPEC: the context has a table
 // with a mirror or glass primitive; a vertex on one makes no light sample and no cosine sample and goes on along the reflected or
 // refracted direction, and what the next path ray finds (an emitter, the environment) counts in full.
-template <int MODE, bool HAS_QUADS, bool ENV, bool SPEC>
+// SURF (include/ptmi.h: "rough metal"): 0 no table; 1 a table of mirror and glass only (SPEC); 2 a table with a rough-metal
+// primitive as well: such a vertex draws what a diffuse one draws, its light sample evaluates the GGX lobe and its BSDF sample
+// comes from rough.h; both are computed here, before the shadow walk, so only `ended` joins the state that crosses a walk.
+template <int MODE, bool HAS_QUADS, bool ENV, int SURF>
 __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, EmitterTable em, EnvTable ev, SurfaceTable sf, TileMap tm, PathState st, FrameParams fp,
                                                           const int* __restrict__ queue, int n, int first, int next_event) {
     extern __shared__ float4 smem[];
+    constexpr bool SPEC = SURF != 0;
     const int idx = blockIdx.x * kBlock + threadIdx.x;
     if (idx >= n) return;                                    // the walks are per lane: no barrier below
     const int slot = queue ? queue[idx] : idx;
@@ -208,6 +230,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
             bool shadow = false;                             // the next walk is the shadow ray (so, sd) of the last vertex
             f3 so = o, sd = d, contrib = mk3(0.0f, 0.0f, 0.0f);
             int s_slot = -1;                                 // the sampled emitter's slot; -1: the environment (visible iff nothing is hit)
+            bool ended = false;                              // SURF = 2: the rough vertex ended the path; its shadow ray is still to walk
             while (true) {
                 const f3 ro = shadow ? so : o, rd = shadow ? sd : d;
                 float t = 0.0f; int k = -1;
@@ -215,6 +238,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                 if (shadow) {                                // visible iff the closest hit is the sampled emitter
                     if (ENV && s_slot < 0 ? !hit : (hit && k == s_slot)) L = L + contrib;
                     shadow = false;
+                    if (SURF == 2 && ended) break;
                     continue;
                 }
                 if (!hit) {                                                               // integrator.h:198-201
@@ -249,10 +273,12 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                 if (length(tp) < 1e-5f) break;                                            // integrator.h:218
                 const f3 sn = dot(d, nrm) < 0 ? nrm : -nrm;                               // integrator.h:221-222
                 const f3 o2 = hp + 1e-4f * sn;                                            // integrator.h:266
+                [[maybe_unused]] bool rough = false;                                      // SURF = 2: this vertex is rough metal (rv)
+                [[maybe_unused]] RoughVertex rv;
                 if constexpr (SPEC) {
                     const float2 sr = sf.rec[k];
                     const int kind = __float_as_int(sr.x);
-                    if (kind != 0) {                                                      // no light sample, no cosine sample
+                    if (SURF == 2 ? kind == 1 || kind == 2 : kind != 0) {                 // no light sample, no cosine sample
                         const f3 un = unit_vector(sn);
                         const float dn = dot(d, un);
                         bool reflect = true;
@@ -281,6 +307,10 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                         continue;
                     }
                     spec_prev = false;
+                    if constexpr (SURF == 2) {
+                        rough = kind == 3;
+                        if (rough) rv = rough_vertex(sn, d, sr.y);
+                    }
                 }
                 if (nee_on && depth + 1 < fp.max_depth && (em.n > 0 || env_on)) {         // NEE: three draws (five with an environment) whatever comes of them
                     float u_sel = rng_uniform(rng);
@@ -304,9 +334,8 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                             const float4 te = ev.texel[r * ev.w + j];
                             const float cos_s = dot(sn, wi);
                             const float p_e = q * te.w;
-                            if (cos_s > 0.0f && p_e > 0.0f && p_e <= FLT_MAX) {
-                                const float p_b = cos_over_pi(cos_s);
-                                const float w = (p_b * mis_power_heuristic(p_e, p_b)) / p_e;
+                            float w;
+                            if (cos_s > 0.0f && p_e > 0.0f && p_e <= FLT_MAX && light_weight<SURF>(rough, rv, wi, cos_s, p_e, w)) {
                                 const f3 c = tp * xyz(te);
                                 contrib = mk3(c.x * w, c.y * w, c.z * w);
                                 so = o2; sd = wi; s_slot = -1;
@@ -329,9 +358,9 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                         const float cos_l = fabsf(dot(xyz(a4), wi));                      // a4: the geometric normal
                         float p_l = (a3.w * dist2) / cos_l;
                         if (env_on) p_l = omq * p_l;
-                        if (cos_s > 0.0f && cos_l > 0.0f && p_l > 0.0f && p_l <= FLT_MAX) {   // a p_l of 0 or inf weighs 0 (no NaN)
-                            const float p_b = cos_over_pi(cos_s);
-                            const float w = (p_b * mis_power_heuristic(p_l, p_b)) / p_l;
+                        float w;
+                        if (cos_s > 0.0f && cos_l > 0.0f && p_l > 0.0f && p_l <= FLT_MAX &&   // a p_l of 0 or inf weighs 0 (no NaN)
+                            light_weight<SURF>(rough, rv, wi, cos_s, p_l, w)) {
                             const f3 c = tp * xyz(rec[5]);
                             contrib = mk3(c.x * w, c.y * w, c.z * w);
                             so = o2; sd = wi; s_slot = __float_as_int(a0.w);
@@ -343,6 +372,27 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                 const float vv = rng_uniform(rng);
                 depth++;
                 if (depth >= fp.max_depth) break;                                         // (no shadow ray pending: NEE needs depth + 1 < max_depth)
+                if constexpr (SURF == 2) {
+                    if (rough) {                                                          // u, vv are the contract's u1, u2
+                        f3 next;
+                        float wgt = 0.0f, p_b = 0.0f;
+                        bool on = rv.ok && rough_sample(rv, u, vv, next, wgt, p_b);       // the grazing exit; a sample below the horizon
+                        if (on) {
+                            const float len2 = dot(next, next);
+                            on = len2 > 0.0f && len2 <= FLT_MAX;                          // no walk starts with a NaN direction
+                        }
+                        if (!on) {                                                        // the path ends; a light sample made above still counts
+                            if (!shadow) break;
+                            ended = true;
+                            continue;
+                        }
+                        tp = mk3(tp.x * wgt, tp.y * wgt, tp.z * wgt);
+                        pb_prev = p_b;
+                        o = o2;
+                        d = unit_vector(next);
+                        continue;
+                    }
+                }
                 const f3 next = cosine_hemisphere(sn, u, vv);                             // integrator.h:230
                 pb_prev = cos_over_pi(fmaxf(dot(sn, next), 0.0f));
                 o = o2;
@@ -356,16 +406,19 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     st.F[slot] = make_uint2(rng.v4, rng.d);
 }
 
-void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, bool next_event,
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, bool rough, bool next_event,
                        const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s) {
     if (n <= 0) return;
     first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
         with_bool(env.texel != nullptr, [&](auto with_env) {
-            with_bool(surf.rec != nullptr, [&](auto with_spec) {
-                hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value, decltype(with_spec)::value>),
+            auto launch = [&](auto surf_kinds) {
+                hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value, decltype(surf_kinds)::value>),
                                    dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, surf, tm, st, fp, queue, n, first ? 1 : 0,
                                    next_event ? 1 : 0);
-            });
+            };
+            if (surf.rec == nullptr) launch(std::integral_constant<int, 0>{});
+            else if (!rough) launch(std::integral_constant<int, 1>{});
+            else launch(std::integral_constant<int, 2>{});
         });
     });
 }

@@ -137,10 +137,15 @@ struct SceneState {
     // specular surfaces (include/ptmi.h: ptmi_set_surfaces): the caller's load-order table by leaf-order slot (csrc/device_scene.h:
     // SurfaceTable).  It indexes primitives, so it goes with the scene (cleanup).  A table whose kinds are all 0 is kept as no
     // table: d_surfaces stays nullptr and a frame takes the route it takes without one.
+    // surface_counts: the table's primitives of kind 0 .. 3 (all 0 without one); a rough-metal primitive (kind 3, "rough metal")
+    // selects the kernel's SURF = 2 instantiations.
     int n_mirror = 0, n_glass = 0;
+    int surface_counts[4] = {0, 0, 0, 0};
     float2* d_surfaces = nullptr;
-    bool hasSpecular() const { return d_surfaces != nullptr; }
-    void setSurfaces(const int* kind, const float* ior);   // checked by the caller (checkSurfaces); kind nullptr drops the table
+    bool hasSpecular() const { return d_surfaces != nullptr; }         // a mirror, glass or rough-metal primitive
+    bool hasRough() const { return d_surfaces != nullptr && surface_counts[3] > 0; }
+    // checked by the caller (checkSurfaces / checkSurfacesRough); kind nullptr drops the table; roughness nullptr: 0.3
+    void setSurfaces(const int* kind, const float* ior, const float* roughness = nullptr);
     SurfaceTable surfaceTable() const { SurfaceTable t; t.rec = d_surfaces; return t; }
     int sweep_max_prims = 64;                        // scenes up to this many primitives use the wave-uniform sweep
     int force_traversal = -1;                        // test/benchmark override (TraversalMode), -1 = automatic

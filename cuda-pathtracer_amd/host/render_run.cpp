@@ -167,13 +167,13 @@ void prepareCostOrder(Run& run, int order_classes) {
 // next-event estimation (include/ptmi.h: ptmi_config.next_event) replaces the frame-begin / bounce loop with ONE launch
 // of ptmi_render_nee on the frame's stream: no chunks, no refill, no launch order by cost; the whole frame, batch or pass
 // a context with an environment (ptmi_set_environment) takes the same route for both values of next_event: the per-lane kernel
-// is the one that looks the map up where a path ray misses; so does a scene with a mirror or glass primitive (ptmi_set_surfaces)
+// is the one that looks the map up where a path ray misses; so does a scene with a mirror, glass or rough-metal primitive (ptmi_set_surfaces, ptmi_set_surfaces_rough)
 void runNeeLaunch(Run& run) {
     ApplicationState& g = run.g;
     const int n = run.queueLength();
     const hipEvent_t e0 = run.stamp(run.s);
     launch_render_nee(g.scene.d_scene, g.scene.d_emitters, g.env.table(g.config.next_event, g.scene.d_emitters.n), g.scene.surfaceTable(),
-                      g.config.next_event, run.r.tile, run.r.d_state, run.fp,
+                      g.scene.hasRough(), g.config.next_event, run.r.tile, run.r.d_state, run.fp,
                       run.pass ? run.chunks[0].d_queue_init : nullptr, n,
                       run.pass ? run.pass->rule.first != 0 : true, run.s);
     PTMI_HIP(hipGetLastError());

@@ -22,6 +22,7 @@ void SceneState::cleanup() {
     if (d_pdf_area) (void)hipFree(d_pdf_area);
     if (d_surfaces) (void)hipFree(d_surfaces);
     d_surfaces = nullptr; n_mirror = n_glass = 0;
+    for (int& c : surface_counts) c = 0;
     d_emit_rec = d_pdf_area = nullptr; d_emit_cdf = nullptr; d_emitters = EmitterTable();
     h_emit_prim.clear(); h_emit_cdf.clear(); h_emit_normal.clear(); h_pdf_area.clear(); h_emit_total = 0.0f;
     freePacked();
@@ -506,19 +507,24 @@ void SceneState::setRadiosity(const float* rgb) {
 }
 
 // specular surfaces (include/ptmi.h: ptmi_set_surfaces): the table by leaf-order slot, as upload() lays out pdf_area
-void SceneState::setSurfaces(const int* kind, const float* ior) {
+void SceneState::setSurfaces(const int* kind, const float* ior, const float* roughness) {
     if (!d_nodes) throw ArgError("setSurfaces: no scene loaded");
     const int n = (int)h_primitives.size();
     float2* nd = nullptr;
-    int mirrors = 0, glasses = 0;
+    int mirrors = 0, glasses = 0, roughs = 0;
     if (kind) {
-        for (int i = 0; i < n; i++) { mirrors += kind[i] == kSurfaceMirror; glasses += kind[i] == kSurfaceGlass; }
-        if (mirrors + glasses > 0) {
+        for (int i = 0; i < n; i++) { mirrors += kind[i] == kSurfaceMirror; glasses += kind[i] == kSurfaceGlass; roughs += kind[i] == kSurfaceRough; }
+        if (mirrors + glasses + roughs > 0) {
             std::vector<float2> slot((size_t)n);
             for (int k = 0; k < n; k++) {                // same leaf-order slots as prims/mats
                 const int src = bvh_indices[k];
                 float bits; std::memcpy(&bits, &kind[src], 4);
-                slot[k] = make_float2(bits, ior ? ior[src] : kSurfaceDefaultIor);
+                float param = ior ? ior[src] : kSurfaceDefaultIor;
+                if (kind[src] == kSurfaceRough) {            // alpha = roughness * roughness, in float
+                    const float r = roughness ? roughness[src] : kSurfaceDefaultRoughness;
+                    param = r * r;
+                }
+                slot[k] = make_float2(bits, param);
             }
             nd = (float2*)hipMallocSafe((size_t)n * sizeof(float2), "d_surfaces");
             const hipError_t e = hipMemcpy(nd, slot.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice);
@@ -527,6 +533,9 @@ void SceneState::setSurfaces(const int* kind, const float* ior) {
     }
     if (d_surfaces) (void)hipFree(d_surfaces);         // nothing has changed before this line
     d_surfaces = nd; n_mirror = mirrors; n_glass = glasses;
+    const bool table = nd != nullptr;
+    surface_counts[0] = table ? n - mirrors - glasses - roughs : 0;
+    surface_counts[1] = mirrors; surface_counts[2] = glasses; surface_counts[3] = roughs;
 }
 
 // RadiosityState: host/radiosity_state.cpp

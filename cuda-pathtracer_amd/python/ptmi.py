@@ -39,6 +39,7 @@ EXPORTS = [
     "ptmi_debug_math", "ptmi_debug_grid_index",
     "ptmi_default_env_params", "ptmi_check_env_params", "ptmi_set_environment", "ptmi_environment_info", "ptmi_host_env_table",
     "ptmi_check_surfaces", "ptmi_set_surfaces", "ptmi_surfaces_info",
+    "ptmi_check_surfaces_rough", "ptmi_set_surfaces_rough", "ptmi_surface_counts",
 ]
 
 
@@ -222,6 +223,9 @@ def lib():
         L.ptmi_check_surfaces.argtypes = [C.c_int, vp, vp]
         L.ptmi_set_surfaces.argtypes = [vp, C.c_int, vp, vp]
         L.ptmi_surfaces_info.argtypes = [vp, ip, ip]
+        L.ptmi_check_surfaces_rough.argtypes = [C.c_int, vp, vp, vp]
+        L.ptmi_set_surfaces_rough.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.ptmi_surface_counts.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -403,19 +407,31 @@ def host_env_table(rgb, **params):
 
 
 SURFACE_DIFFUSE, SURFACE_MIRROR, SURFACE_GLASS = 0, 1, 2      # PTMI_SURFACE_*
+SURFACE_ROUGH = 3                                             # rough metal: ptmi_set_surfaces_rough only
 
 
-def _surface_table(kind, ior):
+def _surface_table(kind, ior, roughness=None):
     kind = np.ascontiguousarray(kind, np.int32).reshape(-1)
     if ior is not None:
         ior = np.ascontiguousarray(np.broadcast_to(np.asarray(ior, np.float32), kind.shape))
-    return kind, ior
+    if roughness is not None:
+        roughness = np.ascontiguousarray(np.broadcast_to(np.asarray(roughness, np.float32), kind.shape))
+    return (kind, ior) if roughness is None else (kind, ior, roughness)
 
 
-def check_surfaces(kind, ior=None):
-    """ptmi_check_surfaces: raises PtmiError for a table ptmi_set_surfaces would reject on its own account (host only)."""
-    kind, ior = _surface_table(kind, ior)
-    _check(lib().ptmi_check_surfaces(len(kind), kind.ctypes.data, None if ior is None else ior.ctypes.data))
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def check_surfaces(kind, ior=None, roughness=None):
+    """ptmi_check_surfaces: raises PtmiError for a table ptmi_set_surfaces would reject on its own account (host only).  With a
+    roughness (a scalar or (n_prims,)): ptmi_check_surfaces_rough, which accepts SURFACE_ROUGH."""
+    if roughness is None:
+        kind, ior = _surface_table(kind, ior)
+        _check(lib().ptmi_check_surfaces(len(kind), kind.ctypes.data, _ptr(ior)))
+        return
+    kind, ior, roughness = _surface_table(kind, ior, roughness)
+    _check(lib().ptmi_check_surfaces_rough(len(kind), kind.ctypes.data, _ptr(ior), roughness.ctypes.data))
 
 
 class Renderer:
@@ -574,14 +590,26 @@ class Renderer:
 
     host_env_table = staticmethod(host_env_table)
 
-    def set_surfaces(self, kind, ior=None):
+    def set_surfaces(self, kind, ior=None, roughness=None):
         """Mirror and glass (include/ptmi.h: "specular surfaces"): kind (n_prims,) of SURFACE_DIFFUSE / _MIRROR / _GLASS in load
-        order, or None to drop the table; ior a scalar or (n_prims,), None: 1.5 everywhere.  A scene load drops the table."""
+        order, or None to drop the table; ior a scalar or (n_prims,), None: 1.5 everywhere.  A scene load drops the table.
+        Rough metal ("rough metal"): with a roughness, a scalar or (n_prims,) in [0.05, 1], the call goes to
+        ptmi_set_surfaces_rough and kind may hold SURFACE_ROUGH; without one SURFACE_ROUGH is rejected."""
         if kind is None:
             self._ck(self.L.ptmi_set_surfaces(self.h, 0, None, None))
             return
-        kind, ior = _surface_table(kind, ior)
-        self._ck(self.L.ptmi_set_surfaces(self.h, len(kind), kind.ctypes.data, None if ior is None else ior.ctypes.data))
+        if roughness is None:
+            kind, ior = _surface_table(kind, ior)
+            self._ck(self.L.ptmi_set_surfaces(self.h, len(kind), kind.ctypes.data, _ptr(ior)))
+            return
+        kind, ior, roughness = _surface_table(kind, ior, roughness)
+        self._ck(self.L.ptmi_set_surfaces_rough(self.h, len(kind), kind.ctypes.data, _ptr(ior), roughness.ctypes.data))
+
+    def surface_counts(self):
+        """ptmi_surface_counts: the table's primitives of kind 0 .. 3, all 0 without a table"""
+        c = np.zeros(4, np.int32)
+        self._ck(self.L.ptmi_surface_counts(self.h, c.ctypes.data))
+        return [int(v) for v in c]
 
     def surfaces_info(self):
         m, g = C.c_int(), C.c_int()

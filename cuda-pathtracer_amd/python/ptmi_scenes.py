@@ -71,9 +71,9 @@ def sky(width, height, sun_dir=(0.35, 0.75, 0.55), sun_radiance=(400.0, 380.0, 3
     return env.astype(np.float32)
 
 
-def cornell_blocks(prims):
+def cornell_blocks(prims, short=1, tall=2):
     """The kind array for Renderer.set_surfaces that makes the Cornell box's short block a mirror (1) and its tall block glass
-    (2).  prims: dict(type, verts, normal, bsdf, Le) of the loaded scene (Renderer.scene_prims(), HostScene.prims()), subdivided
+    (2), or the kinds given as short and tall (3, rough metal, needs set_surfaces' roughness).  prims: dict(type, verts, normal, bsdf, Le) of the loaded scene (Renderer.scene_prims(), HostScene.prims()), subdivided
     or not, triangles or quads.  The blocks are found from the geometry: primitives that share a corner form a body; a block is
     a body that emits nothing and keeps clear of the scene's bounding box in x and z (walls, floor, ceiling and back wall reach
     it); the lower of the two is the short one."""
@@ -112,6 +112,6 @@ def cornell_blocks(prims):
         raise ValueError(f"cornell_blocks: expected two blocks, found {len(blocks)} candidate bodies")
     blocks.sort(key=lambda b: b[0])
     kind = np.zeros(n, np.int32)
-    kind[blocks[0][1]] = 1
-    kind[blocks[1][1]] = 2
+    kind[blocks[0][1]] = short
+    kind[blocks[1][1]] = tall
     return kind

@@ -814,6 +814,77 @@ int  ptmi_check_surfaces(int n_prims, const int* kind, const float* ior /* NULL:
 int  ptmi_set_surfaces(ptmi_ctx*, int n_prims, const int* kind /* NULL drops the table */, const float* ior /* NULL: 1.5 everywhere */);
 int  ptmi_surfaces_info(const ptmi_ctx*, int* n_mirror, int* n_glass);   /* 0, 0 without a table */
 
+/* ---- rough metal: a GGX surface kind with light sampling and MIS (new in this implementation) -----------------------------------
+ * PTMI_SURFACE_ROUGH is an isotropic GGX microfacet reflector with height-correlated Smith masking, sampled by visible normals
+ * (Heitz 2018); the primitive's bsdf colour is a constant tint, as on the mirror (no angle-dependent Fresnel, no energy
+ * compensation for multiple scattering).  Unlike mirror and glass it TAKES light samples, towards emitters and the environment.
+ * ptmi_set_surfaces_rough is ptmi_set_surfaces with kinds 0 .. 3 and one more array: roughness (NULL: 0.3 for every primitive),
+ * every entry finite and in [0.05, 1] (every entry is checked; it is READ for kind 3 only; below 0.05 the mirror is the right
+ * tool).  alpha = roughness * roughness, in float, computed on the host.  Everything "specular surfaces" says of ptmi_set_surfaces
+ * holds for it unchanged: the state a successful call resets, the configs refused while a table with a non-diffuse primitive is
+ * set and the call refused under them, the scene load that drops the table, "an all-diffuse table is no table", the route frames
+ * take.  ptmi_set_surfaces and ptmi_check_surfaces keep rejecting kind 3.  ptmi_check_surfaces_rough makes the checks that need
+ * no context.  ptmi_surface_counts: the table's primitives of kind 0 .. 3, all 0 without a table; ptmi_surfaces_info keeps
+ * reporting the mirror and glass counts of whatever table is set.  A context whose table has no rough primitive renders exactly
+ * what it rendered before this kind existed.
+ *
+ * THE ESTIMATOR is that of "specular surfaces", float32 in the order written, sqrtf correctly rounded, / the IEEE quotient,
+ * sincosf = ptmi_sincosf; a + b + c = (a + b) + c, a * b * c = (a * b) * c, also per component of vectors; dot, mis, beta, L,
+ * p_b_prev, sn, o' as written above; unit_vector(v) = v * (1.0f / sqrtf(dot(v, v))) (vector.h); cross(a, b) = (a.y*b.z - a.z*b.y,
+ * -(a.x*b.z - a.z*b.x), a.x*b.y - a.y*b.x); PI = (float)PTMI_PI_D; alpha and a2 = alpha * alpha are primitive k's.
+ * Steps 1 and 2 are unchanged: emission, roulette, beta = beta * bsdf_k, the |beta| < 1e-5 exit, sn and o'.  A vertex with
+ * kind_k = 3 then sets spec_prev = false and:
+ *   frame    un = unit_vector(sn);  (T, B) is the tangent frame sampleCosineHemisphere (integrator.h:62-85) builds from un:
+ *                if un.z < -0.9999999f:  T = (0, -1, 0), B = (-1, 0, 0)
+ *                else a = 1.0f / (1.0f + un.z);  b = -un.x * un.y * a;
+ *                     T = (1.0f - un.x * un.x * a, b, -un.x);  B = (b, 1.0f - un.y * un.y * a, -un.y)
+ *            wo = (dot(-d, T), dot(-d, B), dot(-d, un));  co = wo.z
+ *            ok(c) := c > 0 and c * c > PTMI_ROUGH_MIN_COS2       (false for a NaN)
+ *            Lambda(c) = 0.5f * (sqrtf(1.0f + a2 * ((1.0f - c * c) / (c * c))) - 1.0f)
+ *            D(h), h a unit half vector: t = (h.x * h.x + h.y * h.y) + a2 * (h.z * h.z);  D = a2 / (PI * t * t)
+ *                (t is h.z^2 (a2 - 1) + 1; that form cancels at the peak of a narrow lobe, where t is about a2, and at roughness
+ *                0.05 leaves D with an error of several per cent)
+ *   draws    the light-sample draws of step 3 (3') under exactly a diffuse vertex's condition, then two draws u1, u2 (the u, v of
+ *            step 4), then depth = depth + 1 and the depth test: a path's draws depend only on the kinds it meets, and a rough
+ *            vertex draws what a diffuse one draws.
+ *   grazing  if ok(co) does not hold (grazing incidence, a zero or non-finite stored normal) the vertex makes no light sample and
+ *            no BSDF sample: the path ends after the draws and the depth count.
+ *   light sample towards wi (an emitter's point or an environment direction), in place of p_b = cos_s / PI and its weight; the
+ *            visibility walk and the tests cos_s > 0 (with sn as stored), cos_l > 0, 0 < p_l <= FLT_MAX stay as they are:
+ *                wl = (dot(wi, T), dot(wi, B), dot(wi, un));  ci = wl.z;  the sample needs ok(ci)
+ *                h = unit_vector(wo + wl)
+ *                g   = D(h) / ((4.0f * co) * (1.0f + Lambda(co) + Lambda(ci)))           f * cos / tint
+ *                p_b = D(h) / ((4.0f * co) * (1.0f + Lambda(co)))                        the density of the BSDF sample below
+ *                w = (g * mis(p_l, p_b)) / p_l;  L = L + (beta * Le_j) * w;  with p_e and E for the environment likewise
+ *   BSDF sample, after the depth test:
+ *                vh = unit_vector((alpha * wo.x, alpha * wo.y, wo.z))
+ *                l2 = vh.x * vh.x + vh.y * vh.y;  T1 = l2 > 0 ? (-vh.y / sqrtf(l2), vh.x / sqrtf(l2), 0) : (1, 0, 0);  T2 = cross(vh, T1)
+ *                r = sqrtf(u1);  (sp, cp) = sincosf((float)((2.0 * PTMI_PI_D) * (double)u2));  t1 = r * cp;  t2 = r * sp
+ *                s = 0.5f * (1.0f + vh.z);  t2 = (1.0f - s) * sqrtf(fmaxf(0, 1.0f - t1 * t1)) + s * t2
+ *                nh = t1 * T1 + t2 * T2 + sqrtf(fmaxf(0, 1.0f - t1 * t1 - t2 * t2)) * vh
+ *                h = unit_vector((alpha * nh.x, alpha * nh.y, fmaxf(0, nh.z)))
+ *                wl = (2.0f * dot(wo, h)) * h - wo;  ci = wl.z;  unless ok(ci) the path ends (the sample went below the horizon)
+ *                beta = beta * ((1.0f + Lambda(co)) / (1.0f + Lambda(co) + Lambda(ci)))
+ *                p_b_prev = D(h) / ((4.0f * co) * (1.0f + Lambda(co)))
+ *                next = wl.x * T + wl.y * B + wl.z * un;  len2 = dot(next, next): unless len2 > 0 and len2 <= FLT_MAX the path ends
+ *                o = o';  d = unit_vector(next)
+ *            A path that ends here keeps the light sample it has just made.  What the next ray finds - an emitter, or the
+ *            environment - is weighed mis(p_b_prev, ...) by steps 1 and 1'.
+ * g / p_b is exactly the weight beta takes, so the two MIS weights of a direction sum to 1 and both values of next_event have
+ * the same expected value; the weight is at most 1 (energy lost to masking is not put back).  PTMI_ROUGH_MIN_COS2 keeps
+ * (1 - c * c) / (c * c) finite (c * c may otherwise be a subnormal number whose quotient overflows, and the weight would be
+ * inf / inf), whatever the device does with subnormal numbers; it ends paths that meet the surface at less than 3.2e-19 rad.
+ * D(h) >= a2 / PI > 0 up to rounding, so p_b > 0.  p_b <= 1 / (2 PI alpha^3) (the largest D, 1 / (PI a2), at normal incidence gives
+ * 1 / (4 PI a2); towards grazing 4 co (1 + Lambda(co)) falls to its limit 2 alpha), which is 1.02e7 at roughness 0.05: no
+ * square in mis overflows. */
+#define PTMI_SURFACE_ROUGH 3
+#define PTMI_ROUGH_MIN_COS2 1e-37f
+/* host only, no context: 0 or PTMI_E_INVALID with the message */
+int  ptmi_check_surfaces_rough(int n_prims, const int* kind, const float* ior /* NULL: none to check */, const float* roughness /* NULL: none to check */);
+int  ptmi_set_surfaces_rough(ptmi_ctx*, int n_prims, const int* kind /* NULL drops the table */, const float* ior /* NULL: 1.5 everywhere */,
+                             const float* roughness /* NULL: 0.3 everywhere */);
+int  ptmi_surface_counts(const ptmi_ctx*, int counts[4]);   /* primitives of kind 0 .. 3; all 0 without a table */
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,9 @@ diff: kernel names missing / new / duplicated, and every kernel whose text or me
 --skip substring are left out of all three counts when their names changed (a new template parameter renames every instantiation).
 siblings: for the kernels whose name holds SUBSTRING, pairs each new instantiation whose added trailing template arguments are all
 false with the parent's instantiation of the same leading arguments and compares registers, spills, scratch and LDS; lists the
-resources of every new instantiation; three result lines.
+resources of every new instantiation; three result lines.  Where the template kept its arity and its last parameter turned from
+a bool into an int (SPEC -> SURF), an instantiation whose arguments the parent has is paired with that one, and every other
+(SURF = 2) is listed next to the new instantiation of the value below (SURF = 1) with the registers it adds.
 """
 import concurrent.futures
 import hashlib
@@ -135,7 +137,15 @@ def siblings(a, b, sub):
     for args in sorted(B):
         m = B[args]["meta"]
         line = "%s<%s>: %s, %d instructions" % (sub, ", ".join(map(str, args)), "  ".join("%s %s" % (r[1:], m[r]) for r in RESOURCES), B[args]["n"])
-        if not any(args[n_lead:]):
+        widened = len(args) == n_lead and args not in A         # same arity, a value the parent's bool does not have
+        if widened:
+            sib = B.get(args[:-1] + (args[-1] - 1,))
+            if sib is None:
+                line += "  | NO SIBLING"; differ += 1
+            else:
+                line += "  | sibling <%s>: %s" % (", ".join(map(str, args[:-1] + (args[-1] - 1,))),
+                                                 "  ".join("%s %+d" % (r[1:], m[r] - sib["meta"][r]) for r in RESOURCES[:5]))
+        elif not any(args[n_lead:]):
             p = A.get(args[:n_lead])
             if p is None:
                 line += "  | NO PARENT"; differ += 1

@@ -15,6 +15,8 @@
   python tools/ptmi_render.py --scene ... --env map.npy --env-rotation 90 --out lit.png      ((h, w, 3) float radiance, row 0 up)
   python tools/ptmi_render.py --scene ... --mirror 12-21 --glass 22-31 --ior 1.5 --max-depth 8 --out blocks.png
                                (load-order primitive indices: cbox.obj's short block a mirror, its tall block glass)
+  python tools/ptmi_render.py --scene ... --rough 22-31 --roughness 0.3 --next-event --max-depth 8 --out metal.png
+                               (the tall block brushed metal: GGX, its Kd the tint)
 """
 import argparse
 import os
@@ -71,6 +73,8 @@ def main():
     ap.add_argument("--env-fraction", type=float, default=0.5, help="with --next-event: share of the light samples that go to the environment")
     ap.add_argument("--mirror", default=None, metavar="LIST", help="specular surfaces: load-order primitive indices and ranges, e.g. 12-23,30")
     ap.add_argument("--glass", default=None, metavar="LIST"); ap.add_argument("--ior", type=float, default=1.5, help="index of refraction of --glass")
+    ap.add_argument("--rough", default=None, metavar="LIST", help="rough metal (GGX): primitive indices and ranges like --mirror")
+    ap.add_argument("--roughness", type=float, default=0.3, help="roughness of --rough, in [0.05, 1]; alpha is its square")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -107,20 +111,22 @@ def main():
         r.set_environment(env, scale=a.env_scale, rotation_deg=a.env_rotation, select_fraction=a.env_fraction)
         ei = r.environment_info()
         print(f"environment: {ei['width']}x{ei['height']}, total power {ei['total']:.4g}")
-    if a.mirror or a.glass:
+    if a.mirror or a.glass or a.rough:
         import numpy as np
         kind = np.zeros(info["n_prims"], np.int32)
-        for text, value in ((a.mirror, ptmi.SURFACE_MIRROR), (a.glass, ptmi.SURFACE_GLASS)):
+        for text, value in ((a.mirror, ptmi.SURFACE_MIRROR), (a.glass, ptmi.SURFACE_GLASS), (a.rough, ptmi.SURFACE_ROUGH)):
             try:
                 idx = index_list(text) if text else []
             except ValueError as e:
-                ap.error(f"--mirror / --glass: {e}")
+                ap.error(f"--mirror / --glass / --rough: {e}")
             if idx and not (0 <= min(idx) and max(idx) < len(kind)):
-                ap.error(f"--mirror / --glass: the scene has primitives 0 .. {len(kind) - 1}")
+                ap.error(f"--mirror / --glass / --rough: the scene has primitives 0 .. {len(kind) - 1}")
             kind[idx] = value
-        r.set_surfaces(kind, a.ior)
+        r.set_surfaces(kind, a.ior, a.roughness if a.rough else None)
         si = r.surfaces_info()
         print(f"surfaces: {si['n_mirror']} mirror, {si['n_glass']} glass primitives, ior {a.ior}")
+        if a.rough:
+            print(f"surfaces: {r.surface_counts()[3]} rough-metal primitives, roughness {a.roughness}")
     if a.orbit > 0:
         orbit(r, a, cam)
         r.close()
