@@ -1,6 +1,7 @@
 // c_api.cpp — the C ABI of libptmi.so (include/ptmi.h) over the host-side state objects.
 #include "../../include/ptmi.h"
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -940,6 +941,30 @@ int ptmi_debug_grid_index(ptmi_ctx* c, int n, const float* dirs, const float* no
         PTMI_HIP(hipGetLastError());
         PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
         d_o.download(out, n);
+    });
+}
+
+int ptmi_debug_nee_call(ptmi_ctx* c, int op, int n, const float* in, float* out_f, int* out_i) {
+    static_assert(kNeeCallIn == PTMI_NEE_CALL_IN && kNeeCallOutF == PTMI_NEE_CALL_OUT_F && kNeeCallOutI == PTMI_NEE_CALL_OUT_I, "ptmi.h and device_scene.h disagree");
+    return guarded([&] {
+        need(c && in && out_f && out_i, "NULL argument");
+        need(n >= 0, "n must not be negative");
+        need(op >= 0 && op < PTMI_NEE_CALL_OPS, "unknown op");
+        const EnvTable ev = c->app.env.table(true, c->app.scene.d_emitters.n);
+        if (op == PTMI_NEE_CALL_ENV_LOOKUP || op == PTMI_NEE_CALL_ENV_SAMPLE) need(ev.texel != nullptr, "the op needs an environment (ptmi_set_environment)");
+        if (op == PTMI_NEE_CALL_EMITTER_SAMPLE) need(c->app.scene.d_emitters.n > 0, "the op needs a scene with an emitter");
+        if (op == PTMI_NEE_CALL_ENV_LOOKUP)                   // (int)(NaN * w) is no column: the kernel never looks a non-finite direction up
+            for (size_t i = 0; i < (size_t)n * kNeeCallIn; i += kNeeCallIn)
+                need(std::isfinite(in[i]) && std::isfinite(in[i + 1]) && std::isfinite(in[i + 2]), "ENV_LOOKUP needs finite directions");
+        if (n == 0) return;
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<float> d_in((size_t)n * kNeeCallIn), d_f((size_t)n * kNeeCallOutF);
+        DevBuf<int> d_i((size_t)n * kNeeCallOutI);
+        d_in.upload(in, (size_t)n * kNeeCallIn);
+        launch_debug_nee_call(c->app.scene.d_scene.has_quads != 0, n, op, c->app.scene.d_emitters, ev, d_in.p, d_f.p, d_i.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d_f.download(out_f, (size_t)n * kNeeCallOutF); d_i.download(out_i, (size_t)n * kNeeCallOutI);
     });
 }
 

@@ -1,6 +1,6 @@
-// debug_hooks.hip — the test hooks: the render kernels' own device functions (traversal.h, shading.h), one call per case.
-// Compile with -ffp-contract=off (kernels.hip).
-#include "shading.h"
+// debug_hooks.hip — the test hooks: the render kernels' own device functions (traversal.h, shading.h, light_sample.h, rough.h),
+// one call per case.  Compile with -ffp-contract=off (kernels.hip).
+#include "light_sample.h"
 #include "../../include/ptmi.h"      // PTMI_MATH_*
 
 namespace ptmi {
@@ -225,6 +225,86 @@ __global__ void ptmi_debug_grid_index_k(int n, const float* __restrict__ dirs, c
 void launch_debug_grid_index(int n, const float* dirs, const float* normals, int* out, hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL(ptmi_debug_grid_index_k, dim3((n + 255) / 256), dim3(256), 0, s, n, dirs, normals, out);
+}
+
+// The light and surface sampling functions of ptmi_render_nee per call (test hook; include/ptmi.h: ptmi_debug_nee_call states
+// each op's inputs and outputs): light_sample.h and rough.h on n cases against the context's own tables - em the loaded scene's
+// emitters, ev the environment as a frame with next_event set sees it (ev.q, ev.sampled).  in: kNeeCallIn floats per case;
+// out_f: kNeeCallOutF floats and out_i: kNeeCallOutI ints per case, zero where an op writes nothing.  An output a function
+// leaves undefined after a false verdict stays zero.
+template <bool HAS_QUADS>
+__global__ __launch_bounds__(kBlock) void ptmi_debug_nee_call_k(int n, int op, EmitterTable em, EnvTable ev, const float* __restrict__ in,
+                                                                float* __restrict__ out_f, int* __restrict__ out_i) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float* a = in + (size_t)i * kNeeCallIn;
+    float f[kNeeCallOutF];
+    int k[kNeeCallOutI];
+    for (int c = 0; c < kNeeCallOutF; c++) f[c] = 0.0f;
+    for (int c = 0; c < kNeeCallOutI; c++) k[c] = 0;
+    const auto put3 = [&](int at, const f3& v) { f[at] = v.x; f[at + 1] = v.y; f[at + 2] = v.z; };
+    if (op == PTMI_NEE_CALL_ENV_LOOKUP) {
+        const int t = env_texel(ev, mk3(a[0], a[1], a[2]));
+        const float4 te = ev.texel[t];
+        k[0] = t / ev.w; k[1] = t - k[0] * ev.w;
+        f[0] = te.x; f[1] = te.y; f[2] = te.z; f[3] = te.w;
+    } else if (op == PTMI_NEE_CALL_ENV_SAMPLE) {
+        f3 wi;
+        const float4 te = env_sample(ev, a[0], a[1], a[2], a[3], k[0], k[1], wi);
+        put3(0, wi);
+        f[3] = te.w; f[4] = te.x; f[5] = te.y; f[6] = te.z;
+    } else if (op == PTMI_NEE_CALL_EMITTER_SAMPLE) {
+        const bool env_on = ev.texel != nullptr && ev.sampled != 0;  // ptmi_render_nee's env_on, q and omq
+        const float q = ev.texel != nullptr ? ev.q : 0.0f, omq = 1.0f - q;
+        const EmitterSample e = emitter_sample<HAS_QUADS>(em, a[0], a[1], a[2], mk3(a[3], a[4], a[5]), env_on, omq);
+        k[0] = e.index; k[1] = e.slot; k[2] = e.ok ? 1 : 0;
+        put3(0, e.wi);
+        f[3] = e.dist2; f[4] = e.cos_l; f[5] = e.p_area; f[6] = e.p_l;
+    } else if (op == PTMI_NEE_CALL_SPECULAR) {
+        const f3 d = mk3(a[0], a[1], a[2]), nrm = mk3(a[3], a[4], a[5]);
+        const f3 sn = dot(d, nrm) < 0 ? nrm : -nrm;                   // integrator.h:221-222, as the kernel turns it
+        bool reflect; float fr; f3 next;
+        const bool walk = specular_vertex(d, nrm, sn, (int)a[6], a[7], a[8], reflect, fr, next);
+        k[0] = reflect ? 1 : 0; k[1] = walk ? 1 : 0;
+        f[0] = fr;
+        put3(1, next);
+        put3(4, unit_vector(next));
+    } else {                                                          // the rough ops: a vertex of (sn, d, alpha) first
+        const bool lw = op == PTMI_NEE_CALL_LIGHT_WEIGHT;
+        const float* b = lw ? a + 1 : a;
+        const RoughVertex v = rough_vertex(mk3(b[0], b[1], b[2]), mk3(b[3], b[4], b[5]), b[6]);
+        if (op == PTMI_NEE_CALL_ROUGH_VERTEX) {
+            k[0] = v.ok ? 1 : 0;
+            put3(0, v.un); put3(3, v.T); put3(6, v.B); put3(9, v.wo);
+            f[12] = v.lo;
+        } else if (op == PTMI_NEE_CALL_ROUGH_EVAL) {
+            float g = 0.0f, p_b = 0.0f;
+            k[0] = rough_eval(v, mk3(b[7], b[8], b[9]), g, p_b) ? 1 : 0;
+            f[0] = g; f[1] = p_b;
+        } else if (op == PTMI_NEE_CALL_ROUGH_SAMPLE) {
+            f3 next = mk3(0.0f, 0.0f, 0.0f);
+            float wgt = 0.0f, p_b = 0.0f;
+            k[0] = v.ok && rough_sample(v, b[7], b[8], next, wgt, p_b) ? 1 : 0;   // as the kernel calls it: the grazing exit first
+            put3(0, next);
+            f[3] = wgt; f[4] = p_b;
+        } else {                                                      // PTMI_NEE_CALL_LIGHT_WEIGHT
+            const bool rough = a[0] != 0.0f;
+            const f3 wi = mk3(b[7], b[8], b[9]);
+            float w0 = 0.0f, w2 = 0.0f;
+            k[0] = light_weight<0>(rough, v, wi, b[10], b[11], w0) ? 1 : 0;
+            k[1] = light_weight<2>(rough, v, wi, b[10], b[11], w2) ? 1 : 0;
+            f[0] = w0; f[1] = w2;
+        }
+    }
+    for (int c = 0; c < kNeeCallOutF; c++) out_f[(size_t)i * kNeeCallOutF + c] = f[c];
+    for (int c = 0; c < kNeeCallOutI; c++) out_i[(size_t)i * kNeeCallOutI + c] = k[c];
+}
+void launch_debug_nee_call(bool has_quads, int n, int op, const EmitterTable& em, const EnvTable& ev, const float* in, float* out_f, int* out_i,
+                           hipStream_t s) {
+    if (n <= 0) return;
+    with_bool(has_quads, [&](auto quads) {
+        hipLaunchKernelGGL(ptmi_debug_nee_call_k<decltype(quads)::value>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n, op, em, ev, in, out_f, out_i);
+    });
 }
 
 }  // namespace ptmi

@@ -373,5 +373,9 @@ void launch_debug_guided(int n, int op, const float* recs, const int* rec_idx, c
                          const uint32_t* states, float* out, int* used, hipStream_t s);
 void launch_debug_math(int n, int op, const float* a, const float* b, double* out /* 2n */, hipStream_t s);
 void launch_debug_grid_index(int n, const float* dirs, const float* normals, int* out, hipStream_t s);
+// ptmi_debug_nee_call (include/ptmi.h): floats in and out and ints out per case
+constexpr int kNeeCallIn = 16, kNeeCallOutF = 16, kNeeCallOutI = 4;
+void launch_debug_nee_call(bool has_quads, int n, int op, const EmitterTable& em, const EnvTable& ev, const float* in /* n * kNeeCallIn */,
+                           float* out_f /* n * kNeeCallOutF */, int* out_i /* n * kNeeCallOutI */, hipStream_t s);
 
 }  // namespace ptmi

@@ -1,8 +1,6 @@
 // first_hit.hip — the kernels that trace one ray at a time to its first hit (traversal.h: first_hit): the Radiosity view, the
 // feature pass and next-event estimation.  Compile with -ffp-contract=off (kernels.hip).
-#include "shading.h"
-#include "prim_sample.h"
-#include "rough.h"
+#include "light_sample.h"
 
 namespace ptmi {
 
@@ -131,66 +129,6 @@ void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams
 // and added if the walk's closest hit is the sampled emitter.  Every RNG draw of a vertex - Russian roulette, u_sel, r1, r2,
 // u, v - is made before its shadow ray is traced, in the contract's order, so visibility never moves a draw.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int emitter_select(const EmitterTable& em, float u) {
-    const float target = u * em.total;                       // u in (0, 1]: target <= total = cdf[n - 1]
-    int lo = 0, hi = em.n - 1;
-    while (lo < hi) {                                        // smallest j with target <= cdf[j]
-        const int mid = (lo + hi) >> 1;
-        if (target <= em.cdf[mid]) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-// cos / M_PI of the reference's pdf_bsdf (integrator.h:128): a binary64 quotient rounded to float
-__device__ __forceinline__ float cos_over_pi(float c) { return (float)((double)c / PTMI_PI_D); }
-
-// ---------------------------------------------------------------------------------------------
-// environment lighting (include/ptmi.h: "environment lighting"; the table: device_scene.h EnvTable).  The searches return the
-// smallest index whose entry satisfies the test, as the contract writes them; every load is per lane from global memory.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int cdf_search(const float* __restrict__ cdf, int n, float u) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {                                        // smallest i with u <= cdf[i] (cdf[n - 1] = 1 >= u)
-        const int mid = (lo + hi) >> 1;
-        if (u <= cdf[mid]) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-__device__ __forceinline__ int env_row(const EnvTable& ev, float y) {
-    int lo = 0, hi = ev.h - 1;
-    while (lo < hi) {                                        // smallest r with z[r + 1] < y; none (y = -1): h - 1
-        const int mid = (lo + hi) >> 1;
-        if (ev.z[mid + 1] < y) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-// the texel a direction looks up: the nearest one, radiance is piecewise constant
-__device__ __forceinline__ int env_texel(const EnvTable& ev, const f3& d) {
-    const int r = env_row(ev, fminf(fmaxf(d.y, -1.0f), 1.0f));
-    const float phi = ptmi_atan2f(d.z, d.x);
-    const float s = (float)((double)phi / (2.0 * PTMI_PI_D));
-    float t = s - ev.rot;
-    t = t - floorf(t);
-    const int j = min((int)(t * (float)ev.w), ev.w - 1);
-    return r * ev.w + j;
-}
-
-// the weight (f * cos * mis(p, p_b)) / p of a light sample of density p towards wi, f * cos without the colour: the cosine lobe,
-// or the GGX lobe of a rough vertex; false: the sample contributes nothing
-template <int SURF>
-__device__ __forceinline__ bool light_weight(bool rough, const RoughVertex& rv, const f3& wi, float cos_s, float p, float& w) {
-    if constexpr (SURF == 2) {
-        if (rough) {
-            float g, p_b;
-            if (!rough_eval(rv, wi, g, p_b)) return false;
-            w = (g * mis_power_heuristic(p, p_b)) / p;
-            return true;
-        }
-    }
-    const float p_b = cos_over_pi(cos_s);
-    w = (p_b * mis_power_heuristic(p, p_b)) / p;
-    return true;
-}
-
 // specular surfaces (include/ptmi.h: "specular surfaces"; the table: device_scene.h SurfaceTable).  SPEC: the context has a table
 // with a mirror or glass primitive; a vertex on one makes no light sample and no cosine sample and goes on along the reflected or
 // refracted direction, and what the next path ray finds (an emitter, the environment) counts in full.
@@ -279,28 +217,15 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                     const float2 sr = sf.rec[k];
                     const int kind = __float_as_int(sr.x);
                     if (SURF == 2 ? kind == 1 || kind == 2 : kind != 0) {                 // no light sample, no cosine sample
-                        const f3 un = unit_vector(sn);
-                        const float dn = dot(d, un);
-                        bool reflect = true;
-                        float eta = 1.0f, ci = 1.0f, ct = 1.0f;
-                        if (kind == 2) {                                                  // glass: one draw whatever comes of it
-                            const float u = rng_uniform(rng);
-                            eta = dot(d, nrm) < 0 ? 1.0f / sr.y : sr.y;                   // n_i / n_t: the stored normal points out of the body
-                            ci = fminf(1.0f, -dn);
-                            const float s2 = (eta * eta) * fmaxf(0.0f, 1.0f - ci * ci);
-                            if (!(s2 >= 1.0f) || eta == 1.0f) {                           // else total internal reflection
-                                ct = eta == 1.0f ? ci : sqrt_rn(1.0f - s2);               // ior 1 is no interface: F = 0 and next = d, exactly
-                                const float rs = (eta * ci - ct) / (eta * ci + ct);
-                                const float rp = (ci - eta * ct) / (ci + eta * ct);
-                                const float fr = 0.5f * (rs * rs + rp * rp);
-                                reflect = u <= fr;
-                            }
-                        }
+                        float u = 1.0f;
+                        if (kind == 2) u = rng_uniform(rng);                              // glass: one draw whatever comes of it
+                        bool reflect;
+                        [[maybe_unused]] float fr;
+                        f3 next;
+                        const bool walk = specular_vertex(d, nrm, sn, kind, sr.y, u, reflect, fr, next);
                         depth++;
                         if (depth >= fp.max_depth) break;
-                        const f3 next = reflect ? d - (2.0f * dn) * un : eta * d + (eta * ci - ct) * un;
-                        const float len2 = dot(next, next);
-                        if (!(len2 > 0.0f && len2 <= FLT_MAX)) break;                     // no walk starts with a NaN direction
+                        if (!walk) break;                                                 // no walk starts with a NaN direction
                         o = reflect ? o2 : hp - 1e-4f * sn;
                         d = unit_vector(next);
                         spec_prev = true;
@@ -322,16 +247,9 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                         const float r4 = rng_uniform(rng);
                         to_env = u_sel <= q;
                         if (to_env) {
-                            const int r = cdf_search(ev.marginal, ev.h, r1);
-                            const int j = cdf_search(ev.row_cdf + (size_t)r * (size_t)ev.w, ev.w, r2);
-                            const float z0 = ev.z[r], z1 = ev.z[r + 1];
-                            const float ct = z1 + r3 * (z0 - z1);
-                            const float sth = sqrt_rn(fmaxf(0.0f, 1.0f - ct * ct));
-                            const float a = ((float)j + r4) / (float)ev.w + ev.rot;
-                            float sphi, cphi;
-                            ptmi_sincosf((float)((2.0 * PTMI_PI_D) * (double)a), &sphi, &cphi);
-                            const f3 wi = mk3(sth * cphi, ct, sth * sphi);
-                            const float4 te = ev.texel[r * ev.w + j];
+                            int r, j;
+                            f3 wi;
+                            const float4 te = env_sample(ev, r1, r2, r3, r4, r, j, wi);
                             const float cos_s = dot(sn, wi);
                             const float p_e = q * te.w;
                             float w;
@@ -344,26 +262,14 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                         } else u_sel = (u_sel - q) / omq;
                     }
                     if (!to_env) {
-                        const float4* rec = em.rec + (size_t)kEmitterStride * (size_t)emitter_select(em, u_sel);
-                        const float4 a0 = rec[0], a1 = rec[1], a2 = rec[2], a3 = rec[3], a4 = rec[4];
-                        Geom g;
-                        g.v0 = xyz(a0); g.v1 = xyz(a1); g.v2 = xyz(a2); g.v3 = xyz(a3);
-                        g.type = __float_as_int(a2.w); g.ratio = a1.w;
-                        const f3 yv = sample_uniform<HAS_QUADS>(g, r1, r2);
-                        const f3 v = yv - o2;
-                        const float dist2 = dot(v, v);
-                        const float dist = sqrt_rn(dist2);
-                        const f3 wi = mk3(v.x / dist, v.y / dist, v.z / dist);
+                        const EmitterSample es = emitter_sample<HAS_QUADS>(em, u_sel, r1, r2, o2, env_on, omq);
+                        const f3 wi = es.wi;
                         const float cos_s = dot(sn, wi);
-                        const float cos_l = fabsf(dot(xyz(a4), wi));                      // a4: the geometric normal
-                        float p_l = (a3.w * dist2) / cos_l;
-                        if (env_on) p_l = omq * p_l;
                         float w;
-                        if (cos_s > 0.0f && cos_l > 0.0f && p_l > 0.0f && p_l <= FLT_MAX &&   // a p_l of 0 or inf weighs 0 (no NaN)
-                            light_weight<SURF>(rough, rv, wi, cos_s, p_l, w)) {
-                            const f3 c = tp * xyz(rec[5]);
+                        if (cos_s > 0.0f && es.ok && light_weight<SURF>(rough, rv, wi, cos_s, es.p_l, w)) {
+                            const f3 c = tp * xyz(es.rec[5]);
                             contrib = mk3(c.x * w, c.y * w, c.z * w);
-                            so = o2; sd = wi; s_slot = __float_as_int(a0.w);
+                            so = o2; sd = wi; s_slot = es.slot;
                             shadow = true;
                         }
                     }

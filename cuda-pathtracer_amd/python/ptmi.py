@@ -36,7 +36,7 @@ EXPORTS = [
     "ptmi_default_temporal_params", "ptmi_check_temporal_params", "ptmi_temporal_reset", "ptmi_temporal_accumulate",
     "ptmi_read_temporal", "ptmi_read_history_counts", "ptmi_denoise_temporal",
     "ptmi_host_emitters",
-    "ptmi_debug_math", "ptmi_debug_grid_index",
+    "ptmi_debug_math", "ptmi_debug_grid_index", "ptmi_debug_nee_call",
     "ptmi_default_env_params", "ptmi_check_env_params", "ptmi_set_environment", "ptmi_environment_info", "ptmi_host_env_table",
     "ptmi_check_surfaces", "ptmi_set_surfaces", "ptmi_surfaces_info",
     "ptmi_check_surfaces_rough", "ptmi_set_surfaces_rough", "ptmi_surface_counts",
@@ -163,6 +163,7 @@ def lib():
         L.ptmi_debug_guided_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
         L.ptmi_debug_math.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
         L.ptmi_debug_grid_index.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.ptmi_debug_nee_call.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
         L.ptmi_debug_set_traversal.argtypes = [vp, C.c_int, C.c_int, ip]
         L.ptmi_debug_set_solver_walk.argtypes = [vp, C.c_int, C.c_int]
         L.ptmi_debug_get_traversal.argtypes = [vp, ip]
@@ -933,6 +934,23 @@ class Renderer:
         out = np.zeros(n, np.int32)
         self._ck(self.L.ptmi_debug_grid_index(self.h, n, dirs.ctypes.data, normals.ctypes.data, out.ctypes.data))
         return out
+
+    (NEE_CALL_ENV_LOOKUP, NEE_CALL_ENV_SAMPLE, NEE_CALL_EMITTER_SAMPLE, NEE_CALL_SPECULAR, NEE_CALL_ROUGH_VERTEX, NEE_CALL_ROUGH_EVAL,
+     NEE_CALL_ROUGH_SAMPLE, NEE_CALL_LIGHT_WEIGHT) = range(8)
+    NEE_CALL_IN, NEE_CALL_OUT_F, NEE_CALL_OUT_I = 16, 16, 4
+
+    def debug_nee_call(self, op, inputs):
+        """ptmi_debug_nee_call: op (NEE_CALL_*) of the next-event kernel's light and surface sampling functions on the cases
+        inputs (n, k <= 16) float32, against the context's emitter and environment tables.  Returns out_f (n, 16) float32 and
+        out_i (n, 4) int32 (include/ptmi.h lists each op's inputs and outputs)."""
+        inputs = np.ascontiguousarray(inputs, np.float32)
+        inputs = inputs.reshape(len(inputs), -1)
+        n = len(inputs)
+        a = np.zeros((n, self.NEE_CALL_IN), np.float32)
+        a[:, :inputs.shape[1]] = inputs
+        out_f = np.zeros((n, self.NEE_CALL_OUT_F), np.float32); out_i = np.zeros((n, self.NEE_CALL_OUT_I), np.int32)
+        self._ck(self.L.ptmi_debug_nee_call(self.h, int(op), n, a.ctypes.data, out_f.ctypes.data, out_i.ctypes.data))
+        return out_f, out_i
 
 
 def write_png(path, rgb8):

@@ -413,6 +413,30 @@ int ptmi_debug_math(ptmi_ctx*, int op, int n, const float* a, const float* b, do
 /* direction_to_grid_index_local (form_factors.h:107-130), the function the form-factor kernel bins with, on n (direction, normal)
  * pairs as given: out[i] = theta row * 16 + phi column.  oracle: po_direction_to_grid_index. */
 int ptmi_debug_grid_index(ptmi_ctx*, int n, const float* dirs, const float* normals, int* out /* n */);
+/* The light and surface sampling functions of the next-event kernel per call (debug_hooks.hip: ptmi_debug_nee_call_k, built with
+ * the kernel's flags, calling the kernel's own functions of csrc/light_sample.h and csrc/rough.h).  One op on n cases against the
+ * context's own device tables: the emitter table of the loaded scene, the table of ptmi_set_environment, and q, omq and env_on as a
+ * frame with next_event set has them (q = 1 without emitters; env_on: the map's total > 0).  in: PTMI_NEE_CALL_IN floats per case,
+ * read from the front in the order listed; out_f: PTMI_NEE_CALL_OUT_F floats and out_i: PTMI_NEE_CALL_OUT_I ints per case, written
+ * from the front in the order listed and zero behind.  Floats a function leaves undefined after a false verdict are unspecified.
+ * n = 0 does nothing.  The ENV ops need an environment, EMITTER_SAMPLE a scene with an emitter, ENV_LOOKUP finite directions (the
+ * kernel never looks up another); anything else is PTMI_E_INVALID. */
+enum {
+    PTMI_NEE_CALL_ENV_LOOKUP     = 0,  /* texel(d)  in: d  out_i: row, column  out_f: texel rgb, texel pdf */
+    PTMI_NEE_CALL_ENV_SAMPLE     = 1,  /* step 3' in: r1, r2, r3, r4  out_i: row, column  out_f: wi, texel pdf, texel rgb */
+    PTMI_NEE_CALL_EMITTER_SAMPLE = 2,  /* in: u_sel (after its rescaling by q), r1, r2, o2  out_i: emitter index j, leaf-order slot, guards
+                                        * (cos_l > 0 and 0 < p_l <= FLT_MAX)  out_f: wi, dist2, cos_l, p_l, p_l times omq where env_on (else p_l) */
+    PTMI_NEE_CALL_SPECULAR       = 3,  /* in: d, stored normal n_k, kind (1 or 2, as a float), ior, u  out_i: reflected, the length test
+                                        * out_f: F (1 for a mirror and under total internal reflection), next, next normalised */
+    PTMI_NEE_CALL_ROUGH_VERTEX   = 4,  /* in: sn, d, alpha  out_i: the grazing test of co  out_f: un, T, B, wo, Lambda(co) (0 where the test fails) */
+    PTMI_NEE_CALL_ROUGH_EVAL     = 5,  /* in: sn, d, alpha, wi  out_i: contributes  out_f: g, p_b */
+    PTMI_NEE_CALL_ROUGH_SAMPLE   = 6,  /* in: sn, d, alpha, u1, u2  out_i: the path goes on  out_f: next (not normalised), weight, p_b */
+    PTMI_NEE_CALL_LIGHT_WEIGHT   = 7,  /* in: rough (0 or 1), sn, d, alpha, wi, cos_s, p  out_i: contributes without and with a rough-metal table
+                                        * out_f: the weight (f cos mis(p, p_b)) / p without such a table (the cosine lobe) and with one */
+    PTMI_NEE_CALL_OPS            = 8,
+    PTMI_NEE_CALL_IN = 16, PTMI_NEE_CALL_OUT_F = 16, PTMI_NEE_CALL_OUT_I = 4
+};
+int ptmi_debug_nee_call(ptmi_ctx*, int op, int n, const float* in, float* out_f, int* out_i);
 
 /* ---- progressive and adaptive accumulation (new in this implementation) -------------------------------------------------
  * A frame is an independent estimate of config.spp samples per pixel.  An ACCUMULATION instead goes on from pass to pass:

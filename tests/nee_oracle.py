@@ -137,6 +137,32 @@ def _unit(v):
     return v * k
 
 
+def select(cdf, total, u_sel):
+    """the emitter u_sel selects: the smallest j with u_sel * total <= cdf[j]"""
+    return min(int(np.searchsorted(cdf, f32(u_sel * total), side="left")), len(cdf) - 1)
+
+
+def emitter_sample(oscene, i, ng_i, pdf_area_i, r1, r2, o2, omq=None):
+    """The light sample towards primitive i (load order) from o2: (wi, dist2, cos_l, p_l, p_l scaled), p_l the area density turned
+    into one per solid angle, scaled by omq where the environment is a light too (omq None: p_l itself)"""
+    yv = np.zeros(3, f32)
+    lib().po_prim_sample_uniform(oscene.h, int(i), r1, r2, yv.ctypes.data)
+    with np.errstate(all="ignore"):
+        vv = (yv - o2).astype(f32)
+        dist2 = _dot(vv, vv)
+        dist = f32(np.sqrt(dist2))
+        wi = (vv / dist).astype(f32)
+        cos_l = abs(_dot(ng_i, wi))
+        p_l = f32(f32(pdf_area_i * dist2) / cos_l)
+        p_s = p_l if omq is None else f32(omq * p_l)
+    return wi, dist2, cos_l, p_l, p_s
+
+
+def sample_counts(cos_l, p_l):
+    """the guards of a light sample on an emitter: seen edge on, or a p_l of 0 or inf, it weighs 0"""
+    return bool(cos_l > 0 and 0 < p_l <= FLT_MAX)
+
+
 class NeeRenderer:
     """Frames of the NEE estimator over an OracleScene with persistent per-pixel streams (as a ptmi context keeps them)."""
 
@@ -195,19 +221,10 @@ class NeeRenderer:
             o2 = p + f32(1e-4) * sn
             if depth + 1 < max_depth and len(self.prim):
                 u_sel, r1, r2 = self._u(st), self._u(st), self._u(st)
-                j = min(int(np.searchsorted(self.cdf, f32(u_sel * self.total), side="left")), len(self.prim) - 1)
-                i = int(self.prim[j])
-                yv = np.zeros(3, f32)
-                L.po_prim_sample_uniform(self.s.h, i, r1, r2, yv.ctypes.data)
-                vv = yv - o2
-                dist2 = _dot(vv, vv)
-                dist = f32(np.sqrt(dist2))
-                wi = vv / dist
+                i = int(self.prim[select(self.cdf, self.total, u_sel)])
+                wi, _, cos_l, _, p_l = emitter_sample(self.s, i, self.ng[i], self.pdf_area[i], r1, r2, o2)
                 cos_s = _dot(sn, wi)
-                cos_l = abs(_dot(self.ng[i], wi))
-                with np.errstate(all="ignore"):
-                    p_l = f32(f32(self.pdf_area[i] * dist2) / cos_l)
-                if cos_s > 0 and cos_l > 0 and 0 < p_l <= FLT_MAX:
+                if cos_s > 0 and sample_counts(cos_l, p_l):
                     hs = self._intersect(o2, wi)
                     if hs.hit and hs.prim == i:
                         p_b = _over_pi(cos_s)

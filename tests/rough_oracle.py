@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from env_oracle import PI_D, lookup, sample_direction, sincosf
-from nee_oracle import FLT_MAX, _dot, _over_pi, _unit, f32, lib
+from nee_oracle import FLT_MAX, _dot, _over_pi, _unit, emitter_sample, f32, lib, sample_counts, select
 from specular_oracle import DIFFUSE, GLASS, SpecRenderer, scatter, shading_normal
 
 ROUGH = 3
@@ -134,6 +134,20 @@ def sample(v, u1, u2):
     return nxt, weight, p_b
 
 
+def light_weight(rv, wi, cos_s, p_light):
+    """(f * cos * mis(p_light, p_b)) / p_light of a light sample of density p_light, without the colour: the cosine lobe (rv None),
+    or the GGX lobe of the rough vertex rv; None where the sample contributes nothing"""
+    mis = lambda a, b: f32(lib().po_mis_power_heuristic(a, b))
+    with np.errstate(all="ignore"):
+        if rv is None:
+            p_b = _over_pi(cos_s)
+            return f32(f32(p_b * mis(p_light, p_b)) / p_light)
+        e = evaluate(rv, wi)
+        if e is None:
+            return None
+        return f32(f32(e[0] * mis(p_light, e[1])) / p_light)
+
+
 class RoughRenderer(SpecRenderer):
     """Frames of a context with a surface table that may hold rough metal: kind (n_prims,) of 0 .. 3, ior and roughness (n_prims,)
     or scalars (None: 1.5, 0.3), load order.  Without a kind 3 this is SpecRenderer's estimator draw for draw."""
@@ -210,15 +224,7 @@ class RoughRenderer(SpecRenderer):
             spec_prev = False
             rv = Vertex(sn, d, self.alpha[k]) if kind == ROUGH else None
 
-            def weight(wi, cos_s, p_light):
-                """(f * cos * mis) / p_light of a light sample, or None"""
-                if rv is None:
-                    p_b = _over_pi(cos_s)
-                    return f32(f32(p_b * mis(p_light, p_b)) / p_light)
-                e = evaluate(rv, wi)
-                if e is None:
-                    return None
-                return f32(f32(e[0] * mis(p_light, e[1])) / p_light)
+            weight = lambda wi, cos_s, p_light: light_weight(rv, wi, cos_s, p_light)
 
             if self.next_event and depth + 1 < max_depth and (len(self.prim) or self.sampled):
                 u_sel, r1, r2 = self._u(st), self._u(st), self._u(st)
@@ -238,21 +244,11 @@ class RoughRenderer(SpecRenderer):
                     else:
                         u_sel = f32(f32(u_sel - q) / omq)
                 if not to_env:
-                    jj = min(int(np.searchsorted(self.cdf, f32(u_sel * self.total), side="left")), len(self.prim) - 1)
-                    i = int(self.prim[jj])
-                    yv = np.zeros(3, f32)
-                    L.po_prim_sample_uniform(self.s.h, i, r1, r2, yv.ctypes.data)
-                    vv = yv - o2
-                    dist2 = _dot(vv, vv)
-                    dist = f32(np.sqrt(dist2))
+                    i = int(self.prim[select(self.cdf, self.total, u_sel)])
+                    wi, _, cos_l, _, p_l = emitter_sample(self.s, i, self.ng[i], self.pdf_area[i], r1, r2, o2, omq if self.sampled else None)
                     with np.errstate(all="ignore"):
-                        wi = vv / dist
                         cos_s = _dot(sn, wi)
-                        cos_l = abs(_dot(self.ng[i], wi))
-                        p_l = f32(f32(self.pdf_area[i] * dist2) / cos_l)
-                        if self.sampled:
-                            p_l = f32(omq * p_l)
-                    if cos_s > 0 and cos_l > 0 and 0 < p_l <= FLT_MAX:
+                    if cos_s > 0 and sample_counts(cos_l, p_l):
                         w = weight(wi, cos_s, p_l)
                         if w is not None:
                             hs = self._intersect(o2, wi)

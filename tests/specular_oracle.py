@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from env_oracle import EnvRenderer, lookup, sample_direction
-from nee_oracle import FLT_MAX, _dot, _over_pi, _unit, f32, lib
+from nee_oracle import FLT_MAX, _dot, _over_pi, _unit, emitter_sample, f32, lib, sample_counts, select
 
 DIFFUSE, MIRROR, GLASS = 0, 1, 2
 ONE, TWO, HALF_F, EPS = f32(1.0), f32(2.0), f32(0.5), f32(1e-4)
@@ -167,21 +167,11 @@ class SpecRenderer(EnvRenderer):
                     else:
                         u_sel = f32(f32(u_sel - q) / omq)
                 if not to_env:
-                    jj = min(int(np.searchsorted(self.cdf, f32(u_sel * self.total), side="left")), len(self.prim) - 1)
-                    i = int(self.prim[jj])
-                    yv = np.zeros(3, f32)
-                    L.po_prim_sample_uniform(self.s.h, i, r1, r2, yv.ctypes.data)
-                    vv = yv - o2
-                    dist2 = _dot(vv, vv)
-                    dist = f32(np.sqrt(dist2))
+                    i = int(self.prim[select(self.cdf, self.total, u_sel)])
+                    wi, _, cos_l, _, p_l = emitter_sample(self.s, i, self.ng[i], self.pdf_area[i], r1, r2, o2, omq if self.sampled else None)
                     with np.errstate(all="ignore"):
-                        wi = vv / dist
                         cos_s = _dot(sn, wi)
-                        cos_l = abs(_dot(self.ng[i], wi))
-                        p_l = f32(f32(self.pdf_area[i] * dist2) / cos_l)
-                        if self.sampled:
-                            p_l = f32(omq * p_l)
-                    if cos_s > 0 and cos_l > 0 and 0 < p_l <= FLT_MAX:
+                    if cos_s > 0 and sample_counts(cos_l, p_l):
                         hs = self._intersect(o2, wi)
                         if hs.hit and hs.prim == i:
                             p_b = _over_pi(cos_s)
