@@ -2,14 +2,12 @@
 
 The table is binary64 where the header says so (Python floats: IEEE + - * / without fma) and float32 elsewhere; ptmi_sincos_d is
 restated from include/ptmi_math.h because the table feeds it a binary64 argument; ptmi_atan2f and ptmi_sincosf come from the
-oracle's po_math_batch.  The estimator extends tests/nee_oracle.py's NeeRenderer, which supplies the scene, the camera, the
-streams and the pieces the header takes from the reference.
+oracle's po_math_batch.  These are the table, the lookup and the sampled direction: the estimator that uses them is
+tests/path_oracle.py's one path loop.
 """
-import ctypes as C
-
 import numpy as np
 
-from nee_oracle import FLT_MAX, NeeRenderer, _dot, _over_pi, _unit, emitter_sample, f32, lib, sample_counts, select
+from nee_oracle import f32
 from oracle_binding import math_batch
 
 PI_D = 3.14159265358979323846
@@ -125,98 +123,6 @@ def sample_direction(tab, r1, r2, r3, r4):
     a = f32(f32(f32(f32(j) + r4) / f32(w)) + tab["rot"])
     sp, cp = sincosf(f32((2.0 * PI_D) * float(a)))
     return r, j, np.array([f32(st * cp), ct, f32(st * sp)], f32)
-
-
-class EnvRenderer(NeeRenderer):
-    """Frames of a context with an environment: next_event False - the reference's estimator plus the lookup where a path ray
-    misses; True - NEE with the environment as a second light.  env_rgb None: no environment (NeeRenderer's estimator for
-    next_event True, the reference's for False)."""
-
-    def __init__(self, oscene, cam, width, height, env_rgb, next_event, scale=1.0, rotation_deg=0.0, select_fraction=0.5, seed_base=2023):
-        super().__init__(oscene, cam, width, height, seed_base)
-        self.tab = None if env_rgb is None else table(env_rgb, scale, rotation_deg)
-        self.next_event = bool(next_event)
-        self.sampled = self.next_event and self.tab is not None and self.tab["total"] > 0
-        self.q = f32(1.0) if len(self.prim) == 0 else f32(select_fraction)
-
-    def sample(self, x, y, st, max_depth):
-        L = lib()
-        u = f32(f32(f32(x) + self._u(st)) / f32(self.w))
-        v = f32(f32(f32(y) + self._u(st)) / f32(self.h))
-        o = np.zeros(3, f32); d = np.zeros(3, f32)
-        L.po_camera_ray(C.byref(self.cf), u, v, o.ctypes.data, d.ctypes.data)
-        tp = np.ones(3, f32); Lr = np.zeros(3, f32)
-        pb_prev = f32(0.0)
-        q = self.q; omq = f32(f32(1.0) - q)
-        mis = lambda a, b: f32(L.po_mis_power_heuristic(a, b))
-        for depth in range(max_depth):
-            h = self._intersect(o, d)
-            if not h.hit:
-                if self.tab is not None:                     # 1'
-                    r, j = lookup(self.tab, d)
-                    E = self.tab["texel"][r, j, :3]; pdf = self.tab["texel"][r, j, 3]
-                    if self.sampled and depth >= 1:
-                        Lr = Lr + (tp * E) * mis(pb_prev, f32(q * pdf))
-                    else:
-                        Lr = Lr + tp * E
-                break
-            k = h.prim
-            n_k = np.array(h.n, f32); Le = np.array(h.Le, f32); kd = np.array(h.bsdf, f32)
-            t = f32(h.t); p = np.array(h.p, f32)
-            pa = self.pdf_area[k] if depth > 0 and self.next_event else f32(0.0)
-            if pa > 0:
-                p_l = f32(f32(pa * f32(t * t)) / abs(_dot(self.ng[k], d)))
-                if self.sampled:
-                    p_l = f32(omq * p_l)
-                Lr = Lr + (tp * Le) * mis(pb_prev, p_l)
-            else:
-                Lr = Lr + tp * Le
-            if depth > 2:
-                rr = min(max(tp[0], max(tp[1], tp[2])), f32(0.95))
-                if self._u(st) > rr:
-                    break
-                tp = tp * f32(f32(1.0) / rr)
-            tp = tp * kd
-            if f32(np.sqrt(_dot(tp, tp))) < f32(1e-5):
-                break
-            sn = n_k if _dot(d, n_k) < 0 else -n_k
-            o2 = p + f32(1e-4) * sn
-            if self.next_event and depth + 1 < max_depth and (len(self.prim) or self.sampled):
-                u_sel, r1, r2 = self._u(st), self._u(st), self._u(st)
-                to_env = False
-                if self.sampled:
-                    r3, r4 = self._u(st), self._u(st)
-                    to_env = u_sel <= q
-                    if to_env:
-                        r, j, wi = sample_direction(self.tab, r1, r2, r3, r4)
-                        E = self.tab["texel"][r, j, :3]; pdf = self.tab["texel"][r, j, 3]
-                        cos_s = _dot(sn, wi)
-                        p_e = f32(q * pdf)
-                        if cos_s > 0 and 0 < p_e <= FLT_MAX and not self._intersect(o2, wi).hit:
-                            p_b = _over_pi(cos_s)
-                            w = f32(f32(p_b * mis(p_e, p_b)) / p_e)
-                            Lr = Lr + (tp * E) * w
-                    else:
-                        u_sel = f32(f32(u_sel - q) / omq)
-                if not to_env:
-                    i = int(self.prim[select(self.cdf, self.total, u_sel)])
-                    wi, _, cos_l, _, p_l = emitter_sample(self.s, i, self.ng[i], self.pdf_area[i], r1, r2, o2, omq if self.sampled else None)
-                    cos_s = _dot(sn, wi)
-                    if cos_s > 0 and sample_counts(cos_l, p_l):
-                        hs = self._intersect(o2, wi)
-                        if hs.hit and hs.prim == i:
-                            p_b = _over_pi(cos_s)
-                            w = f32(f32(p_b * mis(p_l, p_b)) / p_l)
-                            Lr = Lr + (tp * self.prims["Le"][i].astype(f32)) * w
-            uu, vw = self._u(st), self._u(st)
-            if depth + 1 >= max_depth:
-                break
-            nxt = np.zeros(3, f32)
-            L.po_sample_cosine_hemisphere(sn.ctypes.data, uu, vw, nxt.ctypes.data)
-            pb_prev = _over_pi(max(_dot(sn, nxt), f32(0.0)))
-            o = o2
-            d = _unit(nxt)
-        return Lr
 
 
 # ------------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 Every float operation is float32 in the order the header writes it; the pieces the header takes from the reference - the
 closest hit, Primitive::sampleUniform, sampleCosineHemisphere, misPowerHeuristic, area, the camera ray, the RNG, the tone map -
 come from the CPU oracle (oracle/ptmi_oracle.c) through ctypes.  The function types are declared here; oracle_binding.py
-supplies the scene handles and the library path only.
+supplies the scene handles and the library path only.  The estimator that uses these pieces is tests/path_oracle.py's one path loop.
 """
 import ctypes as C
 
@@ -161,111 +161,3 @@ def emitter_sample(oscene, i, ng_i, pdf_area_i, r1, r2, o2, omq=None):
 def sample_counts(cos_l, p_l):
     """the guards of a light sample on an emitter: seen edge on, or a p_l of 0 or inf, it weighs 0"""
     return bool(cos_l > 0 and 0 < p_l <= FLT_MAX)
-
-
-class NeeRenderer:
-    """Frames of the NEE estimator over an OracleScene with persistent per-pixel streams (as a ptmi context keeps them)."""
-
-    def __init__(self, oscene, cam, width, height, seed_base=2023):
-        L = lib()
-        self.s, self.w, self.h = oscene, width, height
-        self.prims = oscene.prims()
-        self.prim, self.cdf, self.pdf_area, self.total = emitter_table(oscene, with_total=True)
-        self.ng = geometric_normals(oscene)
-        self.cf = CameraFrame()
-        L.po_camera_frame_setup(C.byref(cam), width, height, C.byref(self.cf))
-        self.rng = np.zeros((height * width, 6), np.uint32)
-        for pix in range(height * width):
-            L.po_rng_init(seed_base + pix, pix, self.rng[pix].ctypes.data)
-        self.hit = Hit()
-        self.vec = np.zeros(3, f32)
-
-    def _u(self, st):
-        return f32(lib().po_rng_uniform(st.ctypes.data))
-
-    def _intersect(self, o, d):
-        lib().po_intersect(self.s.h, o.ctypes.data, d.ctypes.data, 1e-4, FLT_MAX, 1, C.byref(self.hit))
-        return self.hit
-
-    def sample(self, x, y, st, max_depth):
-        L = lib()
-        u = f32(f32(f32(x) + self._u(st)) / f32(self.w))
-        v = f32(f32(f32(y) + self._u(st)) / f32(self.h))
-        o = np.zeros(3, f32); d = np.zeros(3, f32)
-        L.po_camera_ray(C.byref(self.cf), u, v, o.ctypes.data, d.ctypes.data)
-        tp = np.ones(3, f32); Lr = np.zeros(3, f32)
-        pb_prev = f32(0.0)
-        for depth in range(max_depth):
-            h = self._intersect(o, d)
-            if not h.hit:
-                break
-            k = h.prim
-            n_k = np.array(h.n, f32); Le = np.array(h.Le, f32); kd = np.array(h.bsdf, f32)
-            t = f32(h.t); p = np.array(h.p, f32)
-            pa = self.pdf_area[k] if depth > 0 else f32(0.0)
-            if pa > 0:
-                p_l = f32(f32(pa * f32(t * t)) / abs(_dot(self.ng[k], d)))
-                w = f32(L.po_mis_power_heuristic(pb_prev, p_l))
-                Lr = Lr + (tp * Le) * w
-            else:
-                Lr = Lr + tp * Le
-            if depth > 2:
-                rr = min(max(tp[0], max(tp[1], tp[2])), f32(0.95))
-                if self._u(st) > rr:
-                    break
-                tp = tp * f32(f32(1.0) / rr)
-            tp = tp * kd
-            if f32(np.sqrt(_dot(tp, tp))) < f32(1e-5):
-                break
-            sn = n_k if _dot(d, n_k) < 0 else -n_k
-            o2 = p + f32(1e-4) * sn
-            if depth + 1 < max_depth and len(self.prim):
-                u_sel, r1, r2 = self._u(st), self._u(st), self._u(st)
-                i = int(self.prim[select(self.cdf, self.total, u_sel)])
-                wi, _, cos_l, _, p_l = emitter_sample(self.s, i, self.ng[i], self.pdf_area[i], r1, r2, o2)
-                cos_s = _dot(sn, wi)
-                if cos_s > 0 and sample_counts(cos_l, p_l):
-                    hs = self._intersect(o2, wi)
-                    if hs.hit and hs.prim == i:
-                        p_b = _over_pi(cos_s)
-                        w = f32(f32(p_b * f32(L.po_mis_power_heuristic(p_l, p_b))) / p_l)
-                        Lr = Lr + (tp * self.prims["Le"][i].astype(f32)) * w
-            uu, vw = self._u(st), self._u(st)
-            if depth + 1 >= max_depth:
-                break
-            nxt = np.zeros(3, f32)
-            L.po_sample_cosine_hemisphere(sn.ctypes.data, uu, vw, nxt.ctypes.data)
-            pb_prev = _over_pi(max(_dot(sn, nxt), f32(0.0)))
-            o = o2
-            d = _unit(nxt)
-        return Lr
-
-    def sums(self, spp, max_depth, rows=None, color=None):
-        """Colour sums of spp samples for every pixel of `rows` (default all; row 0 = bottom), going on from `color`"""
-        rows = range(self.h) if rows is None else rows
-        out = np.zeros((self.h, self.w, 3), f32) if color is None else color.copy()
-        for y in rows:
-            for x in range(self.w):
-                st = self.rng[y * self.w + x]
-                c = out[y, x].copy()
-                for _ in range(spp):
-                    c = c + self.sample(x, y, st, max_depth)
-                out[y, x] = c
-        return out
-
-    @staticmethod
-    def resolve(sums, spp):
-        """mean -> Reinhard -> gamma -> 8 bit of a frame's resolve: (rgb8, radiance), each (rows, width, 3)"""
-        L = lib()
-        rad = np.zeros_like(sums); rgb = np.zeros(sums.shape, np.uint8)
-        for idx in np.ndindex(sums.shape[:2]):
-            s = np.ascontiguousarray(sums[idx], f32)
-            L.po_average(s.ctypes.data, int(spp), rad[idx].ctypes.data)
-            c = np.ascontiguousarray(rad[idx]); out = np.zeros(3, np.uint8)
-            L.po_tonemap(c.ctypes.data, out.ctypes.data)
-            rgb[idx] = out
-        return rgb, rad
-
-    def frame(self, spp, max_depth):
-        """One frame (streams carry over to the next call): (rgb8, radiance), row 0 = bottom"""
-        return self.resolve(self.sums(spp, max_depth), spp)

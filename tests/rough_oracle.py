@@ -1,20 +1,17 @@
 """CPU restatement of rough metal (include/ptmi.h, "rough metal"), written from the header.
 
 Every float operation of the estimator is float32 in the order the header writes it; sincosf is ptmi_sincosf through the
-oracle's math batch, as tests/env_oracle.py takes it.  RoughRenderer extends tests/specular_oracle.py's SpecRenderer by the
-kind-3 vertex.  The second half holds binary64 helpers for the analytic values (albedo by quadrature, the sampler's statistics):
+oracle's math batch, as tests/env_oracle.py takes it.  This is the kind-3 vertex alone - its frame, the light sample's weight and
+the BSDF sample: the estimator that meets it is tests/path_oracle.py's one path loop.  The second half holds binary64 helpers for the analytic values (albedo by quadrature, the sampler's statistics):
 they restate the same formulas in vectorised numpy float64 and share no code with the float32 half.
 """
-import ctypes as C
-
 import numpy as np
 
-from env_oracle import PI_D, lookup, sample_direction, sincosf
-from nee_oracle import FLT_MAX, _dot, _over_pi, _unit, emitter_sample, f32, lib, sample_counts, select
-from specular_oracle import DIFFUSE, GLASS, SpecRenderer, scatter, shading_normal
+from env_oracle import PI_D, sincosf
+from nee_oracle import _dot, _over_pi, _unit, f32, lib
 
 ROUGH = 3
-ZERO, ONE, TWO, FOUR, HALF_F, EPS = f32(0.0), f32(1.0), f32(2.0), f32(4.0), f32(0.5), f32(1e-4)
+ZERO, ONE, TWO, FOUR, HALF_F = f32(0.0), f32(1.0), f32(2.0), f32(4.0), f32(0.5)
 PI_F = f32(PI_D)
 MIN_COS2 = f32(1e-37)                     # PTMI_ROUGH_MIN_COS2
 
@@ -146,139 +143,6 @@ def light_weight(rv, wi, cos_s, p_light):
         if e is None:
             return None
         return f32(f32(e[0] * mis(p_light, e[1])) / p_light)
-
-
-class RoughRenderer(SpecRenderer):
-    """Frames of a context with a surface table that may hold rough metal: kind (n_prims,) of 0 .. 3, ior and roughness (n_prims,)
-    or scalars (None: 1.5, 0.3), load order.  Without a kind 3 this is SpecRenderer's estimator draw for draw."""
-
-    def __init__(self, oscene, cam, width, height, kind, ior=None, roughness=None, env_rgb=None, next_event=False, **prm):
-        super().__init__(oscene, cam, width, height, kind, ior, env_rgb, next_event, **prm)
-        n = len(self.kind)
-        r = np.broadcast_to(np.asarray(0.3 if roughness is None else roughness, f32), (n,)).astype(f32)
-        self.alpha = (r * r).astype(f32)
-
-    def sample(self, x, y, st, max_depth):
-        L = lib()
-        self.samples += 1
-        u = f32(f32(f32(x) + self._u(st)) / f32(self.w))
-        v = f32(f32(f32(y) + self._u(st)) / f32(self.h))
-        o = np.zeros(3, f32); d = np.zeros(3, f32)
-        L.po_camera_ray(C.byref(self.cf), u, v, o.ctypes.data, d.ctypes.data)
-        tp = np.ones(3, f32); Lr = np.zeros(3, f32)
-        pb_prev = f32(0.0)
-        spec_prev = False
-        q = self.q; omq = f32(ONE - q)
-        mis = lambda a, b: f32(L.po_mis_power_heuristic(a, b))
-        for depth in range(max_depth):
-            h = self._intersect(o, d)
-            if not h.hit:
-                if self.tab is not None:                     # 1'
-                    r, j = lookup(self.tab, d)
-                    E = self.tab["texel"][r, j, :3]; pdf = self.tab["texel"][r, j, 3]
-                    if self.sampled and depth >= 1 and not spec_prev:
-                        Lr = Lr + (tp * E) * mis(pb_prev, f32(q * pdf))
-                    else:
-                        Lr = Lr + tp * E
-                break
-            before = self.draws
-            k = h.prim
-            n_k = np.array(h.n, f32); Le = np.array(h.Le, f32); kd = np.array(h.bsdf, f32)
-            t = f32(h.t); p = np.array(h.p, f32)
-            pa = self.pdf_area[k] if depth > 0 and self.next_event and not spec_prev else f32(0.0)
-            if pa > 0:
-                p_l = f32(f32(pa * f32(t * t)) / abs(_dot(self.ng[k], d)))
-                if self.sampled:
-                    p_l = f32(omq * p_l)
-                Lr = Lr + (tp * Le) * mis(pb_prev, p_l)
-            else:
-                Lr = Lr + tp * Le
-            if depth > 2:
-                rr = min(max(tp[0], max(tp[1], tp[2])), f32(0.95))
-                if self._u(st) > rr:
-                    self._seen(self.kind[k], depth, before)
-                    break
-                tp = tp * f32(ONE / rr)
-            tp = tp * kd
-            if f32(np.sqrt(_dot(tp, tp))) < f32(1e-5):
-                self._seen(self.kind[k], depth, before)
-                break
-            sn = shading_normal(d, n_k)
-            o2 = p + EPS * sn
-            kind = int(self.kind[k])
-            if kind != DIFFUSE and kind != ROUGH:
-                uu = self._u(st) if kind == GLASS else ONE
-                self._seen(kind, depth, before)
-                if depth + 1 >= max_depth:
-                    self.cut += 1
-                    break
-                nxt, reflected, _ = scatter(d, n_k, kind, self.ior[k], uu)
-                with np.errstate(all="ignore"):
-                    len2 = _dot(nxt, nxt)
-                if not (len2 > 0 and len2 <= FLT_MAX):
-                    break
-                o = o2 if reflected else (p - EPS * sn).astype(f32)
-                d = _unit(nxt)
-                spec_prev = True
-                continue
-            spec_prev = False
-            rv = Vertex(sn, d, self.alpha[k]) if kind == ROUGH else None
-
-            weight = lambda wi, cos_s, p_light: light_weight(rv, wi, cos_s, p_light)
-
-            if self.next_event and depth + 1 < max_depth and (len(self.prim) or self.sampled):
-                u_sel, r1, r2 = self._u(st), self._u(st), self._u(st)
-                to_env = False
-                if self.sampled:
-                    r3, r4 = self._u(st), self._u(st)
-                    to_env = u_sel <= q
-                    if to_env:
-                        r, j, wi = sample_direction(self.tab, r1, r2, r3, r4)
-                        E = self.tab["texel"][r, j, :3]; pdf = self.tab["texel"][r, j, 3]
-                        cos_s = _dot(sn, wi)
-                        p_e = f32(q * pdf)
-                        if cos_s > 0 and 0 < p_e <= FLT_MAX:
-                            w = weight(wi, cos_s, p_e)
-                            if w is not None and not self._intersect(o2, wi).hit:
-                                Lr = Lr + (tp * E) * w
-                    else:
-                        u_sel = f32(f32(u_sel - q) / omq)
-                if not to_env:
-                    i = int(self.prim[select(self.cdf, self.total, u_sel)])
-                    wi, _, cos_l, _, p_l = emitter_sample(self.s, i, self.ng[i], self.pdf_area[i], r1, r2, o2, omq if self.sampled else None)
-                    with np.errstate(all="ignore"):
-                        cos_s = _dot(sn, wi)
-                    if cos_s > 0 and sample_counts(cos_l, p_l):
-                        w = weight(wi, cos_s, p_l)
-                        if w is not None:
-                            hs = self._intersect(o2, wi)
-                            if hs.hit and hs.prim == i:
-                                Lr = Lr + (tp * self.prims["Le"][i].astype(f32)) * w
-            uu, vw = self._u(st), self._u(st)
-            self._seen(kind, depth, before)
-            if depth + 1 >= max_depth:
-                self.cut += 1
-                break
-            if rv is not None:
-                bs = sample(rv, uu, vw) if rv.good else None
-                if bs is None:
-                    break
-                nxt, wgt, p_b = bs
-                with np.errstate(all="ignore"):
-                    len2 = _dot(nxt, nxt)
-                if not (len2 > 0 and len2 <= FLT_MAX):
-                    break
-                tp = (tp * wgt).astype(f32)
-                pb_prev = p_b
-                o = o2
-                d = _unit(nxt)
-                continue
-            nxt = np.zeros(3, f32)
-            L.po_sample_cosine_hemisphere(sn.ctypes.data, uu, vw, nxt.ctypes.data)
-            pb_prev = _over_pi(max(_dot(sn, nxt), f32(0.0)))
-            o = o2
-            d = _unit(nxt)
-        return Lr
 
 
 # ---- binary64: the analytic values ------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """Environment lighting against analytic values on the CPU (include/ptmi.h, "environment lighting") - no GPU.  The restatement of
-the contract (tests/env_oracle.py) alone must reach the values tests/test_gpu_env_expectation.py holds the GPU to: that shows
+the contract (tests/path_oracle.py with tests/env_oracle.py) alone must reach the values tests/test_gpu_env_expectation.py holds the GPU to: that shows
 the contract itself unbiased, and the chosen inputs inside the noise cap, before any kernel runs.
 
 Every case renders 16 x 16 pixels; a pixel has its own stream, so the pixel-to-pixel spread gives the standard error, and the
@@ -12,6 +12,7 @@ import pytest
 
 import env_oracle as EO
 import env_scenes as ES
+import path_oracle as PO
 from oracle_binding import OracleScene, default_camera
 
 SIZE = 16
@@ -72,20 +73,20 @@ def cube():
 def test_cube_plain_estimator_is_exact_per_sample(cube):
     o, inside, outside = cube
     for depth, value in ((1, L0), (2, L0 + RHO * E), (5, L0 + RHO * E)):
-        _, rad = EO.EnvRenderer(o, default_camera(), SIZE, SIZE, ES.constant_map(E), False).frame(2, depth)
+        _, rad = PO.EnvRenderer(o, default_camera(), SIZE, SIZE, ES.constant_map(E), False).frame(2, depth)
         assert np.abs(rad[inside].astype(np.float64) / value - 1.0).max() < 1e-6, depth
         assert (rad[outside] == E.astype(np.float32)).all(), depth
 
 
 def test_cube_with_next_event(cube):
     o, inside, outside = cube
-    r = EO.EnvRenderer(o, default_camera(), SIZE, SIZE, ES.constant_map(E), True)
+    r = PO.EnvRenderer(o, default_camera(), SIZE, SIZE, ES.constant_map(E), True)
     _, rad = r.frame(2, 1)
     assert np.abs(rad[inside].astype(np.float64) / L0 - 1.0).max() < 1e-6
     # the emitter half of the light samples (q = 0.5) finds nothing from a convex body's own surface; the environment half and
     # the BSDF ray share rho * E by their weights.  Measured: 5 SE = 0.28 % of the value at 256 spp over these pixels -> 128 spp:
     # 0.39 %.
-    _, rad = EO.EnvRenderer(o, default_camera(), SIZE, SIZE, ES.constant_map(E), True).frame(128, 2)
+    _, rad = PO.EnvRenderer(o, default_camera(), SIZE, SIZE, ES.constant_map(E), True).frame(128, 2)
     check("cube NEE depth 2", rad[inside], L0 + RHO * E)
     assert (rad[outside] == E.astype(np.float32)).all()
 
@@ -155,7 +156,7 @@ def test_the_scalar_restatement_under_the_sun():
     env, _, v, _ = ES.sun_case()
     rho = np.array((0.3, 0.5, 0.7))
     o = OracleScene.from_arrays(*ES.ground_quad(rho).arrays())
-    _, rad = EO.EnvRenderer(o, ES.top_down_camera(), SIZE, SIZE, env, True).frame(16, 3)
+    _, rad = PO.EnvRenderer(o, ES.top_down_camera(), SIZE, SIZE, env, True).frame(16, 3)
     mean, se = stats(rad, rho * v)
     assert (np.abs(mean - rho * v) < Z_MAX * se).all(), (mean, rho * v, se)
     assert (se < 0.02 * rho * v).all()
@@ -180,6 +181,6 @@ def test_open_furnace(name, q):
     assert (F_RHO ** DEPTH <= 2.5e-4).all()
     o = OracleScene.from_arrays(*open_furnace(name).arrays())
     # measured at 64 spp, blue (the noisiest channel): 5 SE = 0.53 % of the value with the quads at q = 0.75 -> 96 spp: 0.43 %
-    r = EO.EnvRenderer(o, default_camera(), SIZE, SIZE, ES.constant_map(F_E), True, select_fraction=q)
+    r = PO.EnvRenderer(o, default_camera(), SIZE, SIZE, ES.constant_map(F_E), True, select_fraction=q)
     _, rad = r.frame(96, DEPTH)
     check(f"{name} q {q}", rad, F_E, lower=F_E * (1.0 - F_RHO ** DEPTH))

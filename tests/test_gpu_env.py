@@ -1,5 +1,5 @@
 """Environment lighting on the GPU (include/ptmi.h: "environment lighting") against the CPU restatement of the header's contract
-(tests/env_oracle.py), bit for bit, and through every way a context renders: frames, batches, passes, tiles, the denoiser and
+(tests/path_oracle.py), bit for bit, and through every way a context renders: frames, batches, passes, tiles, the denoiser and
 the temporal step."""
 import ctypes as C
 import os
@@ -13,8 +13,9 @@ import denoise_oracle as DO
 import env_scenes as ES
 import ptmi
 import temporal_oracle as TO
-from env_oracle import EnvRenderer
+from gpu_frames import check_frames
 from oracle_binding import OracleScene, SCENES, default_camera
+from path_oracle import EnvRenderer
 from test_gpu_denoise import sigma_x_auto, tone_map
 
 pytestmark = pytest.mark.gpu
@@ -57,16 +58,8 @@ def setup(R, which, spp, depth, next_event, w=W, h=H):
     return o
 
 
-def check_frames(R, o, env, spp, depth, next_event, frames=2, w=W, h=H, **prm):
-    ref = EnvRenderer(o, default_camera(), w, h, env, next_event, **prm)
-    for frame in range(frames):
-        st = R.render_frame()
-        rgb, rad = R.read_image()
-        ergb, erad = ref.frame(spp, depth)
-        assert np.array_equal(bits(rad), bits(erad)), (frame, int((bits(rad) != bits(erad)).sum()))
-        assert np.array_equal(rgb, ergb)
-        assert st.samples == w * h * spp and st.bounce_launches == 1
-    return rad
+def reference(o, env, next_event, **prm):
+    return EnvRenderer(o, default_camera(), W, H, env, next_event, **prm)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -80,7 +73,7 @@ def test_cbox_under_the_sky(R, next_event, depth):
     R.set_environment(env)
     info = R.environment_info()
     assert (info["width"], info["height"]) == (32, 16) and info["total"] == ptmi.host_env_table(env)["total"]
-    rad = check_frames(R, o, env, 3, depth, next_event)
+    _, rad, _ = check_frames(R, reference(o, env, next_event), 3, depth)
     assert rad.max() > 0
 
 
@@ -89,7 +82,7 @@ def test_cbox_quads_with_a_turned_map(R, next_event):
     env = ES.random_map(7, 5, 12)
     o = setup(R, "cbox_quads", 3, 5, next_event)
     R.set_environment(env, rotation_deg=70.0, scale=1.5)
-    check_frames(R, o, env, 3, 5, next_event, rotation_deg=70.0, scale=1.5)
+    check_frames(R, reference(o, env, next_event, rotation_deg=70.0, scale=1.5), 3, 5)
 
 
 @pytest.mark.parametrize("which,walk,next_event", [("soup", "CERTIFIED", False), ("soup", "CERTIFIED", True),
@@ -99,7 +92,7 @@ def test_the_other_walks(R, which, walk, next_event):
     o = setup(R, which, 3, 5, next_event)
     assert R.traversal() == getattr(R, walk)
     R.set_environment(env)
-    check_frames(R, o, env, 3, 5, next_event)
+    check_frames(R, reference(o, env, next_event), 3, 5)
 
 
 def test_a_scene_without_emitters_samples_the_environment_only(R):
@@ -111,7 +104,7 @@ def test_a_scene_without_emitters_samples_the_environment_only(R):
     assert R.read_image()[1].max() == 0
     R.update_resolution(W, H)
     R.set_environment(env, select_fraction=0.25)
-    rad = check_frames(R, o, env, 4, 5, True, select_fraction=0.25)
+    _, rad, _ = check_frames(R, reference(o, env, True, select_fraction=0.25), 4, 5)
     assert rad.max() > 0
 
 
@@ -120,7 +113,7 @@ def test_select_fraction_at_its_ends(R, fraction):
     env = ES.sky_32x16()
     o = setup(R, "cbox", 4, 5, True)
     R.set_environment(env, select_fraction=fraction)
-    check_frames(R, o, env, 4, 5, True, select_fraction=fraction)
+    check_frames(R, reference(o, env, True, select_fraction=fraction), 4, 5)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -165,7 +158,7 @@ def test_the_map_survives_a_scene_load(R):
     o = load(R, "cbox")
     assert R.environment_info()["width"] == 32
     R.update_resolution(W, H)
-    check_frames(R, o, env, 3, 5, True, frames=1, rotation_deg=30.0)
+    check_frames(R, reference(o, env, True, rotation_deg=30.0), 3, 5, frames=1)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """Next-event estimation with MIS on the GPU (include/ptmi.h: ptmi_config.next_event) against the CPU restatement of the header's
-contract (tests/nee_oracle.py), bit for bit, and against the reference's estimator in expectation."""
+contract (tests/path_oracle.py), bit for bit, and against the reference's estimator in expectation."""
 import ctypes as C
 import os
 import subprocess
@@ -10,8 +10,9 @@ import pytest
 
 import ptmi
 import denoise_oracle as DO
-from nee_oracle import NeeRenderer
+from gpu_frames import check_frames
 from oracle_binding import OracleScene, SCENES, default_camera
+from path_oracle import NeeRenderer
 from test_gpu_denoise import sigma_x_auto, tone_map
 
 pytestmark = pytest.mark.gpu
@@ -75,12 +76,8 @@ def test_frames_match_the_restatement(R, which, w, h, spp, depth):
         assert R.traversal() == ptmi.Renderer.CERTIFIED
     ref = NeeRenderer(o, default_camera(), w, h)
     for frame in range(2):
-        st = R.render_frame()
-        rgb, rad = R.read_image()
-        ergb, erad = ref.frame(spp, depth)
-        assert np.array_equal(bits(rad), bits(erad)), (which, frame, int((bits(rad) != bits(erad)).sum()))
-        assert np.array_equal(rgb, ergb)
-        assert st.samples == w * h * spp and st.bounce_launches == 1 and st.rays == 0
+        _, rad, st = check_frames(R, ref, spp, depth, frames=1)
+        assert st.rays == 0
     assert rad.max() > 0
 
 
@@ -104,13 +101,7 @@ def test_furnace_frames_match_the_restatement(R, name, walk):
         assert R.traversal() not in (R.STACK, R.CERTIFIED)
     if name == "emitters_4k":
         assert len(ptmi.HostScene.from_arrays(*arrays).emitters()["prim"]) >= 1000
-    ref = NeeRenderer(o, default_camera(), w, h)
-    for frame in range(2):
-        R.render_frame()
-        rgb, rad = R.read_image()
-        ergb, erad = ref.frame(spp, depth)
-        assert np.array_equal(bits(rad), bits(erad)), (name, frame, int((bits(rad) != bits(erad)).sum()))
-        assert np.array_equal(rgb, ergb)
+    _, rad, _ = check_frames(R, NeeRenderer(o, default_camera(), w, h), spp, depth)
     assert rad.max() > 0
 
 
@@ -127,14 +118,7 @@ def test_without_emitters_the_frame_is_the_references(R):
     R.update_resolution(w, h)
     R.set_config(spp=spp, max_depth=depth, sampling_mode=0, integrator=0, fast_tree=False, next_event=True)
     ref = NeeRenderer(o, default_camera(), w, h)
-    frames = []
-    for frame in range(2):
-        R.render_frame()
-        rgb, rad = R.read_image()
-        ergb, erad = ref.frame(spp, depth)
-        assert np.array_equal(bits(rad), bits(erad)), frame
-        assert np.array_equal(rgb, ergb)
-        frames.append((rgb, rad))
+    frames = [check_frames(R, ref, spp, depth, frames=1)[:2] for frame in range(2)]
     orgb, orad, _ = o.render(default_camera(), w, h, spp, max_depth=depth)
     assert np.array_equal(bits(frames[0][1]), bits(orad)) and np.array_equal(frames[0][0], orgb)
     R.update_resolution(w, h)                              # freshly seeded streams: the reference's estimator, two frames

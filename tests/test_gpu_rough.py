@@ -1,6 +1,6 @@
 """Rough metal on the GPU (include/ptmi.h: "rough metal") against the CPU restatement of the header's contract
-(tests/rough_oracle.py), bit for bit, and through every way a context renders: frames, batches, passes, tiles, the denoiser and
-the temporal step.  Scene loading, the sky and the hidden triangle are tests/test_gpu_specular.py's."""
+(tests/path_oracle.py), bit for bit, and through every way a context renders: frames, batches, passes, tiles, the denoiser and
+the temporal step."""
 import ctypes as C
 import os
 import subprocess
@@ -15,10 +15,10 @@ import ptmi
 import ptmi_scenes
 import rough_scenes as RS
 import temporal_oracle as TO
-from oracle_binding import Camera as OCamera, OracleScene, default_camera
-from rough_oracle import RoughRenderer
+from gpu_frames import CBOX, CBOX_QUADS, ROOT, bits, check_frames, hidden_mirror, ocam, small_sky
+from oracle_binding import OracleScene, default_camera
+from path_oracle import RoughRenderer
 from test_gpu_denoise import sigma_x_auto, tone_map
-from test_gpu_specular import CBOX, CBOX_QUADS, ROOT, bits, hidden_mirror, small_sky
 
 pytestmark = pytest.mark.gpu
 
@@ -33,10 +33,6 @@ def R():
     r = ptmi.Renderer(0)
     yield r
     r.close()
-
-
-def ocam(cam):
-    return OCamera(tuple(cam.origin), tuple(cam.lookat), tuple(cam.vup), cam.vfov_deg, cam.yaw_deg, cam.pitch_deg, cam.orbit)
 
 
 def configure(R, depth, next_event, w=W, h=H, spp=SPP, cam=None):
@@ -66,16 +62,8 @@ def arrays_scene(R, arrays, kind, roughness, depth, next_event, w=W, h=H, spp=SP
     return OracleScene.from_arrays(*arrays)
 
 
-def check_frames(R, o, kind, depth, next_event, w=W, h=H, spp=SPP, roughness=0.3, env=None, frames=2, cam=None):
-    ref = RoughRenderer(o, default_camera() if cam is None else ocam(cam), w, h, kind, None, roughness, env, next_event)
-    for frame in range(frames):
-        st = R.render_frame()
-        rgb, rad = R.read_image()
-        ergb, erad = ref.frame(spp, depth)
-        assert np.array_equal(bits(rad), bits(erad)), (frame, int((bits(rad) != bits(erad)).sum()))
-        assert np.array_equal(rgb, ergb)
-        assert st.samples == w * h * spp and st.bounce_launches == 1
-    return rad, ref
+def reference(o, kind, next_event, w=W, h=H, roughness=0.3, env=None, cam=None):
+    return RoughRenderer(o, default_camera() if cam is None else ocam(cam), w, h, kind, None, roughness, env, next_event)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -91,7 +79,7 @@ def test_cornell_rough_block_17x13(R, which, depth, next_event, sky):
     n_block = int((kind == ROUGH).sum())
     assert n_block in (5, 10) and R.surface_counts() == [len(kind) - 2 * n_block, 0, n_block, n_block]
     assert R.surfaces_info() == dict(n_mirror=0, n_glass=n_block)
-    rad, ref = check_frames(R, o, kind, depth, next_event, env=env)
+    _, rad, _ = check_frames(R, reference(o, kind, next_event, env=env), SPP, depth)
     assert rad.max() > 0
 
 
@@ -99,7 +87,7 @@ def test_cornell_rough_block_17x13(R, which, depth, next_event, sky):
 def test_cornell_rough_block_32x32(R, next_event):
     env = small_sky()
     o, kind = cornell(R, "cbox", 8, next_event, 32, 32, env=env)
-    check_frames(R, o, kind, 8, next_event, 32, 32, env=env)
+    check_frames(R, reference(o, kind, next_event, 32, 32, env=env), SPP, 8)
 
 
 def test_the_rough_block_shows_and_is_met(R):
@@ -130,14 +118,14 @@ def test_the_other_walks(R, which, walk, next_event):
     env = small_sky() if which.startswith("soup") else None
     o = arrays_scene(R, arrays, kind, rough, 5, next_event, spp=3, env=env)
     assert R.traversal() == getattr(R, walk) and R.surface_counts()[3] > 0
-    check_frames(R, o, kind, 5, next_event, spp=3, roughness=rough, env=env)
+    check_frames(R, reference(o, kind, next_event, roughness=rough, env=env), 3, 5)
 
 
 @pytest.mark.parametrize("roughness", [0.05, 1.0])
 @pytest.mark.parametrize("next_event", [False, True])
 def test_roughness_at_its_ends(R, roughness, next_event):
     o, kind = cornell(R, "cbox", 5, next_event, roughness=roughness)
-    check_frames(R, o, kind, 5, next_event, roughness=roughness)
+    check_frames(R, reference(o, kind, next_event, roughness=roughness), SPP, 5)
 
 
 def test_per_primitive_roughness(R):
@@ -146,7 +134,7 @@ def test_per_primitive_roughness(R):
     rough = np.linspace(0.05, 1.0, len(kind)).astype(F)
     configure(R, 8, True)
     R.set_surfaces(kind, None, rough)
-    check_frames(R, OracleScene.load(CBOX_QUADS), kind, 8, True, roughness=rough)
+    check_frames(R, reference(OracleScene.load(CBOX_QUADS), kind, True, roughness=rough), SPP, 8)
 
 
 @pytest.mark.parametrize("next_event", [False, True])
@@ -160,7 +148,7 @@ def test_a_rough_emitter(R, next_event):
     assert le.any(1).sum() == 2
     configure(R, 5, next_event)
     R.set_surfaces(kind, None, 0.5)
-    rad, _ = check_frames(R, OracleScene.load(CBOX), kind, 5, next_event, roughness=0.5)
+    _, rad, _ = check_frames(R, reference(OracleScene.load(CBOX), kind, next_event, roughness=0.5), SPP, 5)
     assert rad.max() > 0
 
 
@@ -168,14 +156,14 @@ def test_a_rough_emitter(R, next_event):
 def test_tilted_and_non_unit_stored_normals(R, next_event):
     arrays, kind = RS.rough_furnace(scale_normals=True)
     o = arrays_scene(R, arrays, kind, 0.3, 8, next_event)
-    check_frames(R, o, kind, 8, next_event)
+    check_frames(R, reference(o, kind, next_event), SPP, 8)
 
 
 def test_a_zero_stored_normal_ends_the_path(R):
     """un is NaN: the grazing test fails, the path ends and the frame stays free of NaN"""
     arrays, kind = RS.rough_furnace(zero_normals=3)
     o = arrays_scene(R, arrays, kind, 0.3, 8, True)
-    rad, _ = check_frames(R, o, kind, 8, True)
+    _, rad, _ = check_frames(R, reference(o, kind, True), SPP, 8)
     assert np.isfinite(rad).all()
 
 
@@ -187,7 +175,8 @@ def test_a_camera_skimming_a_rough_quad(R, next_event):
     env = small_sky()
     for roughness in (0.05, 0.6):
         o = arrays_scene(R, scene.arrays(), kind, roughness, 4, next_event, cam=cam, env=env)
-        rad, ref = check_frames(R, o, kind, 4, next_event, roughness=roughness, env=env, cam=cam, frames=1)
+        ref = reference(o, kind, next_event, roughness=roughness, env=env, cam=cam)
+        _, rad, _ = check_frames(R, ref, SPP, 4, frames=1)
         assert np.isfinite(rad).all()
     ref.trace = []
     ref.sums(1, 4)
@@ -413,7 +402,7 @@ def test_a_scene_load_drops_the_table(R):
     R.load_scene(CBOX, 0)
     assert R.surface_counts() == [0, 0, 0, 0] and R.surfaces_info() == dict(n_mirror=0, n_glass=0)
     R.update_resolution(W, H)
-    check_frames(R, o, np.zeros_like(kind), 5, True, frames=1)
+    check_frames(R, reference(o, np.zeros_like(kind), True), SPP, 5, frames=1)
     R.set_config(fast_tree=False, next_event=False)
     R.set_config(sampling_mode=3)                             # and nothing is left that would refuse a guided mode
     R.set_config(sampling_mode=0)

@@ -1,5 +1,5 @@
 """Specular surfaces on the GPU (include/ptmi.h: "specular surfaces") against the CPU restatement of the header's contract
-(tests/specular_oracle.py), bit for bit, and through every way a context renders: frames, batches, passes, tiles, the denoiser and
+(tests/path_oracle.py), bit for bit, and through every way a context renders: frames, batches, passes, tiles, the denoiser and
 the temporal step."""
 import ctypes as C
 import os
@@ -15,8 +15,10 @@ import ptmi
 import ptmi_scenes
 import specular_scenes as SS
 import temporal_oracle as TO
+from gpu_frames import check_frames, hidden_mirror, small_sky
 from oracle_binding import OracleScene, SCENES, default_camera
-from specular_oracle import GLASS, MIRROR, SpecRenderer
+from path_oracle import SpecRenderer
+from specular_oracle import GLASS, MIRROR
 from test_gpu_denoise import sigma_x_auto, tone_map
 
 pytestmark = pytest.mark.gpu
@@ -38,10 +40,6 @@ def R():
     r = ptmi.Renderer(0)
     yield r
     r.close()
-
-
-def small_sky():
-    return ES.random_map(7, 5, 12)
 
 
 def load(R, which):
@@ -81,16 +79,8 @@ def setup(R, which, depth, next_event, w=W, h=H, spp=SPP, ior=None, env=None, su
     return o, kind
 
 
-def check_frames(R, o, kind, depth, next_event, w=W, h=H, spp=SPP, ior=None, env=None, frames=2):
-    ref = SpecRenderer(o, default_camera(), w, h, kind, ior, env, next_event)
-    for frame in range(frames):
-        st = R.render_frame()
-        rgb, rad = R.read_image()
-        ergb, erad = ref.frame(spp, depth)
-        assert np.array_equal(bits(rad), bits(erad)), (frame, int((bits(rad) != bits(erad)).sum()))
-        assert np.array_equal(rgb, ergb)
-        assert st.samples == w * h * spp and st.bounce_launches == 1
-    return rad, ref
+def reference(o, kind, next_event, w=W, h=H, ior=None, env=None):
+    return SpecRenderer(o, default_camera(), w, h, kind, ior, env, next_event)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -104,7 +94,7 @@ def test_cornell_blocks_17x13(R, which, depth, next_event, sky):
     env = small_sky() if sky else None
     o, kind = setup(R, which, depth, next_event, 17, 13, env=env)
     assert R.surfaces_info() == dict(n_mirror=int((kind == 1).sum()), n_glass=int((kind == 2).sum()))
-    rad, ref = check_frames(R, o, kind, depth, next_event, 17, 13, env=env)
+    _, rad, _ = check_frames(R, reference(o, kind, next_event, 17, 13, env=env), SPP, depth)
     assert rad.max() > 0
 
 
@@ -115,7 +105,7 @@ def test_cornell_blocks_17x13(R, which, depth, next_event, sky):
 def test_cornell_blocks_32x32(R, which, depth, next_event, sky):
     env = small_sky() if sky else None
     o, kind = setup(R, which, depth, next_event, 32, 32, env=env)
-    check_frames(R, o, kind, depth, next_event, 32, 32, env=env)
+    check_frames(R, reference(o, kind, next_event, 32, 32, env=env), SPP, depth)
 
 
 def test_the_blocks_show(R):
@@ -139,7 +129,7 @@ def test_the_other_walks(R, which, walk, next_event):
     """(the Cornell box, a scene of the sweep's size, goes through ptmi_render_nee's LANE walk)"""
     o, kind = setup(R, which, 5, next_event, spp=3)
     assert R.traversal() == getattr(R, walk)
-    check_frames(R, o, kind, 5, next_event, spp=3)
+    check_frames(R, reference(o, kind, next_event), 3, 5)
 
 
 @pytest.mark.parametrize("next_event", [False, True])
@@ -152,14 +142,14 @@ def test_a_glass_emitter(R, next_event):
     R.set_camera(ptmi.default_camera()); R.update_resolution(W, H)
     R.set_config(spp=SPP, max_depth=5, sampling_mode=0, integrator=0, fast_tree=False, next_event=next_event)
     R.set_surfaces(kind)
-    rad, _ = check_frames(R, o, kind, 5, next_event)
+    _, rad, _ = check_frames(R, reference(o, kind, next_event), SPP, 5)
     assert rad.max() > 0
 
 
 @pytest.mark.parametrize("ior", [1.0, 8.0])
 def test_ior_at_its_ends(R, ior):
     o, kind = setup(R, "cbox", 8, True, ior=ior)
-    check_frames(R, o, kind, 8, True, ior=ior)
+    check_frames(R, reference(o, kind, True, ior=ior), SPP, 8)
 
 
 def test_per_primitive_ior(R):
@@ -168,7 +158,7 @@ def test_per_primitive_ior(R):
     R.set_camera(ptmi.default_camera()); R.update_resolution(W, H)
     R.set_config(spp=SPP, max_depth=8, sampling_mode=0, integrator=0, fast_tree=False, next_event=False)
     R.set_surfaces(kind, ior)
-    check_frames(R, o, kind, 8, False, ior=ior)
+    check_frames(R, reference(o, kind, False, ior=ior), SPP, 8)
 
 
 @pytest.mark.parametrize("next_event", [False, True])
@@ -184,7 +174,7 @@ def test_a_tilted_stored_normal_on_a_mirror(R, next_event):
     R.set_camera(ptmi.default_camera()); R.update_resolution(W, H)
     R.set_config(spp=SPP, max_depth=8, sampling_mode=0, integrator=0, fast_tree=False, next_event=next_event)
     R.set_surfaces(kind)
-    check_frames(R, OracleScene.from_arrays(*arrays), kind, 8, next_event)
+    check_frames(R, reference(OracleScene.from_arrays(*arrays), kind, next_event), SPP, 8)
 
 
 def test_a_zero_stored_normal_ends_the_path(R):
@@ -197,28 +187,13 @@ def test_a_zero_stored_normal_ends_the_path(R):
     R.set_camera(ptmi.default_camera()); R.update_resolution(W, H)
     R.set_config(spp=SPP, max_depth=8, sampling_mode=0, integrator=0, fast_tree=False, next_event=True)
     R.set_surfaces(kind)
-    rad, _ = check_frames(R, OracleScene.from_arrays(*arrays), kind, 8, True)
+    _, rad, _ = check_frames(R, reference(OracleScene.from_arrays(*arrays), kind, True), SPP, 8)
     assert np.isfinite(rad).all()
 
 
 # ------------------------------------------------------------------------------------------------
 # a specular primitive that no ray can reach: the SPEC kernel against the kernels this change does not touch
 # ------------------------------------------------------------------------------------------------
-def hidden_mirror(which):
-    """the scene's arrays plus one triangle that no ray can reach; (arrays, its index).  The Cornell box is open towards the
-    camera, so "behind the camera" would not do - a path that leaves through the front could find it.  The triangle lies outside
-    the box behind the middle of the back wall: camera rays that pass the box diverge from that region, and a path that has
-    left the box meets nothing that could turn it round."""
-    hs = ptmi.HostScene.load(CBOX if which == "cbox" else CBOX_QUADS, 2 if which == "cbox_sub" else 0)
-    p = hs.prims()
-    tri = np.zeros((1, 4, 3), F)
-    tri[0, :3] = [(-0.5, 2.0, -7.0), (0.5, 2.0, -7.0), (0.0, 3.0, -7.0)]
-    arrays = (np.append(p["type"], 0).astype(np.int32), np.concatenate([p["verts"], tri]),
-              np.concatenate([p["normal"], [[0.0, 0.0, 1.0]]]).astype(F), np.concatenate([p["bsdf"], [[0.9, 0.9, 0.9]]]).astype(F),
-              np.concatenate([p["Le"], [[0.0, 0.0, 0.0]]]).astype(F))
-    return arrays, len(p["type"])
-
-
 @pytest.mark.parametrize("which", ["cbox", "cbox_quads", "cbox_sub"])
 @pytest.mark.parametrize("next_event", [False, True])
 def test_an_unreachable_mirror_changes_no_bit(R, which, next_event):
@@ -287,7 +262,7 @@ def test_a_scene_load_drops_the_table(R):
     assert R.surfaces_info() == dict(n_mirror=0, n_glass=0)
     assert R.environment_info()["width"] == 7                 # the environment belongs to the context and stays
     R.update_resolution(W, H)
-    check_frames(R, o, np.zeros_like(kind), 5, True, env=small_sky(), frames=1)
+    check_frames(R, reference(o, np.zeros_like(kind), True, env=small_sky()), SPP, 5, frames=1)
     R.set_config(fast_tree=False, next_event=False)
     R.set_environment(None)
     R.set_config(sampling_mode=3)                             # and nothing is left that would refuse a guided mode

@@ -1,6 +1,6 @@
 """White-furnace checks of next-event estimation on the CPU (tests/furnace.py; include/ptmi.h, "next-event estimation") - no
 GPU needed.  The oracle's reference estimator proves every furnace closed and the analytic value right; the restatement of the
-NEE contract (tests/nee_oracle.py) must then reach the same value; the emitter table must stay usable at the edges of float."""
+NEE contract (tests/path_oracle.py) must then reach the same value; the emitter table must stay usable at the edges of float."""
 import os
 
 import numpy as np
@@ -8,8 +8,9 @@ import pytest
 
 import furnace as FN
 import ptmi
-from nee_oracle import NeeRenderer, areas, emitter_table
+from nee_oracle import areas, emitter_table
 from oracle_binding import SCENES, OracleScene, default_camera
+from path_oracle import NeeRenderer
 
 
 

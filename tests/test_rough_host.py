@@ -6,10 +6,10 @@ import os
 import numpy as np
 import pytest
 
+import path_oracle as PO
 import ptmi
 import ptmi_scenes
 import rough_oracle as RO
-import specular_oracle as SO
 from oracle_binding import OracleScene, SCENES, default_camera
 
 F = np.float32
@@ -227,7 +227,7 @@ def test_grazing_and_zero_normals_end_the_vertex():
 def test_a_rough_vertex_draws_what_a_diffuse_one_draws(next_event, depth):
     o = OracleScene.load(CBOX)
     kind = ptmi_scenes.cornell_blocks(o.prims(), short=ptmi.SURFACE_GLASS, tall=ptmi.SURFACE_ROUGH)
-    r = RO.RoughRenderer(o, default_camera(), 16, 16, kind, roughness=0.3, next_event=next_event)
+    r = PO.RoughRenderer(o, default_camera(), 16, 16, kind, roughness=0.3, next_event=next_event)
     r.trace = []
     before = r.draws
     r.sums(2, depth)
@@ -242,22 +242,11 @@ def test_a_rough_vertex_draws_what_a_diffuse_one_draws(next_event, depth):
     assert r.draws - before == 2 * r.samples + sum(n for _, _, n in r.trace)
 
 
-@pytest.mark.parametrize("next_event", [False, True])
-def test_without_a_rough_primitive_it_is_the_specular_estimator(next_event):
-    o = OracleScene.load(CBOX)
-    kind = ptmi_scenes.cornell_blocks(o.prims())
-    a = RO.RoughRenderer(o, default_camera(), 8, 8, kind, roughness=0.7, next_event=next_event)
-    b = SO.SpecRenderer(o, default_camera(), 8, 8, kind, next_event=next_event)
-    for _ in range(2):
-        assert np.array_equal(bits(a.sums(2, 8)), bits(b.sums(2, 8)))
-    assert np.array_equal(a.rng, b.rng)
-
-
 def test_the_rough_block_shows_in_the_restatement():
     o = OracleScene.load(CBOX)
     kind = ptmi_scenes.cornell_blocks(o.prims(), short=0, tall=ptmi.SURFACE_ROUGH)
-    a = RO.RoughRenderer(o, default_camera(), 8, 8, kind, next_event=True).sums(2, 5)
-    b = SO.SpecRenderer(o, default_camera(), 8, 8, np.zeros_like(kind), next_event=True).sums(2, 5)
+    a = PO.RoughRenderer(o, default_camera(), 8, 8, kind, next_event=True).sums(2, 5)
+    b = PO.SpecRenderer(o, default_camera(), 8, 8, np.zeros_like(kind), next_event=True).sums(2, 5)
     assert np.isfinite(a).all() and not np.array_equal(bits(a), bits(b))
 
 

@@ -6,12 +6,12 @@ import os
 import numpy as np
 import pytest
 
+import env_scenes as ES
+import path_oracle as PO
 import ptmi
 import ptmi_scenes
 import specular_oracle as SO
 import specular_scenes as SS
-from env_oracle import EnvRenderer
-from nee_oracle import NeeRenderer
 from oracle_binding import OracleScene, SCENES, default_camera
 
 F = np.float32
@@ -140,7 +140,7 @@ def test_a_zero_normal_ends_the_path_without_a_direction():
     for kind in (SO.MIRROR, SO.GLASS):
         nxt, _, _ = SO.scatter(d, np.zeros(3, F), kind, 1.5, F(0.5))
         len2 = float(np.dot(nxt, nxt))
-        assert not (len2 > 0 and len2 <= SO.FLT_MAX)
+        assert not (len2 > 0 and len2 <= PO.FLT_MAX)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -200,18 +200,27 @@ def test_cornell_blocks(path, sub, short, tall):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("next_event", [False, True])
 def test_all_diffuse_table_is_the_estimator_without_one(next_event):
-    o = OracleScene.load(CBOX)
+    """Every constructor's configuration without next-event estimation, map or table is the reference's estimator: the bits of
+    OracleScene.render, which the C oracle computes independently of the path loop.  next_event on, which is all NeeRenderer
+    offers, is that estimator where the scene has no emitter - primitives whose Le sums to 0 are none, yet shine.  (That each
+    constructor gives what its own loop gave before there was one loop: tests/test_restatement_pinned.py, cases "plain".)"""
     cam = default_camera()
-    spec = SO.SpecRenderer(o, cam, 8, 8, np.zeros(o.n_prims, np.int32), next_event=next_event)
-    plain = NeeRenderer(o, cam, 8, 8) if next_event else EnvRenderer(o, cam, 8, 8, None, False)
-    for _ in range(2):
-        a, b = spec.sums(2, 5), plain.sums(2, 5)
-        assert np.array_equal(bits(a), bits(b))
-    assert np.array_equal(spec.rng, plain.rng)
-    if not next_event:                                        # and that is the reference's estimator
-        _, rad, _ = o.render(cam, 8, 8, 2, max_depth=5)
-        ref = SO.SpecRenderer(o, cam, 8, 8, None)
-        assert np.array_equal(bits(ref.frame(2, 5)[1]), bits(rad))
+    if next_event:
+        arrays = ES.soup()
+        arrays[4][0::2] = (2.0, -1.0, -1.0); arrays[4][1::2] = (0.5, 0.5, -1.0)
+        o = OracleScene.from_arrays(*arrays)
+    else:
+        o = OracleScene.load(CBOX)
+    _, rad, _ = o.render(cam, 8, 8, 2, max_depth=5)
+    assert np.abs(rad).max() > 0
+    refs = [PO.EnvRenderer(o, cam, 8, 8, None, next_event), PO.SpecRenderer(o, cam, 8, 8, None, next_event=next_event),
+            PO.SpecRenderer(o, cam, 8, 8, np.zeros(o.n_prims, np.int32), next_event=next_event),
+            PO.RoughRenderer(o, cam, 8, 8, None, next_event=next_event)]
+    if next_event:
+        refs.append(PO.NeeRenderer(o, cam, 8, 8))
+        assert all(len(r.prim) == 0 for r in refs)
+    for ref in refs:
+        assert np.array_equal(bits(ref.frame(2, 5)[1]), bits(rad)), type(ref).__name__
 
 
 @pytest.mark.parametrize("next_event", [False, True])
@@ -220,7 +229,7 @@ def test_draws_per_vertex(next_event, depth):
     """a mirror vertex draws nothing and a glass vertex one number, beyond the roulette's; a diffuse vertex what it draws today"""
     o = OracleScene.load(CBOX)
     kind = ptmi_scenes.cornell_blocks(o.prims())
-    r = SO.SpecRenderer(o, default_camera(), 16, 16, kind, next_event=next_event)
+    r = PO.SpecRenderer(o, default_camera(), 16, 16, kind, next_event=next_event)
     r.trace = []
     before = r.draws
     r.sums(2, depth)
@@ -240,7 +249,7 @@ def test_black_furnace_depth_cuts_few_samples():
     """the condition on tests/test_gpu_specular_expectation.py's black furnace: at its max_depth at most 1e-4 of the samples are
     ended by the depth limit (each would miss the wall's Le: a bias fifty times below that test's floor)"""
     s, kind = SS.black_furnace()
-    r = SO.SpecRenderer(OracleScene.from_arrays(*s.arrays()), default_camera(), 16, 16, kind)
+    r = PO.SpecRenderer(OracleScene.from_arrays(*s.arrays()), default_camera(), 16, 16, kind)
     r.trace = []
     sums = r.sums(64, SS.BLACK_FURNACE_DEPTH)
     print(f"cut off by max_depth {SS.BLACK_FURNACE_DEPTH}: {r.cut} of {r.samples} samples")
