@@ -1035,6 +1035,46 @@ int ptmi_denoise_timing(const ptmi_ctx* c, double* features_ms, double* denoise_
     });
 }
 
+// ---- the variance-guided filter ----
+static VarianceParams variance_params_from(const ptmi_variance_params& p) {
+    VarianceParams v;
+    v.iterations = p.iterations; v.sigma_luminance = p.sigma_luminance; v.epsilon = p.epsilon; v.sigma_position = p.sigma_position;
+    v.normal_squarings = p.normal_squarings; v.feature_grid = p.feature_grid; v.demodulate = p.demodulate;
+    v.source = p.source; v.spatial_radius = p.spatial_radius;
+    return v;
+}
+void ptmi_default_variance_params(ptmi_variance_params* p) {
+    if (!p) return;
+    const VarianceParams v;
+    p->iterations = v.iterations; p->sigma_luminance = v.sigma_luminance; p->epsilon = v.epsilon; p->sigma_position = v.sigma_position;
+    p->normal_squarings = v.normal_squarings; p->feature_grid = v.feature_grid; p->demodulate = v.demodulate;
+    p->source = v.source; p->spatial_radius = v.spatial_radius;
+}
+int ptmi_check_variance_params(const ptmi_variance_params* p) {
+    return guarded([&] { need(p != nullptr, "params is NULL"); checkVarianceParams(variance_params_from(*p)); });
+}
+int ptmi_denoise_variance(ptmi_ctx* c, const ptmi_variance_params* params) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        ptmi_variance_params p;
+        ptmi_default_variance_params(&p);
+        denoiseVariance(c->app, variance_params_from(params ? *params : p));
+    });
+}
+int ptmi_read_variance(const ptmi_ctx* c, float* variance_in, float* variance_out) {
+    return guarded([&] { need(c != nullptr, "ctx is NULL"); readVariance(c->app, variance_in, variance_out); });
+}
+int ptmi_variance_timing(const ptmi_ctx* c, double* estimate_ms, double* filter_ms) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        if (estimate_ms) *estimate_ms = c->app.render.dn.estimate_ms;
+        if (filter_ms) *filter_ms = c->app.render.dn.filter_ms;
+    });
+}
+int ptmi_read_pass_moments(const ptmi_ctx* c, float* mean, float* m2, uint32_t* passes) {
+    return guarded([&] { need(c != nullptr, "ctx is NULL"); readPassMoments(c->app, mean, m2, passes); });
+}
+
 // ---- temporal accumulation with reprojection ----
 static TemporalParams temporal_params_from(const ptmi_temporal_params& p) {
     TemporalParams t;

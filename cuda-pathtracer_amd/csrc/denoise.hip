@@ -8,11 +8,9 @@
 //   ptmi_denoise_atrous  one iteration: 5 x 5 B3-spline taps of stride 2^i, weighted by colour, normal and position
 //   ptmi_denoise_remod   x albedo again, then the frame's tone map (resolve_pixel at k = 1) -> rgb8 + float radiance
 // One thread per pixel in every kernel and nothing shared between threads: a result does not depend on the launch geometry.
-#include "pt_device.h"
+#include "denoise_common.h"
 
 namespace ptmi {
-
-__device__ __forceinline__ float denoise_lum(float x, float y, float z) { return 0.2126f * x + 0.7152f * y + 0.0722f * z; }
 
 __global__ __launch_bounds__(kBlock) void ptmi_denoise_demod(int n, const float* __restrict__ radiance, const float4* __restrict__ albedo,
                                                              int demodulate, float4* __restrict__ out) {
@@ -27,12 +25,6 @@ __global__ __launch_bounds__(kBlock) void ptmi_denoise_demod(int n, const float*
     }
     out[p] = make_float4(c[0], c[1], c[2], denoise_lum(c[0], c[1], c[2]));
 }
-
-// B3-spline taps {1/16, 1/4, 3/8, 1/4, 1/16} (exact in float)
-__device__ __forceinline__ float b3(int k) { return k == 0 || k == 4 ? 0.0625f : (k == 2 ? 0.375f : 0.25f); }
-
-// 16 x 16 pixels per workgroup: the taps of neighbouring lanes hit the same lines
-constexpr int kTileX = 16, kTileY = 16;
 
 __global__ __launch_bounds__(kTileX * kTileY) void ptmi_denoise_atrous(DenoiseArgs a, FeatureBuffers fb, int stride, float sigma_c,
                                                                        const float4* __restrict__ in, float4* __restrict__ out) {

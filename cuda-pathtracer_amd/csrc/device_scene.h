@@ -231,6 +231,28 @@ struct DenoiseArgs {
 void launch_denoise(const DenoiseArgs& a, const FeatureBuffers& fb, const float* radiance, int iterations, const float* sigma_c,
                     float4* buf, unsigned char* out_rgb8, float* out_radiance, hipStream_t s);
 
+// The variance-guided filter's constants for one run (csrc/denoise_variance.hip; the contract: include/ptmi.h, ptmi_denoise_variance)
+struct VarianceArgs {
+    int width, height;               // the whole frame (a single rank)
+    int demodulate;
+    int normal_squarings;
+    float sigma_x2;                  // sigma_x * sigma_x (> 0)
+    float sigma_l2;                  // sigma_luminance * sigma_luminance
+    float epsilon;
+    int radius;                      // of the spatial estimate's window, 1 .. 3
+    unsigned int two_spp;            // 2 * config.spp: a pass image's pixel with this many samples has two pass means
+};
+// The variance estimate (moments != nullptr: the accumulation's statistics where a pixel has two passes or more - counts: its
+// samples per pixel, local row-major - and the spatial estimate elsewhere; nullptr: spatial everywhere) -> var_in, then
+// iterations passes of the variance-guided a-trous filter over radiance guided by fb; the filtered radiance -> out_radiance, its
+// tone map -> out_rgb8, the filtered variance -> var_out.  buf: 2 x width x height float4 of scratch.  `estimated` is recorded
+// between the estimate and the filter.
+void launch_denoise_variance(const VarianceArgs& a, const FeatureBuffers& fb, const float* radiance, const TileMap& tm,
+                             const AccumBuffers* moments, const unsigned int* counts, int iterations, float4* buf, float* var_in,
+                             float* var_out, unsigned char* out_rgb8, float* out_radiance, hipEvent_t estimated, hipStream_t s);
+// the stopping test's state by slot -> local row-major arrays of n_local each
+void launch_pass_moments(const TileMap& tm, const AccumBuffers& ab, float* mean, float* m2, unsigned int* passes, hipStream_t s);
+
 // ---- temporal accumulation with reprojection (include/ptmi.h: ptmi_temporal_accumulate) ------------------------------------
 // The step's constants (csrc/temporal.hip; the contract is written out in include/ptmi.h)
 struct TemporalArgs {

@@ -269,6 +269,11 @@ struct RenderState {
         float4* d_buf = nullptr;                     // 2 x n_local: the filter's ping-pong buffers
         bool denoised = false;                       // d_rgb8 / d_radiance hold a result
         double features_ms = 0.0, denoise_ms = 0.0;  // device time of the last feature pass / filter run
+        // the variance-guided filter (denoiseVariance): its result goes to d_rgb8 / d_radiance, its scratch is d_buf
+        float* d_var_in = nullptr;                   // the variance that steered the last run, local row-major
+        float* d_var_out = nullptr;                  // that variance after the last iteration
+        bool variance_valid = false;                 // they hold a run's values; stale under the rules of features_valid
+        double estimate_ms = 0.0, filter_ms = 0.0;   // device time of the last variance estimate / variance-guided filter
     } dn;
     // The temporal accumulation's history (temporalAccumulate) and outputs; allocated at first use, freed with the other
     // buffers.  Nothing here is read by a frame, a pass or ptmi_denoise.
@@ -402,6 +407,21 @@ void readFeatures(const ApplicationState& g_state, float* albedo, float* normal,
 void checkDenoiseParams(const DenoiseParams& p);     // throws ArgError for a parameter out of range
 void denoise(ApplicationState& g_state, const DenoiseParams& p);
 void readDenoised(const ApplicationState& g_state, unsigned char* rgb8, float* radiance);
+
+// The variance-guided a-trous filter (include/ptmi.h: ptmi_denoise_variance): ptmi_denoise's inputs and outputs, steered by a
+// per-pixel variance - the accumulation's statistics where they exist, a spatial estimate elsewhere.
+struct VarianceParams {
+    int iterations = 5;
+    float sigma_luminance = 2.0f, epsilon = 1e-2f;   // measured: cbox 128^2, a frame of 8 spp and an adaptive run
+    float sigma_position = 0.0f;                     // <= 0: 2 % of the scene's bounding-box diagonal
+    int normal_squarings = 7, feature_grid = 2, demodulate = 1;
+    int source = 0;                                  // 0: the accumulation's statistics where they exist; 1: always spatial
+    int spatial_radius = 3;
+};
+void checkVarianceParams(const VarianceParams& p);   // throws ArgError for a parameter out of range
+void denoiseVariance(ApplicationState& g_state, const VarianceParams& p);
+void readVariance(const ApplicationState& g_state, float* variance_in, float* variance_out);
+void readPassMoments(const ApplicationState& g_state, float* mean, float* m2, uint32_t* passes);
 
 // Temporal accumulation with reprojection (include/ptmi.h: ptmi_temporal_accumulate).
 struct TemporalParams {

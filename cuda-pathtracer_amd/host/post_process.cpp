@@ -12,6 +12,7 @@ namespace ptmi {
 // ------------------------------------------------------------------------------------------------
 void featuresStale(ApplicationState& g) {
     g.render.dn.features_valid = false;
+    g.render.dn.variance_valid = false;
     g.render.dn.image_current = false;                 // the image shows the scene / view / config as it was before the change
 }
 
@@ -61,15 +62,32 @@ void readFeatures(const ApplicationState& g, float* albedo, float* normal, float
     }
 }
 
+// the parameters the two a-trous filters share
+static void checkIterations(int iterations) {
+    if (iterations < 0 || iterations > 10) throw ArgError("denoise: iterations must be in [0, 10]");
+}
+static void checkGuideParams(float sigma_position, int normal_squarings, int feature_grid, int demodulate) {
+    if (!(sigma_position <= 0.0f || (sigma_position >= 1e-6f && sigma_position <= 1e12f)))
+        throw ArgError("denoise: sigma_position must be <= 0 (automatic) or in [1e-6, 1e12]");
+    if (normal_squarings < 0 || normal_squarings > 10) throw ArgError("denoise: normal_squarings must be in [0, 10]");
+    if (feature_grid < 1 || feature_grid > 4) throw ArgError("denoise: feature_grid must be in [1, 4]");
+    if (demodulate != 0 && demodulate != 1) throw ArgError("denoise: demodulate must be 0 or 1");
+}
+
 void checkDenoiseParams(const DenoiseParams& p) {
-    if (p.iterations < 0 || p.iterations > 10) throw ArgError("denoise: iterations must be in [0, 10]");
+    checkIterations(p.iterations);
     if (!(p.sigma_color >= 1e-4f && p.sigma_color <= 1e4f)) throw ArgError("denoise: sigma_color must be in [1e-4, 1e4]");
     if (!(p.color_floor >= 1e-6f && p.color_floor <= 1e4f)) throw ArgError("denoise: color_floor must be in [1e-6, 1e4]");
-    if (!(p.sigma_position <= 0.0f || (p.sigma_position >= 1e-6f && p.sigma_position <= 1e12f)))
-        throw ArgError("denoise: sigma_position must be <= 0 (automatic) or in [1e-6, 1e12]");
-    if (p.normal_squarings < 0 || p.normal_squarings > 10) throw ArgError("denoise: normal_squarings must be in [0, 10]");
-    if (p.feature_grid < 1 || p.feature_grid > 4) throw ArgError("denoise: feature_grid must be in [1, 4]");
-    if (p.demodulate != 0 && p.demodulate != 1) throw ArgError("denoise: demodulate must be 0 or 1");
+    checkGuideParams(p.sigma_position, p.normal_squarings, p.feature_grid, p.demodulate);
+}
+
+void checkVarianceParams(const VarianceParams& p) {
+    checkIterations(p.iterations);
+    if (!(p.sigma_luminance >= 1e-4f && p.sigma_luminance <= 1e4f)) throw ArgError("denoise: sigma_luminance must be in [1e-4, 1e4]");
+    if (!(p.epsilon >= 1e-12f && p.epsilon <= 1e4f)) throw ArgError("denoise: epsilon must be in [1e-12, 1e4]");
+    checkGuideParams(p.sigma_position, p.normal_squarings, p.feature_grid, p.demodulate);
+    if (p.source != 0 && p.source != 1) throw ArgError("denoise: source must be 0 (automatic) or 1 (spatial)");
+    if (p.spatial_radius < 1 || p.spatial_radius > 3) throw ArgError("denoise: spatial_radius must be in [1, 3]");
 }
 
 // sigma_x of the denoiser and of the temporal step for sigma_position <= 0: fraction x the diagonal of the root box of the
@@ -95,24 +113,31 @@ static DenoiseArgs denoiseArgs(const ApplicationState& g, const DenoiseParams& p
     return a;
 }
 
+// the outputs and scratch of the two filters, allocated together at the first run of either
+static void allocateDenoiseOutputs(RenderState& r) {
+    RenderState::Denoise& d = r.dn;
+    if (d.d_rgb8) return;
+    const size_t n = std::max<size_t>(r.n_local, 1);
+    try {
+        d.d_radiance = (float*)hipMallocSafe(n * 3 * sizeof(float), "denoise.radiance");
+        d.d_buf = (float4*)hipMallocSafe(2 * n * sizeof(float4), "denoise.buf");
+        d.d_var_in = (float*)hipMallocSafe(n * sizeof(float), "denoise.variance_in");
+        d.d_var_out = (float*)hipMallocSafe(n * sizeof(float), "denoise.variance_out");
+        d.d_rgb8 = (unsigned char*)hipMallocSafe(n * 3, "denoise.rgb8");                   // last: set means complete
+    } catch (...) {
+        for (void* q : {(void*)d.d_radiance, (void*)d.d_buf, (void*)d.d_var_in, (void*)d.d_var_out}) if (q) (void)hipFree(q);
+        d.d_radiance = nullptr; d.d_buf = nullptr; d.d_var_in = nullptr; d.d_var_out = nullptr;
+        throw;
+    }
+}
+
 // the filter over radiance guided by fb into the denoiser's outputs (what ptmi_read_denoised returns)
 static void denoiseRun(ApplicationState& g, const DenoiseArgs& a, int iterations, const float* sigma_c, const FeatureBuffers& fb,
                        const float* radiance) {
     RenderState& r = g.render;
     RenderState::Denoise& d = r.dn;
     PTMI_HIP(hipSetDevice(g.device_id));
-    const size_t n = std::max<size_t>(r.n_local, 1);
-    if (!d.d_rgb8) {
-        try {
-            d.d_rgb8 = (unsigned char*)hipMallocSafe(n * 3, "denoise.rgb8");
-            d.d_radiance = (float*)hipMallocSafe(n * 3 * sizeof(float), "denoise.radiance");
-            d.d_buf = (float4*)hipMallocSafe(2 * n * sizeof(float4), "denoise.buf");
-        } catch (...) {
-            for (void* q : {(void*)d.d_rgb8, (void*)d.d_radiance, (void*)d.d_buf}) if (q) (void)hipFree(q);
-            d.d_rgb8 = nullptr; d.d_radiance = nullptr; d.d_buf = nullptr;
-            throw;
-        }
-    }
+    allocateDenoiseOutputs(r);
     while (g.event_pool.size() < 2) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
     d.denoised = false;
     if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));
@@ -125,13 +150,19 @@ static void denoiseRun(ApplicationState& g, const DenoiseArgs& a, int iterations
     d.denoised = true;
 }
 
+// what both filters ask of the context before they look at their parameters
+static void checkFilterable(const ApplicationState& g) {
+    const RenderState& r = g.render;
+    if (r.tile.n_ranks > 1) throw ArgError("denoise: the context is tiled over more than one rank (the filter needs rows of other ranks)");
+    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError("denoise: the Radiosity integrator's image is not denoised");
+    if (!g.scene.d_nodes || !r.d_state.A || !r.dn.image_current)
+        throw ArgError("denoise: no image rendered yet (none since the last change of scene, camera, resolution or config)");
+}
+
 void denoise(ApplicationState& g, const DenoiseParams& p) {
     RenderState& r = g.render;
     RenderState::Denoise& d = r.dn;
-    if (r.tile.n_ranks > 1) throw ArgError("denoise: the context is tiled over more than one rank (the filter needs rows of other ranks)");
-    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError("denoise: the Radiosity integrator's image is not denoised");
-    if (!g.scene.d_nodes || !r.d_state.A || !d.image_current)
-        throw ArgError("denoise: no image rendered yet (none since the last change of scene, camera, resolution or config)");
+    checkFilterable(g);
     float sigma_c[10];
     const DenoiseArgs a = denoiseArgs(g, p, sigma_c);
     if (!d.features_valid || d.grid != p.feature_grid) renderFeatures(g, p.feature_grid);
@@ -144,6 +175,70 @@ void readDenoised(const ApplicationState& g, unsigned char* rgb8, float* radianc
     PTMI_HIP(hipSetDevice(g.device_id));
     if (rgb8 && r.n_local) PTMI_HIP(hipMemcpy(rgb8, r.dn.d_rgb8, r.n_local * 3, hipMemcpyDeviceToHost));
     if (radiance && r.n_local) PTMI_HIP(hipMemcpy(radiance, r.dn.d_radiance, r.n_local * 3 * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+// ------------------------------------------------------------------------------------------------
+// the variance-guided filter (include/ptmi.h: ptmi_denoise_variance)
+// ------------------------------------------------------------------------------------------------
+void denoiseVariance(ApplicationState& g, const VarianceParams& p) {
+    RenderState& r = g.render;
+    RenderState::Denoise& d = r.dn;
+    checkFilterable(g);
+    checkVarianceParams(p);
+    VarianceArgs a;
+    a.width = r.tile.width; a.height = r.tile.local_rows;
+    a.demodulate = p.demodulate; a.normal_squarings = p.normal_squarings;
+    const float sigma_x = p.sigma_position > 0.0f ? p.sigma_position : autoSigmaPosition(g, 0.02f, "denoise");   // 2 %, as ptmi_denoise
+    a.sigma_x2 = sigma_x * sigma_x;
+    a.sigma_l2 = p.sigma_luminance * p.sigma_luminance;
+    a.epsilon = p.epsilon;
+    a.radius = p.spatial_radius;
+    a.two_spp = 2u * (unsigned int)g.config.spp;
+    if (!d.features_valid || d.grid != p.feature_grid) renderFeatures(g, p.feature_grid);
+    // the stopping test's moments describe the image only while it is a pass of the current accumulation
+    const bool moments = p.source == 0 && d.image_pass && r.accum.pass > 0 && r.accum.allocated();
+    PTMI_HIP(hipSetDevice(g.device_id));
+    allocateDenoiseOutputs(r);
+    while (g.event_pool.size() < 3) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
+    d.denoised = false;
+    d.variance_valid = false;
+    if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));
+    PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
+    launch_denoise_variance(a, d.fb, r.d_radiance, r.tile, moments ? &r.accum.ab : nullptr, r.accum.d_counts, p.iterations, d.d_buf,
+                            d.d_var_in, d.d_var_out, d.d_rgb8, d.d_radiance, g.event_pool[2], r.stream);
+    PTMI_HIP(hipGetLastError());
+    PTMI_HIP(hipEventRecord(g.event_pool[1], r.stream));
+    PTMI_HIP(hipStreamSynchronize(r.stream));
+    d.estimate_ms = elapsedMs(g.event_pool[0], g.event_pool[2]);
+    d.filter_ms = elapsedMs(g.event_pool[2], g.event_pool[1]);
+    d.denoised = true;
+    d.variance_valid = true;
+}
+
+void readVariance(const ApplicationState& g, float* variance_in, float* variance_out) {
+    const RenderState& r = g.render;
+    if (!r.dn.variance_valid) throw ArgError("readVariance: no current variance (ptmi_denoise_variance first)");
+    PTMI_HIP(hipSetDevice(g.device_id));
+    if (variance_in && r.n_local) PTMI_HIP(hipMemcpy(variance_in, r.dn.d_var_in, r.n_local * sizeof(float), hipMemcpyDeviceToHost));
+    if (variance_out && r.n_local) PTMI_HIP(hipMemcpy(variance_out, r.dn.d_var_out, r.n_local * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+void readPassMoments(const ApplicationState& g, float* mean, float* m2, uint32_t* passes) {
+    const RenderState& r = g.render;
+    if (!r.d_state.A || r.accum.pass == 0 || !r.accum.allocated()) throw ArgError("readPassMoments: the accumulation has no pass yet (ptmi_accum_pass first)");
+    if (!r.n_local) return;
+    PTMI_HIP(hipSetDevice(g.device_id));
+    const size_t n = r.n_local;
+    float* d_tmp = (float*)hipMallocSafe(3 * n * sizeof(float), "pass_moments");
+    try {
+        launch_pass_moments(r.tile, r.accum.ab, d_tmp, d_tmp + n, (unsigned int*)(d_tmp + 2 * n), r.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(r.stream));
+        if (mean) PTMI_HIP(hipMemcpy(mean, d_tmp, n * sizeof(float), hipMemcpyDeviceToHost));
+        if (m2) PTMI_HIP(hipMemcpy(m2, d_tmp + n, n * sizeof(float), hipMemcpyDeviceToHost));
+        if (passes) PTMI_HIP(hipMemcpy(passes, d_tmp + 2 * n, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    } catch (...) { (void)hipFree(d_tmp); throw; }
+    (void)hipFree(d_tmp);
 }
 
 // ------------------------------------------------------------------------------------------------

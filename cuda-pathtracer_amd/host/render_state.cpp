@@ -144,7 +144,7 @@ void RenderState::freeAccum() {
 }
 
 void RenderState::freeDenoise() {
-    void* ptrs[] = {dn.fb.albedo, dn.fb.normal, dn.fb.position, dn.d_rgb8, dn.d_radiance, dn.d_buf};
+    void* ptrs[] = {dn.fb.albedo, dn.fb.normal, dn.fb.position, dn.d_rgb8, dn.d_radiance, dn.d_buf, dn.d_var_in, dn.d_var_out};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     dn = Denoise();
 }

@@ -33,6 +33,8 @@ EXPORTS = [
     "ptmi_default_adaptive_params", "ptmi_accum_reset", "ptmi_accum_pass", "ptmi_read_sample_counts",
     "ptmi_default_denoise_params", "ptmi_check_denoise_params", "ptmi_render_features", "ptmi_read_features", "ptmi_denoise",
     "ptmi_read_denoised", "ptmi_denoise_timing",
+    "ptmi_default_variance_params", "ptmi_check_variance_params", "ptmi_denoise_variance", "ptmi_read_variance",
+    "ptmi_variance_timing", "ptmi_read_pass_moments",
     "ptmi_default_temporal_params", "ptmi_check_temporal_params", "ptmi_temporal_reset", "ptmi_temporal_accumulate",
     "ptmi_read_temporal", "ptmi_read_history_counts", "ptmi_denoise_temporal",
     "ptmi_host_emitters",
@@ -90,6 +92,12 @@ class PassStats(C.Structure):
 class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("color_floor", C.c_float), ("sigma_position", C.c_float),
                 ("normal_squarings", C.c_int), ("feature_grid", C.c_int), ("demodulate", C.c_int)]
+
+
+class VarianceParams(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("sigma_luminance", C.c_float), ("epsilon", C.c_float), ("sigma_position", C.c_float),
+                ("normal_squarings", C.c_int), ("feature_grid", C.c_int), ("demodulate", C.c_int), ("source", C.c_int),
+                ("spatial_radius", C.c_int)]
 
 
 class TemporalParams(C.Structure):
@@ -209,6 +217,12 @@ def lib():
         L.ptmi_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
         L.ptmi_read_denoised.argtypes = [vp, vp, vp]
         L.ptmi_denoise_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.ptmi_default_variance_params.argtypes = [C.POINTER(VarianceParams)]; L.ptmi_default_variance_params.restype = None
+        L.ptmi_check_variance_params.argtypes = [C.POINTER(VarianceParams)]
+        L.ptmi_denoise_variance.argtypes = [vp, C.POINTER(VarianceParams)]
+        L.ptmi_read_variance.argtypes = [vp, vp, vp]
+        L.ptmi_variance_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.ptmi_read_pass_moments.argtypes = [vp, vp, vp, vp]
         L.ptmi_default_temporal_params.argtypes = [C.POINTER(TemporalParams)]; L.ptmi_default_temporal_params.restype = None
         L.ptmi_check_temporal_params.argtypes = [C.POINTER(TemporalParams)]
         L.ptmi_temporal_reset.argtypes = [vp]
@@ -362,6 +376,17 @@ def default_denoise_params(**params):
     for k, v in params.items():
         if k not in dict(DenoiseParams._fields_):
             raise TypeError(f"unknown denoise parameter {k}")
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def default_variance_params(**params):
+    """ptmi_default_variance_params, with any field overridden by keyword (iterations, sigma_luminance, epsilon, sigma_position,
+    normal_squarings, feature_grid, demodulate, source, spatial_radius)."""
+    p = VarianceParams(); lib().ptmi_default_variance_params(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(VarianceParams._fields_):
+            raise TypeError(f"unknown variance parameter {k}")
         setattr(p, k, type(getattr(p, k))(v))
     return p
 
@@ -709,6 +734,36 @@ class Renderer:
         a = C.c_double(); b = C.c_double()
         self._ck(self.L.ptmi_denoise_timing(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # --- the variance-guided filter (include/ptmi.h: ptmi_denoise_variance) ---
+    def denoise_variance(self, **params):
+        """The variance-guided a-trous filter over the image read_image returns (keyword parameters: fields of VarianceParams
+        over the defaults); returns (rgb8, radiance) like denoise."""
+        p = default_variance_params(**params)
+        self._ck(self.L.ptmi_denoise_variance(self.h, C.byref(p)))
+        return self.read_denoised()
+
+    def variance(self):
+        """(variance_in, variance_out) of the last denoise_variance, (local rows, width) float32 each."""
+        n = len(self.local_rows())
+        vin = np.zeros((n, self.width), np.float32); vout = np.zeros((n, self.width), np.float32)
+        self._ck(self.L.ptmi_read_variance(self.h, vin.ctypes.data, vout.ctypes.data))
+        return vin, vout
+
+    def variance_timing(self):
+        """(ms of the last variance estimate, ms of the last variance-guided filter run), device time"""
+        a = C.c_double(); b = C.c_double()
+        self._ck(self.L.ptmi_variance_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def pass_moments(self):
+        """The stopping test's state of the current accumulation: (mean, M2, passes), (local rows, width) float32, float32,
+        uint32."""
+        n = len(self.local_rows())
+        mean = np.zeros((n, self.width), np.float32); m2 = np.zeros((n, self.width), np.float32)
+        passes = np.zeros((n, self.width), np.uint32)
+        self._ck(self.L.ptmi_read_pass_moments(self.h, mean.ctypes.data, m2.ctypes.data, passes.ctypes.data))
+        return mean, m2, passes
 
     # --- temporal accumulation with reprojection (include/ptmi.h: ptmi_temporal_accumulate) ---
     def temporal_accumulate(self, **params):

@@ -559,6 +559,74 @@ int  ptmi_read_denoised(const ptmi_ctx*, unsigned char* rgb8, float* radiance);
 /* device time (hipEvents) of the last feature pass and of the last filter run (feature pass excluded), in ms */
 int  ptmi_denoise_timing(const ptmi_ctx*, double* features_ms, double* denoise_ms);
 
+/* ---- variance-guided a-trous filter (new in this implementation) ----------------------------------------------------------
+ * ptmi_denoise_variance is the spatial stage of SVGF (Schied et al. 2017): ptmi_denoise's a-trous filter with the colour
+ * edge-stop replaced by a luminance edge-stop whose tolerance is the pixel's own standard deviation, and with that variance
+ * carried through the iterations.  A converged pixel is left nearly alone, a noisy one is blurred.  Inputs, validity rules and
+ * outputs are ptmi_denoise's: it filters the radiance ptmi_read_image would return into the denoiser's output buffers
+ * (ptmi_read_denoised), recomputes stale features, and leaves frames, sums, streams, the accumulation and the temporal history
+ * untouched; a ptmi_denoise after it gives what it gives alone.  The variance it was steered by and the variance left after the
+ * last iteration are kept (ptmi_read_variance) until the next call that makes features stale.
+ *
+ * THE FILTER, float32 in the order written (-ffp-contract=off, correctly rounded division); lum, H, wn, wx and sigma_x are
+ * ptmi_denoise's; taps outside the image are skipped:
+ *   1. c = radiance, demodulated as in ptmi_denoise step 1;  l_p = lum(c_p).
+ *   2. VARIANCE FROM THE ACCUMULATION, with source = 0, where the image is a pass of the current accumulation and the pixel has
+ *      taken k >= 2 passes (M2: the stopping rule's, ptmi_read_pass_moments):
+ *         v  = max(0, M2 / (float)(k * (k - 1)))         (k * (k - 1): uint32, as in the stopping rule) - the variance of the
+ *                                                        mean of the pixel's pass means, in radiance units;
+ *         lr = lum(radiance_p);  if lr > 0:  s = l_p / lr;  v = (v * s) * s        (into the filtered signal's units)
+ *      (the max: Welford's M2 can round to a negative of a few ulps for a pixel whose pass means are all equal; a negative
+ *      variance would make the tolerance of step 4 negative.)
+ *   3. SPATIAL VARIANCE, for every other pixel (a frame, a selected frame, a pixel with one pass, source = 1): over the window
+ *      q = p + (di, dj), dj = -r..r (outer), di = -r..r (inner), r = spatial_radius, p itself included, with w = wn * wx:
+ *         W = sum w;   m = (sum w * l_q) / W;   v = (sum w * ((l_q - m) * (l_q - m))) / W         (sums from +0, in tap order)
+ *      two sweeps over the window, the second with the first's m.  W > 0 does not hold (every feature ray of p missed): v = 0.
+ *      The one-sweep form E[l^2] - E[l]^2 is not used: at l = 1e3 with a spread of 1e-2 both of its terms are 1e6, where a
+ *      float's ulp is 0.06, and their difference, the variance 1e-4, is lost entirely.  The two-sweep form loses only what
+ *      the mean's own rounding costs: with n taps and u = 2^-24 a relative error of at most (n u l / spread)^2 + (n + 2) u,
+ *      about 0.1 there for the 7 x 7 window (measured: 1e-4) and ~1e-5 where l is of the spread's size.
+ *   4. for iteration it = 0 .. iterations-1, stride s = 2^it, on (c.xyz, v) per pixel, every pixel reading the previous
+ *      iteration's values:
+ *         gv = (sum G[dj+1] * G[di+1] * v_q) / (sum G[dj+1] * G[di+1])     over the 3 x 3 window q = p + (di, dj) at stride 1
+ *                                                        (whatever s is), dj outer, di inner, G = {1/4, 1/2, 1/4}; both sums
+ *                                                        (num = num + g * v_q, den = den + g, from +0) over the taps inside the image
+ *         a  = (sigma_luminance * sigma_luminance) * gv + epsilon
+ *      over ptmi_denoise's 5 x 5 taps q = p + (di * s, dj * s), in its order:
+ *         dl = lum(c_p) - lum(c_q);   wl = 1 / (1 + (dl * dl) / a);   w = (((h * wl) * wn) * wx)
+ *         W = W + w;   S.ch = S.ch + w * c_q.ch;   V = V + (w * w) * v_q
+ *      if W > 0:  c'_p = S / W per channel,  v'_p = (V / W) / W;  else both are kept.  (Two divisions, not V / (W * W): for a
+ *      pixel whose taps all but vanish - wn is a 128th power - W * W underflows to 0 while W > 0, and V / 0 is inf or NaN.)
+ *      sigma_luminance does not shrink with the iteration: the variance does, and takes the tolerance with it.  The rational
+ *      kernel stands in for SVGF's exp, as wc and wx do in ptmi_denoise.
+ *   5. remodulation and tone map as ptmi_denoise steps 3 - 4.  variance_in = the v of steps 2 - 3, variance_out = v after the
+ *      last iteration, both in the filtered signal's units (radiance / albedo with demodulate).
+ * With iterations = 0 the output is the input, as ptmi_denoise's; variance_in is computed all the same and variance_out equals it.
+ * PTMI_E_INVALID: ptmi_denoise's conditions with ptmi_denoise's messages; ptmi_read_variance without a current result;
+ * ptmi_read_pass_moments before the accumulation's first pass.
+ * ptmi_read_pass_moments returns the stopping rule's mean, M2 and k per local pixel (pixels that have stopped keep theirs). */
+typedef struct {
+    int   iterations;        /* 5; 0 .. 10 */
+    float sigma_luminance;   /* 2.0; luminance tolerance in standard deviations, 1e-4 .. 1e4 */
+    float epsilon;           /* 0.01; added to the luminance tolerance's square (a floor of 0.1 in luminance), 1e-12 .. 1e4 */
+    float sigma_position;    /* as ptmi_denoise_params */
+    int   normal_squarings;  /* as ptmi_denoise_params */
+    int   feature_grid;      /* as ptmi_denoise_params */
+    int   demodulate;        /* as ptmi_denoise_params */
+    int   source;            /* 0 auto: the accumulation's statistics where they exist, else spatial; 1: always spatial */
+    int   spatial_radius;    /* 3 (a 7 x 7 window); 1 .. 3 */
+} ptmi_variance_params;
+void ptmi_default_variance_params(ptmi_variance_params*);
+/* the parameter check of ptmi_denoise_variance alone (no context, no device): 0 or PTMI_E_INVALID with the message */
+int  ptmi_check_variance_params(const ptmi_variance_params*);
+int  ptmi_denoise_variance(ptmi_ctx*, const ptmi_variance_params* /* NULL: defaults */);
+/* the last ptmi_denoise_variance's variances, one float per pixel, local row-major like ptmi_read_image; either may be NULL */
+int  ptmi_read_variance(const ptmi_ctx*, float* variance_in, float* variance_out);
+/* device time (hipEvents) of the last run's variance estimate (steps 1 - 3) and of its filter (steps 4 - 5), in ms */
+int  ptmi_variance_timing(const ptmi_ctx*, double* estimate_ms, double* filter_ms);
+/* the stopping test's state of the current accumulation, local row-major; any pointer may be NULL */
+int  ptmi_read_pass_moments(const ptmi_ctx*, float* mean, float* m2, uint32_t* passes);
+
 /* ---- temporal accumulation with reprojection (new in this implementation) ------------------------------------------------
  * ptmi_temporal_accumulate blends the current image into a per-pixel HISTORY carried across views: the history of the last
  * view is reprojected into the current one through the feature buffers, accepted where the geometry agrees, and mixed with

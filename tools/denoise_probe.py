@@ -8,7 +8,12 @@
      the whole frame on one GPU; c5tile is an eighth of a 2048^2 frame).  The question it answers: how many spp plus the
      denoiser reach the RMSE of a plain frame, and at what total time.
 
+  3. --variance: the variance-guided filter (ptmi_denoise_variance) beside ptmi_denoise on the same c3 image, in one process,
+     the two alternating: the variance estimate (spatial, radius 3; and the accumulation's after two passes) and the filter
+     proper at 5 iterations; medians with the min .. max of the runs.
+
   python tools/denoise_probe.py [--quick]          (one JSON line per measurement)
+  python tools/denoise_probe.py --variance         (PTMI_LIB=ab_libs/libptmi_unstaged.so: the estimate without its LDS tile)
   (per-kernel breakdown: rocprofv3 --kernel-trace --stats -- python tools/denoise_probe.py --timing-only, in a run of its own)
 """
 import argparse
@@ -57,6 +62,30 @@ def timing(r, name, reps):
                           denoise_5it_ms=float(np.median(d_ms)), reps=reps)), flush=True)
 
 
+def variance_timing(r, reps):
+    depth = setup(r, "c3", 0)
+    r.set_config(spp=1, max_depth=depth)
+    stat = lambda v: dict(median=float(np.median(v)), min=float(np.min(v)), max=float(np.max(v)))
+    for source in ("spatial", "accumulation"):
+        if source == "spatial":
+            r.render_frame()
+        else:
+            r.accum_reset(); r.accum_pass(None); r.accum_pass(None)
+        for _ in range(3):                                     # warm-up (buffers, code objects, clocks)
+            r.denoise(); r.denoise_variance()
+        d_ms, e_ms, f_ms = [], [], []
+        for _ in range(reps):
+            r.denoise()
+            d_ms.append(r.denoise_timing()[1])
+            r.denoise_variance()
+            e, f = r.variance_timing()
+            e_ms.append(e); f_ms.append(f)
+        print(json.dumps(dict(what="variance_timing", lib=os.path.basename(ptmi.LIB_PATH), source=source, width=r.width, height=r.height,
+                              iterations=5, reps=reps, denoise_ms=stat(d_ms), estimate_ms=stat(e_ms), filter_ms=stat(f_ms),
+                              filter_over_denoise=float(np.median(f_ms) / np.median(d_ms)),
+                              estimate_over_denoise=float(np.median(e_ms) / np.median(d_ms)))), flush=True)
+
+
 def quality(r, name, side, ref_spp, spps):
     depth = setup(r, name, side)
     r.set_config(spp=ref_spp, max_depth=depth, seed_base=77)
@@ -79,10 +108,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="fewer repetitions, lower reference spp")
     ap.add_argument("--timing-only", action="store_true")
+    ap.add_argument("--variance", action="store_true", help="only the variance-guided filter's timing beside ptmi_denoise's")
     ap.add_argument("--reps", type=int, default=20)
     a = ap.parse_args()
     r = ptmi.Renderer(0)
     reps = 5 if a.quick else a.reps
+    if a.variance:
+        variance_timing(r, reps)
+        r.close()
+        return
     for name in ("c2", "c3"):
         timing(r, name, reps)
     if not a.timing_only:

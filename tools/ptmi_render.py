@@ -8,6 +8,8 @@
   python tools/ptmi_render.py --scene ... --spp 8 --passes 16 --out progressive.png          (16 passes of 8 samples)
   python tools/ptmi_render.py --scene ... --spp 8 --adaptive 0.02 --counts-png counts.png   (passes until every pixel stops)
   python tools/ptmi_render.py --scene ... --spp 8 --denoise --out denoised.png             (a-trous denoiser, 5 iterations)
+  python tools/ptmi_render.py --scene ... --spp 2 --adaptive --denoise --variance-guided --variance-png sd.png --out denoised.png
+                              (the variance-guided filter, steered by the adaptive run's own per-pixel statistics)
   python tools/ptmi_render.py --scene ... --spp 8 --aov-png aov                              (aov_albedo/normal/depth.png)
   python tools/ptmi_render.py --scene ... --spp 4 --orbit 16 --yaw-step 2 --temporal --denoise --out-prefix orbit_
                                (16 views 2 degrees apart, each through the temporal accumulation and the denoiser)
@@ -60,6 +62,10 @@ def main():
     ap.add_argument("--counts-png", default=None, help="with --passes / --adaptive: grey map of the samples per pixel (white = most)")
     ap.add_argument("--denoise", type=int, nargs="?", const=-1, default=None, metavar="ITERATIONS",
                     help="--out gets the image through the edge-avoiding a-trous denoiser (ITERATIONS, default 5)")
+    ap.add_argument("--variance-guided", action="store_true", help="--denoise runs the variance-guided filter: steered by the "
+                    "accumulation's per-pixel statistics after --adaptive / --passes, by a spatial estimate after a frame")
+    ap.add_argument("--variance-png", default=None, metavar="FILE", help="with --variance-guided: the standard deviation left after "
+                    "the filter, sqrt(variance_out), through the tone map")
     ap.add_argument("--aov-png", default=None, metavar="PREFIX", help="write PREFIX_albedo.png, PREFIX_normal.png, PREFIX_depth.png "
                     "from the feature buffers of the denoiser")
     ap.add_argument("--orbit", type=int, default=0, metavar="FRAMES", help="render FRAMES views, --yaw-step degrees apart, one frame each")
@@ -128,6 +134,8 @@ def main():
         if a.rough:
             print(f"surfaces: {r.surface_counts()[3]} rough-metal primitives, roughness {a.roughness}")
     if a.orbit > 0:
+        if a.variance_guided and a.temporal:
+            ap.error("--variance-guided does not filter the temporal history (no variance is carried in it)")
         orbit(r, a, cam)
         r.close()
         return
@@ -152,7 +160,20 @@ def main():
     else:
         st = r.render_frame()
         print(f"frame: {a.width}x{a.height} x {a.spp} spp in {st.seconds * 1e3:.2f} ms = {st.samples / st.seconds / 1e6:.1f} Msamples/s")
-    if a.denoise is not None:
+    if a.variance_png and not (a.variance_guided and a.denoise is not None):
+        ap.error("--variance-png needs --denoise --variance-guided")
+    if a.denoise is not None and a.variance_guided:
+        prm = {} if a.denoise < 0 else {"iterations": a.denoise}
+        rgb, _ = r.denoise_variance(**prm)
+        ems, fms = r.variance_timing()
+        print(f"denoise (variance-guided): features {r.denoise_timing()[0]:.3f} ms, variance estimate {ems:.3f} ms, filter {fms:.3f} ms")
+        if a.variance_png:
+            import numpy as np
+            sd = np.sqrt(r.variance()[1].astype(np.float64))
+            grey = (255.99 * np.minimum((sd / (sd + 1.0)) ** (1.0 / 2.2), 1.0)).astype(np.uint8)
+            ptmi.write_png(a.variance_png, grey[:, :, None].repeat(3, axis=2))
+            print(f"wrote {a.variance_png}")
+    elif a.denoise is not None:
         prm = {} if a.denoise < 0 else {"iterations": a.denoise}
         rgb, _ = r.denoise(**prm)
         fms, dms = r.denoise_timing()
@@ -183,7 +204,7 @@ def orbit(r, a, cam):
             if a.denoise is not None:
                 rgb, _ = r.denoise_temporal(**prm)
         elif a.denoise is not None:
-            rgb, _ = r.denoise(**prm)
+            rgb, _ = r.denoise_variance(**prm) if a.variance_guided else r.denoise(**prm)
         else:
             rgb, _ = r.read_image()
         print(line)
