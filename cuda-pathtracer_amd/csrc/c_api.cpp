@@ -227,11 +227,7 @@ int ptmi_host_camera_frame(const ptmi_camera* cam, int width, int height, float*
         s.yaw = cam->yaw_deg; s.pitch = cam->pitch_deg;
         s.image_width = width; s.image_height = height;
         s.aspect = (float)width / (float)height;                                        // application_state.h:108
-        s.updateCamera();
-        if (cam->orbit) s.updateCameraOrbit();                                          // application.h:161
-        const CameraFrame f = s.frame();
-        const f3 v[4] = {f.origin, f.lower_left_corner, f.horizontal, f.vertical};
-        for (int i = 0; i < 4; i++) { out12[3 * i] = v[i].x; out12[3 * i + 1] = v[i].y; out12[3 * i + 2] = v[i].z; }
+        cameraFrame12(s, cam->orbit != 0, out12);                                       // application.h:161
     });
 }
 int ptmi_host_cdf_record_layout(int* out10) {
@@ -537,11 +533,7 @@ int ptmi_surfaces_info(const ptmi_ctx* c, int* n_mirror, int* n_glass) {
 int ptmi_get_camera_frame(const ptmi_ctx* c, float* out12) {
     return guarded([&] {
         need(c && out12, "NULL argument");
-        Sensor s = c->app.render.h_camera;                 // copy: what renderFrame() would derive
-        if (c->app.config.orbit) s.updateCameraOrbit(); else s.updateCamera();
-        const CameraFrame f = s.frame();
-        const f3 v[4] = {f.origin, f.lower_left_corner, f.horizontal, f.vertical};
-        for (int i = 0; i < 4; i++) { out12[3 * i] = v[i].x; out12[3 * i + 1] = v[i].y; out12[3 * i + 2] = v[i].z; }
+        cameraFrame12(c->app.render.h_camera, c->app.config.orbit, out12);              // what renderFrame() would derive
     });
 }
 
@@ -591,9 +583,7 @@ int ptmi_read_image(const ptmi_ctx* c, unsigned char* rgb8, float* radiance) {
         need(c != nullptr, "ctx is NULL");
         const RenderState& r = c->app.render;
         need(r.d_image != nullptr, "buffers not allocated");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        if (rgb8) PTMI_HIP(hipMemcpy(rgb8, r.d_image, r.n_local * 3, hipMemcpyDeviceToHost));                       // application.h:211
-        if (radiance) PTMI_HIP(hipMemcpy(radiance, r.d_radiance, r.n_local * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        readImagePair(c->app.device_id, r.n_local, r.d_image, r.d_radiance, rgb8, radiance);                        // application.h:211
     });
 }
 

@@ -217,13 +217,15 @@ struct FeatureBuffers {
     float4* position = nullptr;      // (hit point o + t d .xyz, 0)
 };
 void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams& fp, int g, const FeatureBuffers& fb, hipStream_t s);
-// The filter's constants for one run (csrc/denoise.hip; the contract is written out in include/ptmi.h)
-struct DenoiseArgs {
+// The constants of one run that the two a-trous filters share (csrc/denoise.hip; the contracts are written out in include/ptmi.h)
+struct FilterArgs {
     int width, height;               // the whole frame (a single rank)
     int demodulate;                  // 1: filter radiance / albedo (per channel, where the albedo is not 0)
     int normal_squarings;
-    float color_floor;
     float sigma_x2;                  // sigma_x * sigma_x (> 0)
+};
+struct DenoiseArgs : FilterArgs {
+    float color_floor;
 };
 // iterations passes of the edge-avoiding a-trous filter over radiance (3 floats per pixel, local row-major) guided by fb; the
 // filtered radiance -> out_radiance (3 floats per pixel) and its tone map -> out_rgb8.  buf: 2 x width x height float4 of scratch.
@@ -231,12 +233,8 @@ struct DenoiseArgs {
 void launch_denoise(const DenoiseArgs& a, const FeatureBuffers& fb, const float* radiance, int iterations, const float* sigma_c,
                     float4* buf, unsigned char* out_rgb8, float* out_radiance, hipStream_t s);
 
-// The variance-guided filter's constants for one run (csrc/denoise_variance.hip; the contract: include/ptmi.h, ptmi_denoise_variance)
-struct VarianceArgs {
-    int width, height;               // the whole frame (a single rank)
-    int demodulate;
-    int normal_squarings;
-    float sigma_x2;                  // sigma_x * sigma_x (> 0)
+// The variance-guided filter's own constants (the estimate: csrc/denoise_variance.hip; the contract: include/ptmi.h, ptmi_denoise_variance)
+struct VarianceArgs : FilterArgs {
     float sigma_l2;                  // sigma_luminance * sigma_luminance
     float epsilon;
     int radius;                      // of the spatial estimate's window, 1 .. 3

@@ -401,6 +401,8 @@ struct DenoiseParams {
     float sigma_position = 0.0f;                     // <= 0: 2 % of the scene's bounding-box diagonal
     int normal_squarings = 7, feature_grid = 2, demodulate = 1;
 };
+// an (rgb8, radiance) pair of n_local pixels to the host; either destination may be NULL
+void readImagePair(int device_id, size_t n_local, const unsigned char* d_rgb8, const float* d_radiance, unsigned char* rgb8, float* radiance);
 void featuresStale(ApplicationState& g_state);       // the triggers that restart an accumulation: features and image are stale
 void renderFeatures(ApplicationState& g_state, int grid);
 void readFeatures(const ApplicationState& g_state, float* albedo, float* normal, float* position, float* hit_fraction);

@@ -16,6 +16,16 @@ void featuresStale(ApplicationState& g) {
     g.render.dn.image_current = false;                 // the image shows the scene / view / config as it was before the change
 }
 
+static void needEvents(ApplicationState& g, size_t n) {
+    while (g.event_pool.size() < n) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
+}
+
+void readImagePair(int device_id, size_t n_local, const unsigned char* d_rgb8, const float* d_radiance, unsigned char* rgb8, float* radiance) {
+    PTMI_HIP(hipSetDevice(device_id));
+    if (rgb8 && n_local) PTMI_HIP(hipMemcpy(rgb8, d_rgb8, n_local * 3, hipMemcpyDeviceToHost));
+    if (radiance && n_local) PTMI_HIP(hipMemcpy(radiance, d_radiance, n_local * 3 * sizeof(float), hipMemcpyDeviceToHost));
+}
+
 void renderFeatures(ApplicationState& g, int grid) {
     RenderState& r = g.render;
     RenderState::Denoise& d = r.dn;
@@ -34,7 +44,7 @@ void renderFeatures(ApplicationState& g, int grid) {
     d.features_valid = false;
     FrameParams fp;
     cameraFrameParams(g, fp);
-    while (g.event_pool.size() < 2) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
+    needEvents(g, 2);
     PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
     launch_features(g.scene.d_scene, r.tile, fp, grid, d.fb, r.stream);
     PTMI_HIP(hipGetLastError());
@@ -100,15 +110,21 @@ static float autoSigmaPosition(const ApplicationState& g, float fraction, const 
     return sigma_x;
 }
 
-// the filter's constants for p (parameters checked first); sigma_c[i]: the colour sigma of iteration i
-static DenoiseArgs denoiseArgs(const ApplicationState& g, const DenoiseParams& p, float* sigma_c) {
-    const RenderState& r = g.render;
-    checkDenoiseParams(p);
-    DenoiseArgs a;
-    a.width = r.tile.width; a.height = r.tile.local_rows;
-    a.demodulate = p.demodulate; a.normal_squarings = p.normal_squarings; a.color_floor = p.color_floor;
+// the constants the two filters share, from either's (checked) parameters
+template <class Params>
+static void filterArgs(const ApplicationState& g, const Params& p, FilterArgs& a) {
+    a.width = g.render.tile.width; a.height = g.render.tile.local_rows;
+    a.demodulate = p.demodulate; a.normal_squarings = p.normal_squarings;
     const float sigma_x = p.sigma_position > 0.0f ? p.sigma_position : autoSigmaPosition(g, 0.02f, "denoise");   // 2 %
     a.sigma_x2 = sigma_x * sigma_x;
+}
+
+// the filter's constants for p (parameters checked first); sigma_c[i]: the colour sigma of iteration i
+static DenoiseArgs denoiseArgs(const ApplicationState& g, const DenoiseParams& p, float* sigma_c) {
+    checkDenoiseParams(p);
+    DenoiseArgs a;
+    filterArgs(g, p, a);
+    a.color_floor = p.color_floor;
     for (int i = 0; i < p.iterations; i++) sigma_c[i] = std::ldexp(p.sigma_color, -i);     // sigma_color x 2^-i, exact
     return a;
 }
@@ -131,38 +147,50 @@ static void allocateDenoiseOutputs(RenderState& r) {
     }
 }
 
+// A filter on the context's stream, timed: the outputs allocated, the resolve gate waited for, enqueue(mark) between a begin and
+// an end event, and its end waited for.  *ms: the device time - up to `mark`, which enqueue then records, where ms_after_mark is
+// given, and the rest there.
+template <class Enqueue>
+static void runFilter(ApplicationState& g, Enqueue&& enqueue, double* ms, double* ms_after_mark = nullptr) {
+    RenderState& r = g.render;
+    PTMI_HIP(hipSetDevice(g.device_id));
+    allocateDenoiseOutputs(r);
+    needEvents(g, 3);
+    const hipEvent_t begin = g.event_pool[0], end = g.event_pool[1], mark = g.event_pool[2];
+    r.dn.denoised = false;
+    if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));
+    PTMI_HIP(hipEventRecord(begin, r.stream));
+    enqueue(mark);
+    PTMI_HIP(hipGetLastError());
+    PTMI_HIP(hipEventRecord(end, r.stream));
+    PTMI_HIP(hipStreamSynchronize(r.stream));
+    *ms = elapsedMs(begin, ms_after_mark ? mark : end);
+    if (ms_after_mark) *ms_after_mark = elapsedMs(mark, end);
+    r.dn.denoised = true;
+}
+
 // the filter over radiance guided by fb into the denoiser's outputs (what ptmi_read_denoised returns)
 static void denoiseRun(ApplicationState& g, const DenoiseArgs& a, int iterations, const float* sigma_c, const FeatureBuffers& fb,
                        const float* radiance) {
-    RenderState& r = g.render;
-    RenderState::Denoise& d = r.dn;
-    PTMI_HIP(hipSetDevice(g.device_id));
-    allocateDenoiseOutputs(r);
-    while (g.event_pool.size() < 2) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
-    d.denoised = false;
-    if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));
-    PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
-    launch_denoise(a, fb, radiance, iterations, sigma_c, d.d_buf, d.d_rgb8, d.d_radiance, r.stream);
-    PTMI_HIP(hipGetLastError());
-    PTMI_HIP(hipEventRecord(g.event_pool[1], r.stream));
-    PTMI_HIP(hipStreamSynchronize(r.stream));
-    d.denoise_ms = elapsedMs(g.event_pool[0], g.event_pool[1]);
-    d.denoised = true;
+    RenderState::Denoise& d = g.render.dn;
+    runFilter(g, [&](hipEvent_t) { launch_denoise(a, fb, radiance, iterations, sigma_c, d.d_buf, d.d_rgb8, d.d_radiance, g.render.stream); },
+              &d.denoise_ms);
 }
 
-// what both filters ask of the context before they look at their parameters
-static void checkFilterable(const ApplicationState& g) {
+// what the filters and the temporal step ask of the context before they look at their parameters, in the caller's words
+static void checkFilterable(const ApplicationState& g, const std::string& who, const char* why_one_rank, const char* done) {
     const RenderState& r = g.render;
-    if (r.tile.n_ranks > 1) throw ArgError("denoise: the context is tiled over more than one rank (the filter needs rows of other ranks)");
-    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError("denoise: the Radiosity integrator's image is not denoised");
+    if (r.tile.n_ranks > 1) throw ArgError(who + ": the context is tiled over more than one rank (" + why_one_rank + ")");
+    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError(who + ": the Radiosity integrator's image is not " + done);
     if (!g.scene.d_nodes || !r.d_state.A || !r.dn.image_current)
-        throw ArgError("denoise: no image rendered yet (none since the last change of scene, camera, resolution or config)");
+        throw ArgError(who + ": no image rendered yet (none since the last change of scene, camera, resolution or config)");
 }
+static void checkDenoisable(const ApplicationState& g) { checkFilterable(g, "denoise", "the filter needs rows of other ranks", "denoised"); }
 
 void denoise(ApplicationState& g, const DenoiseParams& p) {
     RenderState& r = g.render;
     RenderState::Denoise& d = r.dn;
-    checkFilterable(g);
+    checkDenoisable(g);
     float sigma_c[10];
     const DenoiseArgs a = denoiseArgs(g, p, sigma_c);
     if (!d.features_valid || d.grid != p.feature_grid) renderFeatures(g, p.feature_grid);
@@ -172,9 +200,7 @@ void denoise(ApplicationState& g, const DenoiseParams& p) {
 void readDenoised(const ApplicationState& g, unsigned char* rgb8, float* radiance) {
     const RenderState& r = g.render;
     if (!r.dn.denoised) throw ArgError("readDenoised: nothing denoised yet (ptmi_denoise first)");
-    PTMI_HIP(hipSetDevice(g.device_id));
-    if (rgb8 && r.n_local) PTMI_HIP(hipMemcpy(rgb8, r.dn.d_rgb8, r.n_local * 3, hipMemcpyDeviceToHost));
-    if (radiance && r.n_local) PTMI_HIP(hipMemcpy(radiance, r.dn.d_radiance, r.n_local * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    readImagePair(g.device_id, r.n_local, r.dn.d_rgb8, r.dn.d_radiance, rgb8, radiance);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -183,13 +209,10 @@ void readDenoised(const ApplicationState& g, unsigned char* rgb8, float* radianc
 void denoiseVariance(ApplicationState& g, const VarianceParams& p) {
     RenderState& r = g.render;
     RenderState::Denoise& d = r.dn;
-    checkFilterable(g);
+    checkDenoisable(g);
     checkVarianceParams(p);
     VarianceArgs a;
-    a.width = r.tile.width; a.height = r.tile.local_rows;
-    a.demodulate = p.demodulate; a.normal_squarings = p.normal_squarings;
-    const float sigma_x = p.sigma_position > 0.0f ? p.sigma_position : autoSigmaPosition(g, 0.02f, "denoise");   // 2 %, as ptmi_denoise
-    a.sigma_x2 = sigma_x * sigma_x;
+    filterArgs(g, p, a);
     a.sigma_l2 = p.sigma_luminance * p.sigma_luminance;
     a.epsilon = p.epsilon;
     a.radius = p.spatial_radius;
@@ -197,21 +220,11 @@ void denoiseVariance(ApplicationState& g, const VarianceParams& p) {
     if (!d.features_valid || d.grid != p.feature_grid) renderFeatures(g, p.feature_grid);
     // the stopping test's moments describe the image only while it is a pass of the current accumulation
     const bool moments = p.source == 0 && d.image_pass && r.accum.pass > 0 && r.accum.allocated();
-    PTMI_HIP(hipSetDevice(g.device_id));
-    allocateDenoiseOutputs(r);
-    while (g.event_pool.size() < 3) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
-    d.denoised = false;
     d.variance_valid = false;
-    if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));
-    PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
-    launch_denoise_variance(a, d.fb, r.d_radiance, r.tile, moments ? &r.accum.ab : nullptr, r.accum.d_counts, p.iterations, d.d_buf,
-                            d.d_var_in, d.d_var_out, d.d_rgb8, d.d_radiance, g.event_pool[2], r.stream);
-    PTMI_HIP(hipGetLastError());
-    PTMI_HIP(hipEventRecord(g.event_pool[1], r.stream));
-    PTMI_HIP(hipStreamSynchronize(r.stream));
-    d.estimate_ms = elapsedMs(g.event_pool[0], g.event_pool[2]);
-    d.filter_ms = elapsedMs(g.event_pool[2], g.event_pool[1]);
-    d.denoised = true;
+    runFilter(g, [&](hipEvent_t estimated) {
+        launch_denoise_variance(a, d.fb, r.d_radiance, r.tile, moments ? &r.accum.ab : nullptr, r.accum.d_counts, p.iterations, d.d_buf,
+                                d.d_var_in, d.d_var_out, d.d_rgb8, d.d_radiance, estimated, r.stream);
+    }, &d.estimate_ms, &d.filter_ms);
     d.variance_valid = true;
 }
 
@@ -255,23 +268,11 @@ void checkTemporalParams(const TemporalParams& p) {
     if (!(p.sigma_albedo >= 0.0f && p.sigma_albedo <= 1e6f)) throw ArgError("temporal: sigma_albedo must be in [0, 1e6]");
 }
 
-// the camera frame the next frame would use (ptmi_get_camera_frame): origin, lower-left corner, horizontal, vertical
-static void viewFrame(const ApplicationState& g, float* out12) {
-    Sensor s = g.render.h_camera;
-    if (g.config.orbit) s.updateCameraOrbit(); else s.updateCamera();
-    const CameraFrame f = s.frame();
-    const f3 v[4] = {f.origin, f.lower_left_corner, f.horizontal, f.vertical};
-    for (int i = 0; i < 4; i++) { out12[3 * i] = v[i].x; out12[3 * i + 1] = v[i].y; out12[3 * i + 2] = v[i].z; }
-}
-
 void temporalAccumulate(ApplicationState& g, const TemporalParams& p, TemporalStats* stats) {
     RenderState& r = g.render;
     RenderState::Temporal& t = r.tp;
     RenderState::Denoise& d = r.dn;
-    if (r.tile.n_ranks > 1) throw ArgError("temporal: the context is tiled over more than one rank (taps cross ranks)");
-    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError("temporal: the Radiosity integrator's image is not accumulated");
-    if (!g.scene.d_nodes || !r.d_state.A || !d.image_current)
-        throw ArgError("temporal: no image rendered yet (none since the last change of scene, camera, resolution or config)");
+    checkFilterable(g, "temporal", "taps cross ranks", "accumulated");
     checkTemporalParams(p);
     TemporalArgs a;
     a.width = r.tile.width; a.height = r.tile.local_rows;
@@ -283,7 +284,7 @@ void temporalAccumulate(ApplicationState& g, const TemporalParams& p, TemporalSt
     a.m = (float)g.config.spp;
     const unsigned int* counts = d.image_pass ? r.accum.d_counts : nullptr;     // a pass: every pixel's own count
     float cam[12];
-    viewFrame(g, cam);
+    cameraFrame12(r.h_camera, g.config.orbit, cam);                             // the frame the next render would use
     double features_ms = 0.0;
     if (!d.features_valid || d.grid != p.feature_grid) { renderFeatures(g, p.feature_grid); features_ms = d.features_ms; }
     PTMI_HIP(hipSetDevice(g.device_id));
@@ -305,7 +306,7 @@ void temporalAccumulate(ApplicationState& g, const TemporalParams& p, TemporalSt
     a.still = t.valid && std::memcmp(cam, t.cam, sizeof cam) == 0 && t.width == a.width && t.height == a.height ? 1 : 0;
     std::memcpy(a.cam, t.cam, sizeof a.cam);
     std::memcpy(a.origin, cam, sizeof a.origin);
-    while (g.event_pool.size() < 2) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
+    needEvents(g, 2);
     const int next = t.cur ^ 1;
     unsigned long long h_stats[3] = {0, 0, 0};
     t.stepped = false;
@@ -333,9 +334,7 @@ void temporalAccumulate(ApplicationState& g, const TemporalParams& p, TemporalSt
 void readTemporal(const ApplicationState& g, unsigned char* rgb8, float* radiance) {
     const RenderState& r = g.render;
     if (!r.tp.stepped) throw ArgError("readTemporal: no temporal step yet (ptmi_temporal_accumulate first)");
-    PTMI_HIP(hipSetDevice(g.device_id));
-    if (rgb8 && r.n_local) PTMI_HIP(hipMemcpy(rgb8, r.tp.d_rgb8, r.n_local * 3, hipMemcpyDeviceToHost));
-    if (radiance && r.n_local) PTMI_HIP(hipMemcpy(radiance, r.tp.d_radiance, r.n_local * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    readImagePair(g.device_id, r.n_local, r.tp.d_rgb8, r.tp.d_radiance, rgb8, radiance);
 }
 
 void readHistoryCounts(const ApplicationState& g, float* counts) {

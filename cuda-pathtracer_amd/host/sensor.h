@@ -57,4 +57,11 @@ private:
     static float toRadian(float deg) { return (float)((double)deg * PTMI_PI_D / (double)180.0f); }   // sensor.h:11
 };
 
+// the frame a render would derive from s (ptmi_get_camera_frame): origin, lower-left corner, horizontal, vertical
+inline void cameraFrame12(Sensor s, bool orbit, float* out12) {
+    if (orbit) s.updateCameraOrbit(); else s.updateCamera();
+    const f3 v[4] = {s.origin, s.lower_left_corner, s.horizontal, s.vertical};
+    for (int i = 0; i < 4; i++) { out12[3 * i] = v[i].x; out12[3 * i + 1] = v[i].y; out12[3 * i + 2] = v[i].z; }
+}
+
 }  // namespace ptmi

@@ -211,7 +211,7 @@ def test_denoise_refuses_an_image_older_than_the_view(R):
 # ------------------------------------------------------------------------------------------------
 # 3. the filter against its numpy restatement
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("which,width,height", [("cbox", 40, 32), ("cbox_quads", W, H), ("soup", W, H)])
+@pytest.mark.parametrize("which,width,height", [("cbox", 40, 32), ("cbox_quads", W, H), ("soup", W, H), ("soup", 5, 3)])
 @pytest.mark.parametrize("iterations", [0, 1, 3, 5])
 def test_filter_matches_numpy(R, which, width, height, iterations):
     load(R, which)

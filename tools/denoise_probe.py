@@ -13,7 +13,7 @@
      proper at 5 iterations; medians with the min .. max of the runs.
 
   python tools/denoise_probe.py [--quick]          (one JSON line per measurement)
-  python tools/denoise_probe.py --variance         (PTMI_LIB=ab_libs/libptmi_unstaged.so: the estimate without its LDS tile)
+  python tools/denoise_probe.py --variance         (PTMI_LIB=ab_libs/libptmi_x.so: another build of the library, make ab-post-lib)
   (per-kernel breakdown: rocprofv3 --kernel-trace --stats -- python tools/denoise_probe.py --timing-only, in a run of its own)
 """
 import argparse
