@@ -865,6 +865,37 @@ int ptmi_debug_rcp_check(ptmi_ctx* c, uint32_t first_bits, uint64_t count, uint6
     });
 }
 
+int ptmi_debug_sqrt_check(ptmi_ctx* c, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad_bits) {
+    return guarded([&] {
+        need(c && mismatches && first_bad_bits, "NULL argument");
+        need(count > 0 && count <= (1ull << 32), "count must be in [1, 2^32]");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<unsigned long long> d(2);
+        const unsigned long long init[2] = {0ull, ~0ull};
+        d.upload(init, 2);
+        launch_debug_sqrt(first_bits, count, d.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        unsigned long long h[2];
+        d.download(h, 2);
+        *mismatches = h[0]; *first_bad_bits = h[0] ? (uint32_t)h[1] : 0u;
+    });
+}
+
+int ptmi_debug_ray_inv(ptmi_ctx* c, int n, const float* d, const int* live, float* out_inv) {
+    return guarded([&] {
+        need(c && d && live && out_inv, "NULL argument");
+        need(n > 0, "n must be positive");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<float> d_d(3 * (size_t)n), d_o(3 * (size_t)n); DevBuf<int> d_l(n);
+        d_d.upload(d, 3 * (size_t)n); d_l.upload(live, n);
+        launch_debug_ray_inv(n, d_d.p, d_l.p, d_o.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d_o.download(out_inv, 3 * (size_t)n);
+    });
+}
+
 int ptmi_debug_cosine_sample(ptmi_ctx* c, int n, const float* normals, const float* u, const float* v, float* out_dirs) {
     return guarded([&] {
         need(c && normals && u && v && out_dirs, "NULL argument");

@@ -117,6 +117,36 @@ void launch_debug_rcp(unsigned int first, unsigned long long count, unsigned lon
     hipLaunchKernelGGL(ptmi_debug_rcp_k, dim3(4096), dim3(256), 0, s, first, count, d_out);
 }
 
+// the same for sqrt_lean against sqrt_rn
+__global__ void ptmi_debug_sqrt_k(unsigned int first, unsigned long long count, unsigned long long* out /* [0]=mismatches [1]=first bad bits */) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    unsigned long long bad = 0, first_bad = ~0ull;
+    for (unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < count; i += stride) {
+        const unsigned int bits = first + (unsigned int)i;
+        const float a = __uint_as_float(bits);
+        const float want = sqrt_rn(a), got = sqrt_lean(a);
+        if (__float_as_uint(want) != __float_as_uint(got) && !(want != want && got != got)) { bad++; if (first_bad == ~0ull) first_bad = bits; }
+    }
+    if (bad) { atomicAdd(&out[0], bad); atomicMin(&out[1], first_bad); }
+}
+void launch_debug_sqrt(unsigned int first, unsigned long long count, unsigned long long* d_out, hipStream_t s) {
+    hipLaunchKernelGGL(ptmi_debug_sqrt_k, dim3(4096), dim3(256), 0, s, first, count, d_out);
+}
+
+// ray_inv, the walks' 1 / d behind its wave vote: case i is lane i & 63 of wave i / 64 (one wave per workgroup), so the caller
+// chooses which directions vote together.  A lane past n rides along as a dead one.
+__global__ __launch_bounds__(64) void ptmi_debug_ray_inv_k(int n, const float* __restrict__ d, const int* __restrict__ live, float* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const bool in = i < n;
+    const f3 dir = in ? mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]) : mk3(0.0f, 0.0f, 0.0f);
+    const f3 inv = ray_inv(dir, in && live[i] != 0);
+    if (in) { out[3 * i] = inv.x; out[3 * i + 1] = inv.y; out[3 * i + 2] = inv.z; }
+}
+void launch_debug_ray_inv(int n, const float* d, const int* live, float* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_ray_inv_k, dim3((n + 63) / 64), dim3(64), 0, s, n, d, live, out);
+}
+
 __global__ void ptmi_debug_cosine_k(int n, const float* normals, const float* u, const float* v, float* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

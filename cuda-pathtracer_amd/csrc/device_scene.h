@@ -388,6 +388,8 @@ void launch_debug_intersect_wide(const DeviceScene& sc, int n, const float* o, c
                                  int* hit, int* prim, float* t, unsigned long long* counts /* 2, may be nullptr */, hipStream_t s);
 void launch_debug_rng(const uint32_t* d_jump, uint64_t seed_base, int n_pixels, const int* pixels, int count, float* out, hipStream_t s);
 void launch_debug_rcp(unsigned int first_bits, unsigned long long count, unsigned long long* d_out, hipStream_t s);
+void launch_debug_sqrt(unsigned int first_bits, unsigned long long count, unsigned long long* d_out, hipStream_t s);
+void launch_debug_ray_inv(int n, const float* d, const int* live, float* out, hipStream_t s);
 void launch_debug_cosine(int n, const float* normals, const float* u, const float* v, float* out, hipStream_t s);
 void launch_debug_guided(int n, int op, const float* recs, const int* rec_idx, const float* normals, const float* in3,
                          const uint32_t* states, float* out, int* used, hipStream_t s);

@@ -32,41 +32,59 @@ __device__ __forceinline__ int global_pixel(const TileMap& tm, int slot, int& x,
 // ---------------------------------------------------------------------------------------------
 // camera (sensor.h:31-33 + ray.h:9-12) and the per-sample jitter (integrator.h:384-385)
 // ---------------------------------------------------------------------------------------------
-// get_ray(u, v) of the sensor: the ray through (u, v) of the image plane
-__device__ __forceinline__ void camera_ray_uv(const FrameParams& fp, float u, float v, f3& o, f3& d) {
+// get_ray(u, v) of the sensor: the ray through (u, v) of the image plane.  camera_dir_raw is its direction before the Ray
+// constructor normalises it; shade_step normalises it together with the bounce directions of the lanes that go on.
+__device__ __forceinline__ f3 camera_dir_raw(const FrameParams& fp, float u, float v, f3& o) {
     const f3 org = mk3(fp.cam_origin[0], fp.cam_origin[1], fp.cam_origin[2]);
     const f3 llc = mk3(fp.cam_llc[0], fp.cam_llc[1], fp.cam_llc[2]);
     const f3 hor = mk3(fp.cam_hor[0], fp.cam_hor[1], fp.cam_hor[2]);
     const f3 ver = mk3(fp.cam_ver[0], fp.cam_ver[1], fp.cam_ver[2]);
     o = org;
-    d = unit_vector(llc + u * hor + v * ver - org);
+    return llc + u * hor + v * ver - org;
+}
+// the per-sample jitter: (x + r1) / width, (y + r2) / height with the two uniforms already drawn.  IEEE divisions: the image
+// size is the caller's.
+__device__ __forceinline__ f3 camera_dir_raw(const FrameParams& fp, const TileMap& tm, int x, int y, float r1, float r2, f3& o) {
+    const float u = ((float)x + r1) / (float)tm.width;
+    const float v = ((float)y + r2) / (float)tm.height;
+    return camera_dir_raw(fp, u, v, o);
+}
+// IEEE 1 / len: nothing bounds the length of a camera's un-normalised direction
+__device__ __forceinline__ void camera_ray_uv(const FrameParams& fp, float u, float v, f3& o, f3& d) {
+    d = unit_vector(camera_dir_raw(fp, u, v, o));
 }
 __device__ __forceinline__ void camera_ray(const FrameParams& fp, const TileMap& tm, int x, int y, Rng& rng, f3& o, f3& d) {
-    const float u = ((float)x + rng_uniform(rng)) / (float)tm.width;
-    const float v = ((float)y + rng_uniform(rng)) / (float)tm.height;
-    camera_ray_uv(fp, u, v, o, d);
+    const float r1 = rng_uniform(rng);
+    const float r2 = rng_uniform(rng);
+    d = unit_vector(camera_dir_raw(fp, tm, x, y, r1, r2, o));
 }
 
 // sampleCosineHemisphere (integrator.h:62-85) with the two uniforms already drawn
+// The lean forms (pt_vec.h) stand where the operand's range is known; each gives sqrt_rn's / rcp_rn's bits on that range:
+//   sqrt_lean(u), sqrt_lean(1 - u): u is a curand uniform, in [2^-33, 1]; 1 - u is 0 or >= 2^-24
+//   1 / (1 + n.z): n is the unit normal of a primitive that was hit, and this branch has n.z >= -0.9999999f = -(1 - 2^-23),
+//     so 1 + n.z is in [2^-23, 2]
+//   the final normalisation: (tangent, bitangent, n) is an orthonormal frame to rounding and x^2 + y^2 + z^2 = u + (1 - u),
+//     so the squared length is 1 to a few ulp - far inside [2^-96, 2^100], and its root inside [2^-100, 2^100]
 __device__ __forceinline__ f3 cosine_hemisphere(f3 n, float u, float v) {
-    const float r = sqrt_rn(u);
+    const float r = sqrt_lean(u);
     const float phi = (float)((double)2.0f * PTMI_PI_D * (double)v);      // 2.0f * M_PI * v with a double M_PI
     float sphi, cphi;
     ptmi_sincosf(phi, &sphi, &cphi);
     const float x = r * cphi;
     const float y = r * sphi;
-    const float z = sqrt_rn(fmaxf(0.0f, 1.0f - u));
+    const float z = sqrt_lean(fmaxf(0.0f, 1.0f - u));
     f3 tangent, bitangent;
     if (n.z < -0.9999999f) {
         tangent = mk3(0.0f, -1.0f, 0.0f);
         bitangent = mk3(-1.0f, 0.0f, 0.0f);
     } else {
-        const float a = rcp_rn(1.0f + n.z);
+        const float a = rcp_exact_normal(1.0f + n.z);
         const float b = -n.x * n.y * a;
         tangent = mk3(1.0f - n.x * n.x * a, b, -n.x);
         bitangent = mk3(b, 1.0f - n.y * n.y * a, -n.y);
     }
-    return unit_vector(x * tangent + y * bitangent + z * n);
+    return unit_vector_lean(x * tangent + y * bitangent + z * n);
 }
 
 // Per-lane path registers (the 88-byte HBM record, unpacked).
@@ -214,23 +232,28 @@ template <bool STATS, bool GUIDED, bool PACKED = false, bool BATCH = false>
 __device__ __forceinline__ bool shade_step(const FrameParams& fp, const TileMap& tm, const MatSource& ms, const float* cdfs, PathRegs& p,
                                            bool hit, float t, int k, LaneCounters& cn, int slot) {
     bool end_sample = !hit;                                                       // integrator.h:198-201
+    // Plain BSDF sampling (!GUIDED): a lane either goes on with its path (go_on) or ends its sample; which of the two is settled
+    // first, and the direction of the next segment - a cosine sample about sn or the next camera ray - is then drawn, built and
+    // normalised ONCE for all lanes in the tail below, instead of once per kind at a fraction of the lanes each.
+    bool go_on = false;
+    f3 hp, sn;                                                                    // of the lanes that go on
     if (hit) {
         if (STATS) cn.hits++;
         f3 n, bsdf, Le; int row;
         fetch_material<PACKED>(ms, k, n, bsdf, Le, row);
-        const f3 hp = p.o + t * p.d;                                              // triangle.h:90
+        hp = p.o + t * p.d;                                                       // triangle.h:90
         p.L = p.L + p.tp * Le;                                                    // integrator.h:204
         if (p.depth > 2) {                                                        // integrator.h:207-212
             const float max_tp = fmaxf(p.tp.x, fmaxf(p.tp.y, p.tp.z));
             const float rr_prob = fminf(max_tp, 0.95f);
             if (rng_uniform(p.rng) > rr_prob) end_sample = true;
-            else p.tp = div_scalar(p.tp, rr_prob);
+            else p.tp = div_scalar(p.tp, rr_prob);                                // IEEE division: rr_prob can be tiny
         }
         if (!end_sample) {
             p.tp = p.tp * bsdf;                                                   // integrator.h:215
-            if (length(p.tp) < 1e-5f) end_sample = true;                          // integrator.h:218
+            if (length_below_1em5(length_squared(p.tp))) end_sample = true;       // integrator.h:218, length(tp) < 1e-5f
             else {
-                const f3 sn = dot(p.d, n) < 0 ? n : -n;                           // integrator.h:221-222
+                sn = dot(p.d, n) < 0 ? n : -n;                                    // integrator.h:221-222
                 // initGridFromPrimitive (integrator.h:31-57): the primitive's precomputed record, if it is valid
                 const float* g = nullptr;
                 if (GUIDED) {
@@ -255,7 +278,7 @@ __device__ __forceinline__ bool shade_step(const FrameParams& fp, const TileMap&
                         p.o = hp + 1e-4f * sn;                                    // integrator.h:266
                         p.d = unit_vector(next);
                     } else end_sample = true;
-                } else {                                                          // BSDF mode, or the cosine fallback :258-261
+                } else if (GUIDED) {                                              // the cosine fallback :258-261
                     const float u = rng_uniform(p.rng);                           // integrator.h:63-64
                     const float v = rng_uniform(p.rng);
                     p.depth++;
@@ -264,6 +287,13 @@ __device__ __forceinline__ bool shade_step(const FrameParams& fp, const TileMap&
                         p.o = hp + 1e-4f * sn;                                    // integrator.h:266
                         p.d = unit_vector(next);                                  // Ray ctor normalises again
                     } else end_sample = true;                                     // loop bound; the draws above are still consumed
+                } else {                                                          // BSDF mode
+                    p.depth++;
+                    if (p.depth < fp.max_depth) go_on = true;
+                    else {                                                        // loop bound: the reference has drawn u and v by now
+                        rng_next(p.rng); rng_next(p.rng);                         // (integrator.h:63-64); the stream moves on, nothing reads them
+                        end_sample = true;
+                    }
                 }
             }
         }
@@ -281,8 +311,27 @@ __device__ __forceinline__ bool shade_step(const FrameParams& fp, const TileMap&
             p.sample_idx = (frame + 1u) << 16;
             p.color = mk3(0.0f, 0.0f, 0.0f);
         }
-        camera_ray(fp, tm, p.px, p.py, p.rng, p.o, p.d);                          // next iteration of the spp loop
-        p.tp = mk3(1.0f, 1.0f, 1.0f); p.L = mk3(0.0f, 0.0f, 0.0f); p.depth = 0;
+        if (GUIDED) {
+            camera_ray(fp, tm, p.px, p.py, p.rng, p.o, p.d);                      // next iteration of the spp loop
+            p.tp = mk3(1.0f, 1.0f, 1.0f); p.L = mk3(0.0f, 0.0f, 0.0f); p.depth = 0;
+        }
+    }
+    if (!GUIDED) {
+        // every lane still here draws two uniforms: (u, v) of sampleCosineHemisphere (integrator.h:63-64) where the path goes on,
+        // the pixel jitter of the next sample (integrator.h:384-385) where it ended - the same two draws, in the same order
+        const float r1 = rng_uniform(p.rng);
+        const float r2 = rng_uniform(p.rng);
+        f3 w;
+        if (go_on) {
+            w = cosine_hemisphere(sn, r1, r2);                                    // integrator.h:230
+            p.o = hp + 1e-4f * sn;                                                // integrator.h:266
+        } else {
+            w = camera_dir_raw(fp, tm, p.px, p.py, r1, r2, p.o);                  // next iteration of the spp loop
+            p.tp = mk3(1.0f, 1.0f, 1.0f); p.L = mk3(0.0f, 0.0f, 0.0f); p.depth = 0;
+        }
+        // the Ray constructor's normalisation (ray.h:9-12) of either kind.  IEEE sqrt and 1 / len: a bounce direction has length
+        // 1 to rounding, but nothing bounds the camera's un-normalised one
+        p.d = unit_vector(w);
     }
     return true;
 }

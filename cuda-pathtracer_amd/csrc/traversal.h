@@ -26,6 +26,21 @@ __device__ __forceinline__ bool box_hit(const float4& n0, const float4& n1, f3 o
     return !(tmax_box < tmin_box);
 }
 
+// 1 / d of the slab tests (scene.h:57-59), per wave.  rcp_exact_normal is the IEEE quotient for 2^-100 <= |x| <= 2^100
+// (tests/test_gpu_parity.py::test_fast_reciprocal_is_exact) and takes 5 instructions where the division takes 11, so ONE vote
+// decides for the wave: if every live lane has all three components in that interval the wave takes the short form, otherwise -
+// a zero, a -0, a denormal, an infinity or a NaN component in any live lane - the whole wave takes the division.  A ray direction
+// is a unit vector, so only the lower bound ever acts; the upper one is tested on |x| + |y| + |z|, which is no smaller than any
+// of the three and a NaN or inf when one of them is (v_min3 alone would ignore a NaN).  Lanes that are not live hold no ray.
+__device__ __forceinline__ f3 ray_inv(f3 d, bool live) {
+    float lo;
+    asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(lo) : "v"(d.x), "v"(d.y), "v"(d.z));
+    const float sum = fabsf(d.x) + fabsf(d.y) + fabsf(d.z);
+    const bool in_range = (lo >= 0x1p-100f) & (sum <= 0x1p+100f);
+    if (__any(live && !in_range)) return mk3(rcp_rn(d.x), rcp_rn(d.y), rcp_rn(d.z));
+    return mk3(rcp_exact_normal(d.x), rcp_exact_normal(d.y), rcp_exact_normal(d.z));
+}
+
 // Primitive::intersect (primitive.h:83-90) + the closer-hit update of scene.h:89-96 for leaf slot k (per-lane k).
 template <bool HAS_QUADS>
 __device__ __forceinline__ void leaf_prim(const float4* __restrict__ prims, int prim_stride, int k, f3 o, f3 d, float t_lo,
@@ -71,7 +86,7 @@ __device__ __forceinline__ bool intersect_stack(const float4* __restrict__ nodes
                                                 float& t_hit, int& slot_hit, LaneCounters& cn) {
     float closest_t = t_max;
     slot_hit = -1;
-    const f3 inv = mk3(rcp_rn(d.x), rcp_rn(d.y), rcp_rn(d.z));
+    const f3 inv = ray_inv(d, live);
     const float t_lo = mt_t_lo(t_min);
     int sp = 0;
     int cur = live ? 0 : -1;
@@ -109,7 +124,7 @@ __device__ __forceinline__ bool intersect_lane(const float4* __restrict__ nodes,
                                                float& t_hit, int& slot_hit, LaneCounters& cn) {
     float closest_t = t_max;
     slot_hit = -1;
-    const f3 inv = mk3(rcp_rn(d.x), rcp_rn(d.y), rcp_rn(d.z));
+    const f3 inv = ray_inv(d, live);
     const float t_lo = mt_t_lo(t_min);
     int cur = live ? 0 : n_nodes;
     while (cur < n_nodes) {
@@ -171,7 +186,7 @@ __device__ __forceinline__ bool intersect_sweep(const float4* nodes, const float
                                                 float& t_hit, int& slot_hit, LaneCounters& cn) {
     float closest_t = t_max;
     slot_hit = -1;
-    const f3 inv = mk3(rcp_rn(d.x), rcp_rn(d.y), rcp_rn(d.z));
+    const f3 inv = ray_inv(d, live);
     const float t_lo = mt_t_lo(t_min);
     int cur = live ? 0 : n_nodes;
     for (int n = 0; n < n_nodes; n++) {

@@ -23,6 +23,7 @@ EXPORTS = [
     "ptmi_copy_image_device", "ptmi_set_radiosity_grids", "ptmi_get_precomputed_cdfs", "ptmi_set_radiosity",
            "ptmi_write_png", "ptmi_apply_grid_filter", "ptmi_use_raw_cdfs", "ptmi_get_filtered_pdfs", "ptmi_default_radiosity_params", "ptmi_run_radiosity_solver", "ptmi_get_radiosity_solution",
     "ptmi_debug_intersect", "ptmi_debug_rng", "ptmi_debug_cosine_sample", "ptmi_debug_guided_sample", "ptmi_debug_set_traversal", "ptmi_debug_rcp_check",
+    "ptmi_debug_sqrt_check", "ptmi_debug_ray_inv",
     "ptmi_host_scene_load", "ptmi_host_scene_from_arrays", "ptmi_host_scene_free", "ptmi_host_scene_info",
     "ptmi_host_scene_get_prims", "ptmi_host_scene_get_bvh", "ptmi_host_camera_frame", "ptmi_host_local_row_map",
     "ptmi_host_cdf_record_layout", "ptmi_host_image",
@@ -176,6 +177,9 @@ def lib():
         L.ptmi_debug_set_solver_walk.argtypes = [vp, C.c_int, C.c_int]
         L.ptmi_debug_get_traversal.argtypes = [vp, ip]
         L.ptmi_debug_rcp_check.argtypes = [vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        if hasattr(L, "ptmi_debug_sqrt_check"):      # an A/B library (PTMI_LIB) built from an older commit has neither
+            L.ptmi_debug_sqrt_check.argtypes = [vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+            L.ptmi_debug_ray_inv.argtypes = [vp, C.c_int, vp, vp, vp]
         L.ptmi_host_scene_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
         L.ptmi_host_scene_from_arrays.argtypes = [C.c_int, vp, vp, vp, vp, vp, C.POINTER(vp)]
         L.ptmi_host_scene_free.argtypes = [vp]; L.ptmi_host_scene_free.restype = None
@@ -915,6 +919,19 @@ class Renderer:
         bad = C.c_uint64(); first = C.c_uint32()
         self._ck(self.L.ptmi_debug_rcp_check(self.h, int(first_bits), int(count), C.byref(bad), C.byref(first)))
         return bad.value, first.value
+
+    def debug_sqrt_check(self, first_bits, count):
+        bad = C.c_uint64(); first = C.c_uint32()
+        self._ck(self.L.ptmi_debug_sqrt_check(self.h, int(first_bits), int(count), C.byref(bad), C.byref(first)))
+        return bad.value, first.value
+
+    def debug_ray_inv(self, d, live=None):
+        """The walks' 1 / d of directions d (n, 3); every 64 consecutive cases vote as one wave, live[i] == 0 takes case i out of it."""
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        live = np.ones(len(d), np.int32) if live is None else np.ascontiguousarray(live, np.int32)
+        out = np.zeros_like(d)
+        self._ck(self.L.ptmi_debug_ray_inv(self.h, len(d), d.ctypes.data, live.ctypes.data, out.ctypes.data))
+        return out
 
     def debug_intersect(self, o, d, t_min=1e-4, t_max=3.4028234663852886e38):
         o = np.ascontiguousarray(o, np.float32).reshape(-1, 3); d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)

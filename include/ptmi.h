@@ -378,6 +378,12 @@ int ptmi_debug_rng(ptmi_ctx*, uint64_t seed_base, int n_pixels, const int* pixel
 /* Compares the kernels' short reciprocal (1 v_rcp + 4 fma, used for Moller-Trumbore's 1/a) with the IEEE quotient for
  * the `count` consecutive float bit patterns starting at first_bits; reports how many differ and the first one. */
 int ptmi_debug_rcp_check(ptmi_ctx*, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad_bits);
+/* The same for the kernels' short square root (v_sqrt_f32 + two residual fmas, no denormal scaling) against the correctly
+ * rounded one. */
+int ptmi_debug_sqrt_check(ptmi_ctx*, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad_bits);
+/* The walks' 1 / d for n directions (3 floats each).  Cases 64w .. 64w + 63 form one wave and share its vote between the short
+ * reciprocal and the IEEE division; live[i] == 0 makes case i a lane without a ray, which has no say in the vote. */
+int ptmi_debug_ray_inv(ptmi_ctx*, int n, const float* d, const int* live, float* out_inv /* 3n */);
 /* sampleCosineHemisphere (integrator.h:62-85) with explicit (u, v). */
 int ptmi_debug_cosine_sample(ptmi_ctx*, int n, const float* normals, const float* u, const float* v, float* out_dirs);
 /* Guided sampling per call, through the bounce kernels' own device functions (debug_hooks.hip: ptmi_debug_guided_k).  Case i
