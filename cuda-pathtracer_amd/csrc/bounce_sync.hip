@@ -37,7 +37,8 @@ __device__ __forceinline__ void bounce_body(const BounceArgs& a) {
         if (STATS && alive) cn.rays++;
         const bool hit = scene_intersect<MODE, HAS_QUADS, STATS>(nodes, prims, a.sc.prim_stride, a.sc.n_nodes, stack, alive,
                                                                p.o, p.d, 1e-4f, FLT_MAX, t, k, cn);
-        if (alive) alive = shade_step<STATS, GUIDED, false, BATCH>(a.fp, a.tm, MatSource{mats, nullptr, nullptr}, a.sc.cdfs, p, hit, t, k, cn, slot);
+        constexpr bool LEAN = MODE == TRAVERSAL_SWEEP && !STATS && !GUIDED;      // shading.h: shade_step
+        if (alive) alive = shade_step<STATS, GUIDED, false, BATCH, LEAN>(a.fp, a.tm, MatSource{mats, nullptr, nullptr}, a.sc.cdfs, p, hit, t, k, cn, slot);
     }
 
     if (active) store_path(a.st, slot, p);

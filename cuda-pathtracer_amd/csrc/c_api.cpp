@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../host/application_state.h"
+#include "shade_lean.h"
 
 using namespace ptmi;
 
@@ -57,6 +58,22 @@ struct DevBuf {
     void upload(const T* h, size_t n) { PTMI_HIP(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice)); }
     void download(T* h, size_t n) { PTMI_HIP(hipMemcpy(h, p, n * sizeof(T), hipMemcpyDeviceToHost)); }
 };
+
+// the wave-vote hooks: n cases of in_per floats in waves of 64, live[i] == 0 a lane that is not active; one launch, out_per
+// floats per case back, zero where a lane was not active
+template <class Launch>
+void run_vote_hook(ptmi_ctx* c, int n, const float* in, int in_per, const int* live, float* out, int out_per, Launch launch) {
+    need(c && in && live && out, "NULL argument");
+    need(n > 0, "n must be positive");
+    PTMI_HIP(hipSetDevice(c->app.device_id));
+    DevBuf<float> d_in((size_t)in_per * n), d_o((size_t)out_per * n); DevBuf<int> d_l(n);
+    d_in.upload(in, (size_t)in_per * n); d_l.upload(live, n);
+    PTMI_HIP(hipMemsetAsync(d_o.p, 0, (size_t)out_per * n * sizeof(float), c->app.render.stream));
+    launch(d_in.p, d_l.p, d_o.p, c->app.render.stream);
+    PTMI_HIP(hipGetLastError());
+    PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+    d_o.download(out, (size_t)out_per * n);
+}
 }  // namespace
 
 static std::vector<Primitive> prims_from_arrays(int n, const int* type, const float* verts, const float* normal,
@@ -893,6 +910,55 @@ int ptmi_debug_ray_inv(ptmi_ctx* c, int n, const float* d, const int* live, floa
         PTMI_HIP(hipGetLastError());
         PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
         d_o.download(out_inv, 3 * (size_t)n);
+    });
+}
+
+int ptmi_debug_sincos_lean_check(ptmi_ctx* c, uint32_t first_bits, uint64_t count, uint64_t* bad_sin, uint64_t* bad_cos,
+                                 uint32_t* first_bad_bits, uint64_t* flagged, uint32_t* flagged_bits, int* n_flagged_bits) {
+    return guarded([&] {
+        need(c && bad_sin && bad_cos && first_bad_bits && flagged && flagged_bits && n_flagged_bits, "NULL argument");
+        need(count > 0 && count <= (1ull << 32), "count must be in [1, 2^32]");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<unsigned long long> d(13);
+        unsigned long long h[13] = {0ull, 0ull, ~0ull};
+        d.upload(h, 13);
+        launch_debug_sincos_lean_check(first_bits, count, d.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d.download(h, 13);
+        *bad_sin = h[0]; *bad_cos = h[1]; *first_bad_bits = (h[0] | h[1]) ? (uint32_t)h[2] : 0u; *flagged = h[3];
+        *n_flagged_bits = (int)std::min<unsigned long long>(h[12], 8ull);
+        for (int i = 0; i < 8; i++) flagged_bits[i] = i < *n_flagged_bits ? (uint32_t)h[4 + i] : 0u;
+    });
+}
+
+int ptmi_debug_sincos_lean(ptmi_ctx* c, int n, const float* x, const int* live, float* out) {
+    return guarded([&] {
+        run_vote_hook(c, n, x, 1, live, out, 4, [&](const float* i, const int* l, float* o, hipStream_t s) { launch_debug_sincos_lean(n, i, l, o, s); });
+    });
+}
+int ptmi_debug_unit_voted(ptmi_ctx* c, int n, const float* w, const int* live, float* out) {
+    return guarded([&] {
+        run_vote_hook(c, n, w, 3, live, out, 6, [&](const float* i, const int* l, float* o, hipStream_t s) { launch_debug_unit_voted(n, i, l, o, s); });
+    });
+}
+
+int ptmi_debug_size_div_check(ptmi_ctx* c, int size, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad_bits, int* lean) {
+    return guarded([&] {
+        need(c && mismatches && first_bad_bits && lean, "NULL argument");
+        need(size >= 1, "size must be positive");
+        need(count > 0 && count <= (1ull << 32), "count must be in [1, 2^32]");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<unsigned long long> d(2);
+        const unsigned long long init[2] = {0ull, ~0ull};
+        d.upload(init, 2);
+        const float inv = ptmi_size_reciprocal(size);                  // as RenderState::allocateBuffers takes TileMap's
+        launch_debug_size_div((float)size, inv, first_bits, count, d.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        unsigned long long h[2];
+        d.download(h, 2);
+        *mismatches = h[0]; *first_bad_bits = h[0] ? (uint32_t)h[1] : 0u; *lean = inv != 0.0f ? 1 : 0;
     });
 }
 

@@ -147,10 +147,97 @@ void launch_debug_ray_inv(int n, const float* d, const int* live, float* out, hi
     hipLaunchKernelGGL(ptmi_debug_ray_inv_k, dim3((n + 63) / 64), dim3(64), 0, s, n, d, live, out);
 }
 
+// sincos_2pi_lean, the cosine sample's sincos behind its wave vote, against ptmi_sincosf over a range of bit patterns.
+// out: [0] patterns whose sin differs, [1] whose cos differs, [2] the first such pattern, [3] lanes that raised the flag,
+// [4..4+kLeanFlaggedKept) the first flagged patterns that were recorded (in no order).  A pattern counts as different if the voted
+// result differs, or if it is not flagged and the short form itself differs (its wave may have gone the long way for a neighbour).
+constexpr int kLeanFlaggedKept = 8;
+__global__ void ptmi_debug_sincos_lean_check_k(unsigned int first, unsigned long long count, unsigned long long* out) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    unsigned long long bad_s = 0, bad_c = 0, first_bad = ~0ull, flagged = 0;
+    for (unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < count; i += stride) {
+        const unsigned int bits = first + (unsigned int)i;
+        const float x = __uint_as_float(bits);
+        float ws, wc, s, c, fs, fc;
+        ptmi_sincosf(x, &ws, &wc);
+        sincos_2pi_lean(x, &s, &c);
+        const bool flag = ptmi_sincos_2pi_fast(x, &fs, &fc) != 0;
+        const bool in_domain = bits <= PTMI_TWO_PI_F_BITS;
+        const bool ds = __float_as_uint(s) != __float_as_uint(ws) || (in_domain && !flag && __float_as_uint(fs) != __float_as_uint(ws));
+        const bool dc = __float_as_uint(c) != __float_as_uint(wc) || (in_domain && !flag && __float_as_uint(fc) != __float_as_uint(wc));
+        bad_s += ds; bad_c += dc;
+        if ((ds || dc) && first_bad == ~0ull) first_bad = bits;
+        if (in_domain && flag) {
+            if (flagged == 0) {
+                const unsigned long long at = atomicAdd(&out[4 + kLeanFlaggedKept], 1ull);
+                if (at < (unsigned long long)kLeanFlaggedKept) out[4 + at] = bits;
+            }
+            flagged++;
+        }
+    }
+    if (bad_s) atomicAdd(&out[0], bad_s);
+    if (bad_c) atomicAdd(&out[1], bad_c);
+    if (first_bad != ~0ull) atomicMin(&out[2], first_bad);
+    if (flagged) atomicAdd(&out[3], flagged);
+}
+void launch_debug_sincos_lean_check(unsigned int first, unsigned long long count, unsigned long long* d_out, hipStream_t s) {
+    hipLaunchKernelGGL(ptmi_debug_sincos_lean_check_k, dim3(4096), dim3(256), 0, s, first, count, d_out);
+}
+
+// sincos_2pi_lean per wave: case i is lane i & 63 of wave i / 64 (one wave per workgroup), as ptmi_debug_ray_inv_k; a case with
+// live[i] == 0 is a lane that is not active at the call.  out: 4 per case - the voted sin and cos, then ptmi_sincosf's.
+__global__ __launch_bounds__(64) void ptmi_debug_sincos_lean_k(int n, const float* __restrict__ x, const int* __restrict__ live, float* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n || live[i] == 0) return;
+    float s, c, ws, wc;
+    sincos_2pi_lean(x[i], &s, &c);
+    ptmi_sincosf(x[i], &ws, &wc);
+    out[4 * i] = s; out[4 * i + 1] = c; out[4 * i + 2] = ws; out[4 * i + 3] = wc;
+}
+void launch_debug_sincos_lean(int n, const float* x, const int* live, float* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_sincos_lean_k, dim3((n + 63) / 64), dim3(64), 0, s, n, x, live, out);
+}
+
+// div_by_size, the pixel jitter's division by an image size W with the reciprocal inv the host took for it (0: the IEEE division),
+// against a / W over a range of bit patterns of a.  W and inv are kernel arguments, as TileMap's are.
+__global__ void ptmi_debug_size_div_k(float W, float inv, unsigned int first, unsigned long long count, unsigned long long* out /* [0]=mismatches [1]=first bad bits */) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    unsigned long long bad = 0, first_bad = ~0ull;
+    for (unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < count; i += stride) {
+        const unsigned int bits = first + (unsigned int)i;
+        const float a = __uint_as_float(bits);
+        const float want = a / W, got = div_by_size(a, W, inv);
+        if (__float_as_uint(want) != __float_as_uint(got) && !(want != want && got != got)) { bad++; if (first_bad == ~0ull) first_bad = bits; }
+    }
+    if (bad) { atomicAdd(&out[0], bad); atomicMin(&out[1], first_bad); }
+}
+void launch_debug_size_div(float W, float inv, unsigned int first, unsigned long long count, unsigned long long* d_out, hipStream_t s) {
+    hipLaunchKernelGGL(ptmi_debug_size_div_k, dim3(4096), dim3(256), 0, s, W, inv, first, count, d_out);
+}
+
+// unit_vector_voted, the Ray constructor's normalisation behind its wave vote, laid out as ptmi_debug_sincos_lean_k.
+// out: 6 per case - the voted vector, then unit_vector's.
+__global__ __launch_bounds__(64) void ptmi_debug_unit_voted_k(int n, const float* __restrict__ w, const int* __restrict__ live, float* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n || live[i] == 0) return;
+    const f3 v = mk3(w[3 * i], w[3 * i + 1], w[3 * i + 2]);
+    const f3 got = unit_vector_voted(v), want = unit_vector(v);
+    out[6 * i] = got.x; out[6 * i + 1] = got.y; out[6 * i + 2] = got.z;
+    out[6 * i + 3] = want.x; out[6 * i + 4] = want.y; out[6 * i + 5] = want.z;
+}
+void launch_debug_unit_voted(int n, const float* w, const int* live, float* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_unit_voted_k, dim3((n + 63) / 64), dim3(64), 0, s, n, w, live, out);
+}
+
+// cosine_hemisphere with explicit (u, v), in its LEAN form: the sweep kernel's, with the voted sincos (tests/test_gpu_parity.py
+// holds it to the oracle).  The form without LEAN, which every other kernel keeps, is op 0 of ptmi_debug_guided_k below
+// (tests/test_gpu_integrator_vs_ref.py).
 __global__ void ptmi_debug_cosine_k(int n, const float* normals, const float* u, const float* v, float* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const f3 r = cosine_hemisphere(mk3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]), u[i], v[i]);
+    const f3 r = cosine_hemisphere<true>(mk3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]), u[i], v[i]);
     out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
 }
 

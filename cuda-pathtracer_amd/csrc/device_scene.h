@@ -121,6 +121,9 @@ struct TileMap {              // local row -> global row (ptmi.h: ptmi_tiling)
     int n_ranks = 1, rank = 0, row_block = 8;
     int local_rows = 0;
     int tile8 = 0;            // 1: consecutive slots enumerate 8x8 pixel tiles (needs width % 8 == 0 and local_rows % 8 == 0)
+    // ptmi_size_reciprocal(width), (height) (shade_lean.h), both set or both 0: the pixel jitter's short division (shading.h:
+    // div_by_size).  0: the IEEE division - a TileMap that nobody gave them, or a size above 2^23.
+    float inv_width = 0.0f, inv_height = 0.0f;
 };
 
 struct FrameParams {
@@ -390,6 +393,11 @@ void launch_debug_rng(const uint32_t* d_jump, uint64_t seed_base, int n_pixels, 
 void launch_debug_rcp(unsigned int first_bits, unsigned long long count, unsigned long long* d_out, hipStream_t s);
 void launch_debug_sqrt(unsigned int first_bits, unsigned long long count, unsigned long long* d_out, hipStream_t s);
 void launch_debug_ray_inv(int n, const float* d, const int* live, float* out, hipStream_t s);
+// the shade step's short forms (debug_hooks.hip); d_out of the sincos check: 13 words, [2] preset to ~0, the rest to 0
+void launch_debug_sincos_lean_check(unsigned int first_bits, unsigned long long count, unsigned long long* d_out, hipStream_t s);
+void launch_debug_sincos_lean(int n, const float* x, const int* live, float* out /* 4n */, hipStream_t s);
+void launch_debug_size_div(float W, float inv, unsigned int first_bits, unsigned long long count, unsigned long long* d_out, hipStream_t s);
+void launch_debug_unit_voted(int n, const float* w, const int* live, float* out /* 6n */, hipStream_t s);
 void launch_debug_cosine(int n, const float* normals, const float* u, const float* v, float* out, hipStream_t s);
 void launch_debug_guided(int n, int op, const float* recs, const int* rec_idx, const float* normals, const float* in3,
                          const uint32_t* states, float* out, int* used, hipStream_t s);

@@ -74,7 +74,19 @@ __device__ __forceinline__ f3 unit_vector_lean(f3 v) {
     const float k = rcp_exact_normal(sqrt_lean(length_squared(v)));
     return mk3(v.x * k, v.y * k, v.z * k);
 }
-PT_HD f3 cross(f3 a, f3 b) {                                                          // vector.h:211-218
+// unit_vector for a vector nothing is known about, per wave: ONE vote decides.  If the squared length of every active lane lies
+// in [2^-96, 2^100] the wave takes unit_vector_lean's operations, otherwise - a zero, a denormal, a huge, an infinite or a NaN
+// squared length in any active lane - the whole wave takes unit_vector's.  Either way every lane gets unit_vector's bits.  Lanes
+// that are not active at the call have no say.  tests/test_gpu_shade_lean_forms.py::test_unit_vector_vote pins it.
+__device__ __forceinline__ f3 unit_vector_voted(f3 v) {
+    const float l2 = length_squared(v);
+    const bool in_range = (l2 >= 0x1p-96f) & (l2 <= 0x1p+100f);             // false for a NaN
+    float k;
+    if (__any(!in_range)) k = rcp_rn(sqrt_rn(l2));
+    else k = rcp_exact_normal(sqrt_lean(l2));
+    return mk3(v.x * k, v.y * k, v.z * k);
+}
+PT_HD f3 cross(f3 a, f3 b) {                                                         // vector.h:211-218
     return mk3(a.y * b.z - a.z * b.y, -(a.x * b.z - a.z * b.x), a.x * b.y - a.y * b.x);
 }
 

@@ -3,6 +3,7 @@
 // depth loop.  Everything is __forceinline__ into the calling kernel.
 #pragma once
 #include "pt_device.h"
+#include "shade_lean.h"
 #include "traversal.h"
 
 namespace ptmi {
@@ -42,11 +43,20 @@ __device__ __forceinline__ f3 camera_dir_raw(const FrameParams& fp, float u, flo
     o = org;
     return llc + u * hor + v * ver - org;
 }
-// the per-sample jitter: (x + r1) / width, (y + r2) / height with the two uniforms already drawn.  IEEE divisions: the image
-// size is the caller's.
+// a / W for an image size W.  inv is TileMap's reciprocal of that size (ptmi_size_reciprocal, taken once on the host): where it
+// is set (1 <= W <= 2^23) the quotient takes ptmi_div_by_size_lean's three operations - the bits of a / W for a in [2^-33, W],
+// shade_lean.h - and where it is 0 the IEEE division.  inv is the same for the whole launch, so this is a scalar branch.
+// tests/test_gpu_shade_lean_forms.py::test_division_by_image_size checks every a for sixteen sizes, and a size above 2^23.
+__device__ __forceinline__ float div_by_size(float a, float W, float inv) {
+    if (inv != 0.0f) return ptmi_div_by_size_lean(a, W, inv);
+    return a / W;
+}
+// the per-sample jitter: (x + r1) / width, (y + r2) / height with the two uniforms already drawn; x + r1 lies in [2^-33, width].
+// LEAN: div_by_size (shade_step's tail in the kernels that take the short forms); otherwise the IEEE divisions.
+template <bool LEAN = false>
 __device__ __forceinline__ f3 camera_dir_raw(const FrameParams& fp, const TileMap& tm, int x, int y, float r1, float r2, f3& o) {
-    const float u = ((float)x + r1) / (float)tm.width;
-    const float v = ((float)y + r2) / (float)tm.height;
+    const float u = LEAN ? div_by_size((float)x + r1, (float)tm.width, tm.inv_width) : ((float)x + r1) / (float)tm.width;
+    const float v = LEAN ? div_by_size((float)y + r2, (float)tm.height, tm.inv_height) : ((float)y + r2) / (float)tm.height;
     return camera_dir_raw(fp, u, v, o);
 }
 // IEEE 1 / len: nothing bounds the length of a camera's un-normalised direction
@@ -59,18 +69,36 @@ __device__ __forceinline__ void camera_ray(const FrameParams& fp, const TileMap&
     d = unit_vector(camera_dir_raw(fp, tm, x, y, r1, r2, o));
 }
 
+// ptmi_sincosf(phi) of the cosine sample's phi = (float)(2 pi v), per wave.  ptmi_sincos_2pi_fast (shade_lean.h: explicit binary64
+// fmas, no quadrant branches, about half of ptmi_sincosf's binary64 operations) gives ptmi_sincosf's bits for every phi in
+// [0, (float)(2 pi)] that it does not flag as next to a rounding boundary (255 of the 1 086 918 620 arguments).  ONE vote decides:
+// if any active lane is flagged or holds a phi outside that interval - a -0, a negative value, a NaN or anything above; one
+// unsigned compare of the bit pattern - the whole wave calls ptmi_sincosf, otherwise every lane keeps the short form's results.
+// tests/test_shade_lean_forms_host.py proves the short form on the host and tests/test_gpu_shade_lean_forms.py on the device,
+// both over all arguments; the latter pins the vote as well.  The domain compare stands first: outside the domain the short
+// form's quadrant comes from a conversion that may be out of range (inf, NaN), and its flag then means nothing and is not read.
+__device__ __forceinline__ void sincos_2pi_lean(float phi, float* s, float* c) {
+    const bool outside = __float_as_uint(phi) > PTMI_TWO_PI_F_BITS;
+    const bool flagged = ptmi_sincos_2pi_fast(phi, s, c) != 0;
+    if (__any(outside || flagged)) ptmi_sincosf(phi, s, c);
+}
+
 // sampleCosineHemisphere (integrator.h:62-85) with the two uniforms already drawn
+//   LEAN: sincos_2pi_lean(phi) for ptmi_sincosf(phi): phi = (float)(2 pi v) with v a curand uniform lies in [0, (float)(2 pi)], and
+//     the vote covers the rest.  The same bits either way; the kernels that keep ptmi_sincosf are listed at shade_step.
 // The lean forms (pt_vec.h) stand where the operand's range is known; each gives sqrt_rn's / rcp_rn's bits on that range:
 //   sqrt_lean(u), sqrt_lean(1 - u): u is a curand uniform, in [2^-33, 1]; 1 - u is 0 or >= 2^-24
 //   1 / (1 + n.z): n is the unit normal of a primitive that was hit, and this branch has n.z >= -0.9999999f = -(1 - 2^-23),
 //     so 1 + n.z is in [2^-23, 2]
 //   the final normalisation: (tangent, bitangent, n) is an orthonormal frame to rounding and x^2 + y^2 + z^2 = u + (1 - u),
 //     so the squared length is 1 to a few ulp - far inside [2^-96, 2^100], and its root inside [2^-100, 2^100]
+template <bool LEAN = false>
 __device__ __forceinline__ f3 cosine_hemisphere(f3 n, float u, float v) {
     const float r = sqrt_lean(u);
     const float phi = (float)((double)2.0f * PTMI_PI_D * (double)v);      // 2.0f * M_PI * v with a double M_PI
     float sphi, cphi;
-    ptmi_sincosf(phi, &sphi, &cphi);
+    if (LEAN) sincos_2pi_lean(phi, &sphi, &cphi);
+    else ptmi_sincosf(phi, &sphi, &cphi);
     const float x = r * cphi;
     const float y = r * sphi;
     const float z = sqrt_lean(fmaxf(0.0f, 1.0f - u));
@@ -228,7 +256,12 @@ __device__ __forceinline__ void fetch_material(const MatSource& ms, int k, f3& n
         bsdf = xyz(ms.mats[3 * k + 1]); Le = xyz(ms.mats[3 * k + 2]);
     }
 }
-template <bool STATS, bool GUIDED, bool PACKED = false, bool BATCH = false>
+// LEAN: the four short forms of the direction tail - sincos_2pi_lean in the cosine sample, div_by_size for the pixel jitter,
+// unit_vector_voted for the Ray constructor's normalisation, rcp_exact_normal for the roulette's 1 / rr_prob.  Each gives the
+// bits of the form it stands for, so LEAN changes no result.  Only ptmi_bounce<SWEEP> without STATS and GUIDED sets it: that
+// kernel keeps its 8 waves per SIMD with all four (54 -> 55 VGPRs), while the phased kernels at 64 VGPRs lose a wave to any one
+// of them and the wide and GUIDED kernels, already spilling at their register caps, spill more (EXPERIMENTS.md).
+template <bool STATS, bool GUIDED, bool PACKED = false, bool BATCH = false, bool LEAN = false>
 __device__ __forceinline__ bool shade_step(const FrameParams& fp, const TileMap& tm, const MatSource& ms, const float* cdfs, PathRegs& p,
                                            bool hit, float t, int k, LaneCounters& cn, int slot) {
     bool end_sample = !hit;                                                       // integrator.h:198-201
@@ -247,7 +280,13 @@ __device__ __forceinline__ bool shade_step(const FrameParams& fp, const TileMap&
             const float max_tp = fmaxf(p.tp.x, fmaxf(p.tp.y, p.tp.z));
             const float rr_prob = fminf(max_tp, 0.95f);
             if (rng_uniform(p.rng) > rr_prob) end_sample = true;
-            else p.tp = div_scalar(p.tp, rr_prob);                                // IEEE division: rr_prob can be tiny
+            else {
+                // 1 / rr_prob (integrator.h:211).  LEAN: by the short reciprocal, no vote: a lane is here with rng_uniform <= rr_prob,
+                // a uniform is >= 2^-33 and rr_prob = fminf(max_tp, 0.95f) <= 0.95 (a NaN max_tp gives 0.95), so rr_prob lies in
+                // [2^-33, 0.95], inside rcp_exact_normal's interval (test_gpu_shade_lean_forms.py::test_roulette_reciprocal)
+                const float inv_rr = LEAN ? rcp_exact_normal(rr_prob) : rcp_rn(rr_prob);
+                p.tp = mk3(p.tp.x * inv_rr, p.tp.y * inv_rr, p.tp.z * inv_rr);
+            }
         }
         if (!end_sample) {
             p.tp = p.tp * bsdf;                                                   // integrator.h:215
@@ -323,15 +362,16 @@ __device__ __forceinline__ bool shade_step(const FrameParams& fp, const TileMap&
         const float r2 = rng_uniform(p.rng);
         f3 w;
         if (go_on) {
-            w = cosine_hemisphere(sn, r1, r2);                                    // integrator.h:230
+            w = cosine_hemisphere<LEAN>(sn, r1, r2);                              // integrator.h:230
             p.o = hp + 1e-4f * sn;                                                // integrator.h:266
         } else {
-            w = camera_dir_raw(fp, tm, p.px, p.py, r1, r2, p.o);                  // next iteration of the spp loop
+            w = camera_dir_raw<LEAN>(fp, tm, p.px, p.py, r1, r2, p.o);            // next iteration of the spp loop
             p.tp = mk3(1.0f, 1.0f, 1.0f); p.L = mk3(0.0f, 0.0f, 0.0f); p.depth = 0;
         }
-        // the Ray constructor's normalisation (ray.h:9-12) of either kind.  IEEE sqrt and 1 / len: a bounce direction has length
-        // 1 to rounding, but nothing bounds the camera's un-normalised one
-        p.d = unit_vector(w);
+        // the Ray constructor's normalisation (ray.h:9-12) of either kind: a bounce direction has length 1 to rounding, but nothing
+        // bounds the camera's un-normalised one: IEEE sqrt and 1 / len, or (LEAN) one vote per wave between the short forms and
+        // those (pt_vec.h)
+        p.d = LEAN ? unit_vector_voted(w) : unit_vector(w);
     }
     return true;
 }

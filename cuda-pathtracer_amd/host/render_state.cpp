@@ -1,6 +1,7 @@
 // render_state.cpp — what a context owns besides its scene: RenderState's buffers and chunks, the environment light, the
 // XORWOW jump matrices, the tiling, and ApplicationState itself.  The launches are render_run.cpp's.
 #include "application_state.h"
+#include "../csrc/shade_lean.h"
 
 #include <algorithm>
 #include <cstring>
@@ -174,6 +175,8 @@ void RenderState::allocateAccum() {
 void RenderState::allocateBuffers() {
     freeBuffers();
     tile.width = width; tile.height = height;
+    tile.inv_width = ptmi_size_reciprocal(width); tile.inv_height = ptmi_size_reciprocal(height);
+    if (tile.inv_width == 0.0f || tile.inv_height == 0.0f) tile.inv_width = tile.inv_height = 0.0f;      // one flag for both
     tile.local_rows = countLocalRows(height, tile.n_ranks, tile.rank, tile.row_block);
     n_local = (size_t)tile.local_rows * (size_t)width;
     tile.tile8 = (allow_tile8 && width % 8 == 0 && tile.local_rows % 8 == 0 && tile.row_block % 8 == 0) ? 1 : 0;

@@ -24,6 +24,7 @@ EXPORTS = [
            "ptmi_write_png", "ptmi_apply_grid_filter", "ptmi_use_raw_cdfs", "ptmi_get_filtered_pdfs", "ptmi_default_radiosity_params", "ptmi_run_radiosity_solver", "ptmi_get_radiosity_solution",
     "ptmi_debug_intersect", "ptmi_debug_rng", "ptmi_debug_cosine_sample", "ptmi_debug_guided_sample", "ptmi_debug_set_traversal", "ptmi_debug_rcp_check",
     "ptmi_debug_sqrt_check", "ptmi_debug_ray_inv",
+    "ptmi_debug_sincos_lean_check", "ptmi_debug_sincos_lean", "ptmi_debug_unit_voted", "ptmi_debug_size_div_check",
     "ptmi_host_scene_load", "ptmi_host_scene_from_arrays", "ptmi_host_scene_free", "ptmi_host_scene_info",
     "ptmi_host_scene_get_prims", "ptmi_host_scene_get_bvh", "ptmi_host_camera_frame", "ptmi_host_local_row_map",
     "ptmi_host_cdf_record_layout", "ptmi_host_image",
@@ -180,6 +181,12 @@ def lib():
         if hasattr(L, "ptmi_debug_sqrt_check"):      # an A/B library (PTMI_LIB) built from an older commit has neither
             L.ptmi_debug_sqrt_check.argtypes = [vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
             L.ptmi_debug_ray_inv.argtypes = [vp, C.c_int, vp, vp, vp]
+        if hasattr(L, "ptmi_debug_sincos_lean_check"):      # likewise
+            p64, p32 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+            L.ptmi_debug_sincos_lean_check.argtypes = [vp, C.c_uint32, C.c_uint64, p64, p64, p32, p64, vp, ip]
+            L.ptmi_debug_sincos_lean.argtypes = [vp, C.c_int, vp, vp, vp]
+            L.ptmi_debug_unit_voted.argtypes = [vp, C.c_int, vp, vp, vp]
+            L.ptmi_debug_size_div_check.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint64, p64, p32, ip]
         L.ptmi_host_scene_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
         L.ptmi_host_scene_from_arrays.argtypes = [C.c_int, vp, vp, vp, vp, vp, C.POINTER(vp)]
         L.ptmi_host_scene_free.argtypes = [vp]; L.ptmi_host_scene_free.restype = None
@@ -932,6 +939,38 @@ class Renderer:
         out = np.zeros_like(d)
         self._ck(self.L.ptmi_debug_ray_inv(self.h, len(d), d.ctypes.data, live.ctypes.data, out.ctypes.data))
         return out
+
+    def debug_sincos_lean_check(self, first_bits, count):
+        """The cosine sample's voted sincos against ptmi_sincosf over a range of bit patterns: (patterns whose sin differs, whose
+        cos differs, the first of them, lanes that raised the ambiguity flag, up to 8 flagged patterns)."""
+        bs = C.c_uint64(); bc = C.c_uint64(); first = C.c_uint32(); fl = C.c_uint64(); n = C.c_int()
+        kept = np.zeros(8, np.uint32)
+        self._ck(self.L.ptmi_debug_sincos_lean_check(self.h, int(first_bits), int(count), C.byref(bs), C.byref(bc), C.byref(first),
+                                                     C.byref(fl), kept.ctypes.data, C.byref(n)))
+        return bs.value, bc.value, first.value, fl.value, kept[:n.value].copy()
+
+    def _vote_hook(self, fn, x, per_in, per_out, live):
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, per_in)
+        live = np.ones(len(x), np.int32) if live is None else np.ascontiguousarray(live, np.int32)
+        out = np.zeros((len(x), per_out), np.float32)
+        self._ck(fn(self.h, len(x), x.ctypes.data, live.ctypes.data, out.ctypes.data))
+        return out
+
+    def debug_sincos_lean(self, x, live=None):
+        """The voted sincos of x (n,); every 64 consecutive cases vote as one wave, live[i] == 0 takes case i out of it.
+        (n, 4): the voted sin and cos, then ptmi_sincosf's."""
+        return self._vote_hook(self.L.ptmi_debug_sincos_lean, x, 1, 4, live)
+
+    def debug_unit_voted(self, w, live=None):
+        """The voted normalisation of w (n, 3), in waves as debug_sincos_lean.  (n, 6): the voted vector, then unit_vector's."""
+        return self._vote_hook(self.L.ptmi_debug_unit_voted, w, 3, 6, live)
+
+    def debug_size_div_check(self, size, first_bits, count):
+        """The pixel jitter's a / size against the IEEE division over a range of bit patterns of a: (mismatches, the first, whether
+        this size takes the short form)."""
+        bad = C.c_uint64(); first = C.c_uint32(); lean = C.c_int()
+        self._ck(self.L.ptmi_debug_size_div_check(self.h, int(size), int(first_bits), int(count), C.byref(bad), C.byref(first), C.byref(lean)))
+        return bad.value, first.value, bool(lean.value)
 
     def debug_intersect(self, o, d, t_min=1e-4, t_max=3.4028234663852886e38):
         o = np.ascontiguousarray(o, np.float32).reshape(-1, 3); d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)

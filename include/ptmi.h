@@ -384,6 +384,21 @@ int ptmi_debug_sqrt_check(ptmi_ctx*, uint32_t first_bits, uint64_t count, uint64
 /* The walks' 1 / d for n directions (3 floats each).  Cases 64w .. 64w + 63 form one wave and share its vote between the short
  * reciprocal and the IEEE division; live[i] == 0 makes case i a lane without a ray, which has no say in the vote. */
 int ptmi_debug_ray_inv(ptmi_ctx*, int n, const float* d, const int* live, float* out_inv /* 3n */);
+/* The shade step's short forms (csrc/shade_lean.h, csrc/shading.h, csrc/pt_vec.h), built with the bounce kernels' flags.
+ * sincos_lean_check: the cosine sample's sincos behind its wave vote against ptmi_sincosf for `count` consecutive bit patterns from
+ * first_bits: patterns whose sin / cos differ (the voted result, or - in [0, (float)(2 pi)] and not flagged - the short form
+ * itself), the first of them, the lanes in that interval that raised the ambiguity flag, and up to 8 of their patterns.
+ * sincos_lean / unit_voted: the voted sincos of x[i] / the voted normalisation of w[3i..3i+3) per wave - cases 64v .. 64v + 63 form
+ * one wave, live[i] == 0 makes case i a lane that is not active, as in ptmi_debug_ray_inv.  out: per case the voted result, then
+ * the long form's (sin, cos, sin, cos / 3 + 3 floats); zero for a case that is not live.
+ * size_div_check: the pixel jitter's a / size for `count` consecutive bit patterns of a against the IEEE division, with the
+ * reciprocal chosen as the renderer chooses it; lean = 1 if this size takes the short form, 0 if it keeps the division. */
+int ptmi_debug_sincos_lean_check(ptmi_ctx*, uint32_t first_bits, uint64_t count, uint64_t* bad_sin, uint64_t* bad_cos,
+                                 uint32_t* first_bad_bits, uint64_t* flagged, uint32_t* flagged_bits /* 8 */, int* n_flagged_bits);
+int ptmi_debug_sincos_lean(ptmi_ctx*, int n, const float* x, const int* live, float* out /* 4n */);
+int ptmi_debug_unit_voted(ptmi_ctx*, int n, const float* w, const int* live, float* out /* 6n */);
+int ptmi_debug_size_div_check(ptmi_ctx*, int size, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad_bits,
+                              int* lean);
 /* sampleCosineHemisphere (integrator.h:62-85) with explicit (u, v). */
 int ptmi_debug_cosine_sample(ptmi_ctx*, int n, const float* normals, const float* u, const float* v, float* out_dirs);
 /* Guided sampling per call, through the bounce kernels' own device functions (debug_hooks.hip: ptmi_debug_guided_k).  Case i
