@@ -3,6 +3,7 @@
 // traversal to its family.
 #pragma once
 #include "shading.h"
+#include "sweep_records.h"
 
 namespace ptmi {
 
@@ -48,14 +49,23 @@ inline bool is_guided(const BounceArgs& a) { return a.fp.sampling_mode != 0 && a
 #define PTMI_TR(...)
 #endif
 
-// stage the scene into LDS (when LDS_GEOM) and return the LDS cursor after it
-template <bool LDS_GEOM>
+// stage the scene into LDS (when LDS_GEOM) and return the LDS cursor after it: [nodes | prims | mats], ptmi_scene_lds_vecs
+// (sweep_records.h) vectors.  SWEEP_RECORDS: the node and primitive records in the sweep's form (ptmi_sweep_prepare) - the one
+// place where a kernel that walks with intersect_sweep gets its records, the bounce kernel and the test hook alike.
+template <bool LDS_GEOM, bool SWEEP_RECORDS = false>
 __device__ __forceinline__ float4* stage_scene(const DeviceScene& sc, float4* lds, const float4*& nodes, const float4*& prims, const float4*& mats) {
+    static_assert(LDS_GEOM || !SWEEP_RECORDS, "the sweep's records exist in LDS only");
     nodes = sc.nodes; prims = sc.prims; mats = sc.mats;
     if (LDS_GEOM) {
         const int n_node_vec = 2 * sc.n_nodes, n_prim_vec = sc.prim_stride * sc.n_prims, n_mat_vec = 3 * sc.n_prims;
-        for (int i = threadIdx.x; i < n_node_vec; i += kBlock) lds[i] = sc.nodes[i];
-        for (int i = threadIdx.x; i < n_prim_vec; i += kBlock) lds[n_node_vec + i] = sc.prims[i];
+        if (SWEEP_RECORDS) {
+            ptmi_sweep_prepare(reinterpret_cast<const ptmi_vec_bits*>(sc.nodes), sc.n_nodes, reinterpret_cast<const ptmi_vec_bits*>(sc.prims),
+                               sc.prim_stride, sc.n_prims, reinterpret_cast<ptmi_vec_bits*>(lds), reinterpret_cast<ptmi_vec_bits*>(lds + n_node_vec),
+                               lds_address(lds), (int)threadIdx.x, kBlock);
+        } else {
+            for (int i = threadIdx.x; i < n_node_vec; i += kBlock) lds[i] = sc.nodes[i];
+            for (int i = threadIdx.x; i < n_prim_vec; i += kBlock) lds[n_node_vec + i] = sc.prims[i];
+        }
         for (int i = threadIdx.x; i < n_mat_vec; i += kBlock) lds[n_node_vec + n_prim_vec + i] = sc.mats[i];
         nodes = lds; prims = lds + n_node_vec; mats = lds + n_node_vec + n_prim_vec;
         lds += n_node_vec + n_prim_vec + n_mat_vec;

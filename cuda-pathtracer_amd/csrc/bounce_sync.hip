@@ -11,6 +11,8 @@ namespace ptmi {
 // (MI355X_MICROARCH.md, residency rule); measured +2.4 %, no spills.
 // GUIDED instantiations would take ~100 VGPRs (4 waves per SIMD); capped at 80 (6 waves, 68 bytes of spills): grid
 // sampling +13 %, MIS +9 % on the benchmark frame (5 waves +8 %, 7 the same as 6, 8 waves +10 % / +3 %).
+// The sweep's BATCH builds and its quad builds without STATS are held to 8 waves per SIMD (64 VGPRs): left alone the quad build
+// takes 65 for the address cursor (traversal.h: intersect_sweep) and drops to 7 waves; held, it takes 63 and spills nothing.
 template <int MODE, bool LDS_GEOM, bool HAS_QUADS, bool STATS, bool GUIDED, bool BATCH>
 __device__ __forceinline__ void bounce_body(const BounceArgs& a) {
     extern __shared__ float4 smem[];
@@ -20,7 +22,7 @@ __device__ __forceinline__ void bounce_body(const BounceArgs& a) {
     const int idx = blockIdx.x * kBlock + threadIdx.x;
     const bool active = idx < n_in;
     const float4 *nodes, *prims, *mats;
-    float4* lds = stage_scene<LDS_GEOM>(a.sc, smem, nodes, prims, mats);
+    float4* lds = stage_scene<LDS_GEOM, MODE == TRAVERSAL_SWEEP>(a.sc, smem, nodes, prims, mats);
     int* stack = reinterpret_cast<int*>(lds) + threadIdx.x;
     if (GUIDED) fill_grid_solid_angles();
 
@@ -45,7 +47,7 @@ __device__ __forceinline__ void bounce_body(const BounceArgs& a) {
     finish_launch<STATS>(a, alive, slot, cn);
 }
 template <int MODE, bool LDS_GEOM, bool HAS_QUADS, bool STATS, bool GUIDED, bool BATCH>
-__global__ __launch_bounds__(kBlock, GUIDED ? 6 : (BATCH && MODE == TRAVERSAL_SWEEP ? 8 : 1)) __attribute__((amdgpu_num_sgpr(80))) void ptmi_bounce(BounceArgs a) {
+__global__ __launch_bounds__(kBlock, GUIDED ? 6 : ((BATCH || (HAS_QUADS && !STATS)) && MODE == TRAVERSAL_SWEEP ? 8 : 1)) __attribute__((amdgpu_num_sgpr(80))) void ptmi_bounce(BounceArgs a) {
     bounce_body<MODE, LDS_GEOM, HAS_QUADS, STATS, GUIDED, BATCH>(a);
     publish_count(a);
 }

@@ -1,5 +1,6 @@
 // debug_hooks.hip — the test hooks: the render kernels' own device functions (traversal.h, shading.h, light_sample.h, rough.h),
 // one call per case.  Compile with -ffp-contract=off (kernels.hip).
+#include "bounce.h"
 #include "light_sample.h"
 #include "../../include/ptmi.h"      // PTMI_MATH_*
 
@@ -13,13 +14,16 @@ __global__ __launch_bounds__(kBlock) void ptmi_debug_intersect_k(DeviceScene sc,
                                                                  float t_max, int* hit, int* prim, float* t_out, float* p_out, float* n_out) {
     extern __shared__ float4 smem[];
     int* stack = reinterpret_cast<int*>(smem) + threadIdx.x;
+    // SWEEP walks the records ptmi_bounce's sweep walks: staged by the same stage_scene (LANE and STACK read global memory here)
+    const float4 *nodes, *prims, *mats;
+    stage_scene<MODE == TRAVERSAL_SWEEP, MODE == TRAVERSAL_SWEEP>(sc, smem, nodes, prims, mats);
     const int i = blockIdx.x * kBlock + threadIdx.x;
     const bool live = i < n;
     const int j = live ? i : 0;
     const f3 ro = mk3(o[3 * j], o[3 * j + 1], o[3 * j + 2]), rd = mk3(d[3 * j], d[3 * j + 1], d[3 * j + 2]);
     LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
     float t = 0.0f; int k = -1;
-    const bool h = scene_intersect<MODE, HAS_QUADS, false>(sc.nodes, sc.prims, sc.prim_stride, sc.n_nodes, stack, live, ro, rd, t_min, t_max, t, k, cn);
+    const bool h = scene_intersect<MODE, HAS_QUADS, false>(nodes, prims, sc.prim_stride, sc.n_nodes, stack, live, ro, rd, t_min, t_max, t, k, cn);
     if (!live) return;
     hit[i] = h ? 1 : 0;
     prim[i] = h ? __float_as_int(sc.mats[3 * k].w) : -1;
@@ -33,9 +37,10 @@ __global__ __launch_bounds__(kBlock) void ptmi_debug_intersect_k(DeviceScene sc,
 void launch_debug_intersect(const DeviceScene& sc, int n, const float* o, const float* d, float t_min, float t_max,
                             int* hit, int* prim, float* t, float* p, float* nrm, hipStream_t s) {
     if (n <= 0) return;
-    const size_t lds = (size_t)sc.stack_entries * kBlock * sizeof(int);
     const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    const int walk = sc.traversal == TRAVERSAL_PHASED || sc.traversal == TRAVERSAL_PACKED || sc.traversal == TRAVERSAL_CERTIFIED ? TRAVERSAL_LANE : sc.traversal;   // the phased kernels walk like LANE
+    // the sweep stages the scene as ptmi_bounce does (bounce_lds_bytes counts it); the other walks need their stacks only
+    const size_t lds = sc.traversal == TRAVERSAL_SWEEP ? bounce_lds_bytes(sc) : (size_t)sc.stack_entries * kBlock * sizeof(int);
+    const int walk =sc.traversal == TRAVERSAL_PHASED || sc.traversal == TRAVERSAL_PACKED || sc.traversal == TRAVERSAL_CERTIFIED ? TRAVERSAL_LANE : sc.traversal;   // the phased kernels walk like LANE
     const auto launch = [&](auto mode) {
         with_bool(sc.has_quads, [&](auto quads) {
             hipLaunchKernelGGL((ptmi_debug_intersect_k<decltype(mode)::value, decltype(quads)::value>), grid, block, lds, s, sc, n, o, d, t_min, t_max, hit, prim, t, p, nrm);

@@ -3,6 +3,7 @@
 // view, the feature pass and next-event estimation (first_hit.hip).  Everything is __forceinline__ into the calling kernel.
 #pragma once
 #include "pt_device.h"
+#include "sweep_records.h"
 #include "wide_walk.h"
 
 namespace ptmi {
@@ -146,68 +147,178 @@ __device__ __forceinline__ bool intersect_lane(const float4* __restrict__ nodes,
     return slot_hit >= 0;
 }
 
-// ---- TRAVERSAL_SWEEP: the WAVE walks the node indices once -----------------------------------------------------
-// Every lane's cursor only moves forward through the pre-order, so one pass n = 0..N-1 with "lanes whose cursor == n
-// take part" visits, per lane, exactly the nodes and primitives of the walks above, in the same order.  n is
-// wave-uniform: node and primitive records come in through scalar loads (s_load_dwordx4 -> SGPR operands), there is
-// no stack, no per-lane LDS read, and lanes at different depths of the tree never serialise against each other.
-// The wave pays for the UNION of its lanes' visits, so this is used only for scenes of a few dozen primitives.
-// Must be called from wave-uniform control flow (dead lanes pass live = false).
+// ---- TRAVERSAL_SWEEP: the WAVE walks the node records once -------------------------------------------------------
+// Every lane's cursor only moves forward through the pre-order, so one pass over the records with "lanes whose cursor stands at
+// this record take part" visits, per lane, exactly the nodes and primitives of the walks above, in the same order.  The pass is
+// wave-uniform: node and primitive records are broadcast LDS reads, there is no stack, and lanes at different depths of the tree
+// never serialise against each other.  The wave pays for the UNION of its lanes' visits, so this is used only for scenes of a
+// few dozen primitives.  Must be called from wave-uniform control flow (dead lanes pass live = false).
+//
+// The walk reads the sweep's own records (sweep_records.h, staged by stage_scene<true, true>) and keeps no books beside them.
+// In every instantiation the cursor is the LDS ADDRESS of a node record and is itself the address of the two reads (an address
+// that all active lanes share is a broadcast read; it stays a per-lane VGPR, pinned, or the optimiser would rebuild it from the
+// scalar trip address with a move per pass).  "Stands at this record" is a compare against the scalar address, "next" is + 32, a
+// miss at an interior node is one select of the record's skip lane, which staging has turned into an address.  The trip count is
+// scalar and bounded by n_nodes, whatever a cursor holds.  Only the leaf flag / count and the leaf's first slot go through
+// readfirstlane (scalar branch, scalar loop bound, scalar address arithmetic).  The primitive stride is a constant of the
+// instantiation: 3 float4 without quads, 4 with (SceneState::chooseTraversal refuses any other).
+// Four more items, each taken by the instantiations it costs no wave per SIMD and no spill (sweep_form below):
+//   SWEEP_ONE_SELECT    the cursor's update is one select ahead of the leaf branch; without it, inside the two branches;
+//   SWEEP_VOTED_UPDATE  closest_t and slot_hit change only behind the (a, u) vote (mt_accept_update below); without it
+//                       mt_accept / mt_candidate and the selects after them, as leaf_prim has them.  Either way the slot comes
+//                       from the record's slot lane, a VGPR already;
+//   SWEEP_PINNED        eps, nextafter(eps) and t_lo are pinned in VGPRs: as SGPR operands of a VOP3 they cost it its full rate;
+//   SWEEP_LEAF_BASE     a leaf's primitives are read at immediate offsets from one VGPR that holds the address of the leaf's
+//                       first record, kSweepLeafUnroll per trip of a loop whose bound is the record's count; without it one
+//                       address per primitive, from the scalar one.
+// No expression of the slab test or of Moller-Trumbore differs from the walks above, and none is reordered.
+//
+// VALU instructions per pass in ptmi_bounce<SWEEP, ..., triangles, timed build> (ISA, before -> after): interior node 31 -> 27,
+// Moller-Trumbore first half 34 + 3 after it -> 32, second half 28 -> 30 (it holds the two selects now), per leaf 3 -> 2; the
+// quad build's node pass 31 -> 28, its primitive passes as before.  MI355X, parent's library against this one, three runs each,
+// alternating: c2 7 667 -> 8 046 Msamples/s (+4.9 %, 35.01 -> 33.36 ms per step), c3 15 935 -> 16 417 (+3.0 %); the parent's
+// runs lie within 0.3 % of each other.  EXPERIMENTS.md has the runs and the counters.
+enum : int { SWEEP_VOTED_UPDATE = 1, SWEEP_PINNED = 2, SWEEP_LEAF_BASE = 4, SWEEP_ONE_SELECT = 8 };
+constexpr int kSweepLeafUnroll = 4;
+
+// The form of each instantiation, judged by registers, waves per SIMD and spills against the walk before these items (DESIGN.md
+// 5 has the table).  The triangle builds take all four: 55-60 -> 59-64 VGPRs, 8 waves per SIMD and no spill as before (the
+// GUIDED ones stay at their cap of 80).  The quad builds stand at 63-64 VGPRs with two Moller-Trumbore halves per record: with
+// any one of the four the BATCH build starts to spill (2-9 VGPRs) and the plain one loses a wave or spills, so they keep
+// leaf_prim's form on the new cursor, which leaves both without spills at 8 waves (63 and 64 VGPRs).
 template <bool HAS_QUADS>
-__device__ __forceinline__ void leaf_prim_uniform(const float4* prims, int prim_stride, int k, f3 o, f3 d, float t_lo,
-                                                  float& closest_t, int& slot_hit) {
-    // k is wave-uniform: these are broadcast LDS reads, the operands land in VGPRs (an SGPR operand would halve
-    // the issue rate of every multiply/subtract that uses it)
-    const float4 p0 = prims[k * prim_stride], p1 = prims[k * prim_stride + 1], p2 = prims[k * prim_stride + 2];
-    const float eps = 1e-8f, eps_up = __uint_as_float(__float_as_uint(1e-8f) + 1u);
-    float t;
-    if (HAS_QUADS && __builtin_amdgcn_readfirstlane(__float_as_int(p0.w)) != 0) {   // wave-uniform branch
-        const float4 p3 = prims[k * prim_stride + 3];
-        // Quad::intersect: closest = t_max (= closest_t); each half accepts t < closest, second half sees the first's result
-        const float t1 = mt_candidate(xyz(p0), xyz(p1), xyz(p2), o, d, eps_up, t_lo);     // (v00, v10, v11), |a| > eps
-        const float c1 = min_raw(t1, closest_t);
-        const float t2 = mt_candidate(xyz(p0), xyz(p2), xyz(p3), o, d, eps_up, t_lo);     // (v00, v11, v01)
-        t = min_raw(t2, c1);                        // == closest_t when neither half was accepted
-    } else {
-        float tt = 0.0f;                                                                  // !(|a| < eps)
-        const bool acc = mt_accept(xyz(p0), xyz(p1), xyz(p2), o, d, eps, t_lo, closest_t, tt);
-        closest_t = acc ? tt : closest_t;
-        slot_hit = acc ? k : slot_hit;
-        return;
-    }
-    const bool closer = t < closest_t;            // quad: hit && temp.t < closest_t (scene.h:89-90)
-    closest_t = min_raw(t, closest_t);
-    slot_hit = closer ? k : slot_hit;
+constexpr int sweep_form() { return HAS_QUADS ? 0 : (SWEEP_ONE_SELECT | SWEEP_VOTED_UPDATE | SWEEP_PINNED | SWEEP_LEAF_BASE); }
+
+// mt_accept (pt_device.h) in the sweep's form: the same arithmetic with the closer-hit update of scene.h:89-96 behind the vote,
+// so that a primitive whose (a, u) test rejects the whole wave costs no select at all and t needs no initial value.  `slot` arrives in a
+// VGPR (the record's slot lane).  A quad half is the same call with eps_for_a = nextafter(eps): mt_candidate's +inf, the min chain
+// and `t < closest_t` of leaf_prim select exactly as (m >= 0) & (t < closest_t) does half by half - min_raw(+inf or a NaN t,
+// closest_t) is closest_t, a half updates iff its t is below the closest so far, and the second half sees the first's result.
+__device__ __forceinline__ void mt_accept_update(f3 v0, f3 edge1, f3 edge2, f3 o, f3 d, float eps_for_a, float t_lo, int slot,
+                                                 float& closest_t, int& slot_hit) {
+    const f3 h = cross(d, edge2);
+    const float a = dot(edge1, h);
+    const float f = rcp_exact_normal(a);
+    const f3 s = o - v0;
+    const float u = f * dot(s, h);
+    const float m1 = min3_raw(fabsf(a) - eps_for_a, u, 1.0f - u);
+    if (!__any(m1 >= 0.0f)) return;
+    const f3 q = cross(s, edge1);
+    const float v = f * dot(d, q);
+    const float t = f * dot(edge2, q);
+    float m = min3_raw(m1, v, 1.0f - (u + v));
+    m = min_raw(m, t - t_lo);
+    const bool acc = (m >= 0.0f) & (t < closest_t);
+    closest_t = acc ? t : closest_t;
+    slot_hit = acc ? slot : slot_hit;
+}
+// LDS by address: the 32-bit address of p, and the i-th float4 from such an address (the host pass only parses them)
+__device__ __forceinline__ unsigned int lds_address(const void* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (unsigned int)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+#else
+    return 0u;
+#endif
+}
+__device__ __forceinline__ float4 lds_vec(unsigned int address, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef float vec4 __attribute__((ext_vector_type(4)));
+    const vec4 v = reinterpret_cast<const __attribute__((address_space(3))) vec4*>(address)[i];
+    return make_float4(v.x, v.y, v.z, v.w);
+#else
+    return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#endif
 }
 
-template <bool HAS_QUADS, bool STATS>
-__device__ __forceinline__ bool intersect_sweep(const float4* nodes, const float4* prims, int prim_stride,
-                                                int n_nodes, bool live, f3 o, f3 d, float t_min, float t_max,
-                                                float& t_hit, int& slot_hit, LaneCounters& cn) {
+template <bool HAS_QUADS, int FORM>
+__device__ __forceinline__ void leaf_prim_sweep(unsigned int rec, int at, f3 o, f3 d, float eps, float eps_up, float t_lo,
+                                                float& closest_t, int& slot_hit) {
+    const float4 p0 = lds_vec(rec, at), p1 = lds_vec(rec, at + 1), p2 = lds_vec(rec, at + 2);   // record at vector `at` from rec
+    const int slot = __float_as_int(p1.w);                                                // the slot lane (sweep_records.h)
+    constexpr bool VOTED = (FORM & SWEEP_VOTED_UPDATE) != 0;
+    if (HAS_QUADS && __builtin_amdgcn_readfirstlane(__float_as_int(p0.w)) != 0) {         // wave-uniform branch
+        const float4 p3 = lds_vec(rec, at + 3);
+        // Quad::intersect: each half accepts t < closest, the second half sees the first's result; |a| > eps
+        if (VOTED) {
+            mt_accept_update(xyz(p0), xyz(p1), xyz(p2), o, d, eps_up, t_lo, slot, closest_t, slot_hit);     // (v00, v10, v11)
+            mt_accept_update(xyz(p0), xyz(p2), xyz(p3), o, d, eps_up, t_lo, slot, closest_t, slot_hit);     // (v00, v11, v01)
+        } else {
+            const float t1 = mt_candidate(xyz(p0), xyz(p1), xyz(p2), o, d, eps_up, t_lo);
+            const float c1 = min_raw(t1, closest_t);
+            const float t2 = mt_candidate(xyz(p0), xyz(p2), xyz(p3), o, d, eps_up, t_lo);
+            const float t = min_raw(t2, c1);                        // == closest_t when neither half was accepted
+            const bool closer = t < closest_t;                      // quad: hit && temp.t < closest_t (scene.h:89-90)
+            closest_t = min_raw(t, closest_t);
+            slot_hit = closer ? slot : slot_hit;
+        }
+    } else if (VOTED) {
+        mt_accept_update(xyz(p0), xyz(p1), xyz(p2), o, d, eps, t_lo, slot, closest_t, slot_hit);            // !(|a| < eps)
+    } else {
+        float tt = 0.0f;
+        const bool acc = mt_accept(xyz(p0), xyz(p1), xyz(p2), o, d, eps, t_lo, closest_t, tt);
+        closest_t = acc ? tt : closest_t;
+        slot_hit = acc ? slot : slot_hit;
+    }
+}
+
+template <bool HAS_QUADS, bool STATS, int FORM>
+__device__ __forceinline__ bool intersect_sweep(const float4* nodes, const float4* prims, int n_nodes, bool live, f3 o, f3 d,
+                                                float t_min, float t_max, float& t_hit, int& slot_hit, LaneCounters& cn) {
+    constexpr int kPrimVecs = HAS_QUADS ? 4 : 3;
+    constexpr unsigned int kPrimBytes = kPrimVecs * PTMI_SWEEP_VEC_BYTES;
     float closest_t = t_max;
     slot_hit = -1;
     const f3 inv = ray_inv(d, live);
-    const float t_lo = mt_t_lo(t_min);
-    int cur = live ? 0 : n_nodes;
-    for (int n = 0; n < n_nodes; n++) {
-        if (cur == n) {
-            // readfirstlane pins the index to an SGPR: inside this branch the optimiser knows cur == n and would
-            // otherwise address the node through the per-lane cursor
-            const int nu = __builtin_amdgcn_readfirstlane(n);
-            const float4 n0 = nodes[2 * nu], n1 = nodes[2 * nu + 1];
+    float t_lo = mt_t_lo(t_min), eps = 1e-8f, eps_up = __uint_as_float(__float_as_uint(1e-8f) + 1u);
+    if (FORM & SWEEP_PINNED) {
+        asm("" : "+v"(t_lo));
+        asm("" : "+v"(eps));
+        if (HAS_QUADS) asm("" : "+v"(eps_up));
+    }
+    const unsigned int first = lds_address(nodes), end = first + (unsigned int)n_nodes * PTMI_SWEEP_NODE_BYTES;
+    const unsigned int prims_at = lds_address(prims);
+    unsigned int cur = live ? first : end;
+    for (unsigned int at = first; at < end; at += PTMI_SWEEP_NODE_BYTES) {
+        if (cur == at) {
+            unsigned int here = cur;
+            asm("" : "+v"(here));
+            const float4 n0 = lds_vec(here, 0), n1 = lds_vec(here, 1);
             if (STATS) cn.node_visits++;
-            const int a = __builtin_amdgcn_readfirstlane(__float_as_int(n0.w));
-            const int b = __builtin_amdgcn_readfirstlane(__float_as_int(n1.w));   // wave-uniform
+            const int b = __builtin_amdgcn_readfirstlane(__float_as_int(n1.w));   // wave-uniform: >= 0 interior, < 0 leaf of -b
             const bool pass = box_hit(n0, n1, o, inv, t_min, closest_t);
-            cur = n + 1;
-            if (b < 0) {
-                if (pass) {
+            const unsigned int next = here + PTMI_SWEEP_NODE_BYTES, skip = __float_as_uint(n0.w);
+            const auto leaf_pass = [&]() {                       // the lanes whose ray meets the leaf's box test its -b primitives
+                const unsigned int leaf = prims_at + (unsigned int)__builtin_amdgcn_readfirstlane(__float_as_int(n0.w)) * kPrimBytes;
+                if constexpr ((FORM & SWEEP_LEAF_BASE) != 0) {
+                    unsigned int rec = leaf;
+                    asm("" : "+v"(rec));
+                    const auto test = [&](int i) {
+                        if (STATS) cn.prim_tests++;
+                        leaf_prim_sweep<HAS_QUADS, FORM>(rec, i * kPrimVecs, o, d, eps, eps_up, t_lo, closest_t, slot_hit);
+                    };
+                    static_assert(kSweepLeafUnroll == 4, "the four calls below");
+                    for (int left = -b; left > 0; left -= kSweepLeafUnroll, rec += kSweepLeafUnroll * kPrimBytes) {
+                        test(0);
+                        if (left > 1) test(1);
+                        if (left > 2) test(2);
+                        if (left > 3) test(3);
+                    }
+                } else {
                     for (int i = 0; i < -b; i++) {
                         if (STATS) cn.prim_tests++;
-                        leaf_prim_uniform<HAS_QUADS>(prims, prim_stride, a + i, o, d, t_lo, closest_t, slot_hit);
+                        leaf_prim_sweep<HAS_QUADS, FORM>(leaf + i * kPrimBytes, 0, o, d, eps, eps_up, t_lo, closest_t, slot_hit);
                     }
                 }
-            } else if (!pass) cur = a;
+            };
+            if constexpr ((FORM & SWEEP_ONE_SELECT) != 0) {
+                cur = ((b >= 0) & !pass) ? skip : next;
+                if (b < 0 && pass) leaf_pass();
+            } else if (b < 0) {
+                cur = next;
+                if (pass) leaf_pass();
+            } else {
+                cur = pass ? next : skip;
+            }
         }
     }
     t_hit = closest_t;
@@ -218,7 +329,7 @@ template <int MODE, bool HAS_QUADS, bool STATS>
 __device__ __forceinline__ bool scene_intersect(const float4* __restrict__ nodes, const float4* __restrict__ prims, int prim_stride,
                                                 int n_nodes, int* stack, bool live, f3 o, f3 d, float t_min, float t_max,
                                                 float& t_hit, int& slot_hit, LaneCounters& cn) {
-    if (MODE == TRAVERSAL_SWEEP) return intersect_sweep<HAS_QUADS, STATS>(nodes, prims, prim_stride, n_nodes, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
+    if (MODE == TRAVERSAL_SWEEP) return intersect_sweep<HAS_QUADS, STATS, sweep_form<HAS_QUADS>()>(nodes, prims, n_nodes, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
     if (MODE == TRAVERSAL_LANE) return intersect_lane<HAS_QUADS, STATS>(nodes, prims, prim_stride, n_nodes, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
     return intersect_stack<HAS_QUADS, STATS>(nodes, prims, prim_stride, stack, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
 }

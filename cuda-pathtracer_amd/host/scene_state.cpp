@@ -613,6 +613,9 @@ void SceneState::chooseTraversal() {
     // CERTIFIED needs the fast tree and the ancestor lists (triangle scenes of depth <= 62); otherwise the exact walk it stands for
     if (d_scene.traversal == TRAVERSAL_CERTIFIED && !d_scene.certified_ready())
         d_scene.traversal = (int)h_primitives.size() <= sweep_max_prims && d_scene.lds_resident ? TRAVERSAL_SWEEP : (d_scene.gnodes ? TRAVERSAL_PACKED : TRAVERSAL_PHASED);
+    // the sweep's kernels have the primitive stride as a constant of the instantiation (traversal.h: intersect_sweep)
+    if (d_scene.traversal == TRAVERSAL_SWEEP && d_scene.prim_stride != (d_scene.has_quads ? 4 : 3))
+        throw ArgError("internal: the sweep reads 3 float4 per primitive without quads and 4 with");
 }
 
 }  // namespace ptmi
