@@ -4,6 +4,7 @@
 #pragma once
 #include "shading.h"
 #include "sweep_records.h"
+#include "frame_block.h"
 
 namespace ptmi {
 
@@ -51,28 +52,38 @@ inline bool is_guided(const BounceArgs& a) { return a.fp.sampling_mode != 0 && a
 
 // stage the scene into LDS (when LDS_GEOM) and return the LDS cursor after it: [nodes | prims | mats], ptmi_scene_lds_vecs
 // (sweep_records.h) vectors.  SWEEP_RECORDS: the node and primitive records in the sweep's form (ptmi_sweep_prepare) - the one
-// place where a kernel that walks with intersect_sweep gets its records, the bounce kernel and the test hook alike.
+// place where a kernel that walks with intersect_sweep gets its records, the bounce kernel and the test hook alike - and, between
+// the primitives and the materials, the frame block of fp / tm (frame_block.h: ptmi_sweep_lds_vecs vectors in all; the hook, which
+// has no frame, passes none and leaves the block's place unwritten).  The block is at mats - PTMI_FRAME_BLOCK_VECS: frame_block_of(mats).
 template <bool LDS_GEOM, bool SWEEP_RECORDS = false>
-__device__ __forceinline__ float4* stage_scene(const DeviceScene& sc, float4* lds, const float4*& nodes, const float4*& prims, const float4*& mats) {
+__device__ __forceinline__ float4* stage_scene(const DeviceScene& sc, float4* lds, const float4*& nodes, const float4*& prims, const float4*& mats,
+                                               const FrameParams* fp = nullptr, const TileMap* tm = nullptr) {
     static_assert(LDS_GEOM || !SWEEP_RECORDS, "the sweep's records exist in LDS only");
     nodes = sc.nodes; prims = sc.prims; mats = sc.mats;
     if (LDS_GEOM) {
         const int n_node_vec = 2 * sc.n_nodes, n_prim_vec = sc.prim_stride * sc.n_prims, n_mat_vec = 3 * sc.n_prims;
+        const int mats_at = n_node_vec + n_prim_vec + (SWEEP_RECORDS ? PTMI_FRAME_BLOCK_VECS : 0);
         if (SWEEP_RECORDS) {
             ptmi_sweep_prepare(reinterpret_cast<const ptmi_vec_bits*>(sc.nodes), sc.n_nodes, reinterpret_cast<const ptmi_vec_bits*>(sc.prims),
                                sc.prim_stride, sc.n_prims, reinterpret_cast<ptmi_vec_bits*>(lds), reinterpret_cast<ptmi_vec_bits*>(lds + n_node_vec),
                                lds_address(lds), (int)threadIdx.x, kBlock);
+            if (fp && threadIdx.x == kBlock - 1)      // one lane of the last wave: the first waves have the most records to prepare
+                ptmi_frame_block_pack(fp->cam_origin, fp->cam_llc, fp->cam_hor, fp->cam_ver, tm->width, tm->height, tm->inv_width, tm->inv_height,
+                                      reinterpret_cast<ptmi_vec_bits*>(lds + n_node_vec + n_prim_vec));
         } else {
             for (int i = threadIdx.x; i < n_node_vec; i += kBlock) lds[i] = sc.nodes[i];
             for (int i = threadIdx.x; i < n_prim_vec; i += kBlock) lds[n_node_vec + i] = sc.prims[i];
         }
-        for (int i = threadIdx.x; i < n_mat_vec; i += kBlock) lds[n_node_vec + n_prim_vec + i] = sc.mats[i];
-        nodes = lds; prims = lds + n_node_vec; mats = lds + n_node_vec + n_prim_vec;
-        lds += n_node_vec + n_prim_vec + n_mat_vec;
+        for (int i = threadIdx.x; i < n_mat_vec; i += kBlock) lds[mats_at + i] = sc.mats[i];
+        nodes = lds; prims = lds + n_node_vec; mats = lds + mats_at;
+        lds += mats_at + n_mat_vec;
         __syncthreads();
     }
     return lds;
 }
+
+// the frame block of a scene staged with SWEEP_RECORDS (mats: what stage_scene handed out)
+__device__ __forceinline__ const float4* frame_block_of(const float4* mats) { return mats - PTMI_FRAME_BLOCK_VECS; }
 
 // kernel tail shared by both bounce kernels: active-path compaction (one atomic per wave reserves queue space, lanes
 // scatter by prefix popcount) and the optional workload counters

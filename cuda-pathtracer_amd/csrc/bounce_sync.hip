@@ -2,6 +2,15 @@
 // Compile with -ffp-contract=off (kernels.hip).
 #include "bounce.h"
 
+// experiment libraries (make ab-lib DEFS=-DPTMI_SWEEP_LATE=0 / -DPTMI_SWEEP_FRAME_BLOCK=0): the sweep's shade step as it was,
+// shade_step; shade_step_sweep with the camera from kernel arguments
+#ifndef PTMI_SWEEP_FRAME_BLOCK
+#define PTMI_SWEEP_FRAME_BLOCK 1
+#endif
+#ifndef PTMI_SWEEP_LATE
+#define PTMI_SWEEP_LATE 1
+#endif
+
 namespace ptmi {
 
 // ---- ptmi_bounce: segment-synchronous form (SWEEP and STACK walks) ------------------------------------------------
@@ -22,7 +31,14 @@ __device__ __forceinline__ void bounce_body(const BounceArgs& a) {
     const int idx = blockIdx.x * kBlock + threadIdx.x;
     const bool active = idx < n_in;
     const float4 *nodes, *prims, *mats;
-    float4* lds = stage_scene<LDS_GEOM, MODE == TRAVERSAL_SWEEP>(a.sc, smem, nodes, prims, mats);
+    float4* lds;
+    if constexpr (MODE == TRAVERSAL_SWEEP) lds = stage_scene<LDS_GEOM, true>(a.sc, smem, nodes, prims, mats, &a.fp, &a.tm);      // with the frame block
+    else lds = stage_scene<LDS_GEOM>(a.sc, smem, nodes, prims, mats);
+    constexpr bool LEAN = MODE == TRAVERSAL_SWEEP && !STATS && !GUIDED;      // shading.h: shade_step
+    constexpr bool LATE = LEAN && PTMI_SWEEP_LATE;                           // shading.h: shade_step_sweep
+    constexpr bool FRAME = LATE && PTMI_SWEEP_FRAME_BLOCK;                   // its camera branch reads the frame block stage_scene laid out
+    FrameBlock fb;
+    if constexpr (FRAME) fb = frame_block(frame_block_of(mats), a.tm);
     int* stack = reinterpret_cast<int*>(lds) + threadIdx.x;
     if (GUIDED) fill_grid_solid_angles();
 
@@ -39,8 +55,11 @@ __device__ __forceinline__ void bounce_body(const BounceArgs& a) {
         if (STATS && alive) cn.rays++;
         const bool hit = scene_intersect<MODE, HAS_QUADS, STATS>(nodes, prims, a.sc.prim_stride, a.sc.n_nodes, stack, alive,
                                                                p.o, p.d, 1e-4f, FLT_MAX, t, k, cn);
-        constexpr bool LEAN = MODE == TRAVERSAL_SWEEP && !STATS && !GUIDED;      // shading.h: shade_step
-        if (alive) alive = shade_step<STATS, GUIDED, false, BATCH, LEAN>(a.fp, a.tm, MatSource{mats, nullptr, nullptr}, a.sc.cdfs, p, hit, t, k, cn, slot);
+        if constexpr (LATE) {
+            if (alive) alive = shade_step_sweep<BATCH, FRAME>(a.fp, a.tm, fb, mats, p, hit, t, k, slot);
+        } else {
+            if (alive) alive = shade_step<STATS, GUIDED, false, BATCH, LEAN>(a.fp, a.tm, MatSource{mats, nullptr, nullptr}, a.sc.cdfs, p, hit, t, k, cn, slot);
+        }
     }
 
     if (active) store_path(a.st, slot, p);

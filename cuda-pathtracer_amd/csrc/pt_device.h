@@ -37,6 +37,34 @@ __device__ __forceinline__ float rng_uniform(Rng& r) {
     return (float)x * 2.3283064e-10f + (2.3283064e-10f / 2.0f);
 }
 
+// The forms below draw the same numbers from the same states; they differ in how the state gets back into its six registers.
+// rng_next under a divergent branch leaves the lanes that drew with the state rotated by one register against the lanes that
+// did not, and the compiler copies at every join behind it.
+// rng_uniform where `draw` holds, in straight-line code: the lanes that do not draw keep their state, by one select per word.
+__device__ __forceinline__ float rng_uniform_if(Rng& r, bool draw) {
+    const uint32_t t = r.v0 ^ (r.v0 >> 2);
+    const uint32_t v = (r.v4 ^ (r.v4 << 4)) ^ (t ^ (t << 1));
+    const uint32_t d = r.d + 362437u;
+    r.v0 = draw ? r.v1 : r.v0; r.v1 = draw ? r.v2 : r.v1; r.v2 = draw ? r.v3 : r.v2; r.v3 = draw ? r.v4 : r.v3;
+    r.v4 = draw ? v : r.v4; r.d = draw ? d : r.d;
+    return (float)(v + d) * 2.3283064e-10f + (2.3283064e-10f / 2.0f);
+}
+// two rng_next in one step: three words move, the two new ones are written where they stay
+__device__ __forceinline__ void rng_next2(Rng& r, uint32_t& x1, uint32_t& x2) {
+    const uint32_t t1 = r.v0 ^ (r.v0 >> 2), t2 = r.v1 ^ (r.v1 >> 2);
+    const uint32_t a = (r.v4 ^ (r.v4 << 4)) ^ (t1 ^ (t1 << 1));
+    const uint32_t b = (a ^ (a << 4)) ^ (t2 ^ (t2 << 1));
+    r.v0 = r.v2; r.v1 = r.v3; r.v2 = r.v4; r.v3 = a; r.v4 = b;
+    r.d += 362437u; x1 = a + r.d;
+    r.d += 362437u; x2 = b + r.d;
+}
+__device__ __forceinline__ void rng_uniform2(Rng& r, float& u1, float& u2) {
+    uint32_t x1, x2;
+    rng_next2(r, x1, x2);
+    u1 = (float)x1 * 2.3283064e-10f + (2.3283064e-10f / 2.0f);
+    u2 = (float)x2 * 2.3283064e-10f + (2.3283064e-10f / 2.0f);
+}
+
 // ---------------------------------------------------------------------------------------------
 // primitive tests
 // ---------------------------------------------------------------------------------------------

@@ -47,10 +47,13 @@ __device__ __forceinline__ f3 camera_dir_raw(const FrameParams& fp, float u, flo
 // is set (1 <= W <= 2^23) the quotient takes ptmi_div_by_size_lean's three operations - the bits of a / W for a in [2^-33, W],
 // shade_lean.h - and where it is 0 the IEEE division.  inv is the same for the whole launch, so this is a scalar branch.
 // tests/test_gpu_shade_lean_forms.py::test_division_by_image_size checks every a for sixteen sizes, and a size above 2^23.
-__device__ __forceinline__ float div_by_size(float a, float W, float inv) {
-    if (inv != 0.0f) return ptmi_div_by_size_lean(a, W, inv);
+// The four-argument form takes the decision from its caller (camera_dir_block: once per launch, in a scalar register); the device
+// hook of that test runs through it as well.
+__device__ __forceinline__ float div_by_size(float a, float W, float inv, bool lean) {
+    if (lean) return ptmi_div_by_size_lean(a, W, inv);
     return a / W;
 }
+__device__ __forceinline__ float div_by_size(float a, float W, float inv) { return div_by_size(a, W, inv, inv != 0.0f); }
 // the per-sample jitter: (x + r1) / width, (y + r2) / height with the two uniforms already drawn; x + r1 lies in [2^-33, width].
 // LEAN: div_by_size (shade_step's tail in the kernels that take the short forms); otherwise the IEEE divisions.
 template <bool LEAN = false>
@@ -58,6 +61,33 @@ __device__ __forceinline__ f3 camera_dir_raw(const FrameParams& fp, const TileMa
     const float u = LEAN ? div_by_size((float)x + r1, (float)tm.width, tm.inv_width) : ((float)x + r1) / (float)tm.width;
     const float v = LEAN ? div_by_size((float)y + r2, (float)tm.height, tm.inv_height) : ((float)y + r2) / (float)tm.height;
     return camera_dir_raw(fp, u, v, o);
+}
+// The frame block a sweep kernel staged in LDS (frame_block.h, bounce.h: stage_scene) and the two decisions of div_by_size, taken
+// once per launch from TileMap's reciprocals: bit 0 width, bit 1 height take the short division.  (bits << 1) != 0 is inv != 0.0f
+// for every float, a NaN included, in scalar integer operations: the value stays in a scalar register and the branch on it scalar.
+struct FrameBlock {
+    const float4* v = nullptr;      // nullptr: a kernel that does not read the block
+    int lean_sizes = 0;
+};
+__device__ __forceinline__ FrameBlock frame_block(const float4* v, const TileMap& tm) {
+    int lean_sizes = ((__float_as_uint(tm.inv_width) << 1) != 0u ? 1 : 0) | ((__float_as_uint(tm.inv_height) << 1) != 0u ? 2 : 0);
+    lean_sizes = __builtin_amdgcn_readfirstlane(lean_sizes);
+    asm("" : "+s"(lean_sizes));      // one scalar register for the length of the kernel, not two kernel arguments fetched again per segment
+    return FrameBlock{v, lean_sizes};
+}
+// camera_dir_raw<true> from the frame block: four broadcast 16-byte LDS reads instead of eighteen scalar kernel arguments, which
+// the segment loop of ptmi_bounce<SWEEP> has no registers for (it parked them in vector lanes and fetched them again per segment),
+// and every operand of the twelve operations in a vector register.  The same expressions on the same bits.
+__device__ __forceinline__ f3 camera_dir_block(const FrameBlock& fb, int x, int y, float r1, float r2, f3& o) {
+    const float4 b0 = fb.v[0], b1 = fb.v[1], b2 = fb.v[2], b3 = fb.v[3];      // (llc, W) (hor, 1 / W) (ver, H) (org, 1 / H)
+    const float a = (float)x + r1, b = (float)y + r2;
+    // read here, not hoisted: in front of the loop the two tests become two 64-bit lane masks, which the loop has no registers for
+    int lean_sizes = fb.lean_sizes;
+    asm volatile("" : "+s"(lean_sizes));
+    const float u = div_by_size(a, b0.w, b1.w, (lean_sizes & 1) != 0);
+    const float v = div_by_size(b, b2.w, b3.w, (lean_sizes & 2) != 0);
+    o = xyz(b3);
+    return xyz(b0) + u * xyz(b1) + v * xyz(b2) - xyz(b3);
 }
 // IEEE 1 / len: nothing bounds the length of a camera's un-normalised direction
 __device__ __forceinline__ void camera_ray_uv(const FrameParams& fp, float u, float v, f3& o, f3& d) {
@@ -373,6 +403,78 @@ __device__ __forceinline__ bool shade_step(const FrameParams& fp, const TileMap&
         // those (pt_vec.h)
         p.d = LEAN ? unit_vector_voted(w) : unit_vector(w);
     }
+    return true;
+}
+
+// shade_step<false, false, false, BATCH, true> as ptmi_bounce<SWEEP> without STATS and GUIDED takes it: the same expressions, the
+// same draws in the same order, every lane the same results - written so that the path state keeps its registers through the
+// segment.  In shade_step the state is assigned inside nested divergent branches, the compiler gives each branch's values
+// registers of their own, and every join copies them back: 62 v_mov_b32 and 4 v_readlane_b32 on the hot path of that kernel's
+// segment loop.  Here
+//   - the decisions (roulette, throughput below the bound, depth limit) are lane flags taken in straight-line code, and each
+//     field of the state is written once, in place, by the lanes the flag selects;
+//   - L is final before tp changes (the scheduler otherwise sinks the emission behind the material's last LDS word and keeps
+//     the old tp alive beside the new one);
+//   - the roulette's draw is rng_uniform_if, the two draws of the tail are rng_uniform2 (pt_device.h);
+//   - FRAME: the next camera ray reads the frame block (camera_dir_block).
+// What the lanes outside a flag compute - a reciprocal of a roulette probability nobody drew against, a material of slot 0 for a
+// lane that hit nothing - is never selected.  A pixel that leaves (return false) stores the fresh path's tp, L and depth, not its
+// last ones: every begin kernel rewrites them.  Between the loop's header and its back edge, outside the walk, the timed triangle
+// build now has 39 v_mov_b32 (was 75 over all blocks, 62 on the hot path), 4 v_readlane_b32 and 4 v_writelane_b32 (8 and 4; all on
+// the sincos vote's cold side now) and no s_load of a kernel argument: `tools/isa_digest.py loop` prints them.
+template <bool BATCH, bool FRAME>
+__device__ __forceinline__ bool shade_step_sweep(const FrameParams& fp, const TileMap& tm, const FrameBlock& fb, const float4* mats, PathRegs& p,
+                                                 bool hit, float t, int k, int slot) {
+    f3 n, bsdf, Le; int row;
+    fetch_material<false>(MatSource{mats, nullptr, nullptr}, hit ? k : 0, n, bsdf, Le, row);
+    const f3 hp = p.o + t * p.d;                                                  // triangle.h:90
+    if (hit) p.L = p.L + p.tp * Le;                                               // integrator.h:204
+    asm("" : "+v"(p.L.x), "+v"(p.L.y), "+v"(p.L.z), "+v"(p.tp.x), "+v"(p.tp.y), "+v"(p.tp.z));
+    // integrator.h:207-212.  1 / rr_prob by the short reciprocal: see shade_step
+    const bool deep = hit && p.depth > 2;
+    const float rr_prob = fminf(fmaxf(p.tp.x, fmaxf(p.tp.y, p.tp.z)), 0.95f);
+    const bool killed = deep && rng_uniform_if(p.rng, deep) > rr_prob;
+    const float inv_rr = rcp_exact_normal(rr_prob);
+    if (deep && !killed) p.tp = mk3(p.tp.x * inv_rr, p.tp.y * inv_rr, p.tp.z * inv_rr);
+    bool end_sample = !hit || killed;                                             // integrator.h:198-201
+    if (!end_sample) p.tp = p.tp * bsdf;                                          // integrator.h:215
+    end_sample = end_sample || length_below_1em5(length_squared(p.tp));           // integrator.h:218, length(tp) < 1e-5f
+    const f3 sn = dot(p.d, n) < 0 ? n : -n;                                       // integrator.h:221-222
+    if (!end_sample) p.depth++;
+    const bool go_on = !end_sample && p.depth < fp.max_depth;
+    if (!end_sample && !go_on) {                                                  // loop bound: the reference has drawn u and v by now
+        uint32_t x1, x2;                                                          // (integrator.h:63-64); the stream moves on, nothing reads them
+        rng_next2(p.rng, x1, x2);
+    }
+    if (!go_on) {
+        p.color = p.color + p.L;                                                  // integrator.h:390
+        p.sample_idx++;
+        // the next iteration of the spp loop starts from a fresh path.  Written here, in place, ahead of the pixel's exit: a pixel
+        // that leaves below then holds what the lanes that go on hold, and no second copy of the state is kept for it
+        p.tp = mk3(1.0f, 1.0f, 1.0f); p.L = mk3(0.0f, 0.0f, 0.0f); p.depth = 0;
+        if (!BATCH) {
+            if (p.sample_idx >= (unsigned int)fp.spp) return false;
+        } else if ((p.sample_idx & fp.sample_mask) >= (unsigned int)fp.spp) {     // the spp loop of this frame is through
+            const unsigned int frame = p.sample_idx >> 16;
+            if (frame + 1u >= (unsigned int)fp.n_frames) return false;
+            // frame batch: see shade_step
+            fp.frame_color[frame * (unsigned int)fp.n_local + (unsigned int)slot] = make_float4(p.color.x, p.color.y, p.color.z, 0.0f);   // < 2^31 (host check)
+            p.sample_idx = (frame + 1u) << 16;
+            p.color = mk3(0.0f, 0.0f, 0.0f);
+        }
+    }
+    // (u, v) of sampleCosineHemisphere where the path goes on, the pixel jitter of the next sample where it ended (shade_step)
+    float r1, r2;
+    rng_uniform2(p.rng, r1, r2);
+    f3 w;
+    if (go_on) {
+        w = cosine_hemisphere<true>(sn, r1, r2);                                  // integrator.h:230
+        p.o = hp + 1e-4f * sn;                                                    // integrator.h:266
+    } else {
+        w = FRAME ? camera_dir_block(fb, p.px, p.py, r1, r2, p.o)                 // next iteration of the spp loop
+                  : camera_dir_raw<true>(fp, tm, p.px, p.py, r1, r2, p.o);
+    }
+    p.d = unit_vector_voted(w);                                                   // ray.h:9-12
     return true;
 }
 

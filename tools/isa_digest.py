@@ -5,6 +5,7 @@ changed no kernel.  No GPU needed.
   python tools/isa_digest.py dump cuda-pathtracer_amd a.json      # compiles every csrc/*.hip for the device only, disassembles
   python tools/isa_digest.py diff parent.json a.json [--skip SUBSTRING]   # --skip: kernels expected to change; their metadata is listed
   python tools/isa_digest.py siblings parent.json a.json SUBSTRING        # a kernel template that gained trailing bool parameters
+  python tools/isa_digest.py loop cuda-pathtracer_amd csrc/bounce_sync.hip SUBSTRING   # register copies in a kernel's segment loop
 
 dump: every .hip is compiled with the Makefile's flags + --cuda-device-only, unbundled, and for each kernel the disassembly
 (comments stripped, trailing padding ignored) and the AMDGPU metadata note (registers, scratch, LDS, kernarg size) are recorded.
@@ -165,8 +166,75 @@ def siblings(a, b, sub):
     return 1 if differ or heavy or len(A) != paired else 0
 
 
+COPIES = ("v_mov_b32", "v_readlane_b32", "v_writelane_b32")
+
+
+def loop_blocks(body):
+    """the basic blocks of one function of hipcc's -S output as (label, innermost loop header or None, is a header, instructions),
+    and each loop header's enclosing headers, from the loop annotations the compiler writes behind every block label"""
+    blocks, parents = [["", None, False, []]], {}
+    lines = body.split("\n")
+    for n, ln in enumerate(lines):
+        lab = re.match(r"^(\.LBB\d+_\d+):(.*)$", ln)
+        if lab:
+            notes = lab.group(2)
+            for more in lines[n + 1:]:                       # a nested header's annotation goes on over comment-only lines
+                if not re.match(r"^\s*;", more):
+                    break
+                notes += more
+            name = lab.group(1)[2:]
+            header = "Loop Header" in notes
+            if header:
+                parents[name] = re.findall(r"Parent Loop (BB\d+_\d+)", notes)
+            inner = name if header else (re.search(r"in Loop: Header=(BB\d+_\d+)", notes) or [None, None])[1]
+            blocks.append([name, inner, header, []])
+            continue
+        ln = ln.split(";")[0].strip()
+        if ln and not ln.startswith(".") and not ln.endswith(":"):
+            blocks[-1][3].append(ln.split()[0])
+    return blocks, parents
+
+
+def loop(pkg, src, sub):
+    """For each kernel whose mangled name holds SUB: its largest outermost loop (a bounce kernel's segment loop), split into the
+    blocks of the loop itself and the blocks of the loops nested in it (the walk), with the instructions that compute nothing.
+    Static counts over all blocks, the rarely taken ones included.  src: a .hip of the package, or a .s that hipcc -S wrote."""
+    if src.endswith(".s"):
+        text = open(src).read()
+    else:
+        pkg = os.path.abspath(pkg)
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "k.s")
+            subprocess.run([os.path.join(ROCM, "bin", "hipcc"), "--offload-arch=" + ARCH, *makefile_flags(pkg), "--cuda-device-only", "-S", src,
+                            "-o", out], check=True, cwd=pkg)
+            text = open(out).read()
+    found = 0
+    for m in re.finditer(r"^(\w+):\s*; @\1\n(.*?)^\.Lfunc_end\d+:", text, re.M | re.S):
+        if sub not in m.group(1):
+            continue
+        found += 1
+        blocks, parents = loop_blocks(m.group(2))
+        outer = [h for h, ps in parents.items() if not ps]
+        size = {h: sum(len(b[3]) for b in blocks if b[1] and (b[1] == h or h in parents[b[1]])) for h in outer}
+        if not size:
+            print("%s: no loop" % m.group(1))
+            continue
+        h = max(size, key=size.get)
+        own = [op for b in blocks if b[1] == h for op in b[3]]
+        nested = [op for b in blocks if b[1] and b[1] != h and h in parents[b[1]] for op in b[3]]
+        print("%s\n  loop at %s" % (m.group(1), h))
+        for tag, ops in (("outside its inner loops", own), ("in its inner loops", nested)):
+            print("  %-24s %4d instructions, %4d VALU:  %s  v_cndmask %d;  s_load %d  s_mov %d  s_waitcnt %d  ds_read %d" % (
+                tag, len(ops), sum(1 for op in ops if op.startswith("v_")), "  ".join("%s %d" % (c, sum(1 for op in ops if op.startswith(c))) for c in COPIES),
+                sum(1 for op in ops if op.startswith("v_cndmask")), sum(1 for op in ops if op.startswith("s_load")),
+                sum(1 for op in ops if op.startswith("s_mov")), ops.count("s_waitcnt"), sum(1 for op in ops if op.startswith("ds_read"))))
+    return 0 if found else 1
+
+
 if __name__ == "__main__":
-    if len(sys.argv) >= 4 and sys.argv[1] == "dump":
+    if len(sys.argv) == 5 and sys.argv[1] == "loop":
+        sys.exit(loop(sys.argv[2], sys.argv[3], sys.argv[4]))
+    elif len(sys.argv) >= 4 and sys.argv[1] == "dump":
         dump(sys.argv[2], sys.argv[3], sys.argv[4:])
     elif len(sys.argv) >= 4 and sys.argv[1] == "diff":
         sys.exit(diff(sys.argv[2], sys.argv[3], sys.argv[5] if len(sys.argv) > 5 and sys.argv[4] == "--skip" else None))

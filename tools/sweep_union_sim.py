@@ -21,7 +21,8 @@ Reported, per wave-segment:
   the estimated traversal instructions (31 per node pass, 31 per first half, 28 per second half - the kernel's ISA) when
   the 256 rays of a workgroup are sorted by a key before they are cut into waves, relative to today's order;
   how many second-half passes remain if a lane latches one pending second half and the wave flushes only when a lane needs
-  a second latch or the leaf ends (closest_t must be final before the next slab test).
+  a second latch or the leaf ends (closest_t must be final before the next slab test); if every lane keeps a list of its own and
+  works it off at the leaf's end; if the wave keeps one queue across its lanes; and the bound, every leaf packed 64 to a pass.
 """
 import argparse
 import os
@@ -164,6 +165,30 @@ def latched_passes(sel, second, leaf_cols):
     return passes
 
 
+def queue_passes(sel, second, leaf_cols, cap=64):
+    """second-half passes of each wave with a per-wave queue across lanes: a leaf's (lane, triangle) second halves join the queue
+    triangle by triangle; when it holds more than `cap` items it is worked off, 64 items to a pass, before the next triangle joins,
+    and again at the leaf's end (closest_t must be final before the next slab test).  cap = 0 is today's pass per triangle."""
+    passes = np.zeros(len(sel), np.int64)
+    for cols in leaf_cols:
+        q = np.zeros(len(sel), np.int64)
+        for c in cols:
+            full = q > cap
+            passes += np.where(full, -(-q // WAVE), 0); q[full] = 0
+            q += second[sel, c].sum(1)
+        passes += -(-q // WAVE)
+    return passes
+
+
+def private_rounds(sel, second, leaf_cols):
+    """second-half passes of each wave when every lane keeps its own pending second halves of the leaf and works them off at the
+    leaf's end, one per round: the rounds of a leaf are the most any lane of the wave holds"""
+    rounds = np.zeros(len(sel), np.int64)
+    for cols in leaf_cols:
+        rounds += second[sel][:, :, cols].sum(2).max(1)
+    return rounds
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scene", default="cbox.obj"); ap.add_argument("--width", type=int, default=1024); ap.add_argument("--height", type=int, default=1024)
@@ -192,7 +217,7 @@ def main():
     today = np.arange(n).reshape(-1, WAVE)
     keys = ["direction octant", "major axis", "octant + origin primitive", "origin primitive", "camera / bounce", "identical node sets"]
     tot = {k: 0.0 for k in ["today"] + keys}
-    acc = dict(nodes=0, first=0, second=0, latched=0, waves=0, lanes_node=0.0, lanes_first=0.0, lanes_second=0.0,
+    acc = dict(nodes=0, first=0, second=0, latched=0, queued=0, private=0, packed=0, waves=0, lanes_node=0.0, lanes_first=0.0, lanes_second=0.0,
                ray_first=0, ray_second=0, rays=0, lanes_at_leaf=0.0, leaves=0)
     for seg in range(a.segments):
         hit, t, nodes, first, second, leaf_cols = walk.run(o, d)
@@ -200,6 +225,8 @@ def main():
             un, uf, us = union_cost(today, nodes, first, second)
             acc["nodes"] += un.sum(); acc["first"] += uf.sum(); acc["second"] += us.sum(); acc["waves"] += len(today)
             acc["latched"] += latched_passes(today, second, leaf_cols).sum()
+            acc["queued"] += queue_passes(today, second, leaf_cols).sum(); acc["private"] += private_rounds(today, second, leaf_cols).sum()
+            acc["packed"] += sum(-(-second[today][:, :, cols].sum((1, 2)) // WAVE) for cols in leaf_cols).sum()
             acc["lanes_node"] += nodes.sum() / WAVE; acc["lanes_first"] += first.sum() / WAVE; acc["lanes_second"] += second.sum() / WAVE
             acc["ray_first"] += first.sum(); acc["ray_second"] += second.sum(); acc["rays"] += n
             for cols in leaf_cols:
@@ -253,6 +280,8 @@ def main():
     print(f"a ray passes the (a, u) test for {acc['ray_second'] / acc['rays']:.1f} of its {acc['ray_first'] / acc['rays']:.1f} triangle tests; "
           f"{acc['lanes_at_leaf'] / max(acc['leaves'], 1):.1f} lanes at a leaf the wave enters")
     print(f"second-half passes with a one-deep latch and flush on conflict: {acc['latched'] / w:.1f} against {acc['second'] / w:.1f} today")
+    print(f"lane-private pending lists, worked off at the leaf's end: {acc['private'] / w:.1f}; a per-wave queue across lanes, worked off above "
+          f"{WAVE} items and at the leaf's end: {acc['queued'] / w:.1f}; every leaf's second halves packed {WAVE} to a pass: {acc['packed'] / w:.1f}")
     print("| regrouping key (256 rays sorted, then cut into waves) | relative traversal cost |")
     print("|---|---|")
     for k in keys:
