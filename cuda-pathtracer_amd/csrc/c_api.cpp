@@ -437,6 +437,11 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
             need(cfg->sampling_mode == 0, "specular surfaces are set: they need sampling_mode 0 (BSDF): the guided modes sample a diffuse lobe at every vertex");
             need(cfg->fast_tree == 0, "specular surfaces are set: they need fast_tree 0: specular frames always trace the reference's hits");
         }
+        if (c->app.scene.hasVertexNormals()) {
+            need(cfg->integrator == 0, "vertex normals are set: they need integrator 0 (PathTracing): the Radiosity view shades nothing");
+            need(cfg->sampling_mode == 0, "vertex normals are set: they need sampling_mode 0 (BSDF): the guided modes' grids lie about the stored normal");
+            need(cfg->fast_tree == 0, "vertex normals are set: they need fast_tree 0: frames with vertex normals always trace the reference's hits");
+        }
         AppConfig& a = c->app.config;                    // every check is above this line: a rejected config changes nothing
         a.spp = cfg->spp; a.max_depth = cfg->max_depth; a.sampling_mode = (SamplingMode)cfg->sampling_mode;
         a.mis_bsdf_fraction = cfg->mis_bsdf_fraction;
@@ -544,6 +549,54 @@ int ptmi_surfaces_info(const ptmi_ctx* c, int* n_mirror, int* n_glass) {
         need(c != nullptr, "ctx is NULL");
         if (n_mirror) *n_mirror = c->app.scene.n_mirror;
         if (n_glass) *n_glass = c->app.scene.n_glass;
+    });
+}
+
+int ptmi_check_vertex_normals(int n_prims, const float* normals) {
+    return guarded([&] { checkVertexNormals(n_prims, normals); });
+}
+int ptmi_host_classify_vertex_normals(int n_prims, const int* type, const float* stored, const float* normals, int* smooth, int* n_smooth) {
+    return guarded([&] {
+        need(type && stored, "NULL argument");
+        checkVertexNormals(n_prims, normals);
+        std::vector<Primitive> prims((size_t)n_prims);
+        for (int i = 0; i < n_prims; i++) {
+            need(type[i] == 0 || type[i] == 1, "type must be 0 (triangle) or 1 (quad)");
+            prims[i].type = type[i] ? PRIM_QUAD : PRIM_TRIANGLE;
+            prims[i].normal = mk3(stored[3 * i], stored[3 * i + 1], stored[3 * i + 2]);
+        }
+        checkVertexNormals(prims, n_prims, normals);
+        std::vector<unsigned char> s;
+        const int count = classifyVertexNormals(prims, normals, s);
+        if (smooth) for (int i = 0; i < n_prims; i++) smooth[i] = s[i];
+        if (n_smooth) *n_smooth = count;
+    });
+}
+int ptmi_set_vertex_normals(ptmi_ctx* c, int n_prims, const float* normals) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        need(c->app.scene.d_nodes != nullptr, "no scene loaded");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        std::vector<unsigned char> smooth;
+        int smooth_count = 0;
+        if (normals) {
+            checkVertexNormals(c->app.scene.h_primitives, n_prims, normals);
+            smooth_count = classifyVertexNormals(c->app.scene.h_primitives, normals, smooth);
+            if (smooth_count > 0) {
+                const AppConfig& a = c->app.config;
+                need(a.current_integrator == IntegratorType::PathTracing, "vertex normals: the config has integrator 1 (Radiosity), which shades nothing");
+                need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "vertex normals: the config has a guided sampling_mode, whose grids lie about the stored normal");
+                need(!a.fast_tree, "vertex normals: the config has fast_tree 1; frames with vertex normals always trace the reference's hits");
+            }
+        }
+        c->app.scene.setVertexNormals(normals, smooth, smooth_count);   // every check is done before anything changes
+        viewChanged(c->app);                                         // other shading: the temporal history holds another image
+    });
+}
+int ptmi_vertex_normals_info(const ptmi_ctx* c, int* n_smooth) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        if (n_smooth) *n_smooth = c->app.scene.n_smooth;
     });
 }
 
@@ -1052,6 +1105,36 @@ int ptmi_debug_nee_call(ptmi_ctx* c, int op, int n, const float* in, float* out_
         PTMI_HIP(hipGetLastError());
         PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
         d_f.download(out_f, (size_t)n * kNeeCallOutF); d_i.download(out_i, (size_t)n * kNeeCallOutI);
+    });
+}
+
+int ptmi_debug_vertex_normal(ptmi_ctx* c, int n, const int* prim, const float* p, float* out) {
+    return guarded([&] {
+        need(c && prim && p && out, "NULL argument");
+        need(n >= 0, "n must not be negative");
+        const SceneState& sc = c->app.scene;
+        need(sc.d_nodes != nullptr, "no scene loaded");
+        const int n_prims = (int)sc.h_primitives.size();
+        for (int i = 0; i < n; i++) need(prim[i] >= 0 && prim[i] < n_prims, "prim out of range");
+        if (n == 0) return;
+        if (!sc.hasVertexNormals()) {                         // no table: the kernel never calls the function
+            for (int i = 0; i < n; i++) {
+                const f3 s = sc.h_primitives[prim[i]].normal;
+                out[4 * i] = s.x; out[4 * i + 1] = s.y; out[4 * i + 2] = s.z; out[4 * i + 3] = 0.0f;
+            }
+            return;
+        }
+        std::vector<int> slot_of((size_t)n_prims), slots((size_t)n);
+        for (int k = 0; k < n_prims; k++) slot_of[sc.bvh_indices[k]] = k;
+        for (int i = 0; i < n; i++) slots[i] = slot_of[prim[i]];
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<int> d_s((size_t)n);
+        DevBuf<float> d_p(3 * (size_t)n), d_o(4 * (size_t)n);
+        d_s.upload(slots.data(), (size_t)n); d_p.upload(p, 3 * (size_t)n);
+        launch_debug_vertex_normal(sc.d_scene, sc.vertexNormalTable(), n, d_s.p, d_p.p, d_o.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d_o.download(out, 4 * (size_t)n);
     });
 }
 

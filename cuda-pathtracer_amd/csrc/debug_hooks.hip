@@ -2,6 +2,7 @@
 // one call per case.  Compile with -ffp-contract=off (kernels.hip).
 #include "bounce.h"
 #include "light_sample.h"
+#include "vertex_normal.h"
 #include "../../include/ptmi.h"      // PTMI_MATH_*
 
 namespace ptmi {
@@ -426,6 +427,25 @@ void launch_debug_nee_call(bool has_quads, int n, int op, const EmitterTable& em
     if (n <= 0) return;
     with_bool(has_quads, [&](auto quads) {
         hipLaunchKernelGGL(ptmi_debug_nee_call_k<decltype(quads)::value>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n, op, em, ev, in, out_f, out_i);
+    });
+}
+
+// vertex_normal (vertex_normal.h) as ptmi_render_nee calls it - nrm comes in as the slot's stored normal - on n (leaf-order slot,
+// point) cases against the context's own scene and table (test hook; include/ptmi.h: ptmi_debug_vertex_normal)
+template <bool HAS_QUADS>
+__global__ __launch_bounds__(kBlock) void ptmi_debug_vertex_normal_k(DeviceScene sc, VertexNormalTable vn, int n, const int* __restrict__ slots,
+                                                                     const float* __restrict__ p, float* __restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int k = slots[i];
+    f3 nrm = xyz(sc.mats[3 * k]);
+    const bool smooth = vertex_normal<HAS_QUADS>(sc, vn, k, mk3(p[3 * i], p[3 * i + 1], p[3 * i + 2]), nrm);
+    out[4 * i] = nrm.x; out[4 * i + 1] = nrm.y; out[4 * i + 2] = nrm.z; out[4 * i + 3] = smooth ? 1.0f : 0.0f;
+}
+void launch_debug_vertex_normal(const DeviceScene& sc, const VertexNormalTable& vn, int n, const int* slots, const float* p, float* out, hipStream_t s) {
+    if (n <= 0) return;
+    with_bool(sc.has_quads != 0, [&](auto quads) {
+        hipLaunchKernelGGL(ptmi_debug_vertex_normal_k<decltype(quads)::value>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, vn, n, slots, p, out);
     });
 }
 

@@ -330,13 +330,23 @@ struct EnvTable {
 struct SurfaceTable {
     const float2* rec = nullptr;
 };
-// fp.n_frames x spp samples per queued pixel.  env.texel == nullptr and surf.rec == nullptr: the NEE kernel exactly as it was;
-// that instantiation IGNORES next_event (the host routes a frame here only when it is set, and the switch folds to true).  Else
-// the ENV and / or SPEC instantiation, which reads next_event and runs either estimator, looks the map up where a path ray
-// misses and continues a path through mirror and glass.  rough: the table holds a rough-metal record (SURF = 2; else the
-// delta kinds' SURF = 1, which never reads a kind 3).
-void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, bool rough, bool next_event,
-                       const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s);
+// ---- vertex normals (include/ptmi.h: ptmi_set_vertex_normals) ---------------------------------------------------------------
+// S = DeviceScene::prim_stride float4 per LEAF-ORDER slot, the order of prims (SceneState::setVertexNormals permutes the caller's
+// load-order table): rec[S * k + c] = (corner c's normal.xyz, c == 0 ? bits(1 smooth | 0 flat) : 0), corners in the order of the
+// primitive's vertices; a triangle's 4th entry in a scene with quads is zero.  An array of its own, as SurfaceTable is and for the
+// same reason.  rec == nullptr: every primitive is flat (no table, or a table without a smooth primitive).
+struct VertexNormalTable {
+    const float4* rec = nullptr;
+};
+// fp.n_frames x spp samples per queued pixel.  env.texel == nullptr, surf.rec == nullptr and vn.rec == nullptr: the NEE kernel
+// exactly as it was; that instantiation IGNORES next_event (the host routes a frame here only when it is set, and the switch folds
+// to true).  Else the ENV, SPEC and / or SMOOTH instantiation, which reads next_event and runs either estimator, looks the map up
+// where a path ray misses, continues a path through mirror and glass and shades a smooth primitive's vertex with the interpolated
+// normal (csrc/vertex_normal.h).  rough: the table holds a rough-metal record (SURF = 2; else the delta kinds' SURF = 1, which
+// never reads a kind 3).
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, const VertexNormalTable& vn,
+                       bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first,
+                       hipStream_t s);
 
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)
@@ -407,5 +417,8 @@ void launch_debug_grid_index(int n, const float* dirs, const float* normals, int
 constexpr int kNeeCallIn = 16, kNeeCallOutF = 16, kNeeCallOutI = 4;
 void launch_debug_nee_call(bool has_quads, int n, int op, const EmitterTable& em, const EnvTable& ev, const float* in /* n * kNeeCallIn */,
                            float* out_f /* n * kNeeCallOutF */, int* out_i /* n * kNeeCallOutI */, hipStream_t s);
+// ptmi_debug_vertex_normal (include/ptmi.h): vertex_normal (vertex_normal.h) of leaf-order slot slots[i] at p[3i ..] -> out[4i ..]
+void launch_debug_vertex_normal(const DeviceScene& sc, const VertexNormalTable& vn, int n, const int* slots, const float* p, float* out /* 4n */,
+                                hipStream_t s);
 
 }  // namespace ptmi

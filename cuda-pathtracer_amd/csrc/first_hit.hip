@@ -1,6 +1,7 @@
 // first_hit.hip — the kernels that trace one ray at a time to its first hit (traversal.h: first_hit): the Radiosity view, the
 // feature pass and next-event estimation.  Compile with -ffp-contract=off (kernels.hip).
 #include "light_sample.h"
+#include "vertex_normal.h"
 
 namespace ptmi {
 
@@ -135,9 +136,12 @@ void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams
 // SURF (include/ptmi.h: "rough metal"): 0 no table; 1 a table of mirror and glass only (SPEC); 2 a table with a rough-metal
 // primitive as well: such a vertex draws what a diffuse one draws, its light sample evaluates the GGX lobe and its BSDF sample
 // comes from rough.h; both are computed here, before the shadow walk, so only `ended` joins the state that crosses a walk.
-template <int MODE, bool HAS_QUADS, bool ENV, int SURF>
+// SMOOTH (include/ptmi.h: "vertex normals"; the table: device_scene.h VertexNormalTable): the context has a table with a smooth
+// primitive; a vertex on one takes the normal interpolated at the hit point (vertex_normal.h) where sn is formed, and everything
+// below reads it from there.  The emitter pdf above keeps the geometric normal.
+template <int MODE, bool HAS_QUADS, bool ENV, int SURF, bool SMOOTH>
 __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, EmitterTable em, EnvTable ev, SurfaceTable sf, TileMap tm, PathState st, FrameParams fp,
-                                                          const int* __restrict__ queue, int n, int first, int next_event) {
+                                                          const int* __restrict__ queue, int n, int first, int next_event, VertexNormalTable vn) {
     extern __shared__ float4 smem[];
     constexpr bool SPEC = SURF != 0;
     const int idx = blockIdx.x * kBlock + threadIdx.x;
@@ -149,8 +153,8 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     Rng rng = {e.x, e.y, e.z, e.w, f.x, f.y};
     f3 color = first ? mk3(0.0f, 0.0f, 0.0f) : xyz(st.D[slot]);
     LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
-    // wave-uniform switches of the ENV and SPEC instantiations; without either they fold to the NEE kernel
-    const bool nee_on = ENV || SPEC ? next_event != 0 : true;   // light samples and MIS weights at all
+    // wave-uniform switches of the ENV, SPEC and SMOOTH instantiations; without any of them they fold to the NEE kernel
+    const bool nee_on = ENV || SPEC || SMOOTH ? next_event != 0 : true;   // light samples and MIS weights at all
     const bool env_on = ENV ? ev.sampled != 0 : false;       // the environment is one of the lights: five draws, selection by q
     const float q = ENV ? ev.q : 0.0f, omq = 1.0f - q;
     for (int frame = 0; frame < fp.n_frames; frame++) {
@@ -190,7 +194,8 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                     }
                     break;
                 }
-                const f3 nrm = xyz(sc.mats[3 * k]), bsdf = xyz(sc.mats[3 * k + 1]), Le = xyz(sc.mats[3 * k + 2]);
+                f3 nrm = xyz(sc.mats[3 * k]);
+                const f3 bsdf = xyz(sc.mats[3 * k + 1]), Le = xyz(sc.mats[3 * k + 2]);
                 const f3 hp = o + t * d;                                                  // triangle.h:90
                 const float4 pe = depth > 0 && nee_on && !(SPEC && spec_prev) ? em.pdf_area[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 const float pa = pe.w;
@@ -209,6 +214,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                 }
                 tp = tp * bsdf;                                                           // integrator.h:215
                 if (length(tp) < 1e-5f) break;                                            // integrator.h:218
+                if constexpr (SMOOTH) vertex_normal<HAS_QUADS>(sc, vn, k, hp, nrm);       // after the throughput exit, not at the hit
                 const f3 sn = dot(d, nrm) < 0 ? nrm : -nrm;                               // integrator.h:221-222
                 const f3 o2 = hp + 1e-4f * sn;                                            // integrator.h:266
                 [[maybe_unused]] bool rough = false;                                      // SURF = 2: this vertex is rough metal (rv)
@@ -312,15 +318,19 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     st.F[slot] = make_uint2(rng.v4, rng.d);
 }
 
-void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, bool rough, bool next_event,
-                       const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s) {
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, const VertexNormalTable& vn,
+                       bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first,
+                       hipStream_t s) {
     if (n <= 0) return;
     first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
         with_bool(env.texel != nullptr, [&](auto with_env) {
             auto launch = [&](auto surf_kinds) {
-                hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value, decltype(surf_kinds)::value>),
-                                   dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, surf, tm, st, fp, queue, n, first ? 1 : 0,
-                                   next_event ? 1 : 0);
+                with_bool(vn.rec != nullptr, [&](auto smooth) {
+                    hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value, decltype(surf_kinds)::value,
+                                                        decltype(smooth)::value>),
+                                       dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, surf, tm, st, fp, queue, n, first ? 1 : 0,
+                                       next_event ? 1 : 0, vn);
+                });
             };
             if (surf.rec == nullptr) launch(std::integral_constant<int, 0>{});
             else if (!rough) launch(std::integral_constant<int, 1>{});

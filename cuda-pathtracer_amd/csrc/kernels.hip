@@ -17,7 +17,9 @@
 //                      ptmi_render_nee    opt-in next-event estimation with MIS (include/ptmi.h): one lane runs a pixel's samples to their end;
 //                                         its ENV instantiation renders every frame of a context with an environment (ptmi_set_environment),
 //                                         its SURF = 1 instantiation every frame of a scene with a mirror or glass primitive (ptmi_set_surfaces),
-//                                         SURF = 2 with a rough-metal primitive as well (ptmi_set_surfaces_rough; rough.h)
+//                                         SURF = 2 with a rough-metal primitive as well (ptmi_set_surfaces_rough; rough.h),
+//                                         its SMOOTH instantiation every frame of a scene with a smooth primitive (ptmi_set_vertex_normals;
+//                                         vertex_normal.h)
 //   debug_hooks.hip    the test hooks
 #include "bounce.h"
 

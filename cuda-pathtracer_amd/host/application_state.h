@@ -18,6 +18,7 @@
 #include "bvh.h"
 #include "environment.h"
 #include "surfaces.h"
+#include "vertex_normals.h"
 #include "file_manager.h"
 #include "pbrt_loader.h"
 #include "sensor.h"
@@ -147,6 +148,16 @@ struct SceneState {
     // checked by the caller (checkSurfaces / checkSurfacesRough); kind nullptr drops the table; roughness nullptr: 0.3
     void setSurfaces(const int* kind, const float* ior, const float* roughness = nullptr);
     SurfaceTable surfaceTable() const { SurfaceTable t; t.rec = d_surfaces; return t; }
+    // vertex normals (include/ptmi.h: ptmi_set_vertex_normals): the caller's load-order table by leaf-order slot (csrc/device_scene.h:
+    // VertexNormalTable).  It goes with the scene (cleanup).  A table without a smooth primitive is kept as no table:
+    // d_vertex_normals stays nullptr and a frame takes the route it takes without one.
+    int n_smooth = 0;
+    float4* d_vertex_normals = nullptr;
+    bool hasVertexNormals() const { return d_vertex_normals != nullptr; }
+    // checked and classified by the caller (checkVertexNormals, classifyVertexNormals: smooth per load-order primitive and their
+    // number); normals nullptr, or no smooth primitive, drops the table
+    void setVertexNormals(const float* normals, const std::vector<unsigned char>& smooth, int smooth_count);
+    VertexNormalTable vertexNormalTable() const { VertexNormalTable t; t.rec = d_vertex_normals; return t; }
     int sweep_max_prims = 64;                        // scenes up to this many primitives use the wave-uniform sweep
     int force_traversal = -1;                        // test/benchmark override (TraversalMode), -1 = automatic
 

@@ -23,6 +23,8 @@ void SceneState::cleanup() {
     if (d_surfaces) (void)hipFree(d_surfaces);
     d_surfaces = nullptr; n_mirror = n_glass = 0;
     for (int& c : surface_counts) c = 0;
+    if (d_vertex_normals) (void)hipFree(d_vertex_normals);
+    d_vertex_normals = nullptr; n_smooth = 0;
     d_emit_rec = d_pdf_area = nullptr; d_emit_cdf = nullptr; d_emitters = EmitterTable();
     h_emit_prim.clear(); h_emit_cdf.clear(); h_emit_normal.clear(); h_pdf_area.clear(); h_emit_total = 0.0f;
     freePacked();
@@ -536,6 +538,33 @@ void SceneState::setSurfaces(const int* kind, const float* ior, const float* rou
     const bool table = nd != nullptr;
     surface_counts[0] = table ? n - mirrors - glasses - roughs : 0;
     surface_counts[1] = mirrors; surface_counts[2] = glasses; surface_counts[3] = roughs;
+}
+
+// vertex normals (include/ptmi.h: ptmi_set_vertex_normals): prim_stride entries per leaf-order slot, as upload() lays out prims
+void SceneState::setVertexNormals(const float* normals, const std::vector<unsigned char>& smooth, int smooth_count) {
+    if (!d_nodes) throw ArgError("setVertexNormals: no scene loaded");
+    const int n = (int)h_primitives.size();
+    const int stride = d_scene.prim_stride;
+    float4* nd = nullptr;
+    if (!normals) smooth_count = 0;
+    else if (smooth.size() != (size_t)n) throw ArgError("setVertexNormals: the classification does not match the scene");
+    if (smooth_count > 0) {
+        auto bits = [](int i) { float f; std::memcpy(&f, &i, 4); return f; };
+        std::vector<float4> slot((size_t)stride * n, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        for (int k = 0; k < n; k++) {                    // same leaf-order slots as prims/mats
+            const int src = bvh_indices[k];
+            const int read = h_primitives[src].type == PRIM_QUAD ? 4 : 3;
+            for (int c = 0; c < read && c < stride; c++) {
+                const float* v = normals + ((size_t)src * kVertexNormalCorners + (size_t)c) * 3;
+                slot[(size_t)stride * k + c] = make_float4(v[0], v[1], v[2], c == 0 ? bits(smooth[src]) : 0.0f);
+            }
+        }
+        nd = (float4*)hipMallocSafe(slot.size() * sizeof(float4), "d_vertex_normals");
+        const hipError_t e = hipMemcpy(nd, slot.data(), slot.size() * sizeof(float4), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(nd); PTMI_HIP(e); }
+    }
+    if (d_vertex_normals) (void)hipFree(d_vertex_normals);   // nothing has changed before this line
+    d_vertex_normals = nd; n_smooth = smooth_count;
 }
 
 // RadiosityState: host/radiosity_state.cpp

@@ -44,6 +44,8 @@ EXPORTS = [
     "ptmi_default_env_params", "ptmi_check_env_params", "ptmi_set_environment", "ptmi_environment_info", "ptmi_host_env_table",
     "ptmi_check_surfaces", "ptmi_set_surfaces", "ptmi_surfaces_info",
     "ptmi_check_surfaces_rough", "ptmi_set_surfaces_rough", "ptmi_surface_counts",
+    "ptmi_check_vertex_normals", "ptmi_host_classify_vertex_normals", "ptmi_set_vertex_normals", "ptmi_vertex_normals_info",
+    "ptmi_debug_vertex_normal",
 ]
 
 
@@ -252,6 +254,12 @@ def lib():
         L.ptmi_check_surfaces_rough.argtypes = [C.c_int, vp, vp, vp]
         L.ptmi_set_surfaces_rough.argtypes = [vp, C.c_int, vp, vp, vp]
         L.ptmi_surface_counts.argtypes = [vp, vp]
+        if hasattr(L, "ptmi_set_vertex_normals"):      # an A/B library (PTMI_LIB) built from an older commit has none of them
+            L.ptmi_check_vertex_normals.argtypes = [C.c_int, vp]
+            L.ptmi_host_classify_vertex_normals.argtypes = [C.c_int, vp, vp, vp, vp, ip]
+            L.ptmi_set_vertex_normals.argtypes = [vp, C.c_int, vp]
+            L.ptmi_vertex_normals_info.argtypes = [vp, ip]
+            L.ptmi_debug_vertex_normal.argtypes = [vp, C.c_int, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -471,6 +479,34 @@ def check_surfaces(kind, ior=None, roughness=None):
     _check(lib().ptmi_check_surfaces_rough(len(kind), kind.ctypes.data, _ptr(ior), roughness.ctypes.data))
 
 
+def _normal_table(normals):
+    normals = np.ascontiguousarray(normals, np.float32)
+    if normals.ndim != 3 or normals.shape[1:] != (4, 3):
+        raise ValueError("vertex normals must be (n_prims, 4, 3)")
+    return normals
+
+
+def check_vertex_normals(normals):
+    """ptmi_check_vertex_normals: raises PtmiError for a table ptmi_set_vertex_normals would reject on its own account (host
+    only): no primitive, or a NaN or infinite component in corners 0 .. 2.  normals (n_prims, 4, 3)."""
+    normals = _normal_table(normals)
+    _check(lib().ptmi_check_vertex_normals(len(normals), normals.ctypes.data))
+
+
+def classify_vertex_normals(types, stored, normals):
+    """ptmi_host_classify_vertex_normals: (n_prims,) bool, True where a primitive is smooth - a corner normal that is read differs
+    (==) from its stored normal (host only).  types (n_prims,), stored (n_prims, 3), normals (n_prims, 4, 3)."""
+    normals = _normal_table(normals)
+    types = np.ascontiguousarray(types, np.int32); stored = np.ascontiguousarray(stored, np.float32)
+    if types.shape != (len(normals),) or stored.shape != (len(normals), 3):
+        raise ValueError("types must be (n_prims,) and stored (n_prims, 3)")
+    smooth = np.zeros(len(normals), np.int32); count = C.c_int()
+    _check(lib().ptmi_host_classify_vertex_normals(len(normals), types.ctypes.data, stored.ctypes.data, normals.ctypes.data,
+                                                   smooth.ctypes.data, C.byref(count)))
+    assert count.value == int(smooth.sum())
+    return smooth.astype(bool)
+
+
 class Renderer:
     """One ApplicationState bound to one GPU."""
 
@@ -652,6 +688,35 @@ class Renderer:
         m, g = C.c_int(), C.c_int()
         self._ck(self.L.ptmi_surfaces_info(self.h, C.byref(m), C.byref(g)))
         return dict(n_mirror=m.value, n_glass=g.value)
+
+    def set_vertex_normals(self, normals):
+        """Smooth shading (include/ptmi.h: "vertex normals"): normals (n_prims, 4, 3), a primitive's corner normals in load order
+        and in the corner order of its vertices (a triangle's 4th is ignored), or None to drop the table.  A primitive whose
+        corner normals all equal its stored normal stays flat.  A scene load drops the table."""
+        if normals is None:
+            self._ck(self.L.ptmi_set_vertex_normals(self.h, 0, None))
+            return
+        normals = _normal_table(normals)
+        self._ck(self.L.ptmi_set_vertex_normals(self.h, len(normals), normals.ctypes.data))
+
+    def vertex_normals_info(self):
+        """ptmi_vertex_normals_info: the number of smooth primitives, 0 without a table"""
+        n = C.c_int()
+        self._ck(self.L.ptmi_vertex_normals_info(self.h, C.byref(n)))
+        return dict(n_smooth=n.value)
+
+    check_vertex_normals = staticmethod(check_vertex_normals)
+
+    def debug_vertex_normal(self, prim, p):
+        """ptmi_debug_vertex_normal: the kernel's shading normal of load-order primitives prim (n,) at the points p (n, 3) on the
+        loaded scene and table.  Returns (n, 4) float32: N, then 1.0 where it was interpolated and 0.0 where the vertex keeps
+        the stored normal."""
+        prim = np.ascontiguousarray(prim, np.int32); p = np.ascontiguousarray(p, np.float32)
+        if prim.ndim != 1 or p.shape != (len(prim), 3):
+            raise ValueError("prim must be (n,) and p (n, 3)")
+        out = np.zeros((len(prim), 4), np.float32)
+        self._ck(self.L.ptmi_debug_vertex_normal(self.h, len(prim), prim.ctypes.data, p.ctypes.data, out.ctypes.data))
+        return out
 
     def camera_frame(self):
         out = np.zeros(12, np.float32)

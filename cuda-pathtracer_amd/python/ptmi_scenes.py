@@ -77,6 +77,15 @@ def cornell_blocks(prims, short=1, tall=2):
     or not, triangles or quads.  The blocks are found from the geometry: primitives that share a corner form a body; a block is
     a body that emits nothing and keeps clear of the scene's bounding box in x and z (walls, floor, ceiling and back wall reach
     it); the lower of the two is the short one."""
+    kind = np.zeros(len(prims["type"]), np.int32)
+    members_short, members_tall = _cornell_block_members(prims)
+    kind[members_short] = short
+    kind[members_tall] = tall
+    return kind
+
+
+def _cornell_block_members(prims):
+    """the primitive indices of the Cornell box's short and tall block (cornell_blocks says how they are found)"""
     types = np.asarray(prims["type"]); le = np.asarray(prims["Le"])
     # corners are joined where their float32 coordinates are EQUAL (+ 0.0 makes -0.0 and 0.0 one key): the loaders copy a shared
     # vertex bit for bit and subdivision takes the midpoint of the same two corners on both sides of an edge.  A scene whose
@@ -111,7 +120,123 @@ def cornell_blocks(prims, short=1, tall=2):
     if len(blocks) != 2:
         raise ValueError(f"cornell_blocks: expected two blocks, found {len(blocks)} candidate bodies")
     blocks.sort(key=lambda b: b[0])
-    kind = np.zeros(n, np.int32)
-    kind[blocks[0][1]] = short
-    kind[blocks[1][1]] = tall
-    return kind
+    return blocks[0][1], blocks[1][1]
+
+
+def _corners(types, verts):
+    """per primitive the (3 or 4, 3) float32 corners that are read, with -0.0 and 0.0 made one"""
+    verts = np.asarray(verts, np.float32) + np.float32(0.0)
+    return [verts[i, :4 if types[i] == 1 else 3] for i in range(len(types))]
+
+
+def icosphere(center, radius, level):
+    """A sphere of 20 * 4**level triangles: the icosahedron, each triangle cut into four `level` times, every vertex pushed onto
+    the sphere.  Returns (types (n,), verts (n, 4, 3), normal (n, 3), corner_normals (n, 4, 3)), float32, in the layout of
+    ptmi_load_scene_arrays and Renderer.set_vertex_normals.  A vertex is computed once, so shared corners are bit-equal; the
+    stored normal is the outward geometric one; a corner's normal is unit(corner - center)."""
+    c = np.asarray(center, np.float64)
+    t = (1.0 + np.sqrt(5.0)) / 2.0
+    pts = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    pts = [np.asarray(p, np.float64) / np.sqrt(1.0 + t * t) for p in pts]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+             (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(int(level)):
+        mid = {}
+
+        def midpoint(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                m = pts[a] + pts[b]
+                pts.append(m / np.linalg.norm(m))
+                mid[key] = len(pts) - 1
+            return mid[key]
+        cut = []
+        for a, b, d in faces:
+            ab, bd, da = midpoint(a, b), midpoint(b, d), midpoint(d, a)
+            cut += [(a, ab, da), (b, bd, ab), (d, da, bd), (ab, bd, da)]
+        faces = cut
+    unit = np.asarray(pts)
+    pos = (c + float(radius) * unit).astype(np.float32)                # one float32 position per vertex: shared corners are bit-equal
+    out = pos.astype(np.float64) - c
+    vn = (out / np.linalg.norm(out, axis=1, keepdims=True)).astype(np.float32)
+    idx = np.asarray(faces)
+    n = len(idx)
+    verts = np.zeros((n, 4, 3), np.float32); corner_normals = np.zeros((n, 4, 3), np.float32)
+    verts[:, :3] = pos[idx]; corner_normals[:, :3] = vn[idx]
+    v = verts.astype(np.float64)
+    g = np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0])
+    g /= np.linalg.norm(g, axis=1, keepdims=True)
+    assert (np.einsum("ij,ij->i", g, v[:, 0] - c) > 0).all()             # counter-clockwise seen from outside
+    return np.zeros(n, np.int32), verts, g.astype(np.float32), corner_normals
+
+
+def smooth_normals(prims, crease_deg=40.0, flat_deg=1.0):
+    """Corner normals for Renderer.set_vertex_normals from the stored normals of any loaded scene: (n_prims, 4, 3) float32.
+    prims: dict(type, verts, normal, ...) (Renderer.scene_prims(), HostScene.prims()).  Corners are joined where their float32
+    coordinates are EQUAL, as cornell_blocks joins them.  A corner's normal is the unit sum of the unit stored normals of the
+    primitives around it - this one included - that lie within crease_deg of this primitive's, each weighted by the angle its
+    primitive has at the corner.  Where every one of them lies within flat_deg of this primitive's stored normal (a planar
+    neighbourhood, a corner nobody shares) or the sum has no direction, the corner keeps the stored normal bit for bit, so a
+    scene of planes such as cbox.obj gives an all-flat table.  flat_deg is 1 degree and not 0 because modelled planes are not
+    exact - the two triangles of cbox.obj's left wall differ by 0.47 degrees - while a curved mesh whose neighbouring facets
+    differ by less than that (a sphere of over 100 000 triangles) shows no facets that interpolation could remove."""
+    types = np.asarray(prims["type"]); stored = np.asarray(prims["normal"], np.float32)
+    corners = _corners(types, prims["verts"])
+    n = len(types)
+    with np.errstate(all="ignore"):
+        un = stored.astype(np.float64) / np.linalg.norm(stored.astype(np.float64), axis=1, keepdims=True)
+    around = {}                                                          # corner -> [(primitive, angle at the corner)]
+    for i in range(n):
+        v = corners[i].astype(np.float64); m = len(v)
+        for k in range(m):
+            a, b = v[(k + 1) % m] - v[k], v[(k - 1) % m] - v[k]
+            la, lb = np.linalg.norm(a), np.linalg.norm(b)
+            ang = np.arccos(np.clip(np.dot(a, b) / (la * lb), -1.0, 1.0)) if la > 0 and lb > 0 else 0.0
+            around.setdefault(corners[i][k].tobytes(), []).append((i, ang))
+    cos_crease = np.cos(np.radians(min(max(float(crease_deg), 0.0), 180.0)))
+    cos_flat = np.cos(np.radians(float(flat_deg)))
+    out = np.repeat(stored[:, None, :], 4, axis=1).copy()
+    for i in range(n):
+        if not np.isfinite(un[i]).all():
+            continue
+        for k in range(len(corners[i])):
+            total = np.zeros(3); planar = True
+            for j, ang in around[corners[i][k].tobytes()]:
+                if np.isfinite(un[j]).all() and np.dot(un[i], un[j]) >= cos_crease - 1e-12:
+                    total += ang * un[j]
+                    planar = planar and (j == i or np.dot(un[i], un[j]) >= cos_flat)
+            length = np.linalg.norm(total)
+            if not planar and length > 0:
+                out[i, k] = (total / length).astype(np.float32)
+    return out
+
+
+def cornell_spheres(prims, level=3):
+    """The Cornell box with each block replaced by a sphere (icosphere of `level`) that stands on the floor over the block's
+    footprint: the centre over the middle of the footprint's extent in x and z, the radius half the smaller of the two, the
+    block's colour.  prims as for cornell_blocks (subdivided or not, triangles or quads).  Returns (arrays, corner_normals, ranges):
+    arrays = (types, verts, normal, bsdf, Le) for Renderer.load_scene_arrays - the scene without the blocks, then the short
+    block's sphere, then the tall one's; corner_normals (n, 4, 3) for Renderer.set_vertex_normals, the stored normal at every
+    corner outside the spheres; ranges = dict(short=(first, end), tall=(first, end)), the spheres' index ranges, for set_surfaces."""
+    F = np.float32
+    types = np.asarray(prims["type"], np.int32)
+    corners = _corners(types, prims["verts"])
+    blocks = _cornell_block_members(prims)
+    keep = np.ones(len(types), bool)
+    for members in blocks:
+        keep[members] = False
+    parts = [[types[keep]], [np.asarray(prims["verts"], F)[keep]], [np.asarray(prims["normal"], F)[keep]], [np.asarray(prims["bsdf"], F)[keep]],
+             [np.asarray(prims["Le"], F)[keep]]]
+    table = [np.repeat(parts[2][0][:, None, :], 4, axis=1)]
+    ranges, first = {}, int(keep.sum())
+    for name, members in zip(("short", "tall"), blocks):
+        v = np.concatenate([corners[i] for i in members]).astype(np.float64)
+        lo, hi = v.min(0), v.max(0)
+        r = 0.5 * min(hi[0] - lo[0], hi[2] - lo[2])
+        st, sv, sn, sc = icosphere((0.5 * (lo[0] + hi[0]), lo[1] + r, 0.5 * (lo[2] + hi[2])), r, level)
+        parts[0].append(st); parts[1].append(sv); parts[2].append(sn)
+        parts[3].append(np.repeat(np.asarray(prims["bsdf"], F)[members[0]][None], len(st), 0)); parts[4].append(np.zeros((len(st), 3), F))
+        table.append(sc)
+        ranges[name] = (first, first + len(st)); first += len(st)
+    arrays = tuple(np.concatenate(p) for p in parts)
+    return arrays, np.concatenate(table).astype(F), ranges

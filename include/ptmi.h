@@ -998,6 +998,71 @@ int  ptmi_set_surfaces_rough(ptmi_ctx*, int n_prims, const int* kind /* NULL dro
                              const float* roughness /* NULL: 0.3 everywhere */);
 int  ptmi_surface_counts(const ptmi_ctx*, int counts[4]);   /* primitives of kind 0 .. 3; all 0 without a table */
 
+/* ---- vertex normals: per-corner normals interpolated at path vertices (new in this implementation) ------------------------------
+ * The loaders keep ONE normal per primitive, as the reference does, so a tessellated sphere shades as a polyhedron.
+ * ptmi_set_vertex_normals gives the loaded scene a table of corner normals, n_prims x 4 x 3 floats in load order, a primitive's
+ * corners in the order of ptmi_load_scene_arrays' verts (v0 v1 v2 | v00 v10 v11 v01); a triangle's 4th entry is ignored.  The
+ * table belongs to the scene exactly as the surface table does: a scene load drops it.
+ *
+ * FLAT AND SMOOTH.  A primitive is flat when every corner normal that is read (3 for a triangle, 4 for a quad) compares equal
+ * (==, component for component, so -0.0 equals 0.0) to its stored normal; otherwise it is smooth.  A flat primitive's vertex takes
+ * the stored normal, untouched.  A table without a smooth primitive is no table: the context takes exactly the route it takes
+ * without one.  A context whose table has a smooth primitive renders both values of next_event through the per-lane kernel of
+ * next-event estimation, as a context with an environment or a specular surface does; frames, batches, passes, tiled contexts,
+ * ptmi_denoise, ptmi_temporal_accumulate and ptmi_gather_frame work as they do without one.
+ * ptmi_run_radiosity_solver, the Radiosity view (integrator = 1) and ptmi_render_features IGNORE the table: the feature normal stays
+ * the stored one.
+ *
+ * ptmi_set_vertex_normals: normals NULL drops the table (n_prims is then ignored).  A successful call restarts an accumulation,
+ * makes features stale and empties the temporal history, as ptmi_set_surfaces does.  PTMI_E_INVALID, with nothing changed (every
+ * check is made before anything changes, and the new array is uploaded before the old one is freed): no scene loaded, n_prims !=
+ * ptmi_scene_info's count, a NaN or infinite component in a corner that is read (zero-length corner normals are allowed), and -
+ * for a table with a smooth primitive - a current config with integrator = 1, sampling_mode != 0 or fast_tree = 1;
+ * ptmi_set_config rejects those three while such a table is set.  ptmi_check_vertex_normals makes the checks that need no context:
+ * n_prims >= 1, normals not NULL, corners 0 .. 2 of every primitive finite (the 4th corner's check needs the primitive's type:
+ * ptmi_set_vertex_normals and ptmi_host_classify_vertex_normals make it for quads).  ptmi_vertex_normals_info: the number of
+ * smooth primitives, 0 without a table.  ptmi_host_classify_vertex_normals: the classification on the host, without a context -
+ * type and stored (n_prims x 3) as ptmi_scene_get_prims gives them; smooth (may be NULL) receives 1 per smooth primitive.
+ *
+ * THE NORMAL of a vertex at p = o + t d on a smooth primitive k; binary32 in the order written, no fused multiply-add, / the IEEE
+ * quotient, dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z and unit_vector(v) = v * (1.0f / sqrtf(dot(v, v))) (vector.h); n_k is
+ * the stored normal, and "take the stored normal" means N = n_k as it is.
+ *   triangle, with v0 and the edges e1 = v1 - v0, e2 = v2 - v0 as the walk holds them (float subtractions) and corner normals
+ *   (n0, n1, n2):
+ *       w = p - v0
+ *       d00 = dot(e1, e1);  d01 = dot(e1, e2);  d11 = dot(e2, e2);  d20 = dot(w, e1);  d21 = dot(w, e2)
+ *       den = d00 * d11 - d01 * d01;   unless den > 0 and den <= FLT_MAX take the stored normal (a zero-area or huge triangle)
+ *       r1 = (d11 * d20 - d01 * d21) / den;   r2 = (d00 * d21 - d01 * d20) / den
+ *       b1 = r1 < 0 ? 0 : (r1 > 1 ? 1 : r1);   m = 1 - b1;   b2 = r2 < 0 ? 0 : (r2 > m ? m : r2);   b0 = m - b2
+ *           (comparisons, not fminf / fmaxf: a NaN stays a NaN; a point outside the primitive clamps onto it)
+ *       S = (b0 * n0 + b1 * n1) + b2 * n2     per component
+ *       len2 = dot(S, S);   unless len2 > 0 and len2 <= FLT_MAX take the stored normal (the corner normals cancel, or a NaN)
+ *       N = unit_vector(S)
+ *   quad, with the edges e1 = v10 - v00, e2 = v11 - v00, e3 = v01 - v00 and corner normals (n00, n10, n11, n01): the two halves
+ *   the walk tests, (v00, v10, v11) and (v00, v11, v01).  den, r1, r2 of the first half are formed over (e1, e2) as above.  If that
+ *   den is valid and the raw r1 >= 0 the first half gives N as a triangle with (n00, n10, n11).  Otherwise the second half does,
+ *   over (e2, e3) with (n00, n11, n01), and where its den is not valid either the vertex takes the stored normal.
+ * THE ESTIMATOR is that of "rough metal" (and of every section it builds on) with ONE change: N replaces n_k where step 2 forms sn
+ * - after the roulette and the |beta| < 1e-5 exit, not at the hit - and everything below reads it from there: sn is N turned
+ * against d, o' = p + 1e-4f * sn, the glass interface's side (dot(d, N) < 0), the mirror, the rough frame, the cosine sample and
+ * every cos_s.  Nothing else moves: step 1's emitter pdf keeps the geometric normal of the emitter table, and draws, depth count,
+ * roulette and exits are unchanged.
+ * WHAT FOLLOWS FROM THIS, and is not corrected: N may lie on the other side of the surface than the geometric normal as seen from
+ * d (near silhouettes of a coarse mesh).  sn then points INTO the body: o' starts below the surface, the cosine lobe faces
+ * inwards, and a light sample's cos_s > 0 test passes for directions behind the geometry.  The results are light leaks and dark
+ * rims on coarse meshes; a finer tessellation narrows them, nothing here removes them.  In a closed scene whose reachable
+ * primitives all have the same Le and Kd the expected value is unchanged all the same. */
+/* host only, no context: 0 or PTMI_E_INVALID with the message */
+int  ptmi_check_vertex_normals(int n_prims, const float* normals);
+int  ptmi_host_classify_vertex_normals(int n_prims, const int* type, const float* stored /* n_prims*3 */, const float* normals,
+                                       int* smooth /* n_prims, may be NULL */, int* n_smooth /* may be NULL */);
+int  ptmi_set_vertex_normals(ptmi_ctx*, int n_prims, const float* normals /* n_prims*4*3, load order, corner order of ptmi_load_scene_arrays' verts; 4th ignored for triangles; NULL drops the table */);
+int  ptmi_vertex_normals_info(const ptmi_ctx*, int* n_smooth);   /* 0 without a table */
+/* test hook: the kernel's own function (csrc/vertex_normal.h) once per case on the loaded scene and table.  prim: load-order
+ * indices; p: 3n points; out: 4n - N.xyz, then 1.0 where N was interpolated and 0.0 where the vertex keeps the stored normal (a
+ * flat primitive, a fallback, no table).  PTMI_E_INVALID: no scene, a prim out of range. */
+int  ptmi_debug_vertex_normal(ptmi_ctx*, int n, const int* prim /* load order */, const float* p /* 3n */, float* out /* 4n */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,10 @@
                                (load-order primitive indices: cbox.obj's short block a mirror, its tall block glass)
   python tools/ptmi_render.py --scene ... --rough 22-31 --roughness 0.3 --next-event --max-depth 8 --out metal.png
                                (the tall block brushed metal: GGX, its Kd the tint)
+  python tools/ptmi_render.py --scene ... --spheres --glass tall --rough short --next-event --max-depth 8 --out spheres.png
+                               (the blocks replaced by smooth-shaded spheres: a glass ball and a brushed-metal one)
+  python tools/ptmi_render.py --scene mesh.obj --smooth 40 --out smooth.png
+                               (corner normals from the stored ones, joined across edges of less than 40 degrees)
 """
 import argparse
 import os
@@ -29,10 +33,14 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import ptmi  # noqa: E402
 
 
-def index_list(text):
-    """'12-23,30' -> [12, ..., 23, 30]; ValueError names the item that is no index and no ascending range"""
+def index_list(text, named=None):
+    """'12-23,30' -> [12, ..., 23, 30]; ValueError names the item that is no index and no ascending range.  named: name ->
+    (first, end) ranges an item may name instead (--spheres: short, tall)"""
     out = []
     for part in text.split(","):
+        if named and part.strip() in named:
+            out.extend(range(*named[part.strip()]))
+            continue
         lo, dash, hi = part.strip().partition("-")
         if not lo.isdigit() or (dash and not hi.isdigit()) or (dash and int(hi) < int(lo)):
             raise ValueError(f"'{part.strip()}' is neither an index nor a range such as 12-23")
@@ -81,6 +89,11 @@ def main():
     ap.add_argument("--glass", default=None, metavar="LIST"); ap.add_argument("--ior", type=float, default=1.5, help="index of refraction of --glass")
     ap.add_argument("--rough", default=None, metavar="LIST", help="rough metal (GGX): primitive indices and ranges like --mirror")
     ap.add_argument("--roughness", type=float, default=0.3, help="roughness of --rough, in [0.05, 1]; alpha is its square")
+    ap.add_argument("--smooth", type=float, nargs="?", const=40.0, default=None, metavar="DEG",
+                    help="smooth shading: corner normals from the stored ones (ptmi_scenes.smooth_normals), creases above DEG (default 40) stay")
+    ap.add_argument("--spheres", type=int, nargs="?", const=3, default=None, metavar="LEVEL",
+                    help="the Cornell box's blocks replaced by smooth-shaded spheres of 20 * 4^LEVEL triangles (default 3); "
+                         "--mirror / --glass / --rough may then name them: short, tall")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -88,6 +101,14 @@ def main():
     r = ptmi.Renderer(a.device)
     t = time.time()
     r.load_scene(a.scene, a.subdivision, a.convert_quads)
+    corner_normals, spheres = None, None
+    if a.spheres is not None:
+        import ptmi_scenes
+        try:
+            arrays, corner_normals, spheres = ptmi_scenes.cornell_spheres(r.scene_prims(), a.spheres)
+        except ValueError as e:
+            ap.error(f"--spheres needs the Cornell box: {e}")
+        r.load_scene_arrays(*arrays)
     info = r.scene_info()
     print(f"scene: {info['n_prims']} primitives ({info['n_tris']} triangles, {info['n_quads']} quads), "
           f"{info['n_bvh_nodes']} BVH nodes, depth {info['bvh_depth']}  [{time.time() - t:.2f} s]")
@@ -122,7 +143,7 @@ def main():
         kind = np.zeros(info["n_prims"], np.int32)
         for text, value in ((a.mirror, ptmi.SURFACE_MIRROR), (a.glass, ptmi.SURFACE_GLASS), (a.rough, ptmi.SURFACE_ROUGH)):
             try:
-                idx = index_list(text) if text else []
+                idx = index_list(text, spheres) if text else []
             except ValueError as e:
                 ap.error(f"--mirror / --glass / --rough: {e}")
             if idx and not (0 <= min(idx) and max(idx) < len(kind)):
@@ -133,6 +154,17 @@ def main():
         print(f"surfaces: {si['n_mirror']} mirror, {si['n_glass']} glass primitives, ior {a.ior}")
         if a.rough:
             print(f"surfaces: {r.surface_counts()[3]} rough-metal primitives, roughness {a.roughness}")
+    if a.smooth is not None:
+        import ptmi_scenes
+        prims = r.scene_prims()
+        table = ptmi_scenes.smooth_normals(prims, a.smooth)
+        if corner_normals is not None:                         # the spheres keep their own
+            first = min(lo for lo, _ in spheres.values())
+            table[first:] = corner_normals[first:]
+        corner_normals = table
+    if corner_normals is not None:
+        r.set_vertex_normals(corner_normals)
+        print(f"vertex normals: {r.vertex_normals_info()['n_smooth']} smooth primitives")
     if a.orbit > 0:
         if a.variance_guided and a.temporal:
             ap.error("--variance-guided does not filter the temporal history (no variance is carried in it)")
