@@ -209,6 +209,13 @@ int ptmi_host_scene_from_arrays(int n, const int* type, const float* verts, cons
     });
 }
 void ptmi_host_scene_free(ptmi_host_scene* s) { delete s; }
+int ptmi_host_scene_check_extent(ptmi_host_scene* s, const float* origin) {
+    return guarded([&] {
+        need(s != nullptr, "scene is NULL");
+        s->scene.checkExtent();
+        if (origin) s->scene.checkQuadOrigin(origin, nullptr, "origin");
+    });
+}
 int ptmi_host_scene_info(const ptmi_host_scene* s, int* n_prims, int* n_tris, int* n_quads, int* n_bvh_nodes, int* bvh_depth) {
     return guarded([&] { need(s != nullptr, "scene is NULL"); scene_info(s->scene, n_prims, n_tris, n_quads, n_bvh_nodes, bvh_depth); });
 }
@@ -826,12 +833,18 @@ int ptmi_debug_set_fast_tree(ptmi_ctx* c, int max_leaf, float c_trav, float c_tr
     });
 }
 
+// the hooks take rays from anywhere: each origin is held to the bound the scene and the camera are held to (SceneState::upload)
+static void check_hook_rays(const SceneState& s, int n, const float* o, const float* d) {
+    for (int i = 0; i < n; i++) s.checkQuadOrigin(o + 3 * (size_t)i, d + 3 * (size_t)i, "ray");
+}
+
 int ptmi_debug_intersect_fast(ptmi_ctx* c, int n, const float* o, const float* d, float t_min, float t_max,
                               int* hit, int* prim, float* t, uint64_t* counts) {
     return guarded([&] {
         need(c && o && d && hit && prim && t, "NULL argument");
         need(c->app.scene.d_nodes != nullptr, "no scene loaded");
         need(n > 0, "n must be positive");
+        check_hook_rays(c->app.scene, n, o, d);
         PTMI_HIP(hipSetDevice(c->app.device_id));
         if (!c->app.scene.fastReady()) c->app.scene.buildFast();
         DevBuf<float> d_o(3 * (size_t)n), d_d(3 * (size_t)n), d_t(n);
@@ -844,6 +857,23 @@ int ptmi_debug_intersect_fast(ptmi_ctx* c, int n, const float* o, const float* d
         PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
         d_hit.download(hit, n); d_prim.download(prim, n); d_t.download(t, n);
         if (counts) { unsigned long long h[2]; d_cnt.download(h, 2); counts[0] = h[0]; counts[1] = h[1]; }
+    });
+}
+
+int ptmi_debug_first_hit(ptmi_ctx* c, int n, const float* o, const float* d, float t_min, int* hit, int* prim, float* t) {
+    return guarded([&] {
+        need(c && o && d && hit && prim && t, "NULL argument");
+        need(c->app.scene.d_nodes != nullptr, "no scene loaded");
+        need(n > 0, "n must be positive");
+        check_hook_rays(c->app.scene, n, o, d);
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<float> d_o(3 * (size_t)n), d_d(3 * (size_t)n), d_t(n);
+        DevBuf<int> d_hit(n), d_prim(n);
+        d_o.upload(o, 3 * (size_t)n); d_d.upload(d, 3 * (size_t)n);
+        launch_debug_first_hit(c->app.scene.d_scene, n, d_o.p, d_d.p, t_min, d_hit.p, d_prim.p, d_t.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d_hit.download(hit, n); d_prim.download(prim, n); d_t.download(t, n);
     });
 }
 
@@ -893,6 +923,7 @@ int ptmi_debug_intersect(ptmi_ctx* c, int n, const float* o, const float* d, flo
         need(c && o && d && hit && prim && t && p && nrm, "NULL argument");
         need(c->app.scene.d_nodes != nullptr, "no scene loaded");
         need(n > 0, "n must be positive");
+        check_hook_rays(c->app.scene, n, o, d);
         PTMI_HIP(hipSetDevice(c->app.device_id));
         DevBuf<float> d_o(3 * (size_t)n), d_d(3 * (size_t)n), d_t(n), d_p(3 * (size_t)n), d_n(3 * (size_t)n);
         DevBuf<int> d_hit(n), d_prim(n);

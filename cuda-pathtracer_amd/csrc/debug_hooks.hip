@@ -80,6 +80,33 @@ void launch_debug_intersect_wide(const DeviceScene& sc, int n, const float* o, c
     });
 }
 
+// first_hit (traversal.h) for n rays (test hook): the walk of the Radiosity view and the feature pass in the scene's own mode -
+// the certified walk where the scene has it, else LANE or STACK - chosen and given its LDS by first_hit_walk as theirs is.  The
+// reference's leaf-order slot becomes the load index.
+template <int MODE, bool HAS_QUADS>
+__global__ __launch_bounds__(kBlock) void ptmi_debug_first_hit_k(DeviceScene sc, int n, const float* o, const float* d, float t_min,
+                                                                 int* hit, int* prim, float* t_out) {
+    extern __shared__ float4 smem[];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = i < n;
+    const int j = live ? i : 0;
+    const f3 ro = mk3(o[3 * j], o[3 * j + 1], o[3 * j + 2]), rd = mk3(d[3 * j], d[3 * j + 1], d[3 * j + 2]);
+    LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
+    float t = 0.0f; int k = -1;
+    const bool h = first_hit<MODE, HAS_QUADS>(sc, smem, live, ro, rd, t_min, t, k, cn);
+    if (!live) return;
+    hit[i] = h ? 1 : 0;
+    prim[i] = h ? __float_as_int(sc.mats[3 * k].w) : -1;
+    t_out[i] = h ? t : 0.0f;
+}
+void launch_debug_first_hit(const DeviceScene& sc, int n, const float* o, const float* d, float t_min, int* hit, int* prim, float* t, hipStream_t s) {
+    if (n <= 0) return;
+    first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
+        hipLaunchKernelGGL((ptmi_debug_first_hit_k<decltype(mode)::value, decltype(quads)::value>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s,
+                           sc, n, o, d, t_min, hit, prim, t);
+    });
+}
+
 __global__ void ptmi_debug_rng_k(const uint32_t* __restrict__ jump, unsigned long long seed_base, int n_pixels,
                                  const int* pixels, int count, float* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

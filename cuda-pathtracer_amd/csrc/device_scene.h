@@ -399,6 +399,7 @@ void launch_debug_intersect(const DeviceScene& sc, int n, const float* o, const 
                             int* hit, int* prim, float* t, float* p, float* nrm, hipStream_t s);
 void launch_debug_intersect_wide(const DeviceScene& sc, int n, const float* o, const float* d, float t_min, float t_max,
                                  int* hit, int* prim, float* t, unsigned long long* counts /* 2, may be nullptr */, hipStream_t s);
+void launch_debug_first_hit(const DeviceScene& sc, int n, const float* o, const float* d, float t_min, int* hit, int* prim, float* t, hipStream_t s);
 void launch_debug_rng(const uint32_t* d_jump, uint64_t seed_base, int n_pixels, const int* pixels, int count, float* out, hipStream_t s);
 void launch_debug_rcp(unsigned int first_bits, unsigned long long count, unsigned long long* d_out, hipStream_t s);
 void launch_debug_sqrt(unsigned int first_bits, unsigned long long count, unsigned long long* d_out, hipStream_t s);

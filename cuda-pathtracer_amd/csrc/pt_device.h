@@ -87,8 +87,12 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) { float r; 
 //   t > eps && t >= t_min  <=>  t - t_lo >= 0  with t_lo = max(t_min, nextafter(eps, +inf))
 // fminf ignores NaN operands exactly where the reference's `x < 0 || x > 1` forms let a NaN through; the final
 // `t < closest_t` (scene.h:90) rejects a NaN t.  Quad halves use the inclusive forms `|a| > eps`, `u >= 0 && ...`,
-// which differ from the above only for |a| == eps (handled through eps_lo = nextafter(eps)) and for NaN u/v; NaNs
-// need overflowing intermediates, which the host rules out (scene extent check) before choosing this code path.
+// which differ from the above only for |a| == eps (handled through eps_lo = nextafter(eps)) and for NaN u/v: the
+// reference's quad rejects a NaN u that this chain ignores (tests/intersect_edge_sets.py: extent_set has the ray).  With
+// |a| > eps, f is finite, so a NaN u or v needs an overflowing product of a quad edge and o - v0.  The host rules that out:
+// SceneState::checkExtent refuses a scene with quads whose largest quad edge times its extent exceeds 2^124, and
+// checkQuadOrigin holds the camera and the test hooks' rays to the same bound.  The bounds on edges (1e18)
+// and coordinates (3e38) alone do not: 2^59 * 2^69 overflows.
 // min/max/cmp/cndmask are half-rate on gfx950, add/sub/mul full-rate: 3 min + 5 sub replace 7 cmp + 7 cndmask.
 __device__ __forceinline__ float mt_candidate(f3 v0, f3 edge1, f3 edge2, f3 o, f3 d, float eps_for_a, float t_lo) {
     const f3 h = cross(d, edge2);

@@ -372,4 +372,19 @@ __device__ __forceinline__ bool first_hit(const DeviceScene& sc, float4* smem, b
     return hit;
 }
 
+// The first-hit walk of the Radiosity view, the feature pass, next-event estimation and the test hook ptmi_debug_first_hit, chosen
+// on the host: MODE TRAVERSAL_CERTIFIED the certified walk (scenes above the sweep's 64 primitives: the 8-wide tree + the proof
+// per hit, else the reference's walk - the reference's hit for every ray);
+// TRAVERSAL_LANE / TRAVERSAL_STACK the reference's walk.  f(integral_constant MODE, integral_constant HAS_QUADS, LDS bytes).
+template <typename F>
+static void first_hit_walk(const DeviceScene& sc, F&& f) {
+    const bool deep = sc.traversal == TRAVERSAL_STACK;                                // per-lane walk from global memory; stack only for deep trees
+    const bool cert = sc.traversal == TRAVERSAL_CERTIFIED && sc.certified_ready();
+    const size_t lds = cert ? (size_t)sc.w_depth * kBlock * sizeof(uint2) : deep ? (size_t)sc.stack_entries * kBlock * sizeof(int) : 0;
+    auto with_quads = [&](auto mode) { with_bool(sc.has_quads, [&](auto quads) { f(mode, quads, lds); }); };
+    if (cert) with_quads(std::integral_constant<int, TRAVERSAL_CERTIFIED>{});
+    else if (deep) with_quads(std::integral_constant<int, TRAVERSAL_STACK>{});
+    else with_quads(std::integral_constant<int, TRAVERSAL_LANE>{});
+}
+
 }  // namespace ptmi

@@ -77,6 +77,18 @@ struct SceneState {
     int bvh_depth = 0;
     int num_tris = 0, num_quads = 0;
     std::string scene_file;
+    // Quad::intersect rejects a NaN u or v, the device's running minimum ignores one (csrc/pt_device.h); a NaN there needs an
+    // overflowing product of a quad edge and o - v0 ("the quad test at the extent check").  upload() refuses a
+    // scene with quads whose largest quad edge times the largest |o - v0| a path can reach exceeds kQuadReachBound, and every
+    // origin that comes from outside the scene - the camera, a test hook's rays - is held to the same bound (checkQuadOrigin).
+    // The camera is a pinhole: every camera ray starts AT the camera's origin, which is what a frame checks.  A camera whose rays start
+    // elsewhere (a lens) has to hand checkQuadOrigin the farthest such point.
+    static constexpr double kQuadReachBound = 0x1p124;
+    float quad_edge_max = 0.0f;                      // largest |component| of a quad's v[k] - v[0]; 0 without quads
+    float coord_lo[3] = {0, 0, 0}, coord_hi[3] = {0, 0, 0};      // bounds of every vertex of the scene
+    void checkExtent();                              // the device's limits on a scene (edges, coordinates, the bound above); throws ArgError
+    double quadReach(const float* o) const;          // largest |o_a - x_a| over the scene's points x, with the rounding of a hit point
+    void checkQuadOrigin(const float* o, const float* d, const char* who) const;     // throws ArgError; non-finite rays pass (no primitive accepts them)
 
     float4 *d_nodes = nullptr, *d_prims = nullptr, *d_mats = nullptr;
     // packed layout for TRAVERSAL_PACKED (csrc/device_scene.h), built for scenes of at least packed_min_nodes nodes

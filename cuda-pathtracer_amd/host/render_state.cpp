@@ -304,6 +304,8 @@ void cameraFrameParams(ApplicationState& g, FrameParams& fp) {
     RenderState& r = g.render;
     if (g.config.orbit) r.h_camera.updateCameraOrbit(); else r.h_camera.updateCamera();
     const CameraFrame cf = r.h_camera.frame();
+    const float eye[3] = {cf.origin.x, cf.origin.y, cf.origin.z};
+    g.scene.checkQuadOrigin(eye, nullptr, "camera");             // the quad test's products must not overflow (SceneState::upload)
     const f3* src[4] = {&cf.origin, &cf.lower_left_corner, &cf.horizontal, &cf.vertical};
     float* dst[4] = {fp.cam_origin, fp.cam_llc, fp.cam_hor, fp.cam_ver};
     for (int i = 0; i < 4; i++) { dst[i][0] = src[i]->x; dst[i][1] = src[i]->y; dst[i][2] = src[i]->z; }

@@ -157,8 +157,9 @@ void SceneState::buildBVH() {
     for (const Primitive& p : h_primitives) (p.type == PRIM_TRIANGLE ? num_tris : num_quads)++;
 }
 
-void SceneState::upload() {
-    const int n = (int)h_primitives.size();
+// What the device's arithmetic asks of a scene; throws ArgError.  Called by upload(), and by the host-only scene's check
+// (ptmi_host_scene_check_extent), which needs no GPU.
+void SceneState::checkExtent() {
     // The kernels' short reciprocal (pt_vec.h: rcp_exact_normal) equals the IEEE quotient while the Moller-Trumbore
     // determinant stays below 2^126; |a| <= 2 |e1| |e2| (|d| = 1), so edge components below 2^60 are always safe.
     for (const Primitive& p : h_primitives)
@@ -168,6 +169,37 @@ void SceneState::upload() {
             const float c = fabsf(p.v[k].x) + fabsf(p.v[k].y) + fabsf(p.v[k].z);
             if (!(m < 1.0e18f) || !(c < 3.0e38f)) throw ArgError("scene coordinates must be finite and primitive edges shorter than 1e18");
         }
+    // The quad halves (Quad::intersect: u >= 0 && u <= 1) reject a NaN u or v that the device's min chain ignores.  u, v are
+    // f * dot(s, h) and f * dot(d, q) with |h_a| <= 2 |d| E, |q_a| <= 2 S E (E: a quad edge, S: |o - v0|, per component), so no
+    // product and no partial sum exceeds 6 |d| S E: below 2^128 nothing overflows and, f being finite (|a| > 1e-8), u and v are
+    // numbers.  S is at most the scene's extent plus the rounding of a hit point o + t d, below 2^-22 of the largest coordinate
+    // (quadReach adds 2^-20 of it), and 6 * 2^124 < 2^127.  Triangles need no such bound: Triangle::intersect (u < 0 || u > 1)
+    // lets a NaN through as the device does.
+    quad_edge_max = 0.0f;
+    bool first = true;
+    for (const Primitive& p : h_primitives)
+        for (int k = 0; k < (p.type == PRIM_QUAD ? 4 : 3); k++) {
+            const float c[3] = {p.v[k].x, p.v[k].y, p.v[k].z};
+            for (int a = 0; a < 3; a++) {
+                coord_lo[a] = first ? c[a] : fminf(coord_lo[a], c[a]);
+                coord_hi[a] = first ? c[a] : fmaxf(coord_hi[a], c[a]);
+            }
+            first = false;
+            if (p.type == PRIM_QUAD) {
+                const f3 e = p.v[k] - p.v[0];
+                quad_edge_max = fmaxf(quad_edge_max, fmaxf(fabsf(e.x), fmaxf(fabsf(e.y), fabsf(e.z))));
+            }
+        }
+    if (quad_edge_max > 0.0f) {
+        const double reach = quadReach(coord_lo);          // from a corner of the scene's box: its extent
+        if (!((double)quad_edge_max * reach <= kQuadReachBound))
+            throw ArgError("scene with quads: the largest quad edge times the scene's extent must not exceed 2^124");
+    }
+}
+
+void SceneState::upload() {
+    const int n = (int)h_primitives.size();
+    checkExtent();
     // ---- SoA re-layout (device_scene.h) ----
     const int stride = num_quads ? 4 : 3;
     auto bits = [](int i) { float f; std::memcpy(&f, &i, 4); return f; };
@@ -626,6 +658,26 @@ void SceneState::precomputeCDFsFromFiltered(bool use_bilateral, float sigma_spat
     PTMI_HIP(hipMemcpy(h_filtered_formfactor.data(), off.p, cells * sizeof(float), hipMemcpyDeviceToHost));
     PTMI_HIP(hipMemcpy(h_filtered_radiosity.data(), orad.p, cells * sizeof(float), hipMemcpyDeviceToHost));
     precomputeCDFsDevice(orad.p, 2, stream);
+}
+
+double SceneState::quadReach(const float* o) const {
+    double far = 0.0, coord = 0.0;
+    for (int a = 0; a < 3; a++) {
+        far = std::max(far, std::max(std::fabs((double)o[a] - (double)coord_lo[a]), std::fabs((double)o[a] - (double)coord_hi[a])));
+        coord = std::max(coord, std::max(std::fabs((double)o[a]), std::max(std::fabs((double)coord_lo[a]), std::fabs((double)coord_hi[a]))));
+    }
+    return far + coord * 0x1p-20;
+}
+
+void SceneState::checkQuadOrigin(const float* o, const float* d, const char* who) const {
+    if (!(quad_edge_max > 0.0f)) return;
+    double dmax = d ? 0.0 : 1.0;                       // d == nullptr: a unit direction
+    for (int a = 0; a < 3; a++) {
+        if (!std::isfinite(o[a]) || (d && !std::isfinite(d[a]))) return;      // t comes out NaN or infinite: accepted by neither side
+        if (d) dmax = std::max(dmax, std::fabs((double)d[a]));
+    }
+    if (!((double)quad_edge_max * quadReach(o) * dmax <= kQuadReachBound))
+        throw ArgError(std::string(who) + ": with quads in the scene, the largest quad edge times the origin's distance from the scene must not exceed 2^124");
 }
 
 // traversal choice (results are identical in all three; see device_scene.h)

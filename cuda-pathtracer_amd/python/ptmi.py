@@ -25,12 +25,12 @@ EXPORTS = [
     "ptmi_debug_intersect", "ptmi_debug_rng", "ptmi_debug_cosine_sample", "ptmi_debug_guided_sample", "ptmi_debug_set_traversal", "ptmi_debug_rcp_check",
     "ptmi_debug_sqrt_check", "ptmi_debug_ray_inv",
     "ptmi_debug_sincos_lean_check", "ptmi_debug_sincos_lean", "ptmi_debug_unit_voted", "ptmi_debug_size_div_check",
-    "ptmi_host_scene_load", "ptmi_host_scene_from_arrays", "ptmi_host_scene_free", "ptmi_host_scene_info",
+    "ptmi_host_scene_load", "ptmi_host_scene_from_arrays", "ptmi_host_scene_free", "ptmi_host_scene_check_extent", "ptmi_host_scene_info",
     "ptmi_host_scene_get_prims", "ptmi_host_scene_get_bvh", "ptmi_host_camera_frame", "ptmi_host_local_row_map",
     "ptmi_host_cdf_record_layout", "ptmi_host_image",
     "ptmi_dist_unique_id", "ptmi_dist_init", "ptmi_dist_finalize", "ptmi_gather_frame", "ptmi_gather_wait", "ptmi_frame_device",
     "ptmi_read_frame", "ptmi_dist_barrier", "ptmi_dist_allreduce_max", "ptmi_debug_place_tiles", "ptmi_debug_set_packed_min_nodes", "ptmi_debug_set_packed_top", "ptmi_render_frames", "ptmi_select_frame",
-    "ptmi_debug_set_fast_tree", "ptmi_debug_intersect_fast", "ptmi_dist_comm_count", "ptmi_host_fast_tree_build", "ptmi_host_fast_tree_intersect", "ptmi_host_fast_tree_stats",
+    "ptmi_debug_set_fast_tree", "ptmi_debug_intersect_fast", "ptmi_debug_first_hit", "ptmi_dist_comm_count", "ptmi_host_fast_tree_build", "ptmi_host_fast_tree_intersect", "ptmi_host_fast_tree_stats",
     "ptmi_debug_set_solver_walk", "ptmi_debug_get_traversal",
     "ptmi_default_adaptive_params", "ptmi_accum_reset", "ptmi_accum_pass", "ptmi_read_sample_counts",
     "ptmi_default_denoise_params", "ptmi_check_denoise_params", "ptmi_render_features", "ptmi_read_features", "ptmi_denoise",
@@ -193,6 +193,7 @@ def lib():
         L.ptmi_host_scene_from_arrays.argtypes = [C.c_int, vp, vp, vp, vp, vp, C.POINTER(vp)]
         L.ptmi_host_scene_free.argtypes = [vp]; L.ptmi_host_scene_free.restype = None
         L.ptmi_host_scene_info.argtypes = [vp, ip, ip, ip, ip, ip]
+        L.ptmi_host_scene_check_extent.argtypes = [vp, vp]
         L.ptmi_host_scene_get_prims.argtypes = [vp] * 6
         L.ptmi_host_scene_get_bvh.argtypes = [vp] * 7
         L.ptmi_host_emitters.argtypes = [vp, ip, vp, vp, vp]
@@ -216,6 +217,7 @@ def lib():
         L.ptmi_debug_place_tiles.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
         L.ptmi_debug_set_fast_tree.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_int, ip, ip, ip]
         L.ptmi_debug_intersect_fast.argtypes = [vp, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp]
+        L.ptmi_debug_first_hit.argtypes = [vp, C.c_int, vp, vp, C.c_float, vp, vp, vp]
         L.ptmi_host_fast_tree_build.argtypes = [vp, C.c_int, C.c_float, C.c_float, ip, ip, C.POINTER(C.c_double)]
         L.ptmi_host_fast_tree_stats.argtypes = [vp, vp]
         L.ptmi_host_fast_tree_intersect.argtypes = [vp, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp, vp]
@@ -297,6 +299,12 @@ class HostScene:
                 lib().ptmi_host_scene_free(self.h)
         except Exception:
             pass
+
+    def check_extent(self, origin=None):
+        """Raises what loading this scene onto the device would raise for its extent (edges, coordinates, quad edge x reach);
+        origin: a ray origin outside the scene, a camera, held to the same bound."""
+        o = None if origin is None else np.ascontiguousarray(origin, np.float32)
+        _check(lib().ptmi_host_scene_check_extent(self.h, None if o is None else o.ctypes.data))
 
     def info(self):
         v = [C.c_int() for _ in range(5)]
@@ -1058,6 +1066,15 @@ class Renderer:
         self._ck(self.L.ptmi_debug_intersect_fast(self.h, n, o.ctypes.data, d.ctypes.data, t_min, t_max, hit.ctypes.data,
                                                   prim.ctypes.data, t.ctypes.data, counts.ctypes.data))
         return dict(hit=hit, prim=prim, t=t, node_visits=int(counts[0]), prim_tests=int(counts[1]))
+
+    def debug_first_hit(self, o, d, t_min=1e-4):
+        """first_hit of the Radiosity view and the feature pass for rays as given, by the walk the loaded scene takes there (the
+        certified walk where it has one, else LANE or STACK); t_max is FLT_MAX.  prim: load index or -1."""
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3); d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        n = len(o)
+        hit = np.zeros(n, np.int32); prim = np.zeros(n, np.int32); t = np.zeros(n, np.float32)
+        self._ck(self.L.ptmi_debug_first_hit(self.h, n, o.ctypes.data, d.ctypes.data, t_min, hit.ctypes.data, prim.ctypes.data, t.ctypes.data))
+        return dict(hit=hit, prim=prim, t=t)
 
     def debug_rng(self, seed_base, pixels, count):
         pixels = np.ascontiguousarray(pixels, np.int32)

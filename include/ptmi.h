@@ -304,6 +304,11 @@ int  ptmi_host_scene_load(const char* filename, int subdivision_count, int conve
 int  ptmi_host_scene_from_arrays(int n, const int* type, const float* verts, const float* normal,
                                  const float* bsdf, const float* Le, ptmi_host_scene** out);
 void ptmi_host_scene_free(ptmi_host_scene*);
+/* The limits a scene must keep to be loaded onto the device, checked without one: finite coordinates, edges shorter than 1e18 and,
+ * where the scene has quads, largest quad edge x the scene's extent <= 2^124 (the products of the quad test must not overflow:
+ * the reference's quad rejects a NaN barycentric that the device's test would not see).  origin (3 floats, may be NULL): a ray
+ * origin outside the scene - a camera - held to the same bound.  PTMI_OK, or the error ptmi_load_scene_arrays / a frame gives. */
+int  ptmi_host_scene_check_extent(ptmi_host_scene*, const float* origin);
 int  ptmi_host_scene_info(const ptmi_host_scene*, int* n_prims, int* n_tris, int* n_quads, int* n_bvh_nodes, int* bvh_depth);
 int  ptmi_host_scene_get_prims(const ptmi_host_scene*, int* type, float* verts, float* normal, float* bsdf, float* Le);
 int  ptmi_host_scene_get_bvh(const ptmi_host_scene*, float* bmin, float* bmax, int* left, int* right, int* count, int* indices);
@@ -366,6 +371,10 @@ int ptmi_debug_set_fast_tree(ptmi_ctx*, int max_leaf, float c_trav, float c_tri,
  * counts (may be NULL): [0] node visits, [1] triangle tests, summed over the rays. */
 int ptmi_debug_intersect_fast(ptmi_ctx*, int n, const float* o, const float* d, float t_min, float t_max,
                               int* hit, int* prim, float* t, uint64_t* counts);
+/* first_hit for n rays as given: the closest hit of the Radiosity view and the feature pass, by the walk they take for the loaded
+ * scene (the certified walk where the scene has it, else the reference's walk, LANE or STACK); t_max is theirs, FLT_MAX.  prim:
+ * load-order index or -1.  The answer is the reference's hit in every mode. */
+int ptmi_debug_first_hit(ptmi_ctx*, int n, const float* o, const float* d, float t_min, int* hit, int* prim, float* t);
 /* Host-only halves of the same: build the fast tree of a host scene, and walk it on the CPU decision for decision as the
  * kernel does (tests of the builder without a GPU). */
 int ptmi_host_fast_tree_build(ptmi_host_scene*, int max_leaf, float c_trav, float c_tri, int* n_nodes, int* depth, double* sah);
