@@ -449,6 +449,11 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
             need(cfg->sampling_mode == 0, "vertex normals are set: they need sampling_mode 0 (BSDF): the guided modes' grids lie about the stored normal");
             need(cfg->fast_tree == 0, "vertex normals are set: they need fast_tree 0: frames with vertex normals always trace the reference's hits");
         }
+        if (c->app.scene.hasAlbedoTexture()) {
+            need(cfg->integrator == 0, "an albedo texture is set: it needs integrator 0 (PathTracing): the Radiosity view ignores the texture");
+            need(cfg->sampling_mode == 0, "an albedo texture is set: it needs sampling_mode 0 (BSDF): the guided modes run through the bounce kernels");
+            need(cfg->fast_tree == 0, "an albedo texture is set: it needs fast_tree 0: textured frames always trace the reference's hits");
+        }
         AppConfig& a = c->app.config;                    // every check is above this line: a rejected config changes nothing
         a.spp = cfg->spp; a.max_depth = cfg->max_depth; a.sampling_mode = (SamplingMode)cfg->sampling_mode;
         a.mis_bsdf_fraction = cfg->mis_bsdf_fraction;
@@ -604,6 +609,38 @@ int ptmi_vertex_normals_info(const ptmi_ctx* c, int* n_smooth) {
     return guarded([&] {
         need(c != nullptr, "ctx is NULL");
         if (n_smooth) *n_smooth = c->app.scene.n_smooth;
+    });
+}
+
+int ptmi_check_albedo_texture(int width, int height, const float* texels, int filter, int n_prims, const float* uv, const int* textured) {
+    return guarded([&] { checkAlbedoTexture(width, height, texels, filter, n_prims, uv, textured); });
+}
+int ptmi_set_albedo_texture(ptmi_ctx* c, int width, int height, const float* texels, int filter, int n_prims, const float* uv, const int* textured) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        need(c->app.scene.d_nodes != nullptr, "no scene loaded");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        if (texels) {
+            checkAlbedoTexture(c->app.scene.h_primitives, width, height, texels, filter, n_prims, uv, textured);
+            if (countTextured(n_prims, textured) > 0) {
+                const AppConfig& a = c->app.config;
+                need(a.current_integrator == IntegratorType::PathTracing, "albedo texture: the config has integrator 1 (Radiosity), which ignores the texture");
+                need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "albedo texture: the config has a guided sampling_mode, which runs through the bounce kernels");
+                need(!a.fast_tree, "albedo texture: the config has fast_tree 1; textured frames always trace the reference's hits");
+            }
+        }
+        c->app.scene.setAlbedoTexture(width, height, texels, filter, uv, textured);   // every check is done before anything changes
+        viewChanged(c->app);                                         // other colours: the temporal history holds another image
+    });
+}
+int ptmi_albedo_texture_info(const ptmi_ctx* c, int* n_textured, int* width, int* height, int* filter) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        const SceneState& sc = c->app.scene;
+        if (n_textured) *n_textured = sc.n_textured;
+        if (width) *width = sc.tex_width;
+        if (height) *height = sc.tex_height;
+        if (filter) *filter = sc.tex_filter;
     });
 }
 
@@ -1166,6 +1203,36 @@ int ptmi_debug_vertex_normal(ptmi_ctx* c, int n, const int* prim, const float* p
         PTMI_HIP(hipGetLastError());
         PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
         d_o.download(out, 4 * (size_t)n);
+    });
+}
+
+int ptmi_debug_albedo(ptmi_ctx* c, int n, const int* prim, const float* p, float* out) {
+    return guarded([&] {
+        need(c && prim && p && out, "NULL argument");
+        need(n >= 0, "n must not be negative");
+        const SceneState& sc = c->app.scene;
+        need(sc.d_nodes != nullptr, "no scene loaded");
+        const int n_prims = (int)sc.h_primitives.size();
+        for (int i = 0; i < n; i++) need(prim[i] >= 0 && prim[i] < n_prims, "prim out of range");
+        if (n == 0) return;
+        if (!sc.hasAlbedoTexture()) {                         // no table: the kernel never calls the function
+            for (int i = 0; i < n; i++) {
+                out[6 * i] = out[6 * i + 1] = out[6 * i + 5] = 0.0f;
+                out[6 * i + 2] = out[6 * i + 3] = out[6 * i + 4] = 1.0f;
+            }
+            return;
+        }
+        std::vector<int> slot_of((size_t)n_prims), slots((size_t)n);
+        for (int k = 0; k < n_prims; k++) slot_of[sc.bvh_indices[k]] = k;
+        for (int i = 0; i < n; i++) slots[i] = slot_of[prim[i]];
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<int> d_s((size_t)n);
+        DevBuf<float> d_p(3 * (size_t)n), d_o(6 * (size_t)n);
+        d_s.upload(slots.data(), (size_t)n); d_p.upload(p, 3 * (size_t)n);
+        launch_debug_albedo(sc.d_scene, sc.albedoTable(), n, d_s.p, d_p.p, d_o.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d_o.download(out, 6 * (size_t)n);
     });
 }
 

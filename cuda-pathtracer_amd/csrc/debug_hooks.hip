@@ -3,6 +3,7 @@
 #include "bounce.h"
 #include "light_sample.h"
 #include "vertex_normal.h"
+#include "albedo_texture.h"
 #include "../../include/ptmi.h"      // PTMI_MATH_*
 
 namespace ptmi {
@@ -473,6 +474,27 @@ void launch_debug_vertex_normal(const DeviceScene& sc, const VertexNormalTable& 
     if (n <= 0) return;
     with_bool(sc.has_quads != 0, [&](auto quads) {
         hipLaunchKernelGGL(ptmi_debug_vertex_normal_k<decltype(quads)::value>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, vn, n, slots, p, out);
+    });
+}
+
+// albedo_at's lookup (albedo_texture.h) as ptmi_render_nee makes it on n (leaf-order slot, point) cases against the context's own
+// scene and table (test hook; include/ptmi.h: ptmi_debug_albedo): the wrapped coordinates, T, and 1.0 for a textured slot
+template <bool HAS_QUADS>
+__global__ __launch_bounds__(kBlock) void ptmi_debug_albedo_k(DeviceScene sc, AlbedoTable at, int n, const int* __restrict__ slots,
+                                                              const float* __restrict__ p, float* __restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const AlbedoLookup r = albedo_lookup<HAS_QUADS>(sc, at, slots[i], mk3(p[3 * i], p[3 * i + 1], p[3 * i + 2]));
+    f3 one = mk3(1.0f, 1.0f, 1.0f);
+    albedo_at<HAS_QUADS>(sc, at, slots[i], mk3(p[3 * i], p[3 * i + 1], p[3 * i + 2]), one);   // the kernel's entry: 1 * T
+    out[6 * i] = r.su; out[6 * i + 1] = r.sv;
+    out[6 * i + 2] = one.x; out[6 * i + 3] = one.y; out[6 * i + 4] = one.z;
+    out[6 * i + 5] = r.textured ? 1.0f : 0.0f;
+}
+void launch_debug_albedo(const DeviceScene& sc, const AlbedoTable& at, int n, const int* slots, const float* p, float* out, hipStream_t s) {
+    if (n <= 0) return;
+    with_bool(sc.has_quads != 0, [&](auto quads) {
+        hipLaunchKernelGGL(ptmi_debug_albedo_k<decltype(quads)::value>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, at, n, slots, p, out);
     });
 }
 

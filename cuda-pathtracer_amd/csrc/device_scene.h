@@ -338,15 +338,29 @@ struct SurfaceTable {
 struct VertexNormalTable {
     const float4* rec = nullptr;
 };
-// fp.n_frames x spp samples per queued pixel.  env.texel == nullptr, surf.rec == nullptr and vn.rec == nullptr: the NEE kernel
-// exactly as it was; that instantiation IGNORES next_event (the host routes a frame here only when it is set, and the switch folds
-// to true).  Else the ENV, SPEC and / or SMOOTH instantiation, which reads next_event and runs either estimator, looks the map up
-// where a path ray misses, continues a path through mirror and glass and shades a smooth primitive's vertex with the interpolated
-// normal (csrc/vertex_normal.h).  rough: the table holds a rough-metal record (SURF = 2; else the delta kinds' SURF = 1, which
+// ---- albedo texture (include/ptmi.h: ptmi_set_albedo_texture) ---------------------------------------------------------------
+// rec: TWO float4 per LEAF-ORDER slot, the order of prims (SceneState::setAlbedoTexture permutes the caller's load-order table),
+// whatever prim_stride is: rec[2 * k] = (u0, v0, u1, v1), rec[2 * k + 1] = (u2, v2, u3, v3), corners in the order of the
+// primitive's vertices; a triangle's (u3, v3) is zero.  An UNTEXTURED slot holds a quiet NaN in rec[2 * k].x (and zeros after it):
+// a textured primitive's UVs are checked finite, so the first 16-byte read decides and the second is made for a textured slot only.
+// texel: height x width float4 (rgb, 0), row-major, row 0 first.  filter: 0 nearest, 1 bilinear.  An array pair of its own, as
+// SurfaceTable and VertexNormalTable are and for the same reason.  rec == nullptr: no primitive is textured (no table, or a table
+// without a textured primitive).
+struct AlbedoTable {
+    const float4* rec = nullptr;
+    const float4* texel = nullptr;
+    int width = 0, height = 0, filter = 0;
+};
+// fp.n_frames x spp samples per queued pixel.  env.texel == nullptr, surf.rec == nullptr, vn.rec == nullptr and at.rec == nullptr:
+// the NEE kernel exactly as it was; that instantiation IGNORES next_event (the host routes a frame here only when it is set, and
+// the switch folds to true).  Else the ENV, SPEC, SMOOTH and / or TEX instantiation, which reads next_event and runs either
+// estimator, looks the map up where a path ray misses, continues a path through mirror and glass, shades a smooth primitive's
+// vertex with the interpolated normal (csrc/vertex_normal.h) and multiplies a textured primitive's Kd by the image's value at the
+// vertex (csrc/albedo_texture.h).  rough: the table holds a rough-metal record (SURF = 2; else the delta kinds' SURF = 1, which
 // never reads a kind 3).
 void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, const VertexNormalTable& vn,
-                       bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first,
-                       hipStream_t s);
+                       const AlbedoTable& at, bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp,
+                       const int* queue, int n, bool first, hipStream_t s);
 
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)
@@ -421,5 +435,7 @@ void launch_debug_nee_call(bool has_quads, int n, int op, const EmitterTable& em
 // ptmi_debug_vertex_normal (include/ptmi.h): vertex_normal (vertex_normal.h) of leaf-order slot slots[i] at p[3i ..] -> out[4i ..]
 void launch_debug_vertex_normal(const DeviceScene& sc, const VertexNormalTable& vn, int n, const int* slots, const float* p, float* out /* 4n */,
                                 hipStream_t s);
+// ptmi_debug_albedo (include/ptmi.h): albedo_at (albedo_texture.h) of leaf-order slot slots[i] at p[3i ..] -> out[6i ..]
+void launch_debug_albedo(const DeviceScene& sc, const AlbedoTable& at, int n, const int* slots, const float* p, float* out /* 6n */, hipStream_t s);
 
 }  // namespace ptmi

@@ -2,6 +2,7 @@
 // feature pass and next-event estimation.  Compile with -ffp-contract=off (kernels.hip).
 #include "light_sample.h"
 #include "vertex_normal.h"
+#include "albedo_texture.h"
 
 namespace ptmi {
 
@@ -125,9 +126,12 @@ void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams
 // SMOOTH (include/ptmi.h: "vertex normals"; the table: device_scene.h VertexNormalTable): the context has a table with a smooth
 // primitive; a vertex on one takes the normal interpolated at the hit point (vertex_normal.h) where sn is formed, and everything
 // below reads it from there.  The emitter pdf above keeps the geometric normal.
-template <int MODE, bool HAS_QUADS, bool ENV, int SURF, bool SMOOTH>
+// TEX (include/ptmi.h: "albedo texture"; the table: device_scene.h AlbedoTable): the context has a table with a textured primitive;
+// a vertex on one multiplies Kd by the image's value at the hit point (albedo_texture.h) directly before the throughput takes it,
+// after the roulette.  at.filter is a wave-uniform runtime switch.
+template <int MODE, bool HAS_QUADS, bool ENV, int SURF, bool SMOOTH, bool TEX>
 __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, EmitterTable em, EnvTable ev, SurfaceTable sf, TileMap tm, PathState st, FrameParams fp,
-                                                          const int* __restrict__ queue, int n, int first, int next_event, VertexNormalTable vn) {
+                                                          const int* __restrict__ queue, int n, int first, int next_event, VertexNormalTable vn, AlbedoTable at) {
     extern __shared__ float4 smem[];
     constexpr bool SPEC = SURF != 0;
     const int idx = blockIdx.x * kBlock + threadIdx.x;
@@ -139,8 +143,8 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     Rng rng = {e.x, e.y, e.z, e.w, f.x, f.y};
     f3 color = first ? mk3(0.0f, 0.0f, 0.0f) : xyz(st.D[slot]);
     LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
-    // wave-uniform switches of the ENV, SPEC and SMOOTH instantiations; without any of them they fold to the NEE kernel
-    const bool nee_on = ENV || SPEC || SMOOTH ? next_event != 0 : true;   // light samples and MIS weights at all
+    // wave-uniform switches of the ENV, SPEC, SMOOTH and TEX instantiations; without any of them they fold to the NEE kernel
+    const bool nee_on = ENV || SPEC || SMOOTH || TEX ? next_event != 0 : true;   // light samples and MIS weights at all
     const bool env_on = ENV ? ev.sampled != 0 : false;       // the environment is one of the lights: five draws, selection by q
     const float q = ENV ? ev.q : 0.0f, omq = 1.0f - q;
     for (int frame = 0; frame < fp.n_frames; frame++) {
@@ -181,7 +185,8 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                     break;
                 }
                 f3 nrm = xyz(sc.mats[3 * k]);
-                const f3 bsdf = xyz(sc.mats[3 * k + 1]), Le = xyz(sc.mats[3 * k + 2]);
+                f3 bsdf = xyz(sc.mats[3 * k + 1]);
+                const f3 Le = xyz(sc.mats[3 * k + 2]);
                 const f3 hp = o + t * d;                                                  // triangle.h:90
                 const float4 pe = depth > 0 && nee_on && !(SPEC && spec_prev) ? em.pdf_area[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 const float pa = pe.w;
@@ -198,6 +203,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                     if (rng_uniform(rng) > rr_prob) break;
                     tp = div_scalar(tp, rr_prob);
                 }
+                if constexpr (TEX) albedo_at<HAS_QUADS>(sc, at, k, hp, bsdf);             // Kd(p) = Kd_k * T, after the roulette
                 tp = tp * bsdf;                                                           // integrator.h:215
                 if (length(tp) < 1e-5f) break;                                            // integrator.h:218
                 if constexpr (SMOOTH) vertex_normal<HAS_QUADS>(sc, vn, k, hp, nrm);       // after the throughput exit, not at the hit
@@ -305,17 +311,19 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
 }
 
 void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, const VertexNormalTable& vn,
-                       bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp, const int* queue, int n, bool first,
-                       hipStream_t s) {
+                       const AlbedoTable& at, bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp,
+                       const int* queue, int n, bool first, hipStream_t s) {
     if (n <= 0) return;
     first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
         with_bool(env.texel != nullptr, [&](auto with_env) {
             auto launch = [&](auto surf_kinds) {
                 with_bool(vn.rec != nullptr, [&](auto smooth) {
-                    hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value, decltype(surf_kinds)::value,
-                                                        decltype(smooth)::value>),
-                                       dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, surf, tm, st, fp, queue, n, first ? 1 : 0,
-                                       next_event ? 1 : 0, vn);
+                    with_bool(at.rec != nullptr, [&](auto tex) {
+                        hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value,
+                                                            decltype(surf_kinds)::value, decltype(smooth)::value, decltype(tex)::value>),
+                                           dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, surf, tm, st, fp, queue, n, first ? 1 : 0,
+                                           next_event ? 1 : 0, vn, at);
+                    });
                 });
             };
             if (surf.rec == nullptr) launch(std::integral_constant<int, 0>{});

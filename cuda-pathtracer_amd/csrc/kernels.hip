@@ -19,7 +19,8 @@
 //                                         its SURF = 1 instantiation every frame of a scene with a mirror or glass primitive (ptmi_set_surfaces),
 //                                         SURF = 2 with a rough-metal primitive as well (ptmi_set_surfaces_rough; rough.h),
 //                                         its SMOOTH instantiation every frame of a scene with a smooth primitive (ptmi_set_vertex_normals;
-//                                         vertex_normal.h)
+//                                         vertex_normal.h), its TEX instantiation every frame of a scene with a textured primitive
+//                                         (ptmi_set_albedo_texture; albedo_texture.h)
 //   debug_hooks.hip    the test hooks
 #include "bounce.h"
 

@@ -21,12 +21,22 @@ __device__ __forceinline__ HalfCoords half_coords(f3 ea, f3 eb, f3 w) {
     return h;
 }
 
+// the clamped weights (b0, b1, b2) of h over (corner 0, corner a, corner b): by comparison, so a NaN stays a NaN.  The normals
+// here and the texture coordinates of albedo_texture.h are blended with these
+struct HalfWeights { float b0, b1, b2; };
+__device__ __forceinline__ HalfWeights clamped_weights(const HalfCoords& h) {
+    HalfWeights w;
+    w.b1 = h.r1 < 0.0f ? 0.0f : (h.r1 > 1.0f ? 1.0f : h.r1);
+    const float m = 1.0f - w.b1;
+    w.b2 = h.r2 < 0.0f ? 0.0f : (h.r2 > m ? m : h.r2);
+    w.b0 = m - w.b2;
+    return w;
+}
+
 // the clamped weights of h and the normal they give over (n0, na, nb); false: the sum has no direction, nrm stays
 __device__ __forceinline__ bool blend_normals(const HalfCoords& h, f3 n0, f3 na, f3 nb, f3& nrm) {
-    const float b1 = h.r1 < 0.0f ? 0.0f : (h.r1 > 1.0f ? 1.0f : h.r1);
-    const float m = 1.0f - b1;
-    const float b2 = h.r2 < 0.0f ? 0.0f : (h.r2 > m ? m : h.r2);
-    const float b0 = m - b2;
+    const HalfWeights cw = clamped_weights(h);
+    const float b0 = cw.b0, b1 = cw.b1, b2 = cw.b2;
     const f3 sum = mk3((b0 * n0.x + b1 * na.x) + b2 * nb.x, (b0 * n0.y + b1 * na.y) + b2 * nb.y, (b0 * n0.z + b1 * na.z) + b2 * nb.z);
     const float len2 = dot(sum, sum);
     if (!(len2 > 0.0f && len2 <= FLT_MAX)) return false;

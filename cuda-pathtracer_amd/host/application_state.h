@@ -19,6 +19,7 @@
 #include "environment.h"
 #include "surfaces.h"
 #include "vertex_normals.h"
+#include "albedo_texture.h"
 #include "file_manager.h"
 #include "pbrt_loader.h"
 #include "sensor.h"
@@ -170,6 +171,18 @@ struct SceneState {
     // number); normals nullptr, or no smooth primitive, drops the table
     void setVertexNormals(const float* normals, const std::vector<unsigned char>& smooth, int smooth_count);
     VertexNormalTable vertexNormalTable() const { VertexNormalTable t; t.rec = d_vertex_normals; return t; }
+    // albedo texture (include/ptmi.h: ptmi_set_albedo_texture): the caller's load-order UV table by leaf-order slot and the image as
+    // float4 texels (csrc/device_scene.h: AlbedoTable).  It goes with the scene (cleanup).  A table without a textured primitive is
+    // kept as no table: both arrays stay nullptr and a frame takes the route it takes without one.
+    int n_textured = 0, tex_width = 0, tex_height = 0, tex_filter = 0;
+    float4* d_albedo_rec = nullptr;
+    float4* d_albedo_texels = nullptr;
+    bool hasAlbedoTexture() const { return d_albedo_rec != nullptr; }
+    // checked by the caller (checkAlbedoTexture); texels nullptr, or no textured primitive, drops the table
+    void setAlbedoTexture(int width, int height, const float* texels, int filter, const float* uv, const int* textured);
+    AlbedoTable albedoTable() const {
+        AlbedoTable t; t.rec = d_albedo_rec; t.texel = d_albedo_texels; t.width = tex_width; t.height = tex_height; t.filter = tex_filter; return t;
+    }
     int sweep_max_prims = 64;                        // scenes up to this many primitives use the wave-uniform sweep
     int force_traversal = -1;                        // test/benchmark override (TraversalMode), -1 = automatic
 

@@ -168,13 +168,13 @@ void prepareCostOrder(Run& run, int order_classes) {
 // of ptmi_render_nee on the frame's stream: no chunks, no refill, no launch order by cost; the whole frame, batch or pass
 // a context with an environment (ptmi_set_environment) takes the same route for both values of next_event: the per-lane kernel
 // is the one that looks the map up where a path ray misses; so does a scene with a mirror, glass or rough-metal primitive (ptmi_set_surfaces, ptmi_set_surfaces_rough)
-// or with a smooth primitive (ptmi_set_vertex_normals)
+// or with a smooth primitive (ptmi_set_vertex_normals) or a textured one (ptmi_set_albedo_texture)
 void runNeeLaunch(Run& run) {
     ApplicationState& g = run.g;
     const int n = run.queueLength();
     const hipEvent_t e0 = run.stamp(run.s);
     launch_render_nee(g.scene.d_scene, g.scene.d_emitters, g.env.table(g.config.next_event, g.scene.d_emitters.n), g.scene.surfaceTable(),
-                      g.scene.vertexNormalTable(), g.scene.hasRough(), g.config.next_event, run.r.tile, run.r.d_state, run.fp,
+                      g.scene.vertexNormalTable(), g.scene.albedoTable(), g.scene.hasRough(), g.config.next_event, run.r.tile, run.r.d_state, run.fp,
                       run.pass ? run.chunks[0].d_queue_init : nullptr, n,
                       run.pass ? run.pass->rule.first != 0 : true, run.s);
     PTMI_HIP(hipGetLastError());
@@ -352,7 +352,8 @@ void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pa
     r.dn.image_current = false;                        // what ptmi_denoise may filter: likewise, only a completed path-tracing run
 
     const bool path_tracing = g.config.current_integrator == IntegratorType::PathTracing;
-    const bool nee = (g.config.next_event || g.env.present() || g.scene.hasSpecular() || g.scene.hasVertexNormals()) && path_tracing;
+    const bool nee = (g.config.next_event || g.env.present() || g.scene.hasSpecular() || g.scene.hasVertexNormals() || g.scene.hasAlbedoTexture()) &&
+                     path_tracing;
     const DeviceScene scene = effectiveScene(g);
     const LaunchOverrides over = LaunchOverrides::fromEnv();
     const LaunchRule rule = planLaunches(g, scene, fp, n_frames, pass != nullptr, nee, over);

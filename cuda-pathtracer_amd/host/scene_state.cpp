@@ -5,6 +5,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <limits>
 
 namespace ptmi {
 
@@ -25,6 +26,9 @@ void SceneState::cleanup() {
     for (int& c : surface_counts) c = 0;
     if (d_vertex_normals) (void)hipFree(d_vertex_normals);
     d_vertex_normals = nullptr; n_smooth = 0;
+    if (d_albedo_rec) (void)hipFree(d_albedo_rec);
+    if (d_albedo_texels) (void)hipFree(d_albedo_texels);
+    d_albedo_rec = d_albedo_texels = nullptr; n_textured = tex_width = tex_height = tex_filter = 0;
     d_emit_rec = d_pdf_area = nullptr; d_emit_cdf = nullptr; d_emitters = EmitterTable();
     h_emit_prim.clear(); h_emit_cdf.clear(); h_emit_normal.clear(); h_pdf_area.clear(); h_emit_total = 0.0f;
     freePacked();
@@ -597,6 +601,40 @@ void SceneState::setVertexNormals(const float* normals, const std::vector<unsign
     }
     if (d_vertex_normals) (void)hipFree(d_vertex_normals);   // nothing has changed before this line
     d_vertex_normals = nd; n_smooth = smooth_count;
+}
+
+// albedo texture (include/ptmi.h: ptmi_set_albedo_texture): two float4 per leaf-order slot and the image as float4 (rgb, 0)
+void SceneState::setAlbedoTexture(int width, int height, const float* texels, int filter, const float* uv, const int* textured) {
+    if (!d_nodes) throw ArgError("setAlbedoTexture: no scene loaded");
+    const int n = (int)h_primitives.size();
+    const int count = texels && uv ? countTextured(n, textured) : 0;
+    float4 *rd = nullptr, *td = nullptr;
+    if (count > 0) {
+        const float untextured = std::numeric_limits<float>::quiet_NaN();
+        std::vector<float4> rec(2 * (size_t)n, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        for (int k = 0; k < n; k++) {                    // same leaf-order slots as prims/mats
+            const int src = bvh_indices[k];
+            if (textured && textured[src] == 0) { rec[2 * (size_t)k].x = untextured; continue; }   // its UVs are never read
+            const float* v = uv + (size_t)src * kAlbedoCorners * 2;
+            const bool quad = h_primitives[src].type == PRIM_QUAD;
+            rec[2 * (size_t)k] = make_float4(v[0], v[1], v[2], v[3]);
+            rec[2 * (size_t)k + 1] = make_float4(v[4], v[5], quad ? v[6] : 0.0f, quad ? v[7] : 0.0f);
+        }
+        std::vector<float4> tex((size_t)width * (size_t)height);
+        for (size_t t = 0; t < tex.size(); t++) tex[t] = make_float4(texels[3 * t], texels[3 * t + 1], texels[3 * t + 2], 0.0f);
+        rd = (float4*)hipMallocSafe(rec.size() * sizeof(float4), "d_albedo_rec");
+        hipError_t e = hipMemcpy(rd, rec.data(), rec.size() * sizeof(float4), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(rd); PTMI_HIP(e); }
+        try {
+            td = (float4*)hipMallocSafe(tex.size() * sizeof(float4), "d_albedo_texels");
+        } catch (...) { (void)hipFree(rd); throw; }
+        e = hipMemcpy(td, tex.data(), tex.size() * sizeof(float4), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(rd); (void)hipFree(td); PTMI_HIP(e); }
+    }
+    if (d_albedo_rec) (void)hipFree(d_albedo_rec);       // nothing has changed before this line
+    if (d_albedo_texels) (void)hipFree(d_albedo_texels);
+    d_albedo_rec = rd; d_albedo_texels = td; n_textured = count;
+    tex_width = count > 0 ? width : 0; tex_height = count > 0 ? height : 0; tex_filter = count > 0 ? filter : 0;
 }
 
 // RadiosityState: host/radiosity_state.cpp

@@ -46,6 +46,7 @@ EXPORTS = [
     "ptmi_check_surfaces_rough", "ptmi_set_surfaces_rough", "ptmi_surface_counts",
     "ptmi_check_vertex_normals", "ptmi_host_classify_vertex_normals", "ptmi_set_vertex_normals", "ptmi_vertex_normals_info",
     "ptmi_debug_vertex_normal",
+    "ptmi_check_albedo_texture", "ptmi_set_albedo_texture", "ptmi_albedo_texture_info", "ptmi_debug_albedo",
 ]
 
 
@@ -262,6 +263,11 @@ def lib():
             L.ptmi_set_vertex_normals.argtypes = [vp, C.c_int, vp]
             L.ptmi_vertex_normals_info.argtypes = [vp, ip]
             L.ptmi_debug_vertex_normal.argtypes = [vp, C.c_int, vp, vp, vp]
+        if hasattr(L, "ptmi_set_albedo_texture"):      # likewise
+            L.ptmi_check_albedo_texture.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+            L.ptmi_set_albedo_texture.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+            L.ptmi_albedo_texture_info.argtypes = [vp, ip, ip, ip, ip]
+            L.ptmi_debug_albedo.argtypes = [vp, C.c_int, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -515,6 +521,36 @@ def classify_vertex_normals(types, stored, normals):
     return smooth.astype(bool)
 
 
+TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1}
+
+
+def _albedo_args(image, uv, textured, filter):
+    """(width, height, texels, filter, n_prims, uv, textured or None) as the C entries take them"""
+    image = np.ascontiguousarray(image, np.float32)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("the image must be (height, width, 3)")
+    uv = np.ascontiguousarray(uv, np.float32)
+    if uv.ndim != 3 or uv.shape[1:] != (4, 2):
+        raise ValueError("uv must be (n_prims, 4, 2)")
+    if textured is not None:
+        textured = np.ascontiguousarray(np.asarray(textured) != 0, np.int32)
+        if textured.shape != (len(uv),):
+            raise ValueError("textured must be (n_prims,)")
+    if isinstance(filter, str):
+        if filter not in TEXTURE_FILTERS:
+            raise ValueError("filter must be 'nearest' or 'bilinear'")
+        filter = TEXTURE_FILTERS[filter]
+    return image.shape[1], image.shape[0], image, int(filter), len(uv), uv, textured
+
+
+def check_albedo_texture(image, uv, textured=None, filter="bilinear"):
+    """ptmi_check_albedo_texture: raises PtmiError for what ptmi_set_albedo_texture would reject on its own account (host only):
+    a side outside 1 .. 4096, a filter other than nearest (0) / bilinear (1), a texel that is not finite or is negative, a UV of
+    corners 0 .. 2 of a textured primitive that is not finite or exceeds 65536 in magnitude.  image (h, w, 3), uv (n_prims, 4, 2)."""
+    w, h, image, filter, n, uv, textured = _albedo_args(image, uv, textured, filter)
+    _check(lib().ptmi_check_albedo_texture(w, h, image.ctypes.data, filter, n, uv.ctypes.data, _ptr(textured)))
+
+
 class Renderer:
     """One ApplicationState bound to one GPU."""
 
@@ -724,6 +760,36 @@ class Renderer:
             raise ValueError("prim must be (n,) and p (n, 3)")
         out = np.zeros((len(prim), 4), np.float32)
         self._ck(self.L.ptmi_debug_vertex_normal(self.h, len(prim), prim.ctypes.data, p.ctypes.data, out.ctypes.data))
+        return out
+
+    def set_albedo_texture(self, image, uv, textured=None, filter="bilinear"):
+        """Albedo texture (include/ptmi.h: "albedo texture"): image (h, w, 3) linear RGB, row 0 at v = 0; uv (n_prims, 4, 2), a
+        primitive's corner UVs in load order and in the corner order of its vertices (a triangle's 4th is ignored); textured
+        (n_prims,) marks the primitives the image applies to (None: all); filter "nearest" or "bilinear".  image None drops the
+        texture.  Kd is multiplied by the image's value at every path vertex on a textured primitive.  A scene load drops it."""
+        if image is None:
+            self._ck(self.L.ptmi_set_albedo_texture(self.h, 0, 0, None, 0, 0, None, None))
+            return
+        w, h, image, filter, n, uv, textured = _albedo_args(image, uv, textured, filter)
+        self._ck(self.L.ptmi_set_albedo_texture(self.h, w, h, image.ctypes.data, filter, n, uv.ctypes.data, _ptr(textured)))
+
+    def albedo_texture_info(self):
+        """ptmi_albedo_texture_info: the number of textured primitives, the image's size and filter; all 0 without a texture"""
+        n, w, h, f = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._ck(self.L.ptmi_albedo_texture_info(self.h, C.byref(n), C.byref(w), C.byref(h), C.byref(f)))
+        return dict(n_textured=n.value, width=w.value, height=h.value, filter=f.value)
+
+    check_albedo_texture = staticmethod(check_albedo_texture)
+
+    def debug_albedo(self, prim, p):
+        """ptmi_debug_albedo: the kernel's lookup for load-order primitives prim (n,) at the points p (n, 3) on the loaded scene
+        and texture.  Returns (n, 6) float32: the wrapped (u, v), T, then 1.0 for a textured primitive; (0, 0, 1, 1, 1, 0) for an
+        untextured one or without a texture."""
+        prim = np.ascontiguousarray(prim, np.int32); p = np.ascontiguousarray(p, np.float32)
+        if prim.ndim != 1 or p.shape != (len(prim), 3):
+            raise ValueError("prim must be (n,) and p (n, 3)")
+        out = np.zeros((len(prim), 6), np.float32)
+        self._ck(self.L.ptmi_debug_albedo(self.h, len(prim), prim.ctypes.data, p.ctypes.data, out.ctypes.data))
         return out
 
     def camera_frame(self):

@@ -240,3 +240,34 @@ def cornell_spheres(prims, level=3):
         ranges[name] = (first, first + len(st)); first += len(st)
     arrays = tuple(np.concatenate(p) for p in parts)
     return arrays, np.concatenate(table).astype(F), ranges
+
+
+def checker(n, a, b):
+    """An (n, n, 3) float32 image of two colours: texel (j, i) is a where i + j is even and b where it is odd (linear RGB, as
+    Renderer.set_albedo_texture takes it)."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("checker: n must be >= 1")
+    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
+    if a.shape != (3,) or b.shape != (3,):
+        raise ValueError("checker: the colours must be (3,)")
+    j, i = np.mgrid[0:n, 0:n]
+    return np.where((((i + j) & 1) == 0)[:, :, None], a, b).astype(np.float32)
+
+
+def box_uvs(prims, scale=1.0, origin=(0, 0, 0)):
+    """(n_prims, 4, 2) float32 corner UVs for Renderer.set_albedo_texture: every primitive is projected onto the plane of its stored
+    normal's dominant axis and uv = (the two remaining coordinates, in x, y, z order, - origin) / scale.  A corner's UV depends on
+    its position and that axis only, so a wall of any tessellation gets one continuous map and coplanar primitives agree bit for
+    bit at shared corners.  prims: Renderer.scene_prims() (type, verts, normal).  A triangle's 4th entry is zero."""
+    types = np.asarray(prims["type"]); verts = np.asarray(prims["verts"], np.float32); normal = np.asarray(prims["normal"], np.float32)
+    scale = np.float32(scale); origin = np.asarray(origin, np.float32)
+    if not (np.isfinite(scale) and scale != 0):
+        raise ValueError("box_uvs: scale must be a finite number other than 0")
+    uv = np.zeros((len(types), 4, 2), np.float32)
+    for i in range(len(types)):
+        axis = int(np.argmax(np.abs(normal[i])))
+        keep = [c for c in range(3) if c != axis]
+        read = 4 if types[i] == 1 else 3
+        uv[i, :read] = (verts[i, :read][:, keep] - origin[keep]) / scale
+    return uv

@@ -1072,6 +1072,68 @@ int  ptmi_vertex_normals_info(const ptmi_ctx*, int* n_smooth);   /* 0 without a 
  * flat primitive, a fallback, no table).  PTMI_E_INVALID: no scene, a prim out of range. */
 int  ptmi_debug_vertex_normal(ptmi_ctx*, int n, const int* prim /* load order */, const float* p /* 3n */, float* out /* 4n */);
 
+/* ---- albedo texture: a UV-mapped image modulating Kd at path vertices (new in this implementation) ------------------------------
+ * The loaders keep ONE colour per primitive, as the reference does (its OBJ loader reads no vt or map_Kd, its PBRT importer counts
+ * a textured Kd as 1 1 1).  ptmi_set_albedo_texture gives the loaded scene ONE image - an atlas covers many materials - of
+ * height x width x 3 floats, linear RGB, row-major, and a table of corner UVs, n_prims x 4 x 2 floats in load order, a primitive's
+ * corners in the order of ptmi_load_scene_arrays' verts (v0 v1 v2 | v00 v10 v11 v01) as in the vertex-normal table; a triangle's
+ * 4th UV is ignored.  textured (n_prims ints, NULL: all) marks the primitives the image applies to; UVs of the others are never
+ * read and may hold anything.  The table belongs to the scene exactly as the surface and vertex-normal tables do: a scene load
+ * drops it.  Ke is never textured.
+ *
+ * A table without a textured primitive is no table: the context takes exactly the route it takes without one.  A context with a
+ * textured primitive renders both values of next_event through the per-lane kernel of next-event estimation, as a context with an
+ * environment, a specular surface or a smooth primitive does; frames, batches, passes, tiled contexts, ptmi_denoise,
+ * ptmi_denoise_variance, ptmi_temporal_accumulate and ptmi_gather_frame work as they do without one.  ptmi_run_radiosity_solver,
+ * the Radiosity view (integrator = 1) and ptmi_render_features IGNORE the texture: the feature albedo stays Kd_k, so the denoisers
+ * demodulate by the untextured colour.
+ *
+ * ptmi_set_albedo_texture: texels NULL drops the texture (every other argument is then ignored).  A successful call restarts an
+ * accumulation, makes features stale and empties the temporal history, as ptmi_set_surfaces does.  PTMI_E_INVALID, with nothing
+ * changed (every check is made before anything changes, and the new arrays are uploaded before the old ones are freed): no scene
+ * loaded; n_prims != ptmi_scene_info's count; width or height outside 1 .. 4096; filter not 0 (nearest) or 1 (bilinear); a texel
+ * component that is not finite or is negative; a UV component that is read, of a textured primitive, that is not finite or whose
+ * magnitude exceeds 65536; and - with a textured primitive - a current config with integrator = 1, sampling_mode != 0 or
+ * fast_tree = 1; ptmi_set_config rejects those three while such a table is set.  ptmi_check_albedo_texture makes the checks that
+ * need no context: n_prims >= 1, texels and uv not NULL, the ranges, the texels, and corners 0 .. 2 of every textured primitive
+ * (the 4th corner's check needs the primitive's type: ptmi_set_albedo_texture makes it for textured quads).
+ * ptmi_albedo_texture_info: the number of textured primitives and the image's width, height and filter, all 0 without a table.
+ *
+ * THE UV of a vertex at p = o + t d on a textured primitive k; binary32 in the order written, no fused multiply-add.  The weights
+ * b0, b1, b2 are those of "vertex normals", character for character: w = p - v0, den, r1, r2 over the edges of the half,
+ * b1 = r1 < 0 ? 0 : (r1 > 1 ? 1 : r1);  m = 1 - b1;  b2 = r2 < 0 ? 0 : (r2 > m ? m : r2);  b0 = m - b2 (comparisons), a triangle's one
+ * half (e1, e2) with corners (0, a, b) = (0, 1, 2), a quad's first half (e1, e2) with corners (0, 1, 2) where its den is valid (den >
+ * 0 and den <= FLT_MAX) and the raw r1 >= 0, otherwise its second half (e2, e3) with corners (0, 2, 3).  Where the half so chosen
+ * has no valid den the weights are (1, 0, 0) and nothing is blended: (u, v) = (u_0, v_0), the first corner's as stored.  Otherwise,
+ * per coordinate:
+ *       u = (b0 * u_0 + b1 * u_a) + b2 * u_b
+ * and then for both:
+ *       s = u - floorf(u);   s = (s >= 0 && s < 1) ? s : 0        (repeat; -1e-9f gives 1.0f and a NaN gives a NaN: both pin to 0)
+ * THE TEXEL.  Row 0 of the image is v in [0, 1 / height); nothing is flipped.  s_u, s_v the wrapped coordinates.
+ *   nearest:   i = (int)(s_u * (float)width);   if (i > width - 1) i = width - 1;   j likewise from s_v and height;
+ *              T = texel[j * width + i]
+ *   bilinear:  x = s_u * (float)width - 0.5f;   x0 = floorf(x);   fx = x - x0;   i0 = (int)x0;   i1 = i0 + 1
+ *              if (i0 < 0) i0 = width - 1;   if (i1 > width - 1) i1 = 0          (repeat at the seam)
+ *              y0, fy, j0, j1 likewise from s_v and height; per channel
+ *              a = (1 - fx) * T[j0][i0] + fx * T[j0][i1];   b = (1 - fx) * T[j1][i0] + fx * T[j1][i1];   T = (1 - fy) * a + fy * b
+ *              every product rounded, every sum rounded.  (1 - f) + f == 1 in binary32 for every f in [0, 1), so an image of all
+ *              ones gives T = 1 exactly under both filters.
+ * THE ESTIMATOR is that of "vertex normals" (and of every section it builds on) with ONE change: Kd(p) = Kd_k * T, per component,
+ * replaces Kd_k wherever step 2 reads the primitive's colour - the beta = beta * Kd before the |beta| < 1e-5 exit - so the texture
+ * tints mirror, glass and rough metal exactly as Kd_k does.  The lookup happens after the roulette: a path the roulette ends never
+ * makes it.  Draws, depth count, roulette, exits, emitter pdf and light sampling are unchanged, and an untextured primitive in a
+ * textured scene uses Kd_k untouched. */
+/* host only, no context: 0 or PTMI_E_INVALID with the message */
+int  ptmi_check_albedo_texture(int width, int height, const float* texels, int filter, int n_prims, const float* uv, const int* textured);
+int  ptmi_set_albedo_texture(ptmi_ctx*, int width, int height, const float* texels /* height*width*3, linear RGB, row-major; NULL drops the texture */,
+                             int filter /* 0 nearest, 1 bilinear */, int n_prims, const float* uv /* n_prims*4*2, load order */,
+                             const int* textured /* n_prims, nonzero: textured; NULL: all */);
+int  ptmi_albedo_texture_info(const ptmi_ctx*, int* n_textured, int* width, int* height, int* filter);   /* all 0 without one */
+/* test hook: the kernel's own function (csrc/albedo_texture.h) once per case on the loaded scene and table.  prim: load-order
+ * indices; p: 3n points; out: 6n - s_u, s_v, T.rgb, then 1.0 for a textured primitive; for an untextured one, or with no table:
+ * 0, 0, 1, 1, 1, 0.  PTMI_E_INVALID: no scene, a prim out of range. */
+int  ptmi_debug_albedo(ptmi_ctx*, int n, const int* prim /* load order */, const float* p /* 3n */, float* out /* 6n */);
+
 #ifdef __cplusplus
 }
 #endif

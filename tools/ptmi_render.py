@@ -23,6 +23,9 @@
                                (the blocks replaced by smooth-shaded spheres: a glass ball and a brushed-metal one)
   python tools/ptmi_render.py --scene mesh.obj --smooth 40 --out smooth.png
                                (corner normals from the stored ones, joined across edges of less than 40 degrees)
+  python tools/ptmi_render.py --scene ... --texture checker:8 --texture-prims 6-7 --texture-scale 2 --out floor.png
+                               (an 8 x 8 checker on cbox.obj's floor, repeating every 2 scene units; --texture FILE.npy takes an
+                                (h, w, 3) float image in LINEAR RGB - nothing is decoded from sRGB)
 """
 import argparse
 import os
@@ -94,6 +97,12 @@ def main():
     ap.add_argument("--spheres", type=int, nargs="?", const=3, default=None, metavar="LEVEL",
                     help="the Cornell box's blocks replaced by smooth-shaded spheres of 20 * 4^LEVEL triangles (default 3); "
                          "--mirror / --glass / --rough may then name them: short, tall")
+    ap.add_argument("--texture", default=None, metavar="FILE.npy|checker[:N]",
+                    help="albedo texture: a (height, width, 3) float image in linear RGB (no sRGB decoding), row 0 at v = 0, or an N x N "
+                         "checker (default 8) of white and 0.2 grey; Kd is multiplied by it, UVs from ptmi_scenes.box_uvs")
+    ap.add_argument("--texture-prims", default=None, metavar="LIST", help="the textured primitives, like --mirror; default: all that emit nothing")
+    ap.add_argument("--texture-scale", type=float, default=1.0, metavar="X", help="scene units per repeat of the image")
+    ap.add_argument("--texture-filter", choices=["nearest", "bilinear"], default="bilinear")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -165,6 +174,32 @@ def main():
     if corner_normals is not None:
         r.set_vertex_normals(corner_normals)
         print(f"vertex normals: {r.vertex_normals_info()['n_smooth']} smooth primitives")
+    if a.texture:
+        import numpy as np
+        import ptmi_scenes
+        if a.texture == "checker" or a.texture.startswith("checker:"):
+            try:
+                image = ptmi_scenes.checker(int(a.texture[8:]) if a.texture[7:] else 8, (1.0, 1.0, 1.0), (0.2, 0.2, 0.2))
+            except ValueError as e:
+                ap.error(f"--texture: {e}")
+        else:
+            image = np.load(a.texture)
+        prims = r.scene_prims()
+        textured = prims["Le"].max(1) <= 0
+        if a.texture_prims:
+            try:
+                idx = index_list(a.texture_prims, spheres)
+            except ValueError as e:
+                ap.error(f"--texture-prims: {e}")
+            if idx and not (0 <= min(idx) and max(idx) < len(textured)):
+                ap.error(f"--texture-prims: the scene has primitives 0 .. {len(textured) - 1}")
+            textured[:] = False
+            textured[idx] = True
+        if not (a.texture_scale > 0):
+            ap.error("--texture-scale must be positive")
+        r.set_albedo_texture(image, ptmi_scenes.box_uvs(prims, a.texture_scale), textured, a.texture_filter)
+        ti = r.albedo_texture_info()
+        print(f"albedo texture: {ti['width']} x {ti['height']}, {a.texture_filter}, {ti['n_textured']} textured primitives")
     if a.orbit > 0:
         if a.variance_guided and a.temporal:
             ap.error("--variance-guided does not filter the temporal history (no variance is carried in it)")

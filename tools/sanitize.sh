@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 OUT=${TMPDIR:-/tmp}/ptmi_sanitize; mkdir -p $OUT
 gcc -O1 -g -std=gnu11 -fPIC -fopenmp -ffp-contract=off -fno-fast-math -march=x86-64-v2 -fsanitize=address,undefined -fno-omit-frame-pointer \
     -shared -o $OUT/libptmi_oracle_asan.so oracle/ptmi_oracle.c -lm
-for f in csrc/kernels.hip csrc/bounce_sync.hip csrc/bounce_phased.hip csrc/bounce_wide.hip csrc/first_hit.hip csrc/debug_hooks.hip csrc/radiosity.hip csrc/form_factors.hip csrc/dist.hip csrc/denoise.hip csrc/denoise_variance.hip csrc/temporal.hip csrc/c_api.cpp host/scene_state.cpp host/render_state.cpp host/render_run.cpp host/post_process.cpp host/environment.cpp host/surfaces.cpp host/vertex_normals.cpp host/radiosity_state.cpp host/bvh.cpp host/file_manager.cpp host/pbrt_loader.cpp host/wide_bvh.cpp; do
+for f in csrc/kernels.hip csrc/bounce_sync.hip csrc/bounce_phased.hip csrc/bounce_wide.hip csrc/first_hit.hip csrc/debug_hooks.hip csrc/radiosity.hip csrc/form_factors.hip csrc/dist.hip csrc/denoise.hip csrc/denoise_variance.hip csrc/temporal.hip csrc/c_api.cpp host/scene_state.cpp host/render_state.cpp host/render_run.cpp host/post_process.cpp host/environment.cpp host/surfaces.cpp host/vertex_normals.cpp host/albedo_texture.cpp host/radiosity_state.cpp host/bvh.cpp host/file_manager.cpp host/pbrt_loader.cpp host/wide_bvh.cpp; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -x hip -O1 -g -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt \
       -fno-slp-vectorize -fsanitize=address,undefined -fno-gpu-sanitize -fno-omit-frame-pointer -c cuda-pathtracer_amd/$f -o $OUT/$(basename $f).o
 done
