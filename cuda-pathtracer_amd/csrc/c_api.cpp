@@ -644,6 +644,28 @@ int ptmi_albedo_texture_info(const ptmi_ctx* c, int* n_textured, int* width, int
     });
 }
 
+static void checkFeatureShading(int flags) {
+    need(flags >= 0 && flags <= 3, "feature shading: flags must be in [0, 3] (PTMI_FEATURE_TEXTURED_ALBEDO | PTMI_FEATURE_SHADING_NORMAL)");
+}
+int ptmi_check_feature_shading(int flags) {
+    return guarded([&] { checkFeatureShading(flags); });
+}
+int ptmi_set_feature_shading(ptmi_ctx* c, int flags) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        checkFeatureShading(flags);
+        if (flags == c->app.feature_shading) return;
+        c->app.feature_shading = flags;
+        featuresRedefined(c->app);                                   // the image and an accumulation stay as they are
+    });
+}
+int ptmi_feature_shading(const ptmi_ctx* c, int* flags) {
+    return guarded([&] {
+        need(c && flags, "NULL argument");
+        *flags = c->app.feature_shading;
+    });
+}
+
 int ptmi_get_camera_frame(const ptmi_ctx* c, float* out12) {
     return guarded([&] {
         need(c && out12, "NULL argument");

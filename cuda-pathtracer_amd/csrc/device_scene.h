@@ -147,7 +147,7 @@ struct StatCounters { unsigned long long rays, node_visits, prim_tests, hits, to
 constexpr int kBlock = 256;
 constexpr int kXorwowJumpWords = 32 * 160 * 5;   // 32 matrices T^(2^67 * 2^k), 160 rows of 5 words
 
-// ---- launchers (kernels.hip; the Radiosity view, the features and NEE: first_hit.hip; the hooks: debug_hooks.hip) ------------------------------------------------
+// ---- launchers (kernels.hip; the Radiosity view and NEE: first_hit.hip; the features: features.hip; the hooks: debug_hooks.hip) ------------------------------------------------
 // render_init (integrator.h:274-280): seeds every local pixel's stream and clears its state.
 void launch_render_init(const TileMap& tm, const PathState& st, const uint32_t* d_jump, uint64_t seed_base, hipStream_t s);
 // First camera ray of the frame for every local pixel (sample 0 of the spp loop, integrator.h:383-387).
@@ -215,11 +215,16 @@ void launch_resolve_counts(const TileMap& tm, const PathState& st, const unsigne
 // ---- feature buffers and the denoiser (include/ptmi.h: ptmi_render_features, ptmi_denoise) ---------------------------------
 // Per local pixel, local row-major (the order of ptmi_read_image), the means over the g x g first hits of the feature pass.
 struct FeatureBuffers {
-    float4* albedo = nullptr;        // (Kd.xyz, hit fraction)
-    float4* normal = nullptr;        // (stored primitive normal.xyz, 0)
+    float4* albedo = nullptr;        // (Kd.xyz, hit fraction); Kd x the image's value where the shaded albedo is asked for
+    float4* normal = nullptr;        // (stored primitive normal.xyz, 0); the interpolated normal where the shaded normal is asked for
     float4* position = nullptr;      // (hit point o + t d .xyz, 0)
 };
-void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams& fp, int g, const FeatureBuffers& fb, hipStream_t s);
+// flags: PTMI_FEATURE_* (include/ptmi.h: "shaded features").  The SHADED instantiation runs only where a flag is set AND its
+// table is present (at.rec for bit 0, vn.rec for bit 1); every other call launches the kernel as it was before the flags.
+struct VertexNormalTable;
+struct AlbedoTable;
+void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams& fp, int g, const FeatureBuffers& fb,
+                     const VertexNormalTable& vn, const AlbedoTable& at, int flags, hipStream_t s);
 // The constants of one run that the two a-trous filters share (csrc/denoise.hip; the contracts are written out in include/ptmi.h)
 struct FilterArgs {
     int width, height;               // the whole frame (a single rank)

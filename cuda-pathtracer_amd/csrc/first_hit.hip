@@ -1,5 +1,5 @@
-// first_hit.hip — the kernels that trace one ray at a time to its first hit (traversal.h: first_hit): the Radiosity view, the
-// feature pass and next-event estimation.  Compile with -ffp-contract=off (kernels.hip).
+// first_hit.hip — the kernels that trace one ray at a time to its first hit (traversal.h: first_hit): the Radiosity view and
+// next-event estimation (the feature pass: features.hip).  Compile with -ffp-contract=off (kernels.hip).
 #include "light_sample.h"
 #include "vertex_normal.h"
 #include "albedo_texture.h"
@@ -57,55 +57,6 @@ void launch_render_radiosity(const DeviceScene& sc, const TileMap& tm, const Pat
     first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
         hipLaunchKernelGGL((ptmi_render_radiosity<decltype(mode)::value, decltype(quads)::value>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s,
                            sc, tm, st, fp, rgb8, radiance);
-    });
-}
-
-// ---------------------------------------------------------------------------------------------
-// feature pass (include/ptmi.h: ptmi_render_features): g x g camera rays per local pixel through the stratum centres, first
-// hit by the walk of the Radiosity view (the reference's hit for every ray), no RNG.  One thread per local pixel, local
-// row-major; sums in stratum order (row j of the strata outer, column i inner), then x rcp_rn((float)(g * g)).
-// ---------------------------------------------------------------------------------------------
-template <int MODE, bool HAS_QUADS>
-__global__ __launch_bounds__(kBlock) void ptmi_features(DeviceScene sc, TileMap tm, FrameParams fp, int g, FeatureBuffers fb) {
-    extern __shared__ float4 smem[];
-    const int n = tm.local_rows * tm.width;
-    const int idx = blockIdx.x * kBlock + threadIdx.x;
-    const bool live = idx < n;
-    const int lr = live ? idx / tm.width : 0;
-    const int x = live ? idx - lr * tm.width : 0;
-    const int y = ((lr / tm.row_block) * tm.n_ranks + tm.rank) * tm.row_block + (lr % tm.row_block);
-    const float gf = (float)g;
-    f3 alb = mk3(0.0f, 0.0f, 0.0f), nrm = mk3(0.0f, 0.0f, 0.0f), pos = mk3(0.0f, 0.0f, 0.0f);
-    float hits = 0.0f;
-    LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
-    for (int j = 0; j < g; j++) {
-        for (int i = 0; i < g; i++) {
-            const float u = ((float)x + ((float)i + 0.5f) / gf) / (float)tm.width;
-            const float v = ((float)y + ((float)j + 0.5f) / gf) / (float)tm.height;
-            f3 o, d;
-            camera_ray_uv(fp, u, v, o, d);
-            float t = 0.0f; int k = -1;
-            const bool hit = first_hit<MODE, HAS_QUADS>(sc, smem, live, o, d, 1e-4f, t, k, cn);
-            if (live && hit) {
-                alb = alb + xyz(sc.mats[3 * k + 1]);
-                nrm = nrm + xyz(sc.mats[3 * k]);
-                pos = pos + (o + t * d);
-                hits = hits + 1.0f;
-            }
-        }
-    }
-    if (!live) return;
-    const float kk = rcp_rn((float)(g * g));
-    fb.albedo[idx] = make_float4(alb.x * kk, alb.y * kk, alb.z * kk, hits * kk);
-    fb.normal[idx] = make_float4(nrm.x * kk, nrm.y * kk, nrm.z * kk, 0.0f);
-    fb.position[idx] = make_float4(pos.x * kk, pos.y * kk, pos.z * kk, 0.0f);
-}
-
-void launch_features(const DeviceScene& sc, const TileMap& tm, const FrameParams& fp, int g, const FeatureBuffers& fb, hipStream_t s) {
-    const int n = tm.local_rows * tm.width;
-    if (n <= 0) return;
-    first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
-        hipLaunchKernelGGL((ptmi_features<decltype(mode)::value, decltype(quads)::value>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, tm, fp, g, fb);
     });
 }
 

@@ -13,7 +13,7 @@
 //                      queue compaction; segment-synchronous, wave-uniform SWEEP walk (or STACK / LANE)
 //   bounce_phased.hip  ptmi_bounce_phased the same work for larger scenes: per-lane stackless walk with wave-scheduled NODE/PRIM/SHADE phases
 //   bounce_wide.hip    ptmi_bounce_wide   the phased scheduling over the opt-in 8-wide tree, plain or certified
-//   first_hit.hip      the Radiosity view, the feature pass, and
+//   first_hit.hip      the Radiosity view, and
 //                      ptmi_render_nee    opt-in next-event estimation with MIS (include/ptmi.h): one lane runs a pixel's samples to their end;
 //                                         its ENV instantiation renders every frame of a context with an environment (ptmi_set_environment),
 //                                         its SURF = 1 instantiation every frame of a scene with a mirror or glass primitive (ptmi_set_surfaces),
@@ -21,6 +21,7 @@
 //                                         its SMOOTH instantiation every frame of a scene with a smooth primitive (ptmi_set_vertex_normals;
 //                                         vertex_normal.h), its TEX instantiation every frame of a scene with a textured primitive
 //                                         (ptmi_set_albedo_texture; albedo_texture.h)
+//   features.hip       ptmi_features      the feature pass; its SHADED instantiation where ptmi_set_feature_shading asks for a table the context has
 //   debug_hooks.hip    the test hooks
 #include "bounce.h"
 

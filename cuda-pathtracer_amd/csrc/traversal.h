@@ -1,6 +1,6 @@
 // traversal.h — the walks of the render kernels, each defined once: the reference's walk in its three forms (STACK, LANE, SWEEP),
 // the certified closest hit over the fast tree (csrc/wide_walk.h) and first_hit, the one-ray-at-a-time call of the Radiosity
-// view, the feature pass and next-event estimation (first_hit.hip).  Everything is __forceinline__ into the calling kernel.
+// view and next-event estimation (first_hit.hip) and the feature pass (features.hip).  Everything is __forceinline__ into the calling kernel.
 #pragma once
 #include "pt_device.h"
 #include "sweep_records.h"

@@ -402,6 +402,7 @@ struct ApplicationState {
     RadiosityState radiosity;
     DistState dist;
     AppConfig config;
+    int feature_shading = 0;                         // PTMI_FEATURE_* (include/ptmi.h: ptmi_set_feature_shading); the context's, not the scene's
     EnvState env;
     std::vector<uint32_t> h_jump;                    // 32 x 160 x 5 words
     std::vector<hipEvent_t> event_pool;
@@ -440,6 +441,7 @@ struct DenoiseParams {
 // an (rgb8, radiance) pair of n_local pixels to the host; either destination may be NULL
 void readImagePair(int device_id, size_t n_local, const unsigned char* d_rgb8, const float* d_radiance, unsigned char* rgb8, float* radiance);
 void featuresStale(ApplicationState& g_state);       // the triggers that restart an accumulation: features and image are stale
+void featuresRedefined(ApplicationState& g_state);   // ptmi_set_feature_shading: features, variance and history go; image and accumulation stay
 void renderFeatures(ApplicationState& g_state, int grid);
 void readFeatures(const ApplicationState& g_state, float* albedo, float* normal, float* position, float* hit_fraction);
 void checkDenoiseParams(const DenoiseParams& p);     // throws ArgError for a parameter out of range

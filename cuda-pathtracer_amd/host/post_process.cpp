@@ -16,6 +16,14 @@ void featuresStale(ApplicationState& g) {
     g.render.dn.image_current = false;                 // the image shows the scene / view / config as it was before the change
 }
 
+// the features change their meaning and the image does not (ptmi_set_feature_shading): the image stays current and an
+// accumulation goes on; the temporal history holds albedo and normal of the old kind
+void featuresRedefined(ApplicationState& g) {
+    g.render.dn.features_valid = false;
+    g.render.dn.variance_valid = false;
+    temporalReset(g);
+}
+
 static void needEvents(ApplicationState& g, size_t n) {
     while (g.event_pool.size() < n) { hipEvent_t ev; PTMI_HIP(hipEventCreate(&ev)); g.event_pool.push_back(ev); }
 }
@@ -46,7 +54,7 @@ void renderFeatures(ApplicationState& g, int grid) {
     cameraFrameParams(g, fp);
     needEvents(g, 2);
     PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
-    launch_features(g.scene.d_scene, r.tile, fp, grid, d.fb, r.stream);
+    launch_features(g.scene.d_scene, r.tile, fp, grid, d.fb, g.scene.vertexNormalTable(), g.scene.albedoTable(), g.feature_shading, r.stream);
     PTMI_HIP(hipGetLastError());
     PTMI_HIP(hipEventRecord(g.event_pool[1], r.stream));
     PTMI_HIP(hipStreamSynchronize(r.stream));

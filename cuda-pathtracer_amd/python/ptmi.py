@@ -47,7 +47,10 @@ EXPORTS = [
     "ptmi_check_vertex_normals", "ptmi_host_classify_vertex_normals", "ptmi_set_vertex_normals", "ptmi_vertex_normals_info",
     "ptmi_debug_vertex_normal",
     "ptmi_check_albedo_texture", "ptmi_set_albedo_texture", "ptmi_albedo_texture_info", "ptmi_debug_albedo",
+    "ptmi_check_feature_shading", "ptmi_set_feature_shading", "ptmi_feature_shading",
 ]
+
+FEATURE_TEXTURED_ALBEDO, FEATURE_SHADING_NORMAL = 1, 2      # PTMI_FEATURE_*
 
 
 class Camera(C.Structure):
@@ -268,6 +271,10 @@ def lib():
             L.ptmi_set_albedo_texture.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]
             L.ptmi_albedo_texture_info.argtypes = [vp, ip, ip, ip, ip]
             L.ptmi_debug_albedo.argtypes = [vp, C.c_int, vp, vp, vp]
+        if hasattr(L, "ptmi_set_feature_shading"):     # likewise
+            L.ptmi_check_feature_shading.argtypes = [C.c_int]
+            L.ptmi_set_feature_shading.argtypes = [vp, C.c_int]
+            L.ptmi_feature_shading.argtypes = [vp, ip]
         _lib = L
     return _lib
 
@@ -551,6 +558,11 @@ def check_albedo_texture(image, uv, textured=None, filter="bilinear"):
     _check(lib().ptmi_check_albedo_texture(w, h, image.ctypes.data, filter, n, uv.ctypes.data, _ptr(textured)))
 
 
+def check_feature_shading(flags):
+    """ptmi_check_feature_shading: raises PtmiError for flags outside 0 .. 3 (host only)"""
+    _check(lib().ptmi_check_feature_shading(int(flags)))
+
+
 class Renderer:
     """One ApplicationState bound to one GPU."""
 
@@ -791,6 +803,23 @@ class Renderer:
         out = np.zeros((len(prim), 6), np.float32)
         self._ck(self.L.ptmi_debug_albedo(self.h, len(prim), prim.ctypes.data, p.ctypes.data, out.ctypes.data))
         return out
+
+    def set_feature_shading(self, albedo=False, normal=False, flags=None):
+        """Shaded features (include/ptmi.h: "shaded features"): albedo - the feature albedo is Kd x the albedo texture's value at
+        the hit; normal - the feature normal is the interpolated vertex normal there.  A switch whose table is not set has no
+        effect.  The context's, kept over scene loads.  A new value invalidates features and variance and empties the temporal
+        history; the image and a running accumulation stay.  flags: the PTMI_FEATURE_* bits as an int, instead of the two."""
+        if flags is None:
+            flags = (FEATURE_TEXTURED_ALBEDO if albedo else 0) | (FEATURE_SHADING_NORMAL if normal else 0)
+        self._ck(self.L.ptmi_set_feature_shading(self.h, int(flags)))
+
+    def feature_shading(self):
+        """ptmi_feature_shading: dict(albedo, normal, flags) of the context"""
+        f = C.c_int()
+        self._ck(self.L.ptmi_feature_shading(self.h, C.byref(f)))
+        return dict(albedo=bool(f.value & FEATURE_TEXTURED_ALBEDO), normal=bool(f.value & FEATURE_SHADING_NORMAL), flags=f.value)
+
+    check_feature_shading = staticmethod(check_feature_shading)
 
     def camera_frame(self):
         out = np.zeros(12, np.float32)

@@ -526,7 +526,8 @@ int  ptmi_read_sample_counts(const ptmi_ctx*, uint32_t* counts);
 
 /* ---- feature buffers and an edge-avoiding a-trous denoiser (new in this implementation) -----------------------------------
  * FEATURE PASS.  ptmi_render_features traces g x g camera rays per local pixel (g = grid, 1..4) through the stratum centres
- * and keeps, per pixel, the means of the first hits' albedo (Kd), stored primitive normal, hit point and hit fraction.  It uses
+ * and keeps, per pixel, the means of the first hits' albedo (Kd), stored primitive normal, hit point and hit fraction ("shaded
+ * features", below, makes the first two the textured colour and the interpolated normal on request).  It uses
  * no RNG (the pixel streams are neither read nor written) and changes no image, sum or accumulation state.  In float32, in
  * the order written (-ffp-contract=off, correctly rounded division):
  *     for j = 0 .. g-1 (outer), i = 0 .. g-1 (inner):
@@ -1019,8 +1020,8 @@ int  ptmi_surface_counts(const ptmi_ctx*, int counts[4]);   /* primitives of kin
  * without one.  A context whose table has a smooth primitive renders both values of next_event through the per-lane kernel of
  * next-event estimation, as a context with an environment or a specular surface does; frames, batches, passes, tiled contexts,
  * ptmi_denoise, ptmi_temporal_accumulate and ptmi_gather_frame work as they do without one.
- * ptmi_run_radiosity_solver, the Radiosity view (integrator = 1) and ptmi_render_features IGNORE the table: the feature normal stays
- * the stored one.
+ * ptmi_run_radiosity_solver and the Radiosity view (integrator = 1) ignore the table, and so does ptmi_render_features unless
+ * ptmi_set_feature_shading asks ("shaded features"): the feature normal stays the stored one.
  *
  * ptmi_set_vertex_normals: normals NULL drops the table (n_prims is then ignored).  A successful call restarts an accumulation,
  * makes features stale and empties the temporal history, as ptmi_set_surfaces does.  PTMI_E_INVALID, with nothing changed (every
@@ -1084,9 +1085,9 @@ int  ptmi_debug_vertex_normal(ptmi_ctx*, int n, const int* prim /* load order */
  * A table without a textured primitive is no table: the context takes exactly the route it takes without one.  A context with a
  * textured primitive renders both values of next_event through the per-lane kernel of next-event estimation, as a context with an
  * environment, a specular surface or a smooth primitive does; frames, batches, passes, tiled contexts, ptmi_denoise,
- * ptmi_denoise_variance, ptmi_temporal_accumulate and ptmi_gather_frame work as they do without one.  ptmi_run_radiosity_solver,
- * the Radiosity view (integrator = 1) and ptmi_render_features IGNORE the texture: the feature albedo stays Kd_k, so the denoisers
- * demodulate by the untextured colour.
+ * ptmi_denoise_variance, ptmi_temporal_accumulate and ptmi_gather_frame work as they do without one.  ptmi_run_radiosity_solver
+ * and the Radiosity view (integrator = 1) ignore the texture, and so does ptmi_render_features unless ptmi_set_feature_shading asks
+ * ("shaded features"): the feature albedo stays Kd_k, so the denoisers demodulate by the untextured colour.
  *
  * ptmi_set_albedo_texture: texels NULL drops the texture (every other argument is then ignored).  A successful call restarts an
  * accumulation, makes features stale and empties the temporal history, as ptmi_set_surfaces does.  PTMI_E_INVALID, with nothing
@@ -1133,6 +1134,42 @@ int  ptmi_albedo_texture_info(const ptmi_ctx*, int* n_textured, int* width, int*
  * indices; p: 3n points; out: 6n - s_u, s_v, T.rgb, then 1.0 for a textured primitive; for an untextured one, or with no table:
  * 0, 0, 1, 1, 1, 0.  PTMI_E_INVALID: no scene, a prim out of range. */
 int  ptmi_debug_albedo(ptmi_ctx*, int n, const int* prim /* load order */, const float* p /* 3n */, float* out /* 6n */);
+
+/* ---- shaded features: textured albedo and interpolated normals in the feature buffers (new in this implementation) --------------
+ * "vertex normals" and "albedo texture" change what a surface is at a path vertex; the feature pass records the stored normal and
+ * the untextured Kd_k all the same, so ptmi_denoise, ptmi_denoise_variance, ptmi_temporal_accumulate and ptmi_denoise_temporal
+ * filter a texture as signal (they demodulate by a constant) and a smooth ball facet by facet.  ptmi_set_feature_shading lets the
+ * feature pass record what the path tracer shades with.  It is opt-in and a property of the CONTEXT, as ptmi_config is: default 0,
+ * kept over scene loads, allowed on tiled contexts and under every config (the feature pass runs under all of them).  A flag whose
+ * table is absent has no effect, at once and for as long as the table stays absent; it takes effect when the table is set.
+ *
+ * THE FEATURE PASS is that of ptmi_render_features, float for float, with TWO changes per hit, inside `if hit`, where k is the hit
+ * primitive and p = o + t * d is the ONE float triple that is also added to P:
+ *   with PTMI_FEATURE_TEXTURED_ALBEDO, an albedo table set and k textured:
+ *       Kd(p) = Kd_k * T  per component (a rounded product);   A = A + Kd(p)  (the rounded sum)
+ *       T is THE TEXEL of "albedo texture" at THE UV of p, filter and wrap as there.  Otherwise A = A + Kd_k.
+ *   with PTMI_FEATURE_SHADING_NORMAL, a vertex-normal table set and k smooth:
+ *       N = N + Ns(p),  Ns(p) THE NORMAL of "vertex normals" at p: the interpolated unit normal, and the stored normal n_k
+ *       wherever that section takes the stored normal (den or len2 not valid).  Otherwise N = N + n_k.
+ * Everything else stays: the strata and their order, the sums' order, rcp_rn((float)(g * g)), misses, tiling, no RNG.  With flags
+ * 0, or with no table that a set flag names, the pass is ptmi_render_features' bit for bit (the same kernel runs).  The interpolated
+ * normal is NOT turned against d, as n_k is not.
+ * The surface table is still ignored: a mirror's or a pane's feature albedo is its (possibly textured) tint, its feature normal
+ * its own (possibly interpolated) normal.  Following a specular chain to the first diffuse vertex is out of scope.
+ * ptmi_run_radiosity_solver and the Radiosity view ignore both tables whatever the flags say.
+ *
+ * ptmi_set_feature_shading with a value other than the context's: the feature buffers and the variance buffers become invalid
+ * (ptmi_read_features / ptmi_read_variance fail until they are computed again; the filters recompute the features) and the temporal
+ * history empties, since it holds albedo and normal of the old kind.  It does NOT restart an accumulation and does NOT make the
+ * image stale - nothing about rendering changed - so a ptmi_denoise directly after it filters the current image with recomputed
+ * features.  With the value the context already has it changes nothing.  PTMI_E_INVALID, with nothing changed: flags outside
+ * 0 .. 3.  ptmi_check_feature_shading makes that check without a context. */
+#define PTMI_FEATURE_TEXTURED_ALBEDO 1   /* the feature albedo is Kd(p) = Kd_k * T of "albedo texture" */
+#define PTMI_FEATURE_SHADING_NORMAL  2   /* the feature normal is the interpolated normal of "vertex normals" */
+/* host only, no context: 0 or PTMI_E_INVALID with the message */
+int  ptmi_check_feature_shading(int flags);
+int  ptmi_set_feature_shading(ptmi_ctx*, int flags);       /* default 0: ptmi_render_features as it is without this section */
+int  ptmi_feature_shading(const ptmi_ctx*, int* flags);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,9 @@
   python tools/ptmi_render.py --scene ... --texture checker:8 --texture-prims 6-7 --texture-scale 2 --out floor.png
                                (an 8 x 8 checker on cbox.obj's floor, repeating every 2 scene units; --texture FILE.npy takes an
                                 (h, w, 3) float image in LINEAR RGB - nothing is decoded from sRGB)
+  python tools/ptmi_render.py --scene ... --texture checker:8 --texture-prims 6-7 --spp 8 --shaded-features --denoise --out floor.png
+                               (the denoiser demodulates by the textured colour, so the checker stays sharp; with --smooth or
+                                --spheres the feature normal is the interpolated one.  --shaded-features albedo | normal | both)
 """
 import argparse
 import os
@@ -79,6 +82,9 @@ def main():
                     "the filter, sqrt(variance_out), through the tone map")
     ap.add_argument("--aov-png", default=None, metavar="PREFIX", help="write PREFIX_albedo.png, PREFIX_normal.png, PREFIX_depth.png "
                     "from the feature buffers of the denoiser")
+    ap.add_argument("--shaded-features", nargs="?", const="both", default=None, choices=["albedo", "normal", "both"],
+                    help="--denoise, --variance-guided, --temporal and --aov-png read feature buffers that hold the textured albedo "
+                    "(--texture) and / or the interpolated normal (--smooth, --spheres); default both")
     ap.add_argument("--orbit", type=int, default=0, metavar="FRAMES", help="render FRAMES views, --yaw-step degrees apart, one frame each")
     ap.add_argument("--yaw-step", type=float, default=2.0, metavar="DEG")
     ap.add_argument("--temporal", action="store_true", help="with --orbit: every view through the temporal accumulation (reprojected history)")
@@ -200,6 +206,10 @@ def main():
         r.set_albedo_texture(image, ptmi_scenes.box_uvs(prims, a.texture_scale), textured, a.texture_filter)
         ti = r.albedo_texture_info()
         print(f"albedo texture: {ti['width']} x {ti['height']}, {a.texture_filter}, {ti['n_textured']} textured primitives")
+    if a.shaded_features:
+        r.set_feature_shading(albedo=a.shaded_features in ("albedo", "both"), normal=a.shaded_features in ("normal", "both"))
+        fs = r.feature_shading()
+        print(f"shaded features: albedo {'on' if fs['albedo'] else 'off'}, normal {'on' if fs['normal'] else 'off'}")
     if a.orbit > 0:
         if a.variance_guided and a.temporal:
             ap.error("--variance-guided does not filter the temporal history (no variance is carried in it)")
