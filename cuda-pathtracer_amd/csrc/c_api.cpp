@@ -454,6 +454,10 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
             need(cfg->sampling_mode == 0, "an albedo texture is set: it needs sampling_mode 0 (BSDF): the guided modes run through the bounce kernels");
             need(cfg->fast_tree == 0, "an albedo texture is set: it needs fast_tree 0: textured frames always trace the reference's hits");
         }
+        if (c->app.lens.on()) {                          // (integrator 1 is allowed: the Radiosity view keeps the pinhole)
+            need(cfg->sampling_mode == 0, "a lens is set: it needs sampling_mode 0 (BSDF): the guided modes run through the bounce kernels");
+            need(cfg->fast_tree == 0, "a lens is set: it needs fast_tree 0: frames through a lens always trace the reference's hits");
+        }
         AppConfig& a = c->app.config;                    // every check is above this line: a rejected config changes nothing
         a.spp = cfg->spp; a.max_depth = cfg->max_depth; a.sampling_mode = (SamplingMode)cfg->sampling_mode;
         a.mis_bsdf_fraction = cfg->mis_bsdf_fraction;
@@ -663,6 +667,90 @@ int ptmi_feature_shading(const ptmi_ctx* c, int* flags) {
     return guarded([&] {
         need(c && flags, "NULL argument");
         *flags = c->app.feature_shading;
+    });
+}
+
+// the frame ptmi_host_camera_frame derives (no context)
+static void hostCameraFrame(const ptmi_camera* cam, int width, int height, float* out12) {
+    Sensor s(v3(cam->origin), v3(cam->lookat), v3(cam->vup), cam->vfov_deg, 1.0f);
+    s.yaw = cam->yaw_deg; s.pitch = cam->pitch_deg;
+    s.image_width = width; s.image_height = height;
+    s.aspect = (float)width / (float)height;
+    cameraFrame12(s, cam->orbit != 0, out12);
+}
+int ptmi_check_lens(float radius, float focus_distance) {
+    return guarded([&] {
+        checkLens(radius, focus_distance);
+        if (!(radius > 0.0f)) return;
+        ptmi_camera cam; ptmi_default_camera(&cam);      // no context, no camera: the block over the default camera, a square image
+        float frame[12], block[kLensBlockFloats];
+        hostCameraFrame(&cam, 1, 1, frame);
+        lensBlock(frame, 1, 1, radius, focus_distance, block);
+    });
+}
+int ptmi_host_lens_block(const ptmi_camera* cam, int width, int height, float radius, float focus_distance, float* out24) {
+    return guarded([&] {
+        need(cam && out24, "NULL argument");
+        need(width > 0 && height > 0, "width and height must be positive");
+        float frame[12], block[kLensBlockFloats];
+        hostCameraFrame(cam, width, height, frame);
+        lensBlock(frame, width, height, radius, focus_distance, block);
+        std::memcpy(out24, block, sizeof block);         // a rejected call writes nothing
+    });
+}
+int ptmi_set_lens(ptmi_ctx* c, float radius, float focus_distance) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        LensState& l = c->app.lens;
+        float focus = focus_distance;
+        if (radius == 0.0f && !(focus_distance > 0.0f) && !std::isnan(focus_distance)) focus = 0.0f;   // "no lens": the focus is the default again
+        else checkLens(radius, focus_distance);
+        if (radius > 0.0f) {
+            const AppConfig& a = c->app.config;
+            need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "lens: the config has a guided sampling_mode, which runs through the bounce kernels");
+            need(!a.fast_tree, "lens: the config has fast_tree 1; frames through a lens always trace the reference's hits");
+            if (c->app.render.tile.width > 0) {          // a resolution is set: the block over the camera as it is now must be finite
+                float frame[12], block[kLensBlockFloats];
+                cameraFrame12(c->app.render.h_camera, a.orbit, frame);
+                lensBlock(frame, c->app.render.tile.width, c->app.render.tile.height, radius, focus, block);
+            }
+        }
+        if (radius == l.radius && focus == l.focus) return;   // every check is above this line
+        l.radius = radius; l.focus = focus;
+        accumReset(c->app);                              // what ptmi_set_camera drops
+        featuresStale(c->app);
+    });
+}
+int ptmi_lens(const ptmi_ctx* c, float* radius, float* focus_distance) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        if (radius) *radius = c->app.lens.radius;
+        if (focus_distance) *focus_distance = lensFocus(c->app);
+    });
+}
+int ptmi_debug_lens_block(ptmi_ctx* c, float* out24) {
+    return guarded([&] {
+        need(c && out24, "NULL argument");
+        need(c->app.lens.on(), "no lens set (radius 0 is the pinhole)");
+        need(c->app.render.tile.width > 0, "no resolution set");
+        const float4* d = lensDeviceBlock(c->app);
+        PTMI_HIP(hipMemcpy(out24, d, kLensBlockFloats * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+int ptmi_debug_lens_ray(ptmi_ctx* c, int n, const int* px, const int* py, const float* r, float* out) {
+    return guarded([&] {
+        need(c && px && py && r && out, "NULL argument");
+        need(n >= 0, "n must not be negative");
+        need(c->app.lens.on(), "no lens set (radius 0 is the pinhole)");
+        need(c->app.render.tile.width > 0, "no resolution set");
+        if (n == 0) return;
+        const float4* d = lensDeviceBlock(c->app);
+        DevBuf<int> d_x(n), d_y(n); DevBuf<float> d_r(4 * (size_t)n), d_o(6 * (size_t)n);
+        d_x.upload(px, n); d_y.upload(py, n); d_r.upload(r, 4 * (size_t)n);
+        launch_debug_lens_ray(d, n, d_x.p, d_y.p, d_r.p, d_o.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d_o.download(out, 6 * (size_t)n);
     });
 }
 

@@ -4,6 +4,7 @@
 #include "light_sample.h"
 #include "vertex_normal.h"
 #include "albedo_texture.h"
+#include "lens.h"
 #include "../../include/ptmi.h"      // PTMI_MATH_*
 
 namespace ptmi {
@@ -496,6 +497,23 @@ void launch_debug_albedo(const DeviceScene& sc, const AlbedoTable& at, int n, co
     with_bool(sc.has_quads != 0, [&](auto quads) {
         hipLaunchKernelGGL(ptmi_debug_albedo_k<decltype(quads)::value>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, at, n, slots, p, out);
     });
+}
+
+// lens_ray_at (lens.h) as ptmi_render_nee calls it, on given uniforms instead of the stream's (test hook; include/ptmi.h:
+// ptmi_debug_lens_ray): the origin on the lens, then the unit direction
+__global__ __launch_bounds__(kBlock) void ptmi_debug_lens_ray_k(const float4* __restrict__ lens, int n, const int* __restrict__ px, const int* __restrict__ py,
+                                                                const float* __restrict__ r, float* __restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    f3 o, d;
+    lens_ray_at(lens, px[i], py[i], r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3], o, d);
+    out[6 * i] = o.x; out[6 * i + 1] = o.y; out[6 * i + 2] = o.z;
+    out[6 * i + 3] = d.x; out[6 * i + 4] = d.y; out[6 * i + 5] = d.z;
+}
+
+void launch_debug_lens_ray(const float4* lens, int n, const int* px, const int* py, const float* r, float* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_lens_ray_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, lens, n, px, py, r, out);
 }
 
 }  // namespace ptmi

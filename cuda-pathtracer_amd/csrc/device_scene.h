@@ -365,7 +365,8 @@ struct AlbedoTable {
 // never reads a kind 3).
 void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, const VertexNormalTable& vn,
                        const AlbedoTable& at, bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp,
-                       const int* queue, int n, bool first, hipStream_t s);
+                       const int* queue, int n, bool first, const float4* lens /* the thin lens's block (host/lens.cpp); nullptr: the pinhole */,
+                       hipStream_t s);
 
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)
@@ -442,5 +443,8 @@ void launch_debug_vertex_normal(const DeviceScene& sc, const VertexNormalTable& 
                                 hipStream_t s);
 // ptmi_debug_albedo (include/ptmi.h): albedo_at (albedo_texture.h) of leaf-order slot slots[i] at p[3i ..] -> out[6i ..]
 void launch_debug_albedo(const DeviceScene& sc, const AlbedoTable& at, int n, const int* slots, const float* p, float* out /* 6n */, hipStream_t s);
+// ptmi_debug_lens_ray (include/ptmi.h): lens_ray_at (lens.h) over the block `lens` for pixel (px[i], py[i]) and the uniforms
+// r[4i ..] = r3 r4 r1 r2 -> out[6i ..] = o, d
+void launch_debug_lens_ray(const float4* lens, int n, const int* px, const int* py, const float* r, float* out /* 6n */, hipStream_t s);
 
 }  // namespace ptmi

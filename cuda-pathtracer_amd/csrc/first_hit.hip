@@ -3,6 +3,7 @@
 #include "light_sample.h"
 #include "vertex_normal.h"
 #include "albedo_texture.h"
+#include "lens.h"
 
 namespace ptmi {
 
@@ -80,9 +81,13 @@ void launch_render_radiosity(const DeviceScene& sc, const TileMap& tm, const Pat
 // TEX (include/ptmi.h: "albedo texture"; the table: device_scene.h AlbedoTable): the context has a table with a textured primitive;
 // a vertex on one multiplies Kd by the image's value at the hit point (albedo_texture.h) directly before the throughput takes it,
 // after the roulette.  at.filter is a wave-uniform runtime switch.
+// lens (include/ptmi.h: "thin lens"; the block: host/lens.cpp) is a wave-uniform runtime switch too, not a template parameter: with
+// a block the sample's primary ray comes from lens.h - two draws in front of the jitter's, an origin on the lens - and nothing
+// below the camera ray changes.  nullptr: the pinhole.
 template <int MODE, bool HAS_QUADS, bool ENV, int SURF, bool SMOOTH, bool TEX>
 __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, EmitterTable em, EnvTable ev, SurfaceTable sf, TileMap tm, PathState st, FrameParams fp,
-                                                          const int* __restrict__ queue, int n, int first, int next_event, VertexNormalTable vn, AlbedoTable at) {
+                                                          const int* __restrict__ queue, int n, int first, int next_event, VertexNormalTable vn, AlbedoTable at,
+                                                          const float4* __restrict__ lens) {
     extern __shared__ float4 smem[];
     constexpr bool SPEC = SURF != 0;
     const int idx = blockIdx.x * kBlock + threadIdx.x;
@@ -95,7 +100,8 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     f3 color = first ? mk3(0.0f, 0.0f, 0.0f) : xyz(st.D[slot]);
     LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
     // wave-uniform switches of the ENV, SPEC, SMOOTH and TEX instantiations; without any of them they fold to the NEE kernel
-    const bool nee_on = ENV || SPEC || SMOOTH || TEX ? next_event != 0 : true;   // light samples and MIS weights at all
+    // (a lens brings next_event = 0 to the instantiation without any of them, which only next_event = 1 reached before)
+    const bool nee_on = ENV || SPEC || SMOOTH || TEX || lens ? next_event != 0 : true;   // light samples and MIS weights at all
     const bool env_on = ENV ? ev.sampled != 0 : false;       // the environment is one of the lights: five draws, selection by q
     const float q = ENV ? ev.q : 0.0f, omq = 1.0f - q;
     for (int frame = 0; frame < fp.n_frames; frame++) {
@@ -105,7 +111,8 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
         }
         for (int s = 0; s < fp.spp; s++) {
             f3 o, d;
-            camera_ray(fp, tm, x, y, rng, o, d);
+            if (lens) lens_ray(lens, x, y, rng, o, d);       // the block is read in there, per sample
+            else camera_ray(fp, tm, x, y, rng, o, d);
             f3 tp = mk3(1.0f, 1.0f, 1.0f), L = mk3(0.0f, 0.0f, 0.0f);
             float pb_prev = 0.0f;                            // pdf of the cosine sample that made the current path ray
             bool spec_prev = false;                          // SPEC: a mirror or glass vertex made the current path ray: no MIS weight
@@ -263,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
 
 void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, const VertexNormalTable& vn,
                        const AlbedoTable& at, bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp,
-                       const int* queue, int n, bool first, hipStream_t s) {
+                       const int* queue, int n, bool first, const float4* lens, hipStream_t s) {
     if (n <= 0) return;
     first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
         with_bool(env.texel != nullptr, [&](auto with_env) {
@@ -273,7 +280,7 @@ void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvT
                         hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value,
                                                             decltype(surf_kinds)::value, decltype(smooth)::value, decltype(tex)::value>),
                                            dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, surf, tm, st, fp, queue, n, first ? 1 : 0,
-                                           next_event ? 1 : 0, vn, at);
+                                           next_event ? 1 : 0, vn, at, lens);
                     });
                 });
             };

@@ -20,6 +20,7 @@
 #include "surfaces.h"
 #include "vertex_normals.h"
 #include "albedo_texture.h"
+#include "lens.h"
 #include "file_manager.h"
 #include "pbrt_loader.h"
 #include "sensor.h"
@@ -388,6 +389,18 @@ struct EnvState {
     ~EnvState() { drop(); }
 };
 
+// The thin lens of a context (include/ptmi.h: "thin lens"): two numbers that belong to the context, like the camera - scene loads,
+// ptmi_update_resolution and ptmi_set_camera keep them - and the device copy of the block derived from them (host/lens.cpp).
+struct LensState {
+    float radius = 0.0f;                             // 0: the pinhole
+    float focus = 0.0f;                              // <= 0: not set - the default, |origin - lookat| of the current camera
+    float4* d_block = nullptr;                       // six float4, allocated by the first run that needs them
+    float h_block[kLensBlockFloats] = {};            // what d_block holds
+    bool uploaded = false;
+    bool on() const { return radius > 0.0f; }
+    ~LensState();
+};
+
 struct FrameStats {
     double seconds = 0, bounce_kernel_ms = 0;
     uint64_t bounce_launches = 0, path_visits = 0, samples = 0, rays = 0, node_visits = 0, prim_tests = 0, hits = 0, top_node_visits = 0,
@@ -404,6 +417,7 @@ struct ApplicationState {
     AppConfig config;
     int feature_shading = 0;                         // PTMI_FEATURE_* (include/ptmi.h: ptmi_set_feature_shading); the context's, not the scene's
     EnvState env;
+    LensState lens;
     std::vector<uint32_t> h_jump;                    // 32 x 160 x 5 words
     std::vector<hipEvent_t> event_pool;
 
@@ -492,5 +506,12 @@ int countLocalRows(int height, int n_ranks, int rank, int row_block);
 
 // camera update (application.h:161-163) and the camera fields of a frame's parameters (render_state.cpp; frames and feature passes)
 void cameraFrameParams(ApplicationState& g_state, FrameParams& fp);
+
+// the focus distance in force: the one ptmi_set_lens gave, else |origin - lookat| of the current camera
+float lensFocus(const ApplicationState& g_state);
+// The lens block for the camera, resolution and lens as they are now, on the device: derived again at every call and uploaded
+// where it differs from what the device holds, so no setter has to remember it.  nullptr: the pinhole.  Throws LensError where
+// the block is not finite.  Nothing may be in flight on the context's streams (every run ends with a synchronise).
+const float4* lensDeviceBlock(ApplicationState& g_state);
 
 }  // namespace ptmi

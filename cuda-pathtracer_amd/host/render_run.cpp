@@ -62,6 +62,7 @@ struct Run {
     size_t n_ev = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> kernel_events = {};   // (e0, e1) around every bounce / NEE launch of a timed run
     uint64_t launches = 0, visits = 0;
+    const float4* lens = nullptr;                      // the thin lens's block on the device (lensDeviceBlock); nullptr: the pinhole
 
     // the run's next event: from the context's pool, in the order asked for - none is created once the pool is warm
     hipEvent_t event() {
@@ -168,7 +169,8 @@ void prepareCostOrder(Run& run, int order_classes) {
 // of ptmi_render_nee on the frame's stream: no chunks, no refill, no launch order by cost; the whole frame, batch or pass
 // a context with an environment (ptmi_set_environment) takes the same route for both values of next_event: the per-lane kernel
 // is the one that looks the map up where a path ray misses; so does a scene with a mirror, glass or rough-metal primitive (ptmi_set_surfaces, ptmi_set_surfaces_rough)
-// or with a smooth primitive (ptmi_set_vertex_normals) or a textured one (ptmi_set_albedo_texture)
+// or with a smooth primitive (ptmi_set_vertex_normals) or a textured one (ptmi_set_albedo_texture); and a context with a thin
+// lens (ptmi_set_lens): the per-lane kernel is the one that starts a sample on the lens
 void runNeeLaunch(Run& run) {
     ApplicationState& g = run.g;
     const int n = run.queueLength();
@@ -176,7 +178,7 @@ void runNeeLaunch(Run& run) {
     launch_render_nee(g.scene.d_scene, g.scene.d_emitters, g.env.table(g.config.next_event, g.scene.d_emitters.n), g.scene.surfaceTable(),
                       g.scene.vertexNormalTable(), g.scene.albedoTable(), g.scene.hasRough(), g.config.next_event, run.r.tile, run.r.d_state, run.fp,
                       run.pass ? run.chunks[0].d_queue_init : nullptr, n,
-                      run.pass ? run.pass->rule.first != 0 : true, run.s);
+                      run.pass ? run.pass->rule.first != 0 : true, run.lens, run.s);
     PTMI_HIP(hipGetLastError());
     const hipEvent_t e1 = run.stamp(run.s);
     if (run.timed) run.kernel_events.push_back({e0, e1});
@@ -352,8 +354,9 @@ void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pa
     r.dn.image_current = false;                        // what ptmi_denoise may filter: likewise, only a completed path-tracing run
 
     const bool path_tracing = g.config.current_integrator == IntegratorType::PathTracing;
-    const bool nee = (g.config.next_event || g.env.present() || g.scene.hasSpecular() || g.scene.hasVertexNormals() || g.scene.hasAlbedoTexture()) &&
-                     path_tracing;
+    const bool nee = (g.config.next_event || g.env.present() || g.scene.hasSpecular() || g.scene.hasVertexNormals() || g.scene.hasAlbedoTexture() ||
+                      g.lens.on()) && path_tracing;
+    const float4* lens = path_tracing ? lensDeviceBlock(g) : nullptr;   // (the Radiosity view keeps the pinhole) throws before anything is launched
     const DeviceScene scene = effectiveScene(g);
     const LaunchOverrides over = LaunchOverrides::fromEnv();
     const LaunchRule rule = planLaunches(g, scene, fp, n_frames, pass != nullptr, nee, over);
@@ -363,6 +366,7 @@ void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pa
     Run run{g, r, scene, fp, n_frames, pass, stats != nullptr, r.stream};
     run.chunks = pass ? &r.accum.chunk : r.chunk;
     run.n_chunks = nee ? 0 : pass ? 1 : r.n_chunks;
+    run.lens = lens;
 
     const hipEvent_t ev_begin = run.record(run.s);
     if (g.config.collect_stats) PTMI_HIP(hipMemsetAsync(r.d_stats, 0, sizeof(StatCounters), run.s));

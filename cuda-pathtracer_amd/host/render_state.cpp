@@ -311,4 +311,26 @@ void cameraFrameParams(ApplicationState& g, FrameParams& fp) {
     for (int i = 0; i < 4; i++) { dst[i][0] = src[i]->x; dst[i][1] = src[i]->y; dst[i][2] = src[i]->z; }
 }
 
+
+// ---- thin lens (include/ptmi.h: ptmi_set_lens) --------------------------------------------------------------------------------
+LensState::~LensState() { if (d_block) (void)hipFree(d_block); }
+
+float lensFocus(const ApplicationState& g) { return g.lens.focus > 0.0f ? g.lens.focus : g.render.h_camera.radius; }
+
+const float4* lensDeviceBlock(ApplicationState& g) {
+    LensState& l = g.lens;
+    if (!l.on()) return nullptr;
+    float frame[12], block[kLensBlockFloats];
+    cameraFrame12(g.render.h_camera, g.config.orbit, frame);     // what cameraFrameParams derives
+    lensBlock(frame, g.render.tile.width, g.render.tile.height, l.radius, lensFocus(g), block);
+    PTMI_HIP(hipSetDevice(g.device_id));
+    if (!l.d_block) { l.d_block = (float4*)hipMallocSafe(sizeof block, "d_lens"); l.uploaded = false; }
+    if (!l.uploaded || std::memcmp(block, l.h_block, sizeof block) != 0) {
+        PTMI_HIP(hipMemcpy(l.d_block, block, sizeof block, hipMemcpyHostToDevice));
+        std::memcpy(l.h_block, block, sizeof block);
+        l.uploaded = true;
+    }
+    return l.d_block;
+}
+
 }  // namespace ptmi

@@ -48,6 +48,7 @@ EXPORTS = [
     "ptmi_debug_vertex_normal",
     "ptmi_check_albedo_texture", "ptmi_set_albedo_texture", "ptmi_albedo_texture_info", "ptmi_debug_albedo",
     "ptmi_check_feature_shading", "ptmi_set_feature_shading", "ptmi_feature_shading",
+    "ptmi_check_lens", "ptmi_set_lens", "ptmi_lens", "ptmi_host_lens_block", "ptmi_debug_lens_block", "ptmi_debug_lens_ray",
 ]
 
 FEATURE_TEXTURED_ALBEDO, FEATURE_SHADING_NORMAL = 1, 2      # PTMI_FEATURE_*
@@ -275,6 +276,14 @@ def lib():
             L.ptmi_check_feature_shading.argtypes = [C.c_int]
             L.ptmi_set_feature_shading.argtypes = [vp, C.c_int]
             L.ptmi_feature_shading.argtypes = [vp, ip]
+        if hasattr(L, "ptmi_set_lens"):                # likewise
+            fp = C.POINTER(C.c_float)
+            L.ptmi_check_lens.argtypes = [C.c_float, C.c_float]
+            L.ptmi_set_lens.argtypes = [vp, C.c_float, C.c_float]
+            L.ptmi_lens.argtypes = [vp, fp, fp]
+            L.ptmi_host_lens_block.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_float, C.c_float, vp]
+            L.ptmi_debug_lens_block.argtypes = [vp, vp]
+            L.ptmi_debug_lens_ray.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -393,6 +402,48 @@ def host_cdf_record_layout():
 
 def default_camera():
     c = Camera(); lib().ptmi_default_camera(C.byref(c)); return c
+
+
+def check_lens(radius, focus_distance):
+    """ptmi_check_lens: raises PtmiError with the message of the first rejection; no context and no GPU"""
+    _check(lib().ptmi_check_lens(float(radius), float(focus_distance)))
+
+
+def host_lens_block(cam, width, height, radius, focus_distance):
+    """ptmi_host_lens_block: the six records (6, 4) float32 of a lens over cam at width x height - (llc_f, W) (hor_f, 1 / W)
+    (ver_f, H) (org, 1 / H) (a, 0) (b, 0); no context and no GPU"""
+    out = np.zeros((6, 4), np.float32)
+    _check(lib().ptmi_host_lens_block(C.byref(cam), int(width), int(height), float(radius), float(focus_distance), out.ctypes.data))
+    return out
+
+
+def default_focus_distance(cam):
+    """|origin - lookat| of cam in binary32, products summed left to right: the focus distance of a context that was given none"""
+    f = np.float32
+    d = np.asarray(cam.origin, f) - np.asarray(cam.lookat, f)
+    s = f(d[0] * d[0]); s = f(s + f(d[1] * d[1])); s = f(s + f(d[2] * d[2]))
+    return float(np.sqrt(s))
+
+
+def pinhole_centre_ray(frame12, width, height, px, py):
+    """The pinhole ray through the centre of pixel (px, py) of the frame (org, llc, hor, ver) in binary32, camera_ray's expressions
+    with both jitter numbers 0.5: (o, d) float32"""
+    f = np.float32
+    org, llc, hor, ver = (np.asarray(frame12, f).reshape(4, 3)[i] for i in range(4))
+    u = f(f(f(px) + f(0.5)) / f(width)); v = f(f(f(py) + f(0.5)) / f(height))
+    w = (((llc + (u * hor).astype(f)).astype(f) + (v * ver).astype(f)).astype(f) - org).astype(f)
+    n2 = f(w[0] * w[0]); n2 = f(n2 + f(w[1] * w[1])); n2 = f(n2 + f(w[2] * w[2]))
+    k = f(f(1.0) / f(np.sqrt(n2)))
+    return org.copy(), (w * k).astype(f)
+
+
+def depth_along_axis(frame12, d, t):
+    """t * dot(d, axis) in binary64, axis = unit(llc + 0.5 hor + 0.5 ver - org): the depth along the optical axis of the point at
+    distance t along the unit direction d - what a focus distance is measured in"""
+    org, llc, hor, ver = (np.asarray(frame12, np.float64).reshape(4, 3)[i] for i in range(4))
+    axis = llc + 0.5 * hor + 0.5 * ver - org
+    axis = axis / np.sqrt(np.dot(axis, axis))
+    return float(t) * float(np.dot(np.asarray(d, np.float64), axis))
 
 
 def default_config():
@@ -572,6 +623,7 @@ class Renderer:
         self._ck(self.L.ptmi_ctx_create(int(device_id), C.byref(self.h)))
         self.width = self.height = 0
         self.config = default_config()
+        self._camera = default_camera()              # what set_lens(radius) takes its default focus distance from
 
     def _ck(self, rc):
         if rc != 0:
@@ -683,6 +735,7 @@ class Renderer:
 
     def set_camera(self, cam):
         self._ck(self.L.ptmi_set_camera(self.h, C.byref(cam)))
+        self._camera = Camera.from_buffer_copy(cam)
 
     def set_config(self, spp=None, max_depth=None, seed_base=None, segments_per_launch=None, collect_stats=None, wave_tiles=None, streams=None,
                    sampling_mode=None, mis_bsdf_fraction=None, integrator=None, download_image=None, fast_tree=None, next_event=None):
@@ -820,6 +873,52 @@ class Renderer:
         return dict(albedo=bool(f.value & FEATURE_TEXTURED_ALBEDO), normal=bool(f.value & FEATURE_SHADING_NORMAL), flags=f.value)
 
     check_feature_shading = staticmethod(check_feature_shading)
+
+    # --- thin lens (include/ptmi.h: "thin lens") ---
+    def set_lens(self, radius, focus_distance=None):
+        """ptmi_set_lens: a thin lens of this radius focused at focus_distance along the optical axis, in scene units.  radius 0 is
+        the pinhole.  focus_distance None: |origin - lookat| of the camera as it is now (with radius 0: "no lens", and the focus
+        distance follows the camera again).  The context's, kept over scene loads, resolutions and cameras; the feature pass and the
+        Radiosity view keep the pinhole.  Changed values restart an accumulation and make the features stale, as set_camera does."""
+        if focus_distance is None:
+            focus_distance = 0.0 if float(radius) == 0.0 else default_focus_distance(self._camera)
+        self._ck(self.L.ptmi_set_lens(self.h, float(radius), float(focus_distance)))
+
+    def lens(self):
+        """ptmi_lens: (radius, focus_distance) of the context; without a focus distance of its own, the camera's |origin - lookat|"""
+        r, f = C.c_float(), C.c_float()
+        self._ck(self.L.ptmi_lens(self.h, C.byref(r), C.byref(f)))
+        return r.value, f.value
+
+    def focus_distance_at(self, px, py):
+        """The focus distance that brings what pixel (px, py) shows into focus: the first hit of the pinhole ray through the
+        pixel's centre (ptmi_debug_first_hit), as a depth along the optical axis, t * dot(d, axis) in binary64.  Raises
+        ValueError where the ray hits nothing."""
+        if not (0 <= int(px) < self.width and 0 <= int(py) < self.height):
+            raise ValueError("pixel (%d, %d) is outside the %d x %d image" % (px, py, self.width, self.height))
+        frame = self.camera_frame()
+        o, d = pinhole_centre_ray(frame, self.width, self.height, int(px), int(py))
+        h = self.debug_first_hit(o[None], d[None])
+        if not h["hit"][0]:
+            raise ValueError("pixel (%d, %d) shows nothing to focus on" % (px, py))
+        return depth_along_axis(frame, d, h["t"][0])
+
+    def debug_lens_block(self):
+        """ptmi_debug_lens_block: the context's lens block as the device holds it after deriving it for the camera, resolution and
+        lens as they are now, (6, 4) float32"""
+        out = np.zeros((6, 4), np.float32)
+        self._ck(self.L.ptmi_debug_lens_block(self.h, out.ctypes.data))
+        return out
+
+    def debug_lens_ray(self, px, py, r):
+        """ptmi_debug_lens_ray: the kernel's lens ray for pixels (px, py) (n,) and the uniforms r (n, 4) = r3 r4 r1 r2 over the
+        context's block.  Returns (n, 6) float32: the origin on the lens, then the unit direction."""
+        px = np.ascontiguousarray(px, np.int32); py = np.ascontiguousarray(py, np.int32); r = np.ascontiguousarray(r, np.float32)
+        if px.ndim != 1 or py.shape != px.shape or r.shape != (len(px), 4):
+            raise ValueError("px and py must be (n,) and r (n, 4)")
+        out = np.zeros((len(px), 6), np.float32)
+        self._ck(self.L.ptmi_debug_lens_ray(self.h, len(px), px.ctypes.data, py.ctypes.data, r.ctypes.data, out.ctypes.data))
+        return out
 
     def camera_frame(self):
         out = np.zeros(12, np.float32)

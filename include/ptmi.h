@@ -1171,6 +1171,69 @@ int  ptmi_check_feature_shading(int flags);
 int  ptmi_set_feature_shading(ptmi_ctx*, int flags);       /* default 0: ptmi_render_features as it is without this section */
 int  ptmi_feature_shading(const ptmi_ctx*, int* flags);
 
+/* ---- thin lens: depth of field with an aperture and a focus distance (new in this implementation) -------------------------------
+ * The reference's sensor is a pinhole.  ptmi_set_lens gives the context a thin lens: a disc of `radius` around the camera's
+ * origin, in the plane that (hor, ver) of ptmi_get_camera_frame span, and a plane of sharp focus at `focus_distance` along the
+ * optical axis, both in scene units.  The two numbers belong to the CONTEXT, as the camera does: a scene load,
+ * ptmi_update_resolution and ptmi_set_camera keep them.  radius >= 0; 0 is the pinhole and the default.  focus_distance > 0; a
+ * context that was given none focuses at |origin - lookat| of the current camera (of ptmi_set_camera's origin and lookat, binary32,
+ * products summed left to right), and follows the camera until ptmi_set_lens names a distance.
+ *
+ * radius == 0 is NO LENS: no extra draws, no block, and the frame takes the route and the kernels it takes without this section,
+ * bit for bit; ptmi_stats.bounce_launches is what it was.  A context with radius > 0 renders both values of next_event through
+ * the per-lane kernel of next-event estimation (one launch), as a context with an environment does; frames, batches,
+ * ptmi_select_frame, passes, tiled contexts, ptmi_denoise, ptmi_denoise_variance, ptmi_temporal_accumulate and ptmi_gather_frame
+ * work as they do without one.
+ * WHAT THE LENS DOES NOT TOUCH.  ptmi_render_features and the Radiosity view (integrator = 1) keep the pinhole through the lens
+ * centre: albedo, normal and position stay sharp while the image blurs, and the filters and the temporal step run unchanged on
+ * those guides (blurred guides and a lens-aware reprojection are out of scope).  ptmi_run_radiosity_solver ignores the lens.
+ *
+ * THE LENS BLOCK is derived on the host from the frame (org, llc, hor, ver) of ptmi_get_camera_frame and the image size W x H,
+ * again whenever the camera, the resolution or the lens has changed; binary32, every operation rounded, no fused multiply-add.
+ * With f = focus_distance, R = radius, per component where a vector is written:
+ *       hor_f = f * hor          ver_f = f * ver          llc_f = org + f * (llc - org)
+ *       a = (R / length(hor)) * hor                       b = (R / length(ver)) * ver          length(v) = sqrtf((v.x^2 + v.y^2) + v.z^2)
+ * as six records of four floats: (llc_f, W) (hor_f, 1/W) (ver_f, H) (org, 1/H) (a, 0) (b, 0); 1/W and 1/H as the sweep's frame block
+ * has them (both 0 where a size exceeds 2^23) and not read by the lens ray.
+ * THE LENS RAY of a sample of pixel (x, y).  The two lens draws come FIRST, the two jitter draws second (the order has no meaning
+ * beyond letting the restatement wrap the pinhole's; tests/lens_oracle.py):
+ *       r3 = uniform   r4 = uniform   r1 = uniform   r2 = uniform
+ *       rho = sqrtf(r3)   phi = (float)(2 pi r4), the product in binary64 as the cosine sample forms it   (s, c) = ptmi_sincosf of phi
+ *       dx = rho * c      dy = rho * s
+ *       o = (org + dx * a) + dy * b
+ *       u = ((float)x + r1) / (float)W      v = ((float)y + r2) / (float)H                          (as without a lens)
+ *       d = unit_vector(((llc_f + u * hor_f) + v * ver_f) - o)
+ * so a lens ray is the sensor's get_ray over the per-sample frame (o, llc_f, hor_f, ver_f), and a point of the plane at depth f
+ * has the same (u, v) from every point of the lens.  Everything after the primary ray - THE ESTIMATOR of whatever sections apply -
+ * is unchanged.
+ *
+ * ptmi_check_lens: host only, no context.  PTMI_E_INVALID with a message: a NaN in either number, an infinite one, radius < 0,
+ * focus_distance <= 0, and - with radius > 0 - a lens block over ptmi_default_camera at a square image that is not finite (a
+ * context's own camera is checked by ptmi_set_lens and at every render).
+ * ptmi_host_lens_block: the block, 24 floats, of a lens with radius > 0 over ptmi_host_camera_frame(cam, width, height); host only.
+ * PTMI_E_INVALID, with out24 untouched: what ptmi_check_lens rejects, radius == 0 (there is no block), width or height < 1, and a
+ * block with a value that is not finite - f so large that f * hor overflows, a frame without extent.
+ * ptmi_set_lens: radius == 0 with focus_distance <= 0 is accepted and means "no lens, no focus distance of the context's own".
+ * Otherwise PTMI_E_INVALID, with nothing changed: what ptmi_check_lens(radius, focus_distance)'s checks of the two numbers reject;
+ * with radius > 0, a current config with sampling_mode != 0 or fast_tree = 1 (ptmi_set_config rejects those two while a lens is
+ * set; integrator = 1 is allowed and ignores the lens), and - once a resolution is set - a block over the current camera that is
+ * not finite.  A camera or resolution set later that makes the block non-finite fails the render call instead, with the same
+ * message.  Values other than the context's invalidate exactly what ptmi_set_camera invalidates: an accumulation restarts and the
+ * feature buffers (with them the variance buffers) go stale; the temporal history is kept, as a camera move keeps it.  The values
+ * the context already has change nothing.
+ * ptmi_lens: the radius and the focus distance in force (the default where the context has none of its own). */
+/* host only, no context: 0 or PTMI_E_INVALID with the message */
+int  ptmi_check_lens(float radius, float focus_distance);
+int  ptmi_host_lens_block(const ptmi_camera*, int width, int height, float radius, float focus_distance, float* out24);
+int  ptmi_set_lens(ptmi_ctx*, float radius, float focus_distance);
+int  ptmi_lens(const ptmi_ctx*, float* radius, float* focus_distance);   /* either may be NULL */
+/* test hooks.  ptmi_debug_lens_block: the block as the device holds it, derived for the camera, resolution and lens as they are
+ * now.  ptmi_debug_lens_ray: the kernel's own function (csrc/lens.h) once per case over that block, on given uniforms instead
+ * of the stream's: pixel (px[i], py[i]), r[4i ..] = r3 r4 r1 r2; out[6i ..] = o, d.  r3 must lie in [2^-33, 1], a uniform's range.
+ * PTMI_E_INVALID: no lens (radius 0), no resolution set. */
+int  ptmi_debug_lens_block(ptmi_ctx*, float* out24);
+int  ptmi_debug_lens_ray(ptmi_ctx*, int n, const int* px, const int* py, const float* r /* 4n */, float* out /* 6n */);
+
 #ifdef __cplusplus
 }
 #endif

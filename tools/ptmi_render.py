@@ -29,6 +29,9 @@
   python tools/ptmi_render.py --scene ... --texture checker:8 --texture-prims 6-7 --spp 8 --shaded-features --denoise --out floor.png
                                (the denoiser demodulates by the textured colour, so the checker stays sharp; with --smooth or
                                 --spheres the feature normal is the interpolated one.  --shaded-features albedo | normal | both)
+  python tools/ptmi_render.py --scene ... --aperture 0.3 --focus-at 400,300 --spp 64 --out dof.png
+                               (a thin lens of radius 0.3 scene units, focused on what pixel (400, 300) shows - x from the left, y
+                                from the bottom; --focus D names the distance along the optical axis instead; neither: the look-at point)
 """
 import argparse
 import os
@@ -109,6 +112,10 @@ def main():
     ap.add_argument("--texture-prims", default=None, metavar="LIST", help="the textured primitives, like --mirror; default: all that emit nothing")
     ap.add_argument("--texture-scale", type=float, default=1.0, metavar="X", help="scene units per repeat of the image")
     ap.add_argument("--texture-filter", choices=["nearest", "bilinear"], default="bilinear")
+    ap.add_argument("--aperture", type=float, default=0.0, metavar="R", help="thin lens: the lens radius in scene units (0: the pinhole)")
+    ap.add_argument("--focus", type=float, default=None, metavar="D", help="with --aperture: the focus distance along the optical axis "
+                    "(default: the distance to the look-at point)")
+    ap.add_argument("--focus-at", default=None, metavar="X,Y", help="with --aperture: focus on what the pixel shows (x from the left, y from the bottom)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -210,6 +217,25 @@ def main():
         r.set_feature_shading(albedo=a.shaded_features in ("albedo", "both"), normal=a.shaded_features in ("normal", "both"))
         fs = r.feature_shading()
         print(f"shaded features: albedo {'on' if fs['albedo'] else 'off'}, normal {'on' if fs['normal'] else 'off'}")
+    if a.focus is not None and a.focus_at is not None:
+        ap.error("--focus and --focus-at exclude each other")
+    if (a.focus is not None or a.focus_at is not None) and not a.aperture > 0:
+        ap.error("--focus / --focus-at need --aperture R with R > 0")
+    if a.aperture != 0:
+        focus = a.focus
+        if a.focus_at is not None:
+            x, comma, y = a.focus_at.partition(",")
+            if not (comma and x.strip().isdigit() and y.strip().isdigit()):
+                ap.error("--focus-at takes a pixel as X,Y")
+            try:
+                focus = r.focus_distance_at(int(x), int(y))
+            except ValueError as e:
+                ap.error(f"--focus-at: {e}")
+        try:
+            r.set_lens(a.aperture, focus)
+        except ptmi.PtmiError as e:
+            ap.error(f"--aperture / --focus: {e}")
+        print("lens: radius %g, focus distance %g" % r.lens())
     if a.orbit > 0:
         if a.variance_guided and a.temporal:
             ap.error("--variance-guided does not filter the temporal history (no variance is carried in it)")
