@@ -1500,4 +1500,58 @@ int ptmi_denoise_temporal(ptmi_ctx* c, const ptmi_denoise_params* params) {
     });
 }
 
+// ---- test hook: the filters' inputs, given instead of rendered ----
+int ptmi_debug_set_filter_inputs(ptmi_ctx* c, const float* radiance, const float* albedo, const float* normal, const float* position,
+                                 const float* hit_fraction, int grid) {
+    return guarded([&] {
+        need(c && radiance && albedo && normal && position && hit_fraction, "NULL argument");
+        ApplicationState& g = c->app;
+        RenderState& r = g.render;
+        RenderState::Denoise& d = r.dn;
+        need(g.scene.d_nodes != nullptr, "no scene loaded");
+        need(r.d_state.A != nullptr && r.d_image != nullptr && r.d_radiance != nullptr, "buffers not allocated (call updateResolution first)");
+        need(r.tile.n_ranks == 1, "the context is tiled over more than one rank");
+        need(g.config.current_integrator != IntegratorType::Radiosity, "the Radiosity integrator's image is not filtered");
+        need(grid >= 1 && grid <= 4, "grid must be in [1, 4]");
+        PTMI_HIP(hipSetDevice(g.device_id));
+        const size_t n = r.n_local;                     // every size is the context's: width x height of the current resolution
+        if (!d.fb.albedo) {                             // as renderFeatures allocates them
+            const size_t cap = n > 0 ? n : 1;
+            try {
+                d.fb.albedo = (float4*)hipMallocSafe(cap * sizeof(float4), "features.albedo");
+                d.fb.normal = (float4*)hipMallocSafe(cap * sizeof(float4), "features.normal");
+                d.fb.position = (float4*)hipMallocSafe(cap * sizeof(float4), "features.position");
+            } catch (...) { r.freeDenoise(); throw; }
+        }
+        // the uploads are enqueued behind whatever the stream still holds of an earlier filter run, and waited for below
+        std::vector<float4> h_a(n), h_n(n), h_x(n);
+        for (size_t i = 0; i < n; i++) {
+            h_a[i] = make_float4(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], hit_fraction[i]);
+            h_n[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], 0.0f);
+            h_x[i] = make_float4(position[3 * i], position[3 * i + 1], position[3 * i + 2], 0.0f);
+        }
+        d.features_valid = false;
+        d.image_current = false;
+        if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));   // a gather may still read the image
+        if (n) {
+            PTMI_HIP(hipMemcpyAsync(d.fb.albedo, h_a.data(), n * sizeof(float4), hipMemcpyHostToDevice, r.stream));
+            PTMI_HIP(hipMemcpyAsync(d.fb.normal, h_n.data(), n * sizeof(float4), hipMemcpyHostToDevice, r.stream));
+            PTMI_HIP(hipMemcpyAsync(d.fb.position, h_x.data(), n * sizeof(float4), hipMemcpyHostToDevice, r.stream));
+            PTMI_HIP(hipMemcpyAsync(r.d_radiance, radiance, n * 3 * sizeof(float), hipMemcpyHostToDevice, r.stream));
+            // rgb8 by the product's resolve at k = 1: the denoiser's tone map in its 0-iteration form reads the radiance alone
+            DenoiseArgs a{};
+            a.width = r.tile.width; a.height = r.tile.local_rows;
+            launch_denoise(a, d.fb, r.d_radiance, 0, nullptr, nullptr, r.d_image, nullptr, r.stream);
+            PTMI_HIP(hipGetLastError());
+        }
+        PTMI_HIP(hipStreamSynchronize(r.stream));
+        d.grid = grid;
+        d.features_valid = true;
+        d.image_current = true;
+        d.image_pass = false;
+        d.variance_valid = false;
+        d.denoised = false;
+    });
+}
+
 }  // extern "C"

@@ -49,6 +49,7 @@ EXPORTS = [
     "ptmi_check_albedo_texture", "ptmi_set_albedo_texture", "ptmi_albedo_texture_info", "ptmi_debug_albedo",
     "ptmi_check_feature_shading", "ptmi_set_feature_shading", "ptmi_feature_shading",
     "ptmi_check_lens", "ptmi_set_lens", "ptmi_lens", "ptmi_host_lens_block", "ptmi_debug_lens_block", "ptmi_debug_lens_ray",
+    "ptmi_debug_set_filter_inputs",
 ]
 
 FEATURE_TEXTURED_ALBEDO, FEATURE_SHADING_NORMAL = 1, 2      # PTMI_FEATURE_*
@@ -284,6 +285,8 @@ def lib():
             L.ptmi_host_lens_block.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_float, C.c_float, vp]
             L.ptmi_debug_lens_block.argtypes = [vp, vp]
             L.ptmi_debug_lens_ray.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        if hasattr(L, "ptmi_debug_set_filter_inputs"): # likewise
+            L.ptmi_debug_set_filter_inputs.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int]
         _lib = L
     return _lib
 
@@ -983,6 +986,17 @@ class Renderer:
     # --- feature buffers and the denoiser (include/ptmi.h: ptmi_render_features, ptmi_denoise) ---
     def render_features(self, grid=2):
         self._ck(self.L.ptmi_render_features(self.h, int(grid)))
+
+    def debug_set_filter_inputs(self, radiance, feat, grid=2):
+        """ptmi_debug_set_filter_inputs: radiance (local rows, width, 3) and the feature dict of features() become the context's
+        image and features, as a finished frame plus a finished feature pass of `grid` would leave them.  Non-finite values
+        are passed on as they are."""
+        n = len(self.local_rows())
+        arrs = [np.ascontiguousarray(radiance, np.float32)] + [np.ascontiguousarray(feat[k], np.float32) for k in ("albedo", "normal", "position")]
+        hf = np.ascontiguousarray(feat["hit_fraction"], np.float32)
+        if any(a.shape != (n, self.width, 3) for a in arrs) or hf.shape != (n, self.width):
+            raise ValueError("radiance, albedo, normal, position must be (%d, %d, 3) and hit_fraction (%d, %d)" % (n, self.width, n, self.width))
+        self._ck(self.L.ptmi_debug_set_filter_inputs(self.h, *[a.ctypes.data for a in arrs], hf.ctypes.data, int(grid)))
 
     def features(self):
         """The current feature buffers: albedo, normal, position (local rows, width, 3) and hit_fraction (local rows, width),

@@ -565,6 +565,22 @@ int  ptmi_read_sample_counts(const ptmi_ctx*, uint32_t* counts);
  *   4. radiance = c; rgb8 = the frame's tone map of c (c / (c + 1), to the power 1 / 2.2f by ptmi_math.h's powf, 255.99f * min(., 1), truncated).
  * Features are the current ones for params->feature_grid, recomputed first if stale or of another grid.  A pixel every
  * feature ray missed has normal 0, so all its taps weigh 0 and it keeps its input.
+ * NON-FINITE VALUES (an overflowed firefly: Inf, then Inf - Inf).  Everywhere in this header's filters min and max are C's fminf
+ * and fmaxf - of a NaN and a number they give the number - and a comparison with a NaN is false, so "if W > 0" fails for a NaN W;
+ * everything else is IEEE arithmetic, in which NaN and Inf propagate.  For step 2, per iteration:
+ *   - a NaN in c_p or c_q makes wc, w and so the W of p NaN: p keeps its value of the previous iteration, whole (c'_p = c_p).  A
+ *     NaN pixel therefore stays NaN and never spreads: each pixel with a tap on it passes through unfiltered in that iteration.
+ *   - c_q = +-Inf next to a finite c_p gives wc = 0 and w * c_q = 0 * Inf = NaN: W stays finite and c'_p becomes NaN in the
+ *     channels that are Inf in c_q.  An Inf pixel itself has the tap p = q with Inf - Inf = NaN and keeps its value.  So an Inf
+ *     turns the pixels that tap it in that iteration (p +- {0, s, 2s} in x and in y) into NaN, which then behave as above.
+ *   - a NaN in n_p or n_q gives wn = max(0, NaN) = 0: the tap weighs 0 like a miss (the pixel is skipped by its neighbours and,
+ *     its own taps all weighing 0, keeps its input), provided wc and wx are finite: 0 * NaN is NaN.
+ *   - position_q = +-Inf gives wx = 0 at a finite p (the tap weighs 0); at p = q, Inf - Inf makes W NaN and p keeps its input.  A NaN
+ *     position makes wx NaN at every tap that reads it: those pixels keep their values in every iteration.
+ * After `iterations` iterations a non-finite input pixel can have changed only the pixels within 2 * (2^iterations - 1) of it in x
+ * and in y (the sum of the strides' reach); of those only the ones named above can be non-finite, the others are finite but are
+ * not what they would be without it.  Every pixel outside that square is bit-identical to a run without the non-finite value.
+ * Steps 1 and 3 are per pixel; step 4's min(., 1) turns a NaN into 255.
  * PTMI_E_INVALID: a context tiled over more than one rank (the filter needs rows of other ranks), the Radiosity integrator, no
  * image to filter, and parameters out of range or NaN.  "No image" means no path-tracing frame or pass has completed since the
  * last call that makes features stale (the list above), so the image and its features always show the same scene and view:
@@ -633,6 +649,16 @@ int  ptmi_denoise_timing(const ptmi_ctx*, double* features_ms, double* denoise_m
  *   5. remodulation and tone map as ptmi_denoise steps 3 - 4.  variance_in = the v of steps 2 - 3, variance_out = v after the
  *      last iteration, both in the filtered signal's units (radiance / albedo with demodulate).
  * With iterations = 0 the output is the input, as ptmi_denoise's; variance_in is computed all the same and variance_out equals it.
+ * NON-FINITE VALUES follow ptmi_denoise's rule (max is fmaxf, a comparison with a NaN is false, the rest is IEEE):
+ *   - step 2: max(0, NaN) = 0 - a NaN M2 gives variance 0.
+ *   - step 3: a NaN or Inf l_q makes m and v NaN at every p whose window holds q and whose W > 0 (0 * Inf is NaN too); a NaN
+ *     n_p or n_q gives wn = 0, a skipped tap; a W that is NaN (a non-finite position of p) fails W > 0: v = 0.
+ *   - step 4: a NaN v_q within the 3 x 3 window makes a NaN, a NaN a or l makes w and W NaN, and p keeps (c_p, v_p) of the
+ *     previous iteration; a NaN v_q at a tap of finite weight makes v'_p NaN and leaves c'_p alone; an Inf c_q at a finite a_p
+ *     gives wl = 0 and w * c_q = NaN: c'_p is NaN in those channels.  Normals and positions act as in ptmi_denoise.
+ * A non-finite input pixel can change - and make non-finite - only the pixels within spatial_radius + 2 * (2^iterations - 1) of
+ * it in x and in y (with iterations = 0: within spatial_radius, variance alone); every other pixel's colour and variances are
+ * bit-identical to a run without it.
  * PTMI_E_INVALID: ptmi_denoise's conditions with ptmi_denoise's messages; ptmi_read_variance without a current result;
  * ptmi_read_pass_moments before the accumulation's first pass.
  * ptmi_read_pass_moments returns the stopping rule's mean, M2 and k per local pixel (pixels that have stopped keep theirs). */
@@ -700,6 +726,13 @@ int  ptmi_read_pass_moments(const ptmi_ctx*, float* mean, float* m2, uint32_t* p
  *      (ptmi_read_temporal).  Then the history becomes the current view's: c, n, the current features, camera frame, resolution.
  *   sigma_x = sigma_position, or for sigma_position <= 0: 0.01f * sqrtf((dx*dx + dy*dy) + dz*dz) with (dx, dy, dz) = max - min
  *   of the root box of the scene's BVH (as ptmi_denoise computes its 2 %).
+ * NON-FINITE VALUES.  Every test of steps 3 and 4 is written so that a NaN fails it (">= normal_min does not hold"): a NaN or
+ * Inf in p's features or in a tap's leaves the tap, or p, without history - a restart.  A NaN or Inf in a kept tap's colour c_t
+ * goes into S and so into c: it travels with the surface point, one bilinear footprint per step, until that point restarts
+ * (max_history = 1 does not stop it: alpha = 1 still computes h + (c_cur - h), which is NaN for a NaN h).  Step 5's min is
+ * fminf: a NaN n_acc (only from a NaN count in the history, which no step writes) gives n' = max_history * m.  A non-finite
+ * c_cur makes c non-finite.  No pixel other than those whose kept taps read a non-finite colour, and p itself for c_cur, is
+ * affected.
  * Stats: accepted = pixels whose history was reused (0 or 5), missed = restarts of pixels with hf = 0, rejected = every other
  * restart (an empty history included); they add up to the local pixel count.
  *
@@ -1233,6 +1266,23 @@ int  ptmi_lens(const ptmi_ctx*, float* radius, float* focus_distance);   /* eith
  * PTMI_E_INVALID: no lens (radius 0), no resolution set. */
 int  ptmi_debug_lens_block(ptmi_ctx*, float* out24);
 int  ptmi_debug_lens_ray(ptmi_ctx*, int n, const int* px, const int* py, const float* r /* 4n */, float* out /* 6n */);
+
+/* test hook: the inputs of ptmi_denoise, ptmi_denoise_variance (source = 1) and ptmi_temporal_accumulate, given instead of
+ * rendered, so that every data-dependent decision of their kernels can be reached on constructed images.  n = width x height
+ * of the current resolution; all arrays local row-major like ptmi_read_image.  The call
+ *   - uploads radiance into the buffer ptmi_read_image reads and writes its rgb8 beside it by the tone map of ptmi_denoise
+ *     step 4 (the denoiser's own 0-iteration kernel; no kernel of the hook's own);
+ *   - uploads the features as ptmi_render_features writes them: albedo.w = hit_fraction, normal.w = position.w = 0;
+ *   - leaves the context as a finished frame plus a finished feature pass of `grid` would: image current and not a pass,
+ *     features valid for `grid`, no current variance, nothing denoised.
+ * It touches nothing else: not the temporal history (so: inject view A, step, ptmi_set_camera(B), inject view B, step - and the
+ * second step's history is constructed), not the accumulation, the colour sums or the streams.  A later frame or pass
+ * overwrites the image, a call that makes features stale makes both stale, as after a rendered frame.  Values are not
+ * checked: non-finite ones are legitimate inputs (see NON-FINITE VALUES under ptmi_denoise).
+ * PTMI_E_INVALID, the context unchanged: a NULL argument, no scene loaded, no resolution set, a context tiled over more than
+ * one rank, the Radiosity integrator, grid outside 1 .. 4. */
+int  ptmi_debug_set_filter_inputs(ptmi_ctx*, const float* radiance /* 3n */, const float* albedo /* 3n */, const float* normal /* 3n */,
+                                  const float* position /* 3n */, const float* hit_fraction /* n */, int grid);
 
 #ifdef __cplusplus
 }

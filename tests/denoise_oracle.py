@@ -38,7 +38,8 @@ def features(scene, cam, width, height, g, rows=None):
 
 
 def lum(c):
-    return F(0.2126) * c[..., 0] + F(0.7152) * c[..., 1] + F(0.0722) * c[..., 2]
+    T = c.dtype.type
+    return T(F(0.2126)) * c[..., 0] + T(F(0.7152)) * c[..., 1] + T(F(0.0722)) * c[..., 2]
 
 
 def auto_sigma_position(bmin, bmax):
@@ -47,56 +48,61 @@ def auto_sigma_position(bmin, bmax):
     return F(0.02) * np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2], dtype=F)
 
 
-def denoise(radiance, feat, iterations, sigma_color, color_floor, sigma_x, normal_squarings, demodulate=True):
-    """The filter of include/ptmi.h on radiance (h, w, 3) float32 with the feature dict; returns the filtered radiance."""
-    rad = np.asarray(radiance, F)
+def denoise(radiance, feat, iterations, sigma_color, color_floor, sigma_x, normal_squarings, demodulate=True, T=F, trace=None):
+    """The filter of include/ptmi.h on radiance (h, w, 3) float32 with the feature dict; returns the filtered radiance.  min and
+    max are fmin and fmax (the header's NON-FINITE VALUES).  With T = np.float64 the same formulas are evaluated in binary64
+    (the constants stay the float32 ones).  trace: a list that receives every iteration's W (h, w)."""
+    rad = np.asarray(radiance, T)
     if iterations == 0:
         return rad.copy()
-    alb = feat["albedo"].astype(F)
-    nrm = feat["normal"].astype(F)
-    pos = feat["position"].astype(F)
+    alb = np.asarray(feat["albedo"], T)
+    nrm = np.asarray(feat["normal"], T)
+    pos = np.asarray(feat["position"], T)
     h, w, _ = rad.shape
     c = rad.copy()
-    if demodulate:
-        nz = alb != 0
-        c[nz] = rad[nz] / alb[nz]
-    sx2 = F(sigma_x) * F(sigma_x)
-    floor = F(color_floor)
-    for it in range(iterations):
-        s = 1 << it
-        sc = F(sigma_color) * F(2.0 ** -it)
-        L = lum(c)
-        W = np.zeros((h, w), F)
-        S = np.zeros((h, w, 3), F)
-        for dj in range(-2, 3):
-            for di in range(-2, 3):
-                # q = p + (di s, dj s); the pixels p whose q is inside the image
-                y0, y1 = max(0, -dj * s), min(h, h - dj * s)
-                x0, x1 = max(0, -di * s), min(w, w - di * s)
-                if y0 >= y1 or x0 >= x1:
-                    continue
-                P = (slice(y0, y1), slice(x0, x1))
-                Q = (slice(y0 + dj * s, y1 + dj * s), slice(x0 + di * s, x1 + di * s))
-                cp, cq = c[P], c[Q]
-                d = cp - cq
-                d2c = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
-                a = sc * (np.minimum(L[P], L[Q]) + floor)
-                wc = F(1) / (F(1) + d2c / (a * a))
-                np_, nq = nrm[P], nrm[Q]
-                wn = np.maximum(F(0), (np_[..., 0] * nq[..., 0] + np_[..., 1] * nq[..., 1]) + np_[..., 2] * nq[..., 2])
-                for _ in range(normal_squarings):
-                    wn = wn * wn
-                e = pos[P] - pos[Q]
-                d2x = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
-                wx = F(1) / (F(1) + d2x / sx2)
-                wt = ((B3[dj + 2] * B3[di + 2]) * wc * wn) * wx
-                W[P] = W[P] + wt
-                S[P] = S[P] + wt[..., None] * cq
-        out = c.copy()
-        ok = W > 0
-        out[ok] = S[ok] / W[ok][:, None]
-        c = out
-    if demodulate:
-        nz = alb != 0
-        c[nz] = c[nz] * alb[nz]
+    with np.errstate(all="ignore"):
+        if demodulate:
+            nz = alb != 0
+            c[nz] = rad[nz] / alb[nz]
+        sx2 = T(F(sigma_x)) * T(F(sigma_x))
+        floor = T(F(color_floor))
+        for it in range(iterations):
+            s = 1 << it
+            sc = T(F(sigma_color)) * T(2.0 ** -it)
+            L = lum(c)
+            W = np.zeros((h, w), T)
+            S = np.zeros((h, w, 3), T)
+            for dj in range(-2, 3):
+                for di in range(-2, 3):
+                    # q = p + (di s, dj s); the pixels p whose q is inside the image
+                    y0, y1 = max(0, -dj * s), min(h, h - dj * s)
+                    x0, x1 = max(0, -di * s), min(w, w - di * s)
+                    if y0 >= y1 or x0 >= x1:
+                        continue
+                    P = (slice(y0, y1), slice(x0, x1))
+                    Q = (slice(y0 + dj * s, y1 + dj * s), slice(x0 + di * s, x1 + di * s))
+                    cp, cq = c[P], c[Q]
+                    d = cp - cq
+                    d2c = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+                    a = sc * (np.fmin(L[P], L[Q]) + floor)
+                    wc = T(1) / (T(1) + d2c / (a * a))
+                    np_, nq = nrm[P], nrm[Q]
+                    wn = np.fmax(T(0), (np_[..., 0] * nq[..., 0] + np_[..., 1] * nq[..., 1]) + np_[..., 2] * nq[..., 2])
+                    for _ in range(normal_squarings):
+                        wn = wn * wn
+                    e = pos[P] - pos[Q]
+                    d2x = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+                    wx = T(1) / (T(1) + d2x / sx2)
+                    wt = ((T(B3[dj + 2] * B3[di + 2])) * wc * wn) * wx
+                    W[P] = W[P] + wt
+                    S[P] = S[P] + wt[..., None] * cq
+            if trace is not None:
+                trace.append(W.copy())
+            out = c.copy()
+            ok = W > 0
+            out[ok] = S[ok] / W[ok][:, None]
+            c = out
+        if demodulate:
+            nz = alb != 0
+            c[nz] = c[nz] * alb[nz]
     return c

@@ -30,10 +30,44 @@ class History:
         self.cam = np.asarray(cam, F).copy()
 
 
-def step(hist, radiance, m, feat, cam, max_history=32, normal_min=0.9, sigma_x=None, sigma_albedo=0.1):
+def reproject(hist_cam, cam_origin, feat, w, h):
+    """Steps 2 - 3 and the tap geometry of step 4 for every pixel of the feature dict (arrays (..., 3) and (...)): a dict of x, nc,
+    ac, den, fn, sp, sc, px, py (as computed, before any test), ok (p has taps at all), x0, y0 (int64), fx, fy."""
+    hist_cam = np.asarray(hist_cam, F); cam_origin = np.asarray(cam_origin, F)
+    hf = np.asarray(feat["hit_fraction"], F)
+    with np.errstate(all="ignore"):
+        x = np.asarray(feat["position"], F) / hf[..., None]
+        nc = np.asarray(feat["normal"], F) / hf[..., None]
+        ac = np.asarray(feat["albedo"], F) / hf[..., None]
+        o, llc, hor, ver = hist_cam[0:3], hist_cam[3:6], hist_cam[6:9], hist_cam[9:12]
+        f = llc - o
+        nrm = cross(hor, ver)
+        d = x - o
+        den = dot(d, nrm)
+        fn = dot(f, nrm)
+        sp = dot(nc, o - x)
+        sc = dot(nc, cam_origin - x)
+        ok = (hf != 0) & (((fn > 0) & (den > 0)) | ((fn < 0) & (den < 0))) & (((sp > 0) & (sc > 0)) | ((sp < 0) & (sc < 0)))
+        s = fn / den
+        q = s[..., None] * d - f
+        u = dot(q, hor) / dot(hor, hor)
+        v = dot(q, ver) / dot(ver, ver)
+        px = u * F(w) - F(0.5)
+        py = v * F(h) - F(0.5)
+        ok = ok & (px >= F(-1)) & (px < F(w)) & (py >= F(-1)) & (py < F(h))
+        pxs = np.where(ok, px, F(0))
+        pys = np.where(ok, py, F(0))
+        x0f, y0f = np.floor(pxs), np.floor(pys)
+        fx, fy = pxs - x0f, pys - y0f
+    return dict(x=x, nc=nc, ac=ac, den=den, fn=fn, sp=sp, sc=sc, px=px, py=py, ok=ok, x0=x0f.astype(np.int64), y0=y0f.astype(np.int64),
+                fx=fx, fy=fy)
+
+
+def step(hist, radiance, m, feat, cam, max_history=32, normal_min=0.9, sigma_x=None, sigma_albedo=0.1, trace=None):
     """One step.  hist: a History or None (empty); radiance (h, w, 3); m: samples per pixel, a number or (h, w); feat: the
     current features (dict of albedo, normal, position (h, w, 3) and hit_fraction (h, w)); cam: the current camera frame (12 floats).
-    Returns (radiance out, the new History, (accepted, rejected, missed))."""
+    Returns (radiance out, the new History, (accepted, rejected, missed)).  min is fmin (the header's NON-FINITE VALUES).
+    trace: a dict that receives reproject()'s values, W (h, w), keep (4, h, w) and the per-tap dot products nn, ee, aa (4, h, w)."""
     cur = np.asarray(radiance, F)
     h, w, _ = cur.shape
     m = np.broadcast_to(np.asarray(m, F), (h, w))
@@ -46,36 +80,16 @@ def step(hist, radiance, m, feat, cam, max_history=32, normal_min=0.9, sigma_x=N
         H, nacc = hist.color.copy(), hist.count.copy()                       # still camera: every pixel's only tap is itself
         reuse[:] = True
     elif hist is not None:
-        with np.errstate(divide="ignore", invalid="ignore"):
-            x = feat["position"] / hf[..., None]
-            nc = feat["normal"] / hf[..., None]
-            ac = feat["albedo"] / hf[..., None]
-            o, llc, hor, ver = hist.cam[0:3], hist.cam[3:6], hist.cam[6:9], hist.cam[9:12]
-            f = llc - o
-            nrm = cross(hor, ver)
-            d = x - o
-            den = dot(d, nrm)
-            fn = dot(f, nrm)
-            sp = dot(nc, o - x)
-            sc = dot(nc, cam[0:3] - x)
-            ok = (hf != 0) & (((fn > 0) & (den > 0)) | ((fn < 0) & (den < 0))) & (((sp > 0) & (sc > 0)) | ((sp < 0) & (sc < 0)))
-            s = fn / den
-            q = s[..., None] * d - f
-            u = dot(q, hor) / dot(hor, hor)
-            v = dot(q, ver) / dot(ver, ver)
-            px = u * F(w) - F(0.5)
-            py = v * F(h) - F(0.5)
-            ok &= (px >= F(-1)) & (px < F(w)) & (py >= F(-1)) & (py < F(h))
-            px = np.where(ok, px, F(0))
-            py = np.where(ok, py, F(0))
-            x0f, y0f = np.floor(px), np.floor(py)
-            fx, fy = px - x0f, py - y0f
+        hh, hw = hist.count.shape                                            # (the history's resolution is the current one's)
+        r = reproject(hist.cam, cam[0:3], feat, w, h)
+        x, nc, ac, ok, x0, y0, fx, fy = r["x"], r["nc"], r["ac"], r["ok"], r["x0"], r["y0"], r["fx"], r["fy"]
+        with np.errstate(all="ignore"):
             gx, gy = F(1) - fx, F(1) - fy
-            x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
             sx2 = F(sigma_x) * F(sigma_x)
             W = np.zeros((h, w), F)
             S = np.zeros((h, w, 3), F)
             Sn = np.zeros((h, w), F)
+            keeps, nns, ees, aas = [], [], [], []
             for k in range(4):
                 tx, ty = x0 + (k & 1), y0 + (k >> 1)
                 wt = (fx if k & 1 else gx) * (fy if k >> 1 else gy)
@@ -84,20 +98,27 @@ def step(hist, radiance, m, feat, cam, max_history=32, normal_min=0.9, sigma_x=N
                 thf = hist.hf[tyc, txc]
                 keep &= thf != 0
                 nt = hist.normal[tyc, txc] / thf[..., None]
-                keep &= dot(nc, nt) >= F(normal_min)
+                nn = dot(nc, nt)
+                keep &= nn >= F(normal_min)
                 e = x - hist.position[tyc, txc] / thf[..., None]
-                keep &= dot(e, e) <= sx2
+                ee = dot(e, e)
+                keep &= ee <= sx2
                 ea = ac - hist.albedo[tyc, txc] / thf[..., None]
-                keep &= dot(ea, ea) <= F(sigma_albedo) * F(sigma_albedo)
+                aa = dot(ea, ea)
+                keep &= aa <= F(sigma_albedo) * F(sigma_albedo)
                 W = np.where(keep, W + wt, W)
                 S = np.where(keep[..., None], S + wt[..., None] * hist.color[tyc, txc], S)
                 Sn = np.where(keep, Sn + wt * hist.count[tyc, txc], Sn)
+                keeps.append(keep); nns.append(nn); ees.append(ee); aas.append(aa)
             reuse = ok & (W > F(0.01))
             H = np.where(reuse[..., None], S / W[..., None], F(0))
             nacc = np.where(reuse, Sn / W, F(0))
-    n = np.minimum(nacc + m, F(max_history) * m)
-    alpha = m / n
-    blended = H + alpha[..., None] * (cur - H)
+        if trace is not None:
+            trace.update(r, W=W, keep=np.array(keeps), nn=np.array(nns), ee=np.array(ees), aa=np.array(aas), reuse=reuse)
+    with np.errstate(all="ignore"):
+        n = np.fmin(nacc + m, F(max_history) * m)
+        alpha = m / n
+        blended = H + alpha[..., None] * (cur - H)
     out = np.where(reuse[..., None], blended, cur).astype(F)
     count = np.where(reuse, n, m).astype(F)
     missed = ~reuse & (hf == 0)

@@ -82,6 +82,12 @@ def test_spatial_source_matches_numpy(R, which, width, height, iterations, radiu
     assert not np.array_equal(bits(got[1]), bits(heuristic))
 
 
+@pytest.mark.parametrize("radius", [1, 3])
+def test_spatial_source_matches_numpy_at_stride_512(R, radius):
+    """iterations = 10 on 5 x 3: from stride 4 on every tap but the centre is outside the image"""
+    test_spatial_source_matches_numpy(R, "soup", 5, 3, 10, radius)
+
+
 # ------------------------------------------------------------------------------------------------
 # 2. the accumulation source: the moments, then the filter on them
 # ------------------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ def _window(h, w, dy, dx):
 
 def _wn(nrm, P, Q, normal_squarings, T):
     a, b = nrm[P], nrm[Q]
-    wn = np.maximum(T(0), (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2])
+    wn = np.fmax(T(0), (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2])
     for _ in range(normal_squarings):
         wn = wn * wn
     return wn
@@ -84,8 +84,9 @@ def spatial_variance(c, nrm, pos, radius, normal_squarings, sigma_x, T=F):
     return v
 
 
-def atrous(c, v, nrm, pos, iterations, sigma_luminance, epsilon, sigma_x, normal_squarings, T=F):
-    """step 4 on the demodulated colour c (h, w, 3) and the variance v (h, w); returns (c, v) after the last iteration"""
+def atrous(c, v, nrm, pos, iterations, sigma_luminance, epsilon, sigma_x, normal_squarings, T=F, trace=None):
+    """step 4 on the demodulated colour c (h, w, 3) and the variance v (h, w); returns (c, v) after the last iteration.
+    trace: a list that receives every iteration's (W, V, gd), each (h, w)"""
     h, w, _ = c.shape
     sx2 = T(sigma_x) * T(sigma_x)
     sl2 = T(sigma_luminance) * T(sigma_luminance)
@@ -118,6 +119,8 @@ def atrous(c, v, nrm, pos, iterations, sigma_luminance, epsilon, sigma_x, normal
                 W[P] = W[P] + wt
                 S[P] = S[P] + wt[..., None] * c[Q]
                 V[P] = V[P] + (wt * wt) * v[Q]
+        if trace is not None:
+            trace.append((W.copy(), V.copy(), gd.copy()))
         ok = W > 0
         c2 = c.copy(); v2 = v.copy()
         c2[ok] = S[ok] / W[ok][:, None]
@@ -127,20 +130,21 @@ def atrous(c, v, nrm, pos, iterations, sigma_luminance, epsilon, sigma_x, normal
 
 
 def denoise_variance(radiance, feat, iterations, sigma_luminance, epsilon, sigma_x, normal_squarings, demodulate=True,
-                     spatial_radius=3, moments=None, T=F):
+                     spatial_radius=3, moments=None, T=F, trace=None):
     """Steps 1 - 5 on radiance (h, w, 3) with the feature dict.  moments: None (spatial everywhere) or (M2, passes) of the
     accumulation whose pass image radiance is (source = 0).  Returns (filtered radiance, variance_in, variance_out)."""
-    rad = np.asarray(radiance, T)
-    alb = np.asarray(feat["albedo"], T); nrm = np.asarray(feat["normal"], T); pos = np.asarray(feat["position"], T)
-    c = demodulated(rad, alb, demodulate, T)
-    v = spatial_variance(c, nrm, pos, spatial_radius, normal_squarings, sigma_x, T)
-    if moments is not None:
-        m2, passes = moments
-        v = np.where(np.asarray(passes) >= 2, accumulation_variance(c, rad, m2, passes, T), v).astype(T)
-    if iterations == 0:
-        return rad.copy(), v, v.copy()
-    c, vo = atrous(c, v, nrm, pos, iterations, sigma_luminance, epsilon, sigma_x, normal_squarings, T)
-    if demodulate:
-        nz = alb != 0
-        c[nz] = c[nz] * alb[nz]
-    return c, v, vo
+    with np.errstate(all="ignore"):                             # non-finite pixels are inputs like any other
+        rad = np.asarray(radiance, T)
+        alb = np.asarray(feat["albedo"], T); nrm = np.asarray(feat["normal"], T); pos = np.asarray(feat["position"], T)
+        c = demodulated(rad, alb, demodulate, T)
+        v = spatial_variance(c, nrm, pos, spatial_radius, normal_squarings, sigma_x, T)
+        if moments is not None:
+            m2, passes = moments
+            v = np.where(np.asarray(passes) >= 2, accumulation_variance(c, rad, m2, passes, T), v).astype(T)
+        if iterations == 0:
+            return rad.copy(), v, v.copy()
+        c, vo = atrous(c, v, nrm, pos, iterations, sigma_luminance, epsilon, sigma_x, normal_squarings, T, trace)
+        if demodulate:
+            nz = alb != 0
+            c[nz] = c[nz] * alb[nz]
+        return c, v, vo
