@@ -1554,4 +1554,36 @@ int ptmi_debug_set_filter_inputs(ptmi_ctx* c, const float* radiance, const float
     });
 }
 
+// ---- test hooks: the accumulation's stopping test and resolve, and the launch order by cost, on given state ----
+int ptmi_debug_accum_step(ptmi_ctx* c, const float* sums, const float* prev, const float* m2, const uint32_t* passes, const int* queue,
+                          int n_queue, const ptmi_adaptive_params* params, int first, int* queue_out, int* n_out) {
+    return guarded([&] {
+        need(c && sums && prev && m2 && passes && queue_out && n_out, "NULL argument");
+        AdaptiveParams prm;
+        if (params) { prm.min_passes = params->min_passes; prm.max_passes = params->max_passes; prm.threshold = params->threshold; prm.floor = params->floor; }
+        *n_out = debugAccumStep(c->app, sums, prev, m2, passes, queue, n_queue, params ? &prm : nullptr, first != 0, queue_out);
+    });
+}
+int ptmi_debug_order_by_cost(ptmi_ctx* c, int n, const int* queue_in, const uint32_t* cost, int n_cost, uint32_t cost_max, int classes,
+                             int* queue_out, int* hist) {
+    return guarded([&] {
+        need(c && cost && queue_out && hist, "NULL argument");
+        need(n > 0 && n_cost > 0, "n and n_cost must be positive");
+        need(classes >= 1, "classes must be positive");
+        need(queue_in != nullptr || n <= n_cost, "the identity queue needs n <= n_cost");
+        if (queue_in) for (int i = 0; i < n; i++) need(queue_in[i] >= 0 && queue_in[i] < n_cost, "a queue entry lies outside cost[]");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        const hipStream_t s = c->app.render.stream;
+        DevBuf<int> d_in(queue_in ? (size_t)n : 1), d_out(n), d_hist(512);
+        DevBuf<unsigned int> d_cost(n_cost), d_max(1);
+        if (queue_in) d_in.upload(queue_in, n);
+        d_cost.upload(cost, n_cost); d_max.upload(&cost_max, 1);
+        PTMI_HIP(hipMemsetAsync(d_out.p, 0xff, (size_t)n * sizeof(int), s));      // a position the pass does not write reads -1
+        launch_order_by_cost(queue_in ? d_in.p : nullptr, n, d_cost.p, d_max.p, d_hist.p, d_out.p, classes, s);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(s));
+        d_out.download(queue_out, n); d_hist.download(hist, 512);
+    });
+}
+
 }  // extern "C"

@@ -444,6 +444,11 @@ struct PassStats {
 void accumReset(ApplicationState& g_state);
 void accumPass(ApplicationState& g_state, const AdaptiveParams* params, PassStats* stats);
 void readSampleCounts(const ApplicationState& g_state, uint32_t* counts);
+// Test hook (include/ptmi.h: ptmi_debug_accum_step): the pass half of a pass's end - stopping test, resolve by counts - on
+// state given by slot instead of rendered; n = n_local.  Returns the length of queue_out
+int debugAccumStep(ApplicationState& g_state, const float* sums /* 3n */, const float* prev /* 4n */, const float* m2 /* n */,
+                   const uint32_t* passes /* n */, const int* queue /* n_queue, or nullptr: 0 .. n_queue - 1 */, int n_queue,
+                   const AdaptiveParams* params, bool first, int* queue_out /* n_queue */);
 
 // Feature buffers and the edge-avoiding a-trous denoiser (include/ptmi.h: ptmi_render_features, ptmi_denoise).
 struct DenoiseParams {

@@ -461,4 +461,77 @@ void readSampleCounts(const ApplicationState& g, uint32_t* counts) {
     PTMI_HIP(hipMemcpy(counts, r.accum.d_counts, r.n_local * sizeof(uint32_t), hipMemcpyDeviceToHost));
 }
 
+// ------------------------------------------------------------------------------------------------
+// test hook: one stopping test plus resolve on given state (include/ptmi.h: ptmi_debug_accum_step)
+// ------------------------------------------------------------------------------------------------
+// What accumPass and finishRun do around a pass's render, without the render: the state by slot goes into the context's own
+// buffers, then the launches of finishRun's pass half, in its order, on the frame's stream.  No kernel of its own.
+int debugAccumStep(ApplicationState& g, const float* sums, const float* prev, const float* m2, const uint32_t* passes, const int* queue,
+                   int n_queue, const AdaptiveParams* params, bool first, int* queue_out) {
+    RenderState& r = g.render;
+    RenderState::Accum& a = r.accum;
+    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError("debugAccumStep: the Radiosity integrator has no accumulation passes");
+    checkRenderable(g, "debugAccumStep");
+    const size_t n = r.n_local;
+    if (n_queue < 0 || (size_t)n_queue > n) throw ArgError("debugAccumStep: the queue's length must be in [0, local pixels]");
+    if (queue) {
+        std::vector<char> seen(n, 0);
+        for (int i = 0; i < n_queue; i++) {
+            if (queue[i] < 0 || (size_t)queue[i] >= n) throw ArgError("debugAccumStep: a queue entry lies outside the local slots");
+            if (seen[queue[i]]) throw ArgError("debugAccumStep: a slot is queued twice");
+            seen[queue[i]] = 1;
+        }
+    }
+    PTMI_HIP(hipSetDevice(g.device_id));
+    if (!a.allocated()) r.allocateAccum();
+    if (a.pass == 0) a.cur = 0;
+    const int k = a.pass + 1;
+    a.pass = 0;                                        // until the step is through, as in accumPass
+    r.batch_frames = 1; r.batch_spp = 0;
+    r.dn.image_current = false;
+    AdaptRule rule;
+    rule.first = first ? 1 : 0;
+    rule.stopping = params ? 1 : 0;
+    rule.min_passes = params ? params->min_passes : 0;
+    rule.max_passes = params ? params->max_passes : 0;
+    rule.threshold = params ? params->threshold : 0.0f;
+    rule.floor_ = params ? params->floor : 0.0f;
+    rule.inv_spp = rcp_rn((float)g.config.spp);
+    std::vector<float4> h_D(n), h_prev(n);
+    for (size_t i = 0; i < n; i++) {
+        h_D[i] = make_float4(sums[3 * i], sums[3 * i + 1], sums[3 * i + 2], 0.0f);      // .w: the sample index, rewritten when a pass begins
+        h_prev[i] = make_float4(prev[4 * i], prev[4 * i + 1], prev[4 * i + 2], prev[4 * i + 3]);
+    }
+    const hipStream_t s = r.stream;
+    Drain drain{r};
+    int n_out = 0;
+    if (n) {
+        PTMI_HIP(hipMemcpyAsync(r.d_state.D, h_D.data(), n * sizeof(float4), hipMemcpyHostToDevice, s));
+        PTMI_HIP(hipMemcpyAsync(a.ab.prev, h_prev.data(), n * sizeof(float4), hipMemcpyHostToDevice, s));
+        PTMI_HIP(hipMemcpyAsync(a.ab.m2, m2, n * sizeof(float), hipMemcpyHostToDevice, s));
+        PTMI_HIP(hipMemcpyAsync(a.ab.passes, passes, n * sizeof(unsigned int), hipMemcpyHostToDevice, s));
+    }
+    if (queue && n_queue) PTMI_HIP(hipMemcpyAsync(a.d_active[a.cur], queue, (size_t)n_queue * sizeof(int), hipMemcpyHostToDevice, s));
+    // the pass half of finishRun
+    PTMI_HIP(hipMemsetAsync(a.d_out_count, 0, sizeof(int), s));
+    launch_adapt(r.d_state, a.ab, rule, queue ? a.d_active[a.cur] : nullptr, n_queue, a.d_active[a.cur ^ 1], a.d_out_count, s);
+    PTMI_HIP(hipGetLastError());
+    if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(s, r.resolve_gate, 0));
+    launch_resolve_counts(r.tile, r.d_state, a.ab.passes, g.config.spp, r.d_image, r.d_radiance, a.d_counts, s);
+    PTMI_HIP(hipGetLastError());
+    PTMI_HIP(hipMemcpyAsync(&n_out, a.d_out_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (r.download_image && n) PTMI_HIP(hipMemcpyAsync(r.h_image, r.d_image, n * 3, hipMemcpyDeviceToHost, s));
+    PTMI_HIP(hipStreamSynchronize(s));
+    PTMI_HIP(hipGetLastError());
+    if (n_out < 0 || n_out > n_queue) throw HipError(hipErrorUnknown, "debugAccumStep: the stopping test returned a count outside its queue");
+    if (n_out) PTMI_HIP(hipMemcpy(queue_out, a.d_active[a.cur ^ 1], (size_t)n_out * sizeof(int), hipMemcpyDeviceToHost));
+    drain.armed = false;
+    r.dn.image_current = true;
+    r.dn.image_pass = true;
+    a.pass = k;
+    a.cur ^= 1;
+    a.n_active = n_out;
+    return n_out;
+}
+
 }  // namespace ptmi

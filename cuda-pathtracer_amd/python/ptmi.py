@@ -50,6 +50,7 @@ EXPORTS = [
     "ptmi_check_feature_shading", "ptmi_set_feature_shading", "ptmi_feature_shading",
     "ptmi_check_lens", "ptmi_set_lens", "ptmi_lens", "ptmi_host_lens_block", "ptmi_debug_lens_block", "ptmi_debug_lens_ray",
     "ptmi_debug_set_filter_inputs",
+    "ptmi_debug_accum_step", "ptmi_debug_order_by_cost",
 ]
 
 FEATURE_TEXTURED_ALBEDO, FEATURE_SHADING_NORMAL = 1, 2      # PTMI_FEATURE_*
@@ -287,6 +288,9 @@ def lib():
             L.ptmi_debug_lens_ray.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         if hasattr(L, "ptmi_debug_set_filter_inputs"): # likewise
             L.ptmi_debug_set_filter_inputs.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int]
+        if hasattr(L, "ptmi_debug_accum_step"):        # likewise
+            L.ptmi_debug_accum_step.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(AdaptiveParams), C.c_int, vp, ip]
+            L.ptmi_debug_order_by_cost.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint32, C.c_int, vp, vp]
         _lib = L
     return _lib
 
@@ -997,6 +1001,43 @@ class Renderer:
         if any(a.shape != (n, self.width, 3) for a in arrs) or hf.shape != (n, self.width):
             raise ValueError("radiance, albedo, normal, position must be (%d, %d, 3) and hit_fraction (%d, %d)" % (n, self.width, n, self.width))
         self._ck(self.L.ptmi_debug_set_filter_inputs(self.h, *[a.ctypes.data for a in arrs], hf.ctypes.data, int(grid)))
+
+    def debug_accum_step(self, sums, prev, m2, passes, queue=None, n_queue=None, params=None, first=False):
+        """ptmi_debug_accum_step: one stopping test plus resolve on state given BY SLOT - sums (n, 3), prev (n, 4: S_{k-1}.xyz and
+        the mean), m2 (n) float32, passes (n) uint32, n = local rows x width; queue: int32 slots (None: the slots 0 .. n_queue - 1,
+        n_queue None: all); params: an AdaptiveParams, a dict of its fields or None (progressive).  Returns the next pass's queue."""
+        n = len(self.local_rows()) * self.width
+        sums = np.ascontiguousarray(sums, np.float32); prev = np.ascontiguousarray(prev, np.float32)
+        m2 = np.ascontiguousarray(m2, np.float32); passes = np.ascontiguousarray(passes, np.uint32)
+        if sums.shape != (n, 3) or prev.shape != (n, 4) or m2.shape != (n,) or passes.shape != (n,):
+            raise ValueError("sums must be (%d, 3), prev (%d, 4), m2 and passes (%d,)" % (n, n, n))
+        if queue is not None:
+            queue = np.ascontiguousarray(queue, np.int32)
+            if queue.ndim != 1 or (n_queue is not None and n_queue != len(queue)):
+                raise ValueError("queue must be one-dimensional and n_queue its length")
+            n_queue = len(queue)
+        elif n_queue is None:
+            n_queue = n
+        if isinstance(params, dict):
+            params = default_adaptive_params(**params)
+        out = np.full(max(int(n_queue), 1), -1, np.int32); n_out = C.c_int(-1)
+        self._ck(self.L.ptmi_debug_accum_step(self.h, sums.ctypes.data, prev.ctypes.data, m2.ctypes.data, passes.ctypes.data,
+                                              queue.ctypes.data if queue is not None else None, int(n_queue),
+                                              C.byref(params) if params is not None else None, int(bool(first)), out.ctypes.data, C.byref(n_out)))
+        return out[:n_out.value].copy()
+
+    def debug_order_by_cost(self, n, cost, cost_max, classes, queue_in=None):
+        """ptmi_debug_order_by_cost: (queue_out (n) int32, hist (512) int32) of the launch order by cost for cost (uint32 per
+        entry), cost_max and classes over queue_in (int32, None: 0 .. n - 1)."""
+        cost = np.ascontiguousarray(cost, np.uint32)
+        if queue_in is not None:
+            queue_in = np.ascontiguousarray(queue_in, np.int32)
+            if queue_in.shape != (n,):
+                raise ValueError("queue_in must hold n entries")
+        out = np.full(max(int(n), 1), -2, np.int32); hist = np.full(512, -2, np.int32)
+        self._ck(self.L.ptmi_debug_order_by_cost(self.h, int(n), queue_in.ctypes.data if queue_in is not None else None, cost.ctypes.data,
+                                                 int(cost.size), int(cost_max), int(classes), out.ctypes.data, hist.ctypes.data))
+        return out[:n], hist
 
     def features(self):
         """The current feature buffers: albedo, normal, position (local rows, width, 3) and hit_fraction (local rows, width),

@@ -495,6 +495,15 @@ int ptmi_debug_nee_call(ptmi_ctx*, int op, int n, const float* in, float* out_f,
  * i.e. the standard error of the mean of the pass means, sqrt(M2 / (k (k - 1))), is at most threshold x (mean + floor).  It
  * reads nothing but the pixel's own sums: neighbours, launch order, tiling and the walk never change a decision.
  * params == NULL: a plain progressive pass - every pixel renders, none stops.
+ * NON-FINITE VALUES (an overflowed firefly in S: Inf, then Inf - Inf).  The rule is IEEE arithmetic and nothing else: a NaN or
+ * infinite channel of S makes y, mean and M2 non-finite (an Inf d gives mean = Inf and y - mean = NaN), and a NaN M2 stays a NaN
+ * in every later pass.  A comparison with a NaN is false, so "M2 <= ..." fails for a NaN M2 and for a NaN bound: such a pixel
+ * never stops by its spread and runs until k == max_passes stops it, which needs no M2.  An M2 a few ulps below zero (the
+ * update can round it there) compares like a zero and stops; with threshold == 0 the bound is 0 and only M2 <= 0 stops.  The
+ * pixel resolves as its sum says (NaN and Inf tone-map to 255, see ptmi_denoise's NON-FINITE VALUES).  No other pixel is
+ * affected - not its moments, its decision, its place among the survivors of its wave, its image - since the test reads the
+ * pixel's own sums alone.  ptmi_denoise_variance (source = 0) takes max(0, M2 / (k (k - 1))) by fmaxf: a negative and a NaN M2
+ * both give variance 0.
  *
  * Multi-GPU: every rank adapts its own rows.  The distributed loop, per pass on every rank:
  *     ptmi_accum_pass(ctx, &params, &st); double a = (double)st.active_after; ptmi_dist_allreduce_max(ctx, &a);
@@ -1283,6 +1292,50 @@ int  ptmi_debug_lens_ray(ptmi_ctx*, int n, const int* px, const int* py, const f
  * one rank, the Radiosity integrator, grid outside 1 .. 4. */
 int  ptmi_debug_set_filter_inputs(ptmi_ctx*, const float* radiance /* 3n */, const float* albedo /* 3n */, const float* normal /* 3n */,
                                   const float* position /* 3n */, const float* hit_fraction /* n */, int grid);
+
+/* test hook: one stopping test plus resolve of an accumulation on state given instead of rendered, so that every decision of
+ * THE STOPPING RULE, the compaction of the next pass's queue and the resolve at per-pixel counts can be reached on constructed
+ * values.  n = the local pixels of the current resolution.  All inputs lie BY SLOT, as the kernels hold them, not by pixel:
+ * without 8 x 8 slot tiles (config.wave_tiles = 0, or a width, local row count or row_block that is no multiple of 8) slot s is
+ * local pixel (row s / width, column s % width); with them, slot s is pixel (in & 7, in >> 3) of tile s >> 6 (in = s & 63), the
+ * tiles row-major, width / 8 to a row.
+ *   sums   S_k.xyz: the colour sums after the pass                  prev   S_{k-1}.xyz and the mean, 4 floats per slot
+ *   m2, passes      M2 and the passes taken BEFORE this one (k = passes + 1)
+ *   queue  n_queue distinct slots, the pixels that took the pass; NULL: the slots 0 .. n_queue - 1
+ *   params NULL: a plain progressive pass.  Its fields are used as given (not range-checked as ptmi_accum_pass checks them)
+ *   first  != 0: pass 1 - prev, m2 and passes are not read for the queued slots (they count as zero)
+ * The call
+ *   - uploads the inputs into the context's own buffers (allocated, if there are none yet, as a first pass allocates them);
+ *   - zeroes the output count and runs the product's stopping test over the queue, then its resolve by counts over all local
+ *     pixels, exactly as the end of ptmi_accum_pass does (no kernel of the hook's own): the queued slots take the rule with
+ *     inv_spp of config.spp; every slot, queued or not, is resolved at passes[slot] * config.spp samples;
+ *   - returns the next pass's queue in queue_out (room for n_queue entries) and its length in *n_out.  The queue's contract is
+ *     the product's: the slots that go on, once each; the survivors of each 64 consecutive input positions contiguous and in
+ *     input order; the order of those groups among themselves unspecified;
+ *   - leaves the context as a finished pass leaves it: an accumulation with a pass count one higher, *n_out pixels active, that
+ *     queue the next pass's, the image current and marked as a pass.
+ * So ptmi_read_image, ptmi_read_sample_counts, ptmi_read_pass_moments, ptmi_denoise_variance (source = 0) and a following
+ * ptmi_accum_pass act on the constructed state.  The streams, the features and the temporal history are untouched.  It works on
+ * a tiled context (its local slots).  Values are not checked: non-finite sums and moments are legitimate inputs (NON-FINITE
+ * VALUES under THE STOPPING RULE).
+ * PTMI_E_INVALID: a NULL argument other than queue and params, no scene loaded, no resolution set, the Radiosity integrator,
+ * n_queue outside [0, n], a queue entry outside [0, n) or repeated. */
+int  ptmi_debug_accum_step(ptmi_ctx*, const float* sums /* 3n */, const float* prev /* 4n */, const float* m2 /* n */,
+                           const uint32_t* passes /* n */, const int* queue /* n_queue, or NULL */, int n_queue,
+                           const ptmi_adaptive_params* params /* or NULL */, int first, int* queue_out /* n_queue */, int* n_out);
+
+/* test hook: the launch order of a refill frame on given costs.  queue_out = the n entries of queue_in (NULL: 0 .. n - 1) as the
+ * product's ordering pass places them for cost[entry] (n_cost values), cost_max and `classes`:
+ *     shift = the smallest s in 0 .. 7 with (256 >> s) <= classes, 7 if there is none    (classes >= 256: 0; 1 or 2: 7)
+ *     class(entry) = (255 - floor(256 * min(cost, cost_max) / (cost_max + 1))) >> shift          (64-bit integers)
+ * Classes ascend along queue_out, i.e. costs descend class by class; inside a class the entries of one block of 256 consecutive
+ * input positions are contiguous and in input order, the order of the blocks among themselves unspecified.  hist: the pass's
+ * 512 ints when it is through - hist[c] = entries of class c, hist[256 + c] = the END of class c in queue_out.  The call uses
+ * buffers of its own and changes nothing in the context.
+ * PTMI_E_INVALID: a NULL argument other than queue_in, n or n_cost < 1, classes < 1, a queue entry outside [0, n_cost), and
+ * without queue_in n > n_cost. */
+int  ptmi_debug_order_by_cost(ptmi_ctx*, int n, const int* queue_in /* n, or NULL */, const uint32_t* cost /* n_cost */, int n_cost,
+                              uint32_t cost_max, int classes, int* queue_out /* n */, int* hist /* 512 */);
 
 #ifdef __cplusplus
 }
