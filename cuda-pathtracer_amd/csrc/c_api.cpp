@@ -1586,4 +1586,70 @@ int ptmi_debug_order_by_cost(ptmi_ctx* c, int n, const int* queue_in, const uint
     });
 }
 
+// ---- test hooks: the guided-record kernels (csrc/radiosity.hip) on given grids and form factors ----
+int ptmi_debug_cdf_records(ptmi_ctx* c, int n, int src_kind, const float* src, float* out) {
+    return guarded([&] {
+        need(c && src && out, "NULL argument");
+        need(n >= 1, "n must be positive");
+        need(src_kind >= 0 && src_kind <= 2, "src_kind must be 0, 1 or 2");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        const hipStream_t s = c->app.render.stream;
+        const size_t per = (size_t)kGridSize * (src_kind == 0 ? 4 : src_kind == 1 ? 3 : 1);
+        DevBuf<float> d_src(per * n), d_out((size_t)n * kCdfDwords);
+        d_src.upload(src, per * n);
+        launch_cdf_records(n, d_src.p, src_kind, d_out.p, s);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(s));
+        d_out.download(out, (size_t)n * kCdfDwords);
+    });
+}
+int ptmi_debug_filter_pdfs(ptmi_ctx* c, int n, const float* rgb, const float* counts, int use_bilateral, float sigma_spatial,
+                           float sigma_range, float* out_formfactor, float* out_radiosity) {
+    return guarded([&] {
+        need(c && rgb && out_formfactor && out_radiosity, "NULL argument");
+        need(n >= 1, "n must be positive");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        const hipStream_t s = c->app.render.stream;
+        const size_t cells = (size_t)n * kGridSize;
+        DevBuf<float> d_rgb(3 * cells), d_cnt(counts ? cells : 1), d_ff(cells), d_rad(cells);
+        d_rgb.upload(rgb, 3 * cells);
+        if (counts) d_cnt.upload(counts, cells);
+        launch_filter_pdfs(n, d_rgb.p, counts ? d_cnt.p : nullptr, d_ff.p, d_rad.p, use_bilateral != 0, sigma_spatial, sigma_range, s);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(s));
+        d_ff.download(out_formfactor, cells); d_rad.download(out_radiosity, cells);
+    });
+}
+int ptmi_debug_radiosity_grid(ptmi_ctx* c, int n, const float* centre, const float* normal, const float* form_factors,
+                              const float* radiosity, int enable_filtering, int use_bilateral, float sigma_spatial, float sigma_range,
+                              float* out) {
+    return guarded([&] {
+        need(c && centre && normal && form_factors && radiosity && out, "NULL argument");
+        need(n >= 1, "n must be positive");
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        const hipStream_t s = c->app.render.stream;
+        const size_t cells = (size_t)n * kGridSize;
+        // geo: only the normal [4] and the centroid [5] of each primitive's six records are read by the kernel
+        std::vector<float4> h_geo(6 * (size_t)n, make_float4(0.0f, 0.0f, 0.0f, 0.0f)), h_rad(n), h_grid(cells);
+        for (int i = 0; i < n; i++) {
+            h_geo[6 * (size_t)i + 4] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], 0.0f);
+            h_geo[6 * (size_t)i + 5] = make_float4(centre[3 * i], centre[3 * i + 1], centre[3 * i + 2], 0.0f);
+            h_rad[i] = make_float4(radiosity[3 * i], radiosity[3 * i + 1], radiosity[3 * i + 2], 0.0f);
+        }
+        DevBuf<float4> d_geo(6 * (size_t)n), d_rad(n), d_grid(cells);
+        DevBuf<float> d_ff((size_t)n * n);
+        d_geo.upload(h_geo.data(), 6 * (size_t)n); d_rad.upload(h_rad.data(), n); d_ff.upload(form_factors, (size_t)n * n);
+        RadiosityBuffers rb;
+        rb.geo = d_geo.p; rb.radiosity = d_rad.p; rb.form_factors = d_ff.p; rb.rad_grid = d_grid.p; rb.n = n;
+        RadiosityParams prm{};
+        prm.enable_filtering = enable_filtering != 0; prm.use_bilateral = use_bilateral != 0;
+        prm.filter_sigma_spatial = sigma_spatial; prm.filter_sigma_range = sigma_range;
+        launch_radiosity_grid(rb, prm, s);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(s));
+        d_grid.download(h_grid.data(), cells);
+        for (size_t k = 0; k < cells; k++) { out[3 * k] = h_grid[k].x; out[3 * k + 1] = h_grid[k].y; out[3 * k + 2] = h_grid[k].z; }
+    });
+}
+
 }  // extern "C"

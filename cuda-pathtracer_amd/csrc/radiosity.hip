@@ -242,7 +242,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_radiosity_grid(RadiosityBuffers r
         for (int jj = tid; jj < m; jj += kBlock) {
             const int j = base + jj;
             unsigned short c = 0xffffu;
-            if (j != i && row[j] > 0.0f) {
+            if (j != i && !(row[j] <= 0.0f)) {                // form_factors.h:424 skips F_ij <= 0: a NaN form factor is taken
                 f3 dir_ij = xyz(rb.geo[6 * j + 5]) - center_i;
                 const float r = length(dir_ij);
                 if (!(r < 1e-6f)) {

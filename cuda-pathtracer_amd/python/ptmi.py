@@ -51,6 +51,7 @@ EXPORTS = [
     "ptmi_check_lens", "ptmi_set_lens", "ptmi_lens", "ptmi_host_lens_block", "ptmi_debug_lens_block", "ptmi_debug_lens_ray",
     "ptmi_debug_set_filter_inputs",
     "ptmi_debug_accum_step", "ptmi_debug_order_by_cost",
+    "ptmi_debug_cdf_records", "ptmi_debug_filter_pdfs", "ptmi_debug_radiosity_grid",
 ]
 
 FEATURE_TEXTURED_ALBEDO, FEATURE_SHADING_NORMAL = 1, 2      # PTMI_FEATURE_*
@@ -291,6 +292,10 @@ def lib():
         if hasattr(L, "ptmi_debug_accum_step"):        # likewise
             L.ptmi_debug_accum_step.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(AdaptiveParams), C.c_int, vp, ip]
             L.ptmi_debug_order_by_cost.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_uint32, C.c_int, vp, vp]
+        if hasattr(L, "ptmi_debug_cdf_records"):       # likewise
+            L.ptmi_debug_cdf_records.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+            L.ptmi_debug_filter_pdfs.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_float, C.c_float, vp, vp]
+            L.ptmi_debug_radiosity_grid.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, vp]
         _lib = L
     return _lib
 
@@ -1038,6 +1043,45 @@ class Renderer:
         self._ck(self.L.ptmi_debug_order_by_cost(self.h, int(n), queue_in.ctypes.data if queue_in is not None else None, cost.ctypes.data,
                                                  int(cost.size), int(cost_max), int(classes), out.ctypes.data, hist.ctypes.data))
         return out[:n], hist
+
+    def debug_cdf_records(self, src_kind, src):
+        """ptmi_debug_cdf_records: the (n, 530) records of n grids; src (n, 256, 4 | 3) for src_kind 0 | 1, (n, 256) for 2."""
+        src = np.ascontiguousarray(src, np.float32)
+        want = {0: (256, 4), 1: (256, 3), 2: (256,)}.get(int(src_kind))
+        if want is not None and src.shape[1:] != want:
+            raise ValueError(f"src_kind {src_kind} takes grids of shape (n,) + {want}")
+        out = np.zeros((len(src), 530), np.float32)
+        self._ck(self.L.ptmi_debug_cdf_records(self.h, len(src), int(src_kind), src.ctypes.data, out.ctypes.data))
+        return out
+
+    def debug_filter_pdfs(self, rgb, counts=None, use_bilateral=True, sigma_spatial=1.5, sigma_range=0.3):
+        """ptmi_debug_filter_pdfs: (formfactor, radiosity) pdfs, (n, 256) each, of rgb (n, 256, 3) and counts (n, 256) or None."""
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.ndim != 3 or rgb.shape[1:] != (256, 3):
+            raise ValueError("rgb must be (n, 256, 3)")
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, np.float32)
+            if counts.shape != rgb.shape[:2]:
+                raise ValueError("counts must be (n, 256)")
+        ff = np.zeros(rgb.shape[:2], np.float32); rad = np.zeros(rgb.shape[:2], np.float32)
+        self._ck(self.L.ptmi_debug_filter_pdfs(self.h, len(rgb), rgb.ctypes.data, counts.ctypes.data if counts is not None else None,
+                                               int(bool(use_bilateral)), sigma_spatial, sigma_range, ff.ctypes.data, rad.ctypes.data))
+        return ff, rad
+
+    def debug_radiosity_grid(self, centre, normal, form_factors, radiosity, enable_filtering=False, use_bilateral=True,
+                             sigma_spatial=1.5, sigma_range=0.3):
+        """ptmi_debug_radiosity_grid: the (n, 256, 3) radiosity grids of a world of n primitives given by centre, normal (n, 3),
+        form_factors (n, n) and radiosity (n, 3)."""
+        centre, normal, radiosity = (np.ascontiguousarray(a, np.float32) for a in (centre, normal, radiosity))
+        form_factors = np.ascontiguousarray(form_factors, np.float32)
+        n = len(centre)
+        if centre.shape != (n, 3) or normal.shape != (n, 3) or radiosity.shape != (n, 3) or form_factors.shape != (n, n):
+            raise ValueError("centre, normal, radiosity must be (n, 3) and form_factors (n, n)")
+        out = np.zeros((n, 256, 3), np.float32)
+        self._ck(self.L.ptmi_debug_radiosity_grid(self.h, n, centre.ctypes.data, normal.ctypes.data, form_factors.ctypes.data,
+                                                  radiosity.ctypes.data, int(bool(enable_filtering)), int(bool(use_bilateral)),
+                                                  sigma_spatial, sigma_range, out.ctypes.data))
+        return out
 
     def features(self):
         """The current feature buffers: albedo, normal, position (local rows, width, 3) and hit_fraction (local rows, width),

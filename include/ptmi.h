@@ -202,7 +202,10 @@ int ptmi_set_radiosity(ptmi_ctx*, int n_prims, const float* rgb);
  * radiosity grids and the count grids through the 5x5 bilateral / gaussian float filter, each primitive normalised to
  * sum 1) + SceneState::precomputeCDFsFromFiltered (application_state.h:587-680): the guided sampling modes then use
  * records built from the filtered luminance.  Needs radiosity grids (a solver run or ptmi_set_radiosity_grids).
- * "Use Raw CDFs" (ui_windows.h:173-177) = ptmi_use_raw_cdfs: precomputeCDFs() again from the unfiltered grids. */
+ * "Use Raw CDFs" (ui_windows.h:173-177) = ptmi_use_raw_cdfs: precomputeCDFs() again from the unfiltered grids.
+ * NON-FINITE VALUES in grids, form factors and sigmas (a NaN against each comparison, the NaN entries a VALID record can hold,
+ * a sigma whose 2 * sigma * sigma is 0, a non-finite direction): see the paragraph of that name under ptmi_debug_cdf_records,
+ * whose hooks run these calls' kernels on given values. */
 int ptmi_apply_grid_filter(ptmi_ctx*, int use_bilateral, float sigma_spatial, float sigma_range);
 int ptmi_use_raw_cdfs(ptmi_ctx*);
 /* d_filtered_formfactor / d_filtered_radiosity (application_state.h:160-161), n_prims * 256 floats each; either may be NULL */
@@ -1336,6 +1339,36 @@ int  ptmi_debug_accum_step(ptmi_ctx*, const float* sums /* 3n */, const float* p
  * without queue_in n > n_cost. */
 int  ptmi_debug_order_by_cost(ptmi_ctx*, int n, const int* queue_in /* n, or NULL */, const uint32_t* cost /* n_cost */, int n_cost,
                               uint32_t cost_max, int classes, int* queue_out /* n */, int* hist /* 512 */);
+
+/* test hooks: the kernels that turn a radiosity solution into the records guided sampling reads (csrc/radiosity.hip), on given
+ * grids and form factors.  Each uses buffers of its own, changes nothing in the context, launches the product's own kernel through
+ * its own launch function and has no kernel of its own.  Values are not checked: non-finite ones are legitimate inputs.
+ * ptmi_debug_cdf_records: n PrecomputedCDF records of 530 words (ptmi_host_cdf_record_layout) from n grids of 256 cells, row-major
+ *   (theta, phi).  src_kind 0: four floats per cell (r, g, b, w) as the solver holds them - w is not read;  1: three floats per
+ *   cell, as ptmi_set_radiosity_grids takes them;  2: one float per cell, a ready pdf, as ptmi_apply_grid_filter's records take it.
+ *   Kinds 0 and 1 take pdf = 0.2126f * r + 0.7152f * g + 0.0722f * b, every operation rounded, left to right.
+ * ptmi_debug_filter_pdfs: "Apply Filter & Rebuild CDFs" up to the pdfs: the luminance of rgb and the count grid (NULL: zero), each
+ *   through the 5 x 5 float filter and divided by its sequential 256-term sum unless that sum <= 1e-12f; out_formfactor from the
+ *   counts, out_radiosity from the luminance, n * 256 each.
+ * ptmi_debug_radiosity_grid: update_radiosity_grid of the solver over a world of n primitives given by centre and normal alone:
+ *   out[i] = primitive i's 16 x 16 rgb grid, cell(direction i -> j) += form_factors[i * n + j] * radiosity[j] in ascending j, for
+ *   every j != i unless F_ij <= 0.0f or the distance r < 1e-6f; then, with enable_filtering, the 5 x 5 rgb filter.
+ * NON-FINITE VALUES.  The comparisons are the reference's and a NaN fails each of them: a NaN form factor is not `<= 0` and IS
+ *   added (it makes its cell NaN); a NaN distance is not `< 1e-6f`; a NaN sum is not `<= 1e-12f` and divides; a NaN filter weight
+ *   total is not `> 1e-6f`, so the cell keeps its centre value - which is also what a sigma so small that 2 * sigma * sigma is 0
+ *   in binary32 gives everywhere (the centre weight is exp(-0 / 0)).  A NaN row sum is not `< 1e-6f`: the row's CDF is NaN up to
+ *   its forced last entry 1.  A record is valid where total > 1e-6f, and a VALID record can hold NaN: an inf cell gives total =
+ *   inf, 1 / total = 0 and a marginal of inf * 0 up to its forced last entry, so sampling always picks row 7.  Sampling such
+ *   records is defined (the linear search takes the first entry with xi <= cdf, a NaN never) and pinned by the tests.  Centres
+ *   and normals must be finite and normals nonzero: a non-finite direction makes the cell index a float -> int conversion of a
+ *   NaN, which is undefined on the host and on the device alike and is not specified here.
+ * PTMI_E_INVALID: a NULL argument other than counts, n < 1, src_kind outside 0 .. 2. */
+int  ptmi_debug_cdf_records(ptmi_ctx*, int n, int src_kind, const float* src /* n * 256 * (4 | 3 | 1) */, float* out /* n * 530 */);
+int  ptmi_debug_filter_pdfs(ptmi_ctx*, int n, const float* rgb /* n*256*3 */, const float* counts /* n*256, or NULL */, int use_bilateral,
+                            float sigma_spatial, float sigma_range, float* out_formfactor /* n*256 */, float* out_radiosity /* n*256 */);
+int  ptmi_debug_radiosity_grid(ptmi_ctx*, int n, const float* centre /* 3n */, const float* normal /* 3n */,
+                               const float* form_factors /* n*n */, const float* radiosity /* 3n */, int enable_filtering,
+                               int use_bilateral, float sigma_spatial, float sigma_range, float* out /* n*256*3 */);
 
 #ifdef __cplusplus
 }

@@ -1314,6 +1314,38 @@ static v3 filter_cell(const v3* input_grid, int center_i, int center_j, int bila
     return center_val;
 }
 
+/* update_radiosity_grid (form_factors.h:408-442) of receiver i + the optional filter (application_state.h:759-767) */
+static void update_radiosity_grid_row(int n, int i, const v3* centroid, v3 normal_i, const float* ff_row, const v3* radiosity,
+                                      int enable_filtering, int use_bilateral, float sigma_spatial, float sigma_range, v3* rg) {
+    for (int k = 0; k < GRID_SIZE; k++) rg[k] = V(0.0f, 0.0f, 0.0f);
+    for (int j = 0; j < n; ++j) {
+        if (i == j) continue;
+        const float F_ij = ff_row[j];
+        if (F_ij <= 0.0f) continue;
+        v3 dir_ij = vsub(centroid[j], centroid[i]);
+        const float r = vlen(dir_ij);
+        if (r < 1e-6f) continue;
+        dir_ij = vdivs(dir_ij, r);
+        const int grid_idx = direction_to_grid_index_local(dir_ij, normal_i);
+        rg[grid_idx] = vadd(rg[grid_idx], vscale(F_ij, radiosity[j]));
+    }
+    if (enable_filtering) {
+        v3 tmp[GRID_SIZE];
+        for (int c = 0; c < GRID_SIZE; c++) tmp[c] = filter_cell(rg, c / GRID_RES, c % GRID_RES, use_bilateral, sigma_spatial, sigma_range);
+        memcpy(rg, tmp, sizeof tmp);
+    }
+}
+/* stage hook: the grid update alone, on a world given by centres and normals (n * 3 each), form factors (n * n) and radiosity
+ * (n * 3); out: n * 256 * 3 */
+int po_radiosity_grid_update(int n, const float* centre, const float* normal, const float* form_factors, const float* radiosity,
+                             int enable_filtering, int use_bilateral, float sigma_spatial, float sigma_range, float* out) {
+    if (n < 1 || !centre || !normal || !form_factors || !radiosity || !out) return -1;
+    for (int i = 0; i < n; i++)
+        update_radiosity_grid_row(n, i, (const v3*)centre, V(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]), form_factors + (size_t)i * n,
+                                  (const v3*)radiosity, enable_filtering, use_bilateral, sigma_spatial, sigma_range, (v3*)out + (size_t)i * GRID_SIZE);
+    return 0;
+}
+
 /* rows of the form-factor matrix are independent of each other: a subset, for spot checks at sizes where the whole
  * matrix is too slow on the CPU.  rows: n_rows receiver indices; out_ff n_rows*n, out_grid n_rows*256 (may be NULL) */
 int po_form_factor_rows(const po_scene* sc, const po_radiosity_params* prm, int n_threads, int n_rows, const int* rows,
@@ -1401,27 +1433,9 @@ int po_radiosity_solve(po_scene* sc, const po_radiosity_params* prm, int n_threa
     }
     if (prm->num_iterations > 0) {
 #pragma omp parallel for schedule(dynamic, 4) num_threads(n_threads)
-        for (int i = 0; i < n; i++) {
-            v3* rg = rad_grid + (size_t)i * GRID_SIZE;
-            for (int k = 0; k < GRID_SIZE; k++) rg[k] = V(0.0f, 0.0f, 0.0f);
-            for (int j = 0; j < n; ++j) {
-                if (i == j) continue;
-                const float F_ij = ff[(size_t)i * n + j];
-                if (F_ij <= 0.0f) continue;
-                v3 dir_ij = vsub(centroid[j], centroid[i]);
-                const float r = vlen(dir_ij);
-                if (r < 1e-6f) continue;
-                dir_ij = vdivs(dir_ij, r);
-                const int grid_idx = direction_to_grid_index_local(dir_ij, sc->prims[i].normal);
-                rg[grid_idx] = vadd(rg[grid_idx], vscale(F_ij, radiosity[j]));
-            }
-            if (prm->enable_filtering) {                                            /* application_state.h:759-767 */
-                v3 tmp[GRID_SIZE];
-                for (int c = 0; c < GRID_SIZE; c++)
-                    tmp[c] = filter_cell(rg, c / GRID_RES, c % GRID_RES, prm->use_bilateral, prm->filter_sigma_spatial, prm->filter_sigma_range);
-                memcpy(rg, tmp, sizeof tmp);
-            }
-        }
+        for (int i = 0; i < n; i++)
+            update_radiosity_grid_row(n, i, centroid, sc->prims[i].normal, ff + (size_t)i * n, radiosity, prm->enable_filtering,
+                                      prm->use_bilateral, prm->filter_sigma_spatial, prm->filter_sigma_range, rad_grid + (size_t)i * GRID_SIZE);
     }
     if (out_form_factors) memcpy(out_form_factors, ff, sizeof(float) * (size_t)n * (size_t)n);
     if (out_radiosity) memcpy(out_radiosity, radiosity, sizeof(v3) * (size_t)n);
@@ -1463,21 +1477,41 @@ static void filter_and_normalize(const float* in, float* out, int bilateral, flo
     if (sum <= 1e-12f) return;
     for (int c = 0; c < GRID_SIZE; c++) out[c] = out[c] / sum;
 }
+static void filter_pdfs(int n, const v3* rad_grid, const float* count_grid, int use_bilateral, float sigma_spatial, float sigma_range,
+                        float* ff, float* rad) {
+    for (int p = 0; p < n; p++) {
+        float lum[GRID_SIZE], cnt[GRID_SIZE];
+        for (int c = 0; c < GRID_SIZE; c++) {
+            lum[c] = luminance_from_rgb(rad_grid[(size_t)p * GRID_SIZE + c]);   /* compute_radiosity_luminance_kernel :324-336 */
+            cnt[c] = count_grid ? count_grid[(size_t)p * GRID_SIZE + c] : 0.0f;
+        }
+        filter_and_normalize(cnt, ff + (size_t)p * GRID_SIZE, use_bilateral, sigma_spatial, sigma_range);
+        filter_and_normalize(lum, rad + (size_t)p * GRID_SIZE, use_bilateral, sigma_spatial, sigma_range);
+    }
+}
+/* stage hooks: the filter alone on given rgb (n * 256 * 3) and count grids (n * 256, or NULL = zero), and the records alone
+ * on given pdfs (n * 256; out: n * 530 words) */
+int po_filter_pdfs(int n, const float* rgb, const float* counts, int use_bilateral, float sigma_spatial, float sigma_range,
+                   float* out_formfactor, float* out_radiosity) {
+    if (n < 1 || !rgb || !out_formfactor || !out_radiosity) return -1;
+    filter_pdfs(n, (const v3*)rgb, counts, use_bilateral, sigma_spatial, sigma_range, out_formfactor, out_radiosity);
+    return 0;
+}
+int po_cdf_records(int n, const float* pdfs, float* out) {
+    if (n < 1 || !pdfs || !out) return -1;
+    po_scene s; memset(&s, 0, sizeof s); s.n_prims = n;
+    build_cdf_records(&s, pdfs);
+    memcpy(out, s.cdfs, (size_t)n * sizeof(ocdf));
+    free(s.cdfs);
+    return 0;
+}
 int po_scene_apply_grid_filter(po_scene* s, int use_bilateral, float sigma_spatial, float sigma_range,
                                float* out_formfactor, float* out_radiosity) {
     if (!s || !s->rad_grid) return -1;
     const int n = s->n_prims;
     float* ff = (float*)malloc(sizeof(float) * (size_t)n * GRID_SIZE);
     float* rad = (float*)malloc(sizeof(float) * (size_t)n * GRID_SIZE);
-    for (int p = 0; p < n; p++) {
-        float lum[GRID_SIZE], cnt[GRID_SIZE];
-        for (int c = 0; c < GRID_SIZE; c++) {
-            lum[c] = luminance_from_rgb(s->rad_grid[(size_t)p * GRID_SIZE + c]);   /* compute_radiosity_luminance_kernel :324-336 */
-            cnt[c] = s->count_grid ? s->count_grid[(size_t)p * GRID_SIZE + c] : 0.0f;
-        }
-        filter_and_normalize(cnt, ff + (size_t)p * GRID_SIZE, use_bilateral, sigma_spatial, sigma_range);
-        filter_and_normalize(lum, rad + (size_t)p * GRID_SIZE, use_bilateral, sigma_spatial, sigma_range);
-    }
+    filter_pdfs(n, s->rad_grid, s->count_grid, use_bilateral, sigma_spatial, sigma_range, ff, rad);
     build_cdf_records(s, rad);
     if (out_formfactor) memcpy(out_formfactor, ff, sizeof(float) * (size_t)n * GRID_SIZE);
     if (out_radiosity) memcpy(out_radiosity, rad, sizeof(float) * (size_t)n * GRID_SIZE);

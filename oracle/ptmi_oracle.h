@@ -78,6 +78,11 @@ int po_scene_apply_grid_filter(po_scene*, int use_bilateral, float sigma_spatial
 int po_form_factor_rows(const po_scene*, const po_radiosity_params*, int n_threads, int n_rows, const int* rows,
                         float* out_ff, float* out_grid);
 /* stage hooks for the tests */
+int po_radiosity_grid_update(int n, const float* centre, const float* normal, const float* form_factors, const float* radiosity,
+                             int enable_filtering, int use_bilateral, float sigma_spatial, float sigma_range, float* out /* n*256*3 */);
+int po_filter_pdfs(int n, const float* rgb, const float* counts /* or NULL */, int use_bilateral, float sigma_spatial, float sigma_range,
+                   float* out_formfactor, float* out_radiosity);
+int po_cdf_records(int n, const float* pdfs /* n*256 */, float* out /* n*530 */);
 float po_expf(float x);
 void po_prim_geometry(const po_scene*, int i, float* area, float centroid[3]);
 void po_prim_sample_uniform(const po_scene*, int i, float r1, float r2, float out[3]);

@@ -18,8 +18,11 @@
 // The only restated code is ref_radiance(): render()'s six-line sample loop around integrator() with a free max_depth
 // (render() fixes 5) and the radiance kept before the tone-map.
 //
-// Not reachable here: SceneState::precomputeCDFs lives in application_state.h (GL); the PrecomputedCDF records are the
-// oracle's (po_scene_get_cdfs), whose layout tests/test_oracle_vs_ref.py pins.
+// SceneState::precomputeCDFs itself lives in application_state.h (GL) and is not reachable here, but its arithmetic for the
+// upper hemisphere is Grid::initFromRadiosity / initFromFormFactor + buildCDFs (grid.h:51-134), which leaves its result in
+// public arrays: ref_grid_record() runs it, and tests/test_guided_record_sets_host.py requires the oracle's records
+// (po_scene_get_cdfs, po_cdf_records) to be those, bit for bit, on constructed edge grids.  The records' layout is pinned by
+// tests/test_oracle_vs_ref.py.
 #include <cuda_runtime.h>
 
 #include <algorithm>
@@ -162,6 +165,30 @@ int ref_sample_mis(const float* rec, const float* n, float bsdf_prob, const uint
     put3(out_dir, sampleMIS(g, v3(n), &s, w, bsdf_prob, used));
     *out_weight = w; *out_used_bsdf = used ? 1 : 0;
     return consumed(s);
+}
+
+// ---- records ----
+// Grid::initFromRadiosity (kind 1: 256 rgb triples) or Grid::initFromFormFactor (kind 2: 256 ready pdf values) + buildCDFs
+// (grid.h:51-134) on one grid, copied out in the PrecomputedCDF layout.  buildCDFs fills the upper hemisphere only: the
+// words of row_cdfs[128..255] are returned as zero (application_state.h:560-565 fills them; the tests assert that formula).
+int ref_grid_record(int kind, const float* src, float* out_rec) {
+    if (kind != 1 && kind != 2) return -1;
+    Grid g;
+    if (kind == 1) {
+        std::vector<Vector3f> rgb(GRID_SIZE);
+        for (int c = 0; c < GRID_SIZE; c++) rgb[c] = v3(src + 3 * c);
+        g.initFromRadiosity(rgb.data());
+    } else g.initFromFormFactor(src);
+    PrecomputedCDF rec;
+    std::memset(&rec, 0, sizeof rec);
+    std::memcpy(rec.pdf, g.pdf, sizeof g.pdf);
+    std::memcpy(rec.row_sums, g.row_sums, sizeof g.row_sums);
+    std::memcpy(rec.marginal_cdf, g.marginal_cdf, sizeof g.marginal_cdf);
+    std::memcpy(rec.row_cdfs, g.row_cdfs, sizeof(float) * GRID_HALF_RES * GRID_RES);
+    rec.total_weight = g.total_weight;
+    rec.is_valid = g.isValid() ? 1 : 0;
+    std::memcpy(out_rec, &rec, sizeof rec);
+    return 0;
 }
 
 // ---- scenes ----

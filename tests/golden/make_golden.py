@@ -9,8 +9,9 @@ pin the ORACLE (regression) and give the GPU tests a fixture that does not need 
 
 Run from the repo root:  python tests/golden/make_golden.py
 With --ref-only, only what the compiled reference (oracle/_ref) answers to tests/test_oracle_vs_ref.py,
-tests/test_pbrt_loader.py, tests/test_integrator_vs_ref.py and tests/test_intersect_edge_sets_host.py: golden/ref_geometry.npz,
-golden/ref_pbrt.npz, golden/ref_integrator.npz and golden/ref_intersect_edges.npz.
+tests/test_pbrt_loader.py, tests/test_integrator_vs_ref.py, tests/test_intersect_edge_sets_host.py and
+tests/test_guided_record_sets_host.py: golden/ref_geometry.npz, golden/ref_pbrt.npz, golden/ref_integrator.npz,
+golden/ref_intersect_edges.npz and golden/ref_grid_records.npz.
 """
 import json
 import os
@@ -27,7 +28,8 @@ if "--ref-only" in sys.argv:
     sys.exit(subprocess.call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(os.path.dirname(HERE), "test_oracle_vs_ref.py"),
                              os.path.join(os.path.dirname(HERE), "test_pbrt_loader.py"),
                              os.path.join(os.path.dirname(HERE), "test_integrator_vs_ref.py"),
-                             os.path.join(os.path.dirname(HERE), "test_intersect_edge_sets_host.py")],
+                             os.path.join(os.path.dirname(HERE), "test_intersect_edge_sets_host.py"),
+                             os.path.join(os.path.dirname(HERE), "test_guided_record_sets_host.py")],
                              env=dict(os.environ, PTMI_RECORD_REF_ANSWERS="1")))
 
 CASES = [  # scene, subdivision, convert_quads, W, H, spp, max_depth

@@ -140,6 +140,9 @@ def oracle_lib():
         L.po_visibility_blocked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int]
         L.po_cdf_layout.argtypes = [C.c_void_p]; L.po_cdf_layout.restype = None
         L.po_grid_constants.argtypes = [C.c_void_p]; L.po_grid_constants.restype = None
+        L.po_radiosity_grid_update.argtypes = [C.c_int] + [vp] * 4 + [C.c_int, C.c_int, f, f, vp]
+        L.po_filter_pdfs.argtypes = [C.c_int, vp, vp, C.c_int, f, f, vp, vp]
+        L.po_cdf_records.argtypes = [C.c_int, vp, vp]
         _oracle = L
     return _oracle
 
@@ -309,6 +312,35 @@ def math_batch(op, a, b=None):
     b = np.zeros(n, np.float32) if b is None else np.ascontiguousarray(b, np.float32).reshape(n)
     out = np.zeros((n, 2), np.float64)
     oracle_lib().po_math_batch(int(op), n, a.ctypes.data, b.ctypes.data, out.ctypes.data)
+    return out
+
+
+def oracle_cdf_records(pdfs):
+    """po_cdf_records: the (n, 530) PrecomputedCDF records of (n, 256) pdf values."""
+    pdfs = np.ascontiguousarray(pdfs, np.float32); assert pdfs.ndim == 2 and pdfs.shape[1] == 256
+    out = np.zeros((len(pdfs), 530), np.float32)
+    assert oracle_lib().po_cdf_records(len(pdfs), pdfs.ctypes.data, out.ctypes.data) == 0
+    return out
+
+
+def oracle_filter_pdfs(rgb, counts, use_bilateral, sigma_spatial, sigma_range):
+    """po_filter_pdfs: (formfactor, radiosity) pdfs of rgb (n, 256, 3) and counts (n, 256) or None."""
+    rgb = np.ascontiguousarray(rgb, np.float32); assert rgb.ndim == 3 and rgb.shape[1:] == (256, 3)
+    counts = None if counts is None else np.ascontiguousarray(counts, np.float32)
+    ff = np.zeros(rgb.shape[:2], np.float32); rad = np.zeros(rgb.shape[:2], np.float32)
+    assert oracle_lib().po_filter_pdfs(len(rgb), rgb.ctypes.data, None if counts is None else counts.ctypes.data, int(use_bilateral),
+                                       sigma_spatial, sigma_range, ff.ctypes.data, rad.ctypes.data) == 0
+    return ff, rad
+
+
+def oracle_radiosity_grid(centre, normal, form_factors, radiosity, enable_filtering=False, use_bilateral=True, sigma_spatial=1.5,
+                          sigma_range=0.3):
+    """po_radiosity_grid_update: the (n, 256, 3) grids of a world given by centres, normals, form factors and radiosity."""
+    centre, normal, radiosity, form_factors = (np.ascontiguousarray(a, np.float32) for a in (centre, normal, radiosity, form_factors))
+    n = len(centre); assert form_factors.shape == (n, n)
+    out = np.zeros((n, 256, 3), np.float32)
+    assert oracle_lib().po_radiosity_grid_update(n, centre.ctypes.data, normal.ctypes.data, form_factors.ctypes.data, radiosity.ctypes.data,
+                                                 int(enable_filtering), int(use_bilateral), sigma_spatial, sigma_range, out.ctypes.data) == 0
     return out
 
 
@@ -528,6 +560,8 @@ def ref_int_lib():
         L.ref_render.argtypes = [vp, vp, i, i, i, i, i, vp]
         L.ref_render_radiosity.argtypes = [vp, vp, i, i, i, i, vp]
         L.ref_radiance.argtypes = [vp, vp, i, i, i, i, i, i, vp]
+        if hasattr(L, "ref_grid_record"):
+            L.ref_grid_record.argtypes = [i, vp, vp]
         _ref_int = L
     return _ref_int
 

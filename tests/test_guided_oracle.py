@@ -1,6 +1,9 @@
 """Guided sampling modes in the oracle: properties that need no GPU.
-Parity status: restated from grid.h / integrator.h:91-263 / application_state.h:492-585; like integrator() itself these
-cannot be compiled from the reference here (curand), so they are pinned by inspection and by the properties below."""
+Parity status: restated from grid.h / integrator.h:91-263 / application_state.h:492-585.  What pins them: the sampling
+functions and integrator() against the reference's own, compiled over a stand-in for cuRAND (tests/test_integrator_vs_ref.py);
+the PrecomputedCDF records against the reference's Grid::initFromRadiosity / initFromFormFactor + buildCDFs on constructed edge
+grids, and the filter and the grid update against an independent numpy restatement (tests/test_guided_record_sets_host.py).
+The tests below are the properties that need neither."""
 import numpy as np
 
 from guided_fixtures import synthetic_radiosity_grids

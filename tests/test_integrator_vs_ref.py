@@ -75,7 +75,8 @@ def one_hot(t, p, value=1.0):
 
 
 def grid_cases():
-    """(name, 16 x 16 x 3 radiosity grid).  The records are the oracle's precomputeCDFs of these grids."""
+    """(name, 16 x 16 x 3 radiosity grid).  The records are the oracle's precomputeCDFs of these grids, which
+    tests/test_guided_record_sets_host.py pins to the reference's own Grid::initFromRadiosity + buildCDFs."""
     rng = np.random.default_rng(5)
     smooth = synthetic_radiosity_grids(1, seed=3, empty_every=0)[0].reshape(16, 16, 3)
     ties = np.ones((16, 16, 3), F)                                   # marginal k/8, rows (u+1)/16: exact binary fractions
