@@ -55,16 +55,22 @@ inline bool is_guided(const BounceArgs& a) { return a.fp.sampling_mode != 0 && a
 // place where a kernel that walks with intersect_sweep gets its records, the bounce kernel and the test hook alike - and, between
 // the primitives and the materials, the frame block of fp / tm (frame_block.h: ptmi_sweep_lds_vecs vectors in all; the hook, which
 // has no frame, passes none and leaves the block's place unwritten).  The block is at mats - PTMI_FRAME_BLOCK_VECS: frame_block_of(mats).
-template <bool LDS_GEOM, bool SWEEP_RECORDS = false>
+// SWEEP_FORM: the form of the walk that will read the records (traversal.h: sweep_form) - with SWEEP_NEAR_FAR the nodes are the
+// near/far records of sweep_near_far.h, 4 vectors each (ptmi_sweep_near_far_lds_vecs vectors in all), otherwise 2 each.
+template <bool LDS_GEOM, bool SWEEP_RECORDS = false, int SWEEP_FORM = 0>
 __device__ __forceinline__ float4* stage_scene(const DeviceScene& sc, float4* lds, const float4*& nodes, const float4*& prims, const float4*& mats,
                                                const FrameParams* fp = nullptr, const TileMap* tm = nullptr) {
     static_assert(LDS_GEOM || !SWEEP_RECORDS, "the sweep's records exist in LDS only");
+    static_assert(SWEEP_RECORDS || SWEEP_FORM == 0, "a form belongs to the sweep's records");
+    constexpr bool NEAR_FAR = (SWEEP_FORM & SWEEP_NEAR_FAR) != 0;
     nodes = sc.nodes; prims = sc.prims; mats = sc.mats;
     if (LDS_GEOM) {
-        const int n_node_vec = 2 * sc.n_nodes, n_prim_vec = sc.prim_stride * sc.n_prims, n_mat_vec = 3 * sc.n_prims;
+        const int n_node_vec = sweep_node_vecs(SWEEP_FORM) * sc.n_nodes, n_prim_vec = sc.prim_stride * sc.n_prims, n_mat_vec = 3 * sc.n_prims;
         const int mats_at = n_node_vec + n_prim_vec + (SWEEP_RECORDS ? PTMI_FRAME_BLOCK_VECS : 0);
         if (SWEEP_RECORDS) {
-            ptmi_sweep_prepare(reinterpret_cast<const ptmi_vec_bits*>(sc.nodes), sc.n_nodes, reinterpret_cast<const ptmi_vec_bits*>(sc.prims),
+            if (NEAR_FAR) ptmi_sweep_near_far_prepare(reinterpret_cast<const ptmi_vec_bits*>(sc.nodes), sc.n_nodes, reinterpret_cast<ptmi_vec_bits*>(lds),
+                                                      lds_address(lds), (int)threadIdx.x, kBlock);
+            ptmi_sweep_prepare(reinterpret_cast<const ptmi_vec_bits*>(sc.nodes), NEAR_FAR ? 0 : sc.n_nodes, reinterpret_cast<const ptmi_vec_bits*>(sc.prims),
                                sc.prim_stride, sc.n_prims, reinterpret_cast<ptmi_vec_bits*>(lds), reinterpret_cast<ptmi_vec_bits*>(lds + n_node_vec),
                                lds_address(lds), (int)threadIdx.x, kBlock);
             if (fp && threadIdx.x == kBlock - 1)      // one lane of the last wave: the first waves have the most records to prepare

@@ -17,9 +17,10 @@ __global__ __launch_bounds__(kBlock) void ptmi_debug_intersect_k(DeviceScene sc,
                                                                  float t_max, int* hit, int* prim, float* t_out, float* p_out, float* n_out) {
     extern __shared__ float4 smem[];
     int* stack = reinterpret_cast<int*>(smem) + threadIdx.x;
-    // SWEEP walks the records ptmi_bounce's sweep walks: staged by the same stage_scene (LANE and STACK read global memory here)
+    // SWEEP walks the records ptmi_bounce's sweep walks, in the timed build's form: staged by the same stage_scene (LANE and STACK
+    // read global memory here)
     const float4 *nodes, *prims, *mats;
-    stage_scene<MODE == TRAVERSAL_SWEEP, MODE == TRAVERSAL_SWEEP>(sc, smem, nodes, prims, mats);
+    stage_scene<MODE == TRAVERSAL_SWEEP, MODE == TRAVERSAL_SWEEP, MODE == TRAVERSAL_SWEEP ? sweep_form<HAS_QUADS, false, false>() : 0>(sc, smem, nodes, prims, mats);
     const int i = blockIdx.x * kBlock + threadIdx.x;
     const bool live = i < n;
     const int j = live ? i : 0;

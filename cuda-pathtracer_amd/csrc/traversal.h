@@ -4,6 +4,7 @@
 #pragma once
 #include "pt_device.h"
 #include "sweep_records.h"
+#include "sweep_near_far.h"
 #include "wide_walk.h"
 
 namespace ptmi {
@@ -22,6 +23,19 @@ __device__ __forceinline__ bool box_hit(const float4& n0, const float4& n1, f3 o
     float t0z = (n0.z - o.z) * inv.z, t1z = (n1.z - o.z) * inv.z;
     if (inv.z < 0.0f) { const float tmp = t0z; t0z = t1z; t1z = tmp; }
     // max/min are associative and NaN-ignoring, so folding the three axes in one max3/min3 keeps the reference's result
+    const float tmin_box = max3_raw(max_raw(t0x, t_min), t0y, t0z);
+    const float tmax_box = min3_raw(min_raw(t1x, closest_t), t1y, t1z);
+    return !(tmax_box < tmin_box);
+}
+
+// box_hit over a near/far node record (sweep_near_far.h): bx = (near, far) along x as this lane read it, at the offset its
+// inv.x < 0.0f chose - (lo, hi), or (hi, lo) where box_hit would have swapped the two products.  The plane the swap would have
+// put into a place is the one read into it, by the same predicate, so t0* and t1* have box_hit's bits for every input (a +-0,
+// denormal or non-finite inv included) and the two folds are box_hit's own.
+__device__ __forceinline__ bool box_hit_near_far(float2 bx, float2 by, float2 bz, f3 o, f3 inv, float t_min, float closest_t) {
+    const float t0x = (bx.x - o.x) * inv.x, t1x = (bx.y - o.x) * inv.x;
+    const float t0y = (by.x - o.y) * inv.y, t1y = (by.y - o.y) * inv.y;
+    const float t0z = (bz.x - o.z) * inv.z, t1z = (bz.y - o.z) * inv.z;
     const float tmin_box = max3_raw(max_raw(t0x, t_min), t0y, t0z);
     const float tmax_box = min3_raw(min_raw(t1x, closest_t), t1y, t1z);
     return !(tmax_box < tmin_box);
@@ -154,15 +168,15 @@ __device__ __forceinline__ bool intersect_lane(const float4* __restrict__ nodes,
 // never serialise against each other.  The wave pays for the UNION of its lanes' visits, so this is used only for scenes of a
 // few dozen primitives.  Must be called from wave-uniform control flow (dead lanes pass live = false).
 //
-// The walk reads the sweep's own records (sweep_records.h, staged by stage_scene<true, true>) and keeps no books beside them.
+// The walk reads the sweep's own records (sweep_records.h, sweep_near_far.h; staged by stage_scene<true, true, form>) and keeps no books beside them.
 // In every instantiation the cursor is the LDS ADDRESS of a node record and is itself the address of the two reads (an address
 // that all active lanes share is a broadcast read; it stays a per-lane VGPR, pinned, or the optimiser would rebuild it from the
-// scalar trip address with a move per pass).  "Stands at this record" is a compare against the scalar address, "next" is + 32, a
+// scalar trip address with a move per pass).  "Stands at this record" is a compare against the scalar address, "next" is + the record's size, a
 // miss at an interior node is one select of the record's skip lane, which staging has turned into an address.  The trip count is
 // scalar and bounded by n_nodes, whatever a cursor holds.  Only the leaf flag / count and the leaf's first slot go through
 // readfirstlane (scalar branch, scalar loop bound, scalar address arithmetic).  The primitive stride is a constant of the
 // instantiation: 3 float4 without quads, 4 with (SceneState::chooseTraversal refuses any other).
-// Four more items, each taken by the instantiations it costs no wave per SIMD and no spill (sweep_form below):
+// Five more items, each taken by the instantiations it costs no wave per SIMD and no spill (sweep_form below):
 //   SWEEP_ONE_SELECT    the cursor's update is one select ahead of the leaf branch; without it, inside the two branches;
 //   SWEEP_VOTED_UPDATE  closest_t and slot_hit change only behind the (a, u) vote (mt_accept_update below); without it
 //                       mt_accept / mt_candidate and the selects after them, as leaf_prim has them.  Either way the slot comes
@@ -171,14 +185,27 @@ __device__ __forceinline__ bool intersect_lane(const float4* __restrict__ nodes,
 //   SWEEP_LEAF_BASE     a leaf's primitives are read at immediate offsets from one VGPR that holds the address of the leaf's
 //                       first record, kSweepLeafUnroll per trip of a loop whose bound is the record's count; without it one
 //                       address per primitive, from the scalar one.
+//   SWEEP_NEAR_FAR      the node records are the 64-byte near/far records of sweep_near_far.h and the cursor strides by 64: each
+//                       lane reads (near, far) of an axis - 8 bytes - at the record's address + the axis group + 8 where its
+//                       1 / d is negative, three offsets fixed per ray and pinned in VGPRs, and the two w lanes from a fourth
+//                       pair; box_hit_near_far has no swap.  Per pass three v_add_u32 and four ds_read_b64 (the lanes of one
+//                       read use at most two addresses, 8 bytes apart) for six v_cndmask by SGPR lane masks and two
+//                       ds_read_b128.  The predicate that chose the read is box_hit's own, so the plane box_hit would have
+//                       swapped into a place after the multiplication is the one read into it before: t0* and t1* keep their
+//                       bits for every input, a +-0, denormal or non-finite 1 / d included.
 // No expression of the slab test or of Moller-Trumbore differs from the walks above, and none is reordered.
 //
 // VALU instructions per pass in ptmi_bounce<SWEEP, ..., triangles, timed build> (ISA, before -> after): interior node 31 -> 27,
 // Moller-Trumbore first half 34 + 3 after it -> 32, second half 28 -> 30 (it holds the two selects now), per leaf 3 -> 2; the
 // quad build's node pass 31 -> 28, its primitive passes as before.  MI355X, parent's library against this one, three runs each,
 // alternating: c2 7 667 -> 8 046 Msamples/s (+4.9 %, 35.01 -> 33.36 ms per step), c3 15 935 -> 16 417 (+3.0 %); the parent's
-// runs lie within 0.3 % of each other.  EXPERIMENTS.md has the runs and the counters.
-enum : int { SWEEP_VOTED_UPDATE = 1, SWEEP_PINNED = 2, SWEEP_LEAF_BASE = 4, SWEEP_ONE_SELECT = 8 };
+// runs lie within 0.3 % of each other.  With SWEEP_NEAR_FAR on top of that, the timed triangle build's interior node pass 27 -> 24,
+// none of the slab test's with an SGPR mask, the same protocol: c2 8 248 -> 8 393 Msamples/s (+1.75 %, 32.55 -> 31.98 ms per step),
+// every run above every run of the parent, whose runs lie within 0.45 % of each other; c4 9 454 -> 9 702 (+2.6 %, one pair); 52
+// fewer VALU wave-instructions per wave-segment, 37 more LDS instructions, the LDS's busy cycles unchanged, its bank conflicts
+// up 0.3 - 0.4 % (16.9 -> 17.0 cycles per wave-segment), a little beyond the parent's run-to-run difference of 0.24 %.
+// EXPERIMENTS.md has the runs and the counters.
+enum : int { SWEEP_VOTED_UPDATE = 1, SWEEP_PINNED = 2, SWEEP_LEAF_BASE = 4, SWEEP_ONE_SELECT = 8, SWEEP_NEAR_FAR = 16 };
 constexpr int kSweepLeafUnroll = 4;
 
 // The form of each instantiation, judged by registers, waves per SIMD and spills against the walk before these items (DESIGN.md
@@ -186,8 +213,16 @@ constexpr int kSweepLeafUnroll = 4;
 // GUIDED ones stay at their cap of 80).  The quad builds stand at 63-64 VGPRs with two Moller-Trumbore halves per record: with
 // any one of the four the BATCH build starts to spill (2-9 VGPRs) and the plain one loses a wave or spills, so they keep
 // leaf_prim's form on the new cursor, which leaves both without spills at 8 waves (63 and 64 VGPRs).
-template <bool HAS_QUADS>
-constexpr int sweep_form() { return HAS_QUADS ? 0 : (SWEEP_ONE_SELECT | SWEEP_VOTED_UPDATE | SWEEP_PINNED | SWEEP_LEAF_BASE); }
+// SWEEP_NEAR_FAR holds three more VGPRs through the walk.  The triangle builds without STATS and GUIDED have them: 58 -> 61 and,
+// BATCH, 59 -> 62, 8 waves, no scratch.  With STATS the plain build would go 64 -> 67 and lose a wave and the BATCH one spill 12
+// bytes; the quad builds (64 VGPRs) spill 8-12 bytes, and with the three offsets packed into one VGPR they keep 64 / 8 / 0 but
+// c3 ran 1.8 % slower (EXPERIMENTS.md); the GUIDED builds stand at their cap.  Those keep the two-vector records.
+template <bool HAS_QUADS, bool STATS, bool GUIDED>
+constexpr int sweep_form() {
+    return HAS_QUADS ? 0 : ((SWEEP_ONE_SELECT | SWEEP_VOTED_UPDATE | SWEEP_PINNED | SWEEP_LEAF_BASE) | (!STATS && !GUIDED ? SWEEP_NEAR_FAR : 0));
+}
+// 16-byte vectors per node record in the LDS image of a form (stage_scene lays them out, the walk strides by them)
+constexpr int sweep_node_vecs(int form) { return (form & SWEEP_NEAR_FAR) ? PTMI_SWEEP_NF_NODE_VECS : 2; }
 
 // mt_accept (pt_device.h) in the sweep's form: the same arithmetic with the closer-hit update of scene.h:89-96 behind the vote,
 // so that a primitive whose (a, u) test rejects the whole wave costs no select at all and t needs no initial value.  `slot` arrives in a
@@ -227,6 +262,16 @@ __device__ __forceinline__ float4 lds_vec(unsigned int address, int i) {
     return make_float4(v.x, v.y, v.z, v.w);
 #else
     return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#endif
+}
+// the i-th pair of floats (8 bytes) from such an address
+__device__ __forceinline__ float2 lds_pair(unsigned int address, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef float vec2 __attribute__((ext_vector_type(2)));
+    const vec2 v = reinterpret_cast<const __attribute__((address_space(3))) vec2*>(address)[i];
+    return make_float2(v.x, v.y);
+#else
+    return make_float2(0.0f, 0.0f);
 #endif
 }
 
@@ -275,20 +320,46 @@ __device__ __forceinline__ bool intersect_sweep(const float4* nodes, const float
         asm("" : "+v"(eps));
         if (HAS_QUADS) asm("" : "+v"(eps_up));
     }
-    const unsigned int first = lds_address(nodes), end = first + (unsigned int)n_nodes * PTMI_SWEEP_NODE_BYTES;
+    constexpr bool NEAR_FAR = (FORM & SWEEP_NEAR_FAR) != 0;
+    constexpr unsigned int kNodeBytes = sweep_node_vecs(FORM) * PTMI_SWEEP_VEC_BYTES;
+    unsigned int far_x = 0, far_y = 0, far_z = 0;             // NEAR_FAR: where in an axis group this lane's (near, far) stands
+    if constexpr (NEAR_FAR) {
+        far_x = inv.x < 0.0f ? PTMI_SWEEP_NF_FAR_FIRST : 0;   // box_hit's own predicates
+        far_y = inv.y < 0.0f ? PTMI_SWEEP_NF_FAR_FIRST : 0;
+        far_z = inv.z < 0.0f ? PTMI_SWEEP_NF_FAR_FIRST : 0;
+        asm("" : "+v"(far_x));
+        asm("" : "+v"(far_y));
+        asm("" : "+v"(far_z));
+    }
+    const unsigned int first = lds_address(nodes), end = first + (unsigned int)n_nodes * kNodeBytes;
     const unsigned int prims_at = lds_address(prims);
     unsigned int cur = live ? first : end;
-    for (unsigned int at = first; at < end; at += PTMI_SWEEP_NODE_BYTES) {
+    for (unsigned int at = first; at < end; at += kNodeBytes) {
         if (cur == at) {
             unsigned int here = cur;
             asm("" : "+v"(here));
-            const float4 n0 = lds_vec(here, 0), n1 = lds_vec(here, 1);
-            if (STATS) cn.node_visits++;
-            const int b = __builtin_amdgcn_readfirstlane(__float_as_int(n1.w));   // wave-uniform: >= 0 interior, < 0 leaf of -b
-            const bool pass = box_hit(n0, n1, o, inv, t_min, closest_t);
-            const unsigned int next = here + PTMI_SWEEP_NODE_BYTES, skip = __float_as_uint(n0.w);
+            float w0, w1;                                         // the record's two w lanes
+            int b;                                                // wave-uniform: >= 0 interior, < 0 leaf of -b
+            bool pass;
+            const auto leaf_flag = [&]() {                        // between the reads and the slab test in either form
+                if (STATS) cn.node_visits++;
+                b = __builtin_amdgcn_readfirstlane(__float_as_int(w1));
+            };
+            if constexpr (NEAR_FAR) {                             // (near, far) along each axis for this lane's ray
+                const float2 bx = lds_pair(here + far_x, 0), by = lds_pair(here + far_y, 2), bz = lds_pair(here + far_z, 4);
+                const float2 w = lds_pair(here, 6);
+                w0 = w.x; w1 = w.y;
+                leaf_flag();
+                pass = box_hit_near_far(bx, by, bz, o, inv, t_min, closest_t);
+            } else {
+                const float4 n0 = lds_vec(here, 0), n1 = lds_vec(here, 1);
+                w0 = n0.w; w1 = n1.w;
+                leaf_flag();
+                pass = box_hit(n0, n1, o, inv, t_min, closest_t);
+            }
+            const unsigned int next = here + kNodeBytes, skip = __float_as_uint(w0);
             const auto leaf_pass = [&]() {                       // the lanes whose ray meets the leaf's box test its -b primitives
-                const unsigned int leaf = prims_at + (unsigned int)__builtin_amdgcn_readfirstlane(__float_as_int(n0.w)) * kPrimBytes;
+                const unsigned int leaf = prims_at + (unsigned int)__builtin_amdgcn_readfirstlane(__float_as_int(w0)) * kPrimBytes;
                 if constexpr ((FORM & SWEEP_LEAF_BASE) != 0) {
                     unsigned int rec = leaf;
                     asm("" : "+v"(rec));
@@ -325,11 +396,12 @@ __device__ __forceinline__ bool intersect_sweep(const float4* nodes, const float
     return slot_hit >= 0;
 }
 
-template <int MODE, bool HAS_QUADS, bool STATS>
+// GUIDED: only the sweep's form depends on it (sweep_form); the caller stages the records of that form
+template <int MODE, bool HAS_QUADS, bool STATS, bool GUIDED = false>
 __device__ __forceinline__ bool scene_intersect(const float4* __restrict__ nodes, const float4* __restrict__ prims, int prim_stride,
                                                 int n_nodes, int* stack, bool live, f3 o, f3 d, float t_min, float t_max,
                                                 float& t_hit, int& slot_hit, LaneCounters& cn) {
-    if (MODE == TRAVERSAL_SWEEP) return intersect_sweep<HAS_QUADS, STATS, sweep_form<HAS_QUADS>()>(nodes, prims, n_nodes, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
+    if (MODE == TRAVERSAL_SWEEP) return intersect_sweep<HAS_QUADS, STATS, sweep_form<HAS_QUADS, STATS, GUIDED>()>(nodes, prims, n_nodes, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
     if (MODE == TRAVERSAL_LANE) return intersect_lane<HAS_QUADS, STATS>(nodes, prims, prim_stride, n_nodes, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
     return intersect_stack<HAS_QUADS, STATS>(nodes, prims, prim_stride, stack, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
 }

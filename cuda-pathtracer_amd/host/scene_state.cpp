@@ -1,5 +1,6 @@
 // scene_state.cpp — SceneState: host loading, the emitter table, upload, and the packed / fast layouts
 #include "application_state.h"
+#include "../csrc/sweep_near_far.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -727,11 +728,13 @@ void SceneState::chooseTraversal() {
     // PHASED: measured faster than the segment-synchronous LANE walk from 128 primitives up (LDS-resident or not); PACKED: the
     // phased walk over the packed layout of scenes too large for LDS; LANE stays available through the override
     if (force_traversal >= 0 && !(force_traversal != TRAVERSAL_STACK && bvh_depth > 62)) d_scene.traversal = force_traversal;
-    if (d_scene.traversal == TRAVERSAL_SWEEP && !d_scene.lds_resident) d_scene.traversal = TRAVERSAL_LANE;   // the sweep reads through LDS
+    // the sweep reads through LDS, and its image - near/far node records, frame block (csrc/kernels.hip: bounce_lds_bytes) - is the larger one
+    const bool sweep_fits = d_scene.lds_resident && ptmi_sweep_near_far_lds_vecs(d_scene.n_nodes, d_scene.prim_stride, d_scene.n_prims) * sizeof(float4) <= 64 * 1024;
+    if (d_scene.traversal == TRAVERSAL_SWEEP && !sweep_fits) d_scene.traversal = TRAVERSAL_LANE;
     if (d_scene.traversal == TRAVERSAL_PACKED && !d_scene.gnodes) d_scene.traversal = TRAVERSAL_PHASED;
     // CERTIFIED needs the fast tree and the ancestor lists (triangle scenes of depth <= 62); otherwise the exact walk it stands for
     if (d_scene.traversal == TRAVERSAL_CERTIFIED && !d_scene.certified_ready())
-        d_scene.traversal = (int)h_primitives.size() <= sweep_max_prims && d_scene.lds_resident ? TRAVERSAL_SWEEP : (d_scene.gnodes ? TRAVERSAL_PACKED : TRAVERSAL_PHASED);
+        d_scene.traversal = (int)h_primitives.size() <= sweep_max_prims && sweep_fits ? TRAVERSAL_SWEEP : (d_scene.gnodes ? TRAVERSAL_PACKED : TRAVERSAL_PHASED);
     // the sweep's kernels have the primitive stride as a constant of the instantiation (traversal.h: intersect_sweep)
     if (d_scene.traversal == TRAVERSAL_SWEEP && d_scene.prim_stride != (d_scene.has_quads ? 4 : 3))
         throw ArgError("internal: the sweep reads 3 float4 per primitive without quads and 4 with");
