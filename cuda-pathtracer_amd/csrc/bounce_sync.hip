@@ -3,7 +3,8 @@
 #include "bounce.h"
 
 // experiment libraries (make ab-lib DEFS=-DPTMI_SWEEP_LATE=0 / -DPTMI_SWEEP_FRAME_BLOCK=0): the sweep's shade step as it was,
-// shade_step; shade_step_sweep with the camera from kernel arguments
+// shade_step; shade_step_sweep with the camera from kernel arguments.  The walk's own switches, -DPTMI_SWEEP_MASKED_HIT=0 and
+// -DPTMI_SWEEP_MASKED_CURSOR=0, stand beside sweep_form in traversal.h, which the intersect hook reads too
 #ifndef PTMI_SWEEP_FRAME_BLOCK
 #define PTMI_SWEEP_FRAME_BLOCK 1
 #endif

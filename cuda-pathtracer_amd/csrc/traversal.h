@@ -193,6 +193,15 @@ __device__ __forceinline__ bool intersect_lane(const float4* __restrict__ nodes,
 //                       ds_read_b128.  The predicate that chose the read is box_hit's own, so the plane box_hit would have
 //                       swapped into a place after the multiplication is the one read into it before: t0* and t1* keep their
 //                       bits for every input, a +-0, denormal or non-finite 1 / d included.
+// Two more, taken by the builds that take SWEEP_NEAR_FAR, replace a select (half rate) by a move (full rate) under a narrowed EXEC:
+//   SWEEP_MASKED_HIT    mt_accept_update writes closest_t and slot_hit in a branch on the accept mask, (m >= 0) & (t < closest_t)
+//                       as before: s_and_saveexec, two v_mov_b32, s_or exec for two v_cndmask.  A lane that does not accept is
+//                       not written at all, where the select copied its value into itself;
+//   SWEEP_MASKED_CURSOR every lane of a node pass takes here + 64, then the lanes that miss an interior node take the skip
+//                       address in a branch on (b >= 0) & !pass: one v_mov_b32 for the v_cndmask by an SGPR mask.
+//                       The leaf branch keeps its place and its mask.
+// An empty asm volatile in each branch keeps it a branch (the optimiser would make the selects again); the compiler leaves an
+// s_cbranch_execz in front of such a block, taken when no lane of the pass accepts / misses.
 // No expression of the slab test or of Moller-Trumbore differs from the walks above, and none is reordered.
 //
 // VALU instructions per pass in ptmi_bounce<SWEEP, ..., triangles, timed build> (ISA, before -> after): interior node 31 -> 27,
@@ -204,9 +213,26 @@ __device__ __forceinline__ bool intersect_lane(const float4* __restrict__ nodes,
 // every run above every run of the parent, whose runs lie within 0.45 % of each other; c4 9 454 -> 9 702 (+2.6 %, one pair); 52
 // fewer VALU wave-instructions per wave-segment, 37 more LDS instructions, the LDS's busy cycles unchanged, its bank conflicts
 // up 0.3 - 0.4 % (16.9 -> 17.0 cycles per wave-segment), a little beyond the parent's run-to-run difference of 0.24 %.
+// With the two masked moves on top of that the counts per pass stay - interior node 24 VALU, one of them the cursor's v_mov_b32
+// where the v_cndmask was; second half 30, two v_mov_b32 where its two v_cndmask were - and each masked block adds
+// s_and_saveexec, s_cbranch_execz and s_or exec; 61 -> 60 VGPRs and, BATCH, 62 -> 61.  The same protocol: c2 8 321 -> 8 437
+// Msamples/s (+1.4 %, 32.26 -> 31.82 ms per step), every run above every run of the parent, whose runs lie within 0.19 % of each
+// other; each move alone, two runs: the hit's 8 379 and 8 445, the cursor's 8 386 and 8 403; c4 9 751 -> 9 873 (+1.2 %, one pair).
+// A third item, keeping s = o - v0 from one triangle test to the next where two records of a leaf share v0, is not built: in
+// cbox.obj 2 of 32 records follow a record with the same v0 in their leaf (tests/test_sweep_shared_s_host.py).
 // EXPERIMENTS.md has the runs and the counters.
-enum : int { SWEEP_VOTED_UPDATE = 1, SWEEP_PINNED = 2, SWEEP_LEAF_BASE = 4, SWEEP_ONE_SELECT = 8, SWEEP_NEAR_FAR = 16 };
+enum : int { SWEEP_VOTED_UPDATE = 1, SWEEP_PINNED = 2, SWEEP_LEAF_BASE = 4, SWEEP_ONE_SELECT = 8, SWEEP_NEAR_FAR = 16, SWEEP_MASKED_HIT = 32, SWEEP_MASKED_CURSOR = 64 };
 constexpr int kSweepLeafUnroll = 4;
+
+// experiment libraries (make ab-lib DEFS="-DPTMI_SWEEP_MASKED_HIT=0 -DPTMI_SWEEP_MASKED_CURSOR=0"): the builds that take
+// SWEEP_NEAR_FAR without one or both of the masked moves.  Here and not beside bounce_sync.hip's switches: the intersect hook
+// (debug_hooks.hip) takes the timed build's form from sweep_form too.
+#ifndef PTMI_SWEEP_MASKED_HIT
+#define PTMI_SWEEP_MASKED_HIT 1
+#endif
+#ifndef PTMI_SWEEP_MASKED_CURSOR
+#define PTMI_SWEEP_MASKED_CURSOR 1
+#endif
 
 // The form of each instantiation, judged by registers, waves per SIMD and spills against the walk before these items (DESIGN.md
 // 5 has the table).  The triangle builds take all four: 55-60 -> 59-64 VGPRs, 8 waves per SIMD and no spill as before (the
@@ -217,9 +243,12 @@ constexpr int kSweepLeafUnroll = 4;
 // BATCH, 59 -> 62, 8 waves, no scratch.  With STATS the plain build would go 64 -> 67 and lose a wave and the BATCH one spill 12
 // bytes; the quad builds (64 VGPRs) spill 8-12 bytes, and with the three offsets packed into one VGPR they keep 64 / 8 / 0 but
 // c3 ran 1.8 % slower (EXPERIMENTS.md); the GUIDED builds stand at their cap.  Those keep the two-vector records.
+// SWEEP_MASKED_HIT and SWEEP_MASKED_CURSOR go to the builds that take SWEEP_NEAR_FAR, which give a VGPR back with them (61 -> 60,
+// BATCH 62 -> 61); every other build is the code it was, byte for byte.
 template <bool HAS_QUADS, bool STATS, bool GUIDED>
 constexpr int sweep_form() {
-    return HAS_QUADS ? 0 : ((SWEEP_ONE_SELECT | SWEEP_VOTED_UPDATE | SWEEP_PINNED | SWEEP_LEAF_BASE) | (!STATS && !GUIDED ? SWEEP_NEAR_FAR : 0));
+    constexpr int timed = SWEEP_NEAR_FAR | (PTMI_SWEEP_MASKED_HIT ? SWEEP_MASKED_HIT : 0) | (PTMI_SWEEP_MASKED_CURSOR ? SWEEP_MASKED_CURSOR : 0);
+    return HAS_QUADS ? 0 : ((SWEEP_ONE_SELECT | SWEEP_VOTED_UPDATE | SWEEP_PINNED | SWEEP_LEAF_BASE) | (!STATS && !GUIDED ? timed : 0));
 }
 // 16-byte vectors per node record in the LDS image of a form (stage_scene lays them out, the walk strides by them)
 constexpr int sweep_node_vecs(int form) { return (form & SWEEP_NEAR_FAR) ? PTMI_SWEEP_NF_NODE_VECS : 2; }
@@ -229,6 +258,7 @@ constexpr int sweep_node_vecs(int form) { return (form & SWEEP_NEAR_FAR) ? PTMI_
 // VGPR (the record's slot lane).  A quad half is the same call with eps_for_a = nextafter(eps): mt_candidate's +inf, the min chain
 // and `t < closest_t` of leaf_prim select exactly as (m >= 0) & (t < closest_t) does half by half - min_raw(+inf or a NaN t,
 // closest_t) is closest_t, a half updates iff its t is below the closest so far, and the second half sees the first's result.
+template <bool MASKED = false>
 __device__ __forceinline__ void mt_accept_update(f3 v0, f3 edge1, f3 edge2, f3 o, f3 d, float eps_for_a, float t_lo, int slot,
                                                  float& closest_t, int& slot_hit) {
     const f3 h = cross(d, edge2);
@@ -244,8 +274,16 @@ __device__ __forceinline__ void mt_accept_update(f3 v0, f3 edge1, f3 edge2, f3 o
     float m = min3_raw(m1, v, 1.0f - (u + v));
     m = min_raw(m, t - t_lo);
     const bool acc = (m >= 0.0f) & (t < closest_t);
-    closest_t = acc ? t : closest_t;
-    slot_hit = acc ? slot : slot_hit;
+    if constexpr (MASKED) {
+        if (acc) {                                     // the accepting lanes alone: EXEC narrowed around two moves
+            closest_t = t;
+            slot_hit = slot;
+            asm volatile("" : "+v"(closest_t), "+v"(slot_hit));      // or the optimiser turns the branch back into two selects
+        }
+    } else {
+        closest_t = acc ? t : closest_t;
+        slot_hit = acc ? slot : slot_hit;
+    }
 }
 // LDS by address: the 32-bit address of p, and the i-th float4 from such an address (the host pass only parses them)
 __device__ __forceinline__ unsigned int lds_address(const void* p) {
@@ -297,7 +335,7 @@ __device__ __forceinline__ void leaf_prim_sweep(unsigned int rec, int at, f3 o, 
             slot_hit = closer ? slot : slot_hit;
         }
     } else if (VOTED) {
-        mt_accept_update(xyz(p0), xyz(p1), xyz(p2), o, d, eps, t_lo, slot, closest_t, slot_hit);            // !(|a| < eps)
+        mt_accept_update<(FORM & SWEEP_MASKED_HIT) != 0>(xyz(p0), xyz(p1), xyz(p2), o, d, eps, t_lo, slot, closest_t, slot_hit);            // !(|a| < eps)
     } else {
         float tt = 0.0f;
         const bool acc = mt_accept(xyz(p0), xyz(p1), xyz(p2), o, d, eps, t_lo, closest_t, tt);
@@ -381,7 +419,14 @@ __device__ __forceinline__ bool intersect_sweep(const float4* nodes, const float
                     }
                 }
             };
-            if constexpr ((FORM & SWEEP_ONE_SELECT) != 0) {
+            if constexpr ((FORM & SWEEP_MASKED_CURSOR) != 0) {
+                cur = next;
+                if ((b >= 0) & !pass) {                          // the lanes that miss an interior node: EXEC narrowed around one move
+                    cur = skip;
+                    asm volatile("" : "+v"(cur));                // or the optimiser turns the branch back into a select
+                }
+                if (b < 0 && pass) leaf_pass();
+            } else if constexpr ((FORM & SWEEP_ONE_SELECT) != 0) {
                 cur = ((b >= 0) & !pass) ? skip : next;
                 if (b < 0 && pass) leaf_pass();
             } else if (b < 0) {
