@@ -1091,11 +1091,14 @@ static void integrator(const po_scene* sc, ray_t ray, v3* L, int max_depth, uint
 /* ------------------------------------------------------------------------ */
 /* the radiosity pre-pass.  RadiosityState::runSolver            */
 /* (application_state.h:688-777) and its kernels (form_factors.h:71-467,       */
-/* grid_filter.h:35-312).  Restated; form_factors.h/grid_filter.h include      */
-/* <cuda_runtime.h>/<curand_kernel.h> and cannot be compiled here, so this part */
-/* is pinned only through the pieces that live in primitive.h (area, centroid, */
-/* sampleUniform: checked against the compiled reference in                    */
-/* tests/test_oracle_vs_ref.py) and by properties (tests/test_radiosity_solver).*/
+/* grid_filter.h:35-507).  Restated, and pinned stage by stage against the     */
+/* reference's own form_factors.h / grid_filter.h compiled on the host         */
+/* (oracle/ref_solver_harness.cpp, tests/test_solver_vs_ref.py): grid index,    */
+/* visibility, seeding, Monte-Carlo pairs on scripted draws, rows of both      */
+/* kernels, the grid update, the Jacobi step, every filter, subdivision and     */
+/* whole solves, bit for bit.  Only runSolver's launch sequence (GL header)    */
+/* stays restated on both sides; convertQuadsToTriangles and precomputeCDFs     */
+/* stay behind GL too.                                                          */
 /*                                                                            */
 /* Two places where the reference is not a function of its inputs:            */
 /*  - radiosity_iteration_kernel (form_factors.h:441-465) reads unshot_rad of  */
@@ -1200,10 +1203,19 @@ int po_visibility_blocked(const po_scene* sc, const float o[3], const float d[3]
 
 typedef struct { const float* area; const v3* centroid; const v3* radiosity; } solver_geom;
 
+/* the pair's draws: the stream formfactor_rand_init seeds, or (test hook po_form_factor_mc_pair_words) caller-supplied raw
+ * words mapped as curand_uniform maps them; a draw past the end of the script sets overrun and gives 1.0f */
+typedef struct { uint32_t st[6]; const uint32_t* script; int n_script, used, overrun; } ff_rng;
+static inline float ff_draw(ff_rng* g) {
+    if (!g->script) { g->used++; return rng_uniform(g->st); }
+    if (g->used >= g->n_script) { g->overrun = 1; return 1.0f; }
+    return (float)g->script[g->used++] * 2.3283064e-10f + (2.3283064e-10f / 2.0f);
+}
+
 /* form_factors.h:219-366 calculate_form_factors_mc_kernel, one (i, j) pair; adds the pair's partial sums to row i's
- * grids; returns F_ij */
+ * grids; returns F_ij.  scripted: NULL, or the draws to use in place of the pair's stream */
 static float form_factor_mc_pair(const po_scene* sc, const solver_geom* g, int i, int j, int n_samples,
-                                 float* grid_i, v3* rad_grid_i, uint64_t* rays) {
+                                 float* grid_i, v3* rad_grid_i, uint64_t* rays, ff_rng* scripted) {
     const int num_primitives = sc->n_prims;
     const int ff_idx = i * num_primitives + j;
     if (i == j) return 0.0f;
@@ -1223,16 +1235,19 @@ static float form_factor_mc_pair(const po_scene* sc, const solver_geom* g, int i
     if (approx_ff < 0.001f) actual_samples = n_samples / 4 > 1 ? n_samples / 4 : 1;
     else if (approx_ff < 0.01f) actual_samples = n_samples / 2 > 2 ? n_samples / 2 : 2;
 
-    uint32_t local_state[6];
-    po_rng_init(12345u + (uint64_t)(int64_t)ff_idx, (uint64_t)(int64_t)ff_idx, local_state);   /* :85-89 formfactor_rand_init */
+    ff_rng stream; ff_rng* local_state = scripted ? scripted : &stream;
+    if (!scripted) {
+        memset(&stream, 0, sizeof stream);
+        po_rng_init(12345u + (uint64_t)(int64_t)ff_idx, (uint64_t)(int64_t)ff_idx, stream.st);   /* :85-89 formfactor_rand_init */
+    }
     float visibility_sum = 0.0f, cos_i_sum = 0.0f, cos_j_sum = 0.0f, dist_sum = 0.0f;
     int valid_samples = 0;
     float local_grid[GRID_SIZE]; v3 local_rad_grid[GRID_SIZE];
     for (int k = 0; k < GRID_SIZE; k++) { local_grid[k] = 0.0f; local_rad_grid[k] = V(0.0f, 0.0f, 0.0f); }
     for (int s = 0; s < actual_samples; ++s) {
-        float r1 = rng_uniform(local_state), r2 = rng_uniform(local_state);
+        float r1 = ff_draw(local_state), r2 = ff_draw(local_state);
         const v3 p_i = prim_sample_uniform(prim_i, r1, r2);
-        r1 = rng_uniform(local_state); r2 = rng_uniform(local_state);
+        r1 = ff_draw(local_state); r2 = ff_draw(local_state);
         const v3 p_j = prim_sample_uniform(prim_j, r1, r2);
         v3 sample_dir = vsub(p_j, p_i);
         const float r = vlen(sample_dir);
@@ -1369,12 +1384,34 @@ int po_form_factor_rows(const po_scene* sc, const po_radiosity_params* prm, int 
         float grid[GRID_SIZE]; v3 rad_grid[GRID_SIZE]; uint64_t rays = 0;
         memset(grid, 0, sizeof grid); memset(rad_grid, 0, sizeof rad_grid);
         for (int j = 0; j < n; j++)
-            out_ff[(size_t)r * n + j] = prm->use_monte_carlo ? form_factor_mc_pair(sc, &g, i, j, prm->mc_samples, grid, rad_grid, &rays)
+            out_ff[(size_t)r * n + j] = prm->use_monte_carlo ? form_factor_mc_pair(sc, &g, i, j, prm->mc_samples, grid, rad_grid, &rays, NULL)
                                                              : form_factor_p2p_pair(sc, &g, i, j, &rays);
         if (out_grid) memcpy(out_grid + (size_t)r * GRID_SIZE, grid, sizeof grid);
     }
     free(area); free(centroid); free(radiosity);
     return 0;
+}
+
+/* test hook: one (i, j) pair of the Monte-Carlo kernel on scripted raw words, with radiosity = Le and empty grids as
+ * runSolver leaves them before the kernel.  out_grid 256, out_rad_grid 256 * 3: receiver i's grids after this pair alone.
+ * Returns the words drawn; *out_overrun is set where the script ran out. */
+int po_form_factor_mc_pair_words(const po_scene* sc, int i, int j, int n_samples, const uint32_t* words, int n_words, float* out_F,
+                                 float* out_grid, float* out_rad_grid, int* out_overrun) {
+    if (!sc || i < 0 || j < 0 || i >= sc->n_prims || j >= sc->n_prims || n_samples < 1 || !words || !out_F || !out_grid || !out_rad_grid) return -1;
+    const int n = sc->n_prims;
+    float* area = (float*)malloc(sizeof(float) * (size_t)n);
+    v3* centroid = (v3*)malloc(sizeof(v3) * (size_t)n);
+    v3* radiosity = (v3*)malloc(sizeof(v3) * (size_t)n);
+    for (int k = 0; k < n; k++) { area[k] = prim_area(&sc->prims[k]); centroid[k] = prim_centroid(&sc->prims[k]); radiosity[k] = sc->prims[k].Le; }
+    const solver_geom g = { area, centroid, radiosity };
+    ff_rng script; memset(&script, 0, sizeof script);
+    script.script = words; script.n_script = n_words;
+    uint64_t rays = 0;
+    memset(out_grid, 0, sizeof(float) * GRID_SIZE); memset(out_rad_grid, 0, sizeof(v3) * GRID_SIZE);
+    *out_F = form_factor_mc_pair(sc, &g, i, j, n_samples, out_grid, (v3*)out_rad_grid, &rays, &script);
+    if (out_overrun) *out_overrun = script.overrun;
+    free(area); free(centroid); free(radiosity);
+    return script.used;
 }
 
 int po_radiosity_solve(po_scene* sc, const po_radiosity_params* prm, int n_threads, float* out_form_factors,
@@ -1406,7 +1443,7 @@ int po_radiosity_solve(po_scene* sc, const po_radiosity_params* prm, int n_threa
         uint64_t rays = 0;
         for (int j = 0; j < n; j++)
             ff[(size_t)i * n + j] = prm->use_monte_carlo
-                ? form_factor_mc_pair(sc, &g, i, j, prm->mc_samples, grid + (size_t)i * GRID_SIZE, rad_grid + (size_t)i * GRID_SIZE, &rays)
+                ? form_factor_mc_pair(sc, &g, i, j, prm->mc_samples, grid + (size_t)i * GRID_SIZE, rad_grid + (size_t)i * GRID_SIZE, &rays, NULL)
                 : form_factor_p2p_pair(sc, &g, i, j, &rays);
         rays_total += rays;
     }

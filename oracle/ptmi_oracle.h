@@ -83,6 +83,10 @@ int po_radiosity_grid_update(int n, const float* centre, const float* normal, co
 int po_filter_pdfs(int n, const float* rgb, const float* counts /* or NULL */, int use_bilateral, float sigma_spatial, float sigma_range,
                    float* out_formfactor, float* out_radiosity);
 int po_cdf_records(int n, const float* pdfs /* n*256 */, float* out /* n*530 */);
+/* one (i, j) pair of the Monte-Carlo form-factor kernel on scripted raw 32-bit words (tests/test_solver_vs_ref.py): F_ij,
+ * receiver i's count grid (256) and radiosity grid (256*3) after this pair alone; returns the words drawn */
+int po_form_factor_mc_pair_words(const po_scene*, int i, int j, int n_samples, const uint32_t* words, int n_words, float* out_F,
+                                 float* out_grid, float* out_rad_grid, int* out_overrun);
 float po_expf(float x);
 void po_prim_geometry(const po_scene*, int i, float* area, float centroid[3]);
 void po_prim_sample_uniform(const po_scene*, int i, float r1, float r2, float out[3]);

@@ -14,9 +14,11 @@
 // utils/file_manager.h (loadOBJ / loadMTL) is compiled too, in ref_obj_harness.cpp: it needs <cuda_runtime.h>, and
 // NVIDIA's genuine header ships in this image's Triton wheel (oracle/Makefile finds it).
 // rendering/grid.h and integrator.h are compiled in ref_integrator_harness.cpp, against NVIDIA's genuine <cuda_runtime.h> and
-// a project-written stand-in for the closed <curand_kernel.h> API (oracle/shim/).  What is NOT compilable here:
-// rendering/form_factors.h includes rendering/grid_filter.h, which launches kernels with <<< >>> from host wrappers (no
-// g++ can parse it); application_state.h includes GL/glew.h and GLFW.  Those are restated in ptmi_oracle.c only.
+// a project-written stand-in for the closed <curand_kernel.h> API (oracle/shim/).  rendering/form_factors.h and
+// rendering/grid_filter.h are compiled in ref_solver_harness.cpp against the same two headers; grid_filter.h's host wrappers
+// launch kernels with <<< >>>, which no g++ can parse, so oracle/delaunch.py rewrites those statements - and nothing else -
+// in a temporary copy outside the repository.  What is NOT compilable here: application_state.h includes GL/glew.h and GLFW,
+// so runSolver's launch sequence, convertQuadsToTriangles and precomputeCDFs are restated only.
 #include <hip/amd_detail/host_defines.h>
 
 #include <cfloat>

@@ -9,9 +9,9 @@
 //
 // What this pins: loadOBJ + loadMTL, end to end, on any .obj file - primitive type, vertices, stored normal, Kd ("bsdf"),
 // Ke ("Le"), the accept/reject decision, and (through the returned count) every skipped-token and default-material rule.
-// What it cannot pin: convertQuadsToTriangles lives in application_state.h (GL, GLFW and cuRAND headers) and
-// subdivide_primitives in form_factors.h (<curand_kernel.h>: not in that directory, a closed NVIDIA library) - those stay
-// pinned through the constructors they call (ref_harness.cpp) and the survey's known answers.
+// What it cannot pin: convertQuadsToTriangles lives in application_state.h (GL, GLFW and cuRAND headers) and stays pinned
+// through the constructors it calls (ref_harness.cpp) and the survey's known answers.  subdivide_primitives (form_factors.h)
+// is compiled and pinned in ref_solver_harness.cpp.
 #include <cuda_runtime.h>
 
 #include <cfloat>

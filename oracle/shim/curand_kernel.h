@@ -1,6 +1,7 @@
 // curand_kernel.h — project-written stand-in for the part of NVIDIA's closed cuRAND device API that the reference's
-// integrator.h and grid.h call: curandState, curand_init, curand_uniform.  TEST INFRASTRUCTURE ONLY: it is found on the
-// include path of oracle/ref_integrator_harness.cpp and nowhere else.  It restates nothing of the reference.
+// integrator.h, grid.h and form_factors.h call: curandState, curand_init, curand_uniform.  TEST INFRASTRUCTURE ONLY: it is
+// found on the include paths of oracle/ref_integrator_harness.cpp and oracle/ref_solver_harness.cpp and nowhere else.  It
+// restates nothing of the reference.
 //
 // Two modes, chosen per state:
 //   stream   (script == nullptr): curand_init(seed, subsequence, 0) is the oracle's po_rng_init and curand_uniform the
@@ -30,7 +31,7 @@ static inline float ptmi_shim_word_to_uniform(uint32_t x) { return (float)x * 0x
 
 static inline void curand_init(unsigned long long seed, unsigned long long subsequence, unsigned long long offset,
                                curandState* state) {
-    (void)offset;   // 0 at every call site of the reference (integrator.h render_init)
+    (void)offset;   // 0 at every call site of the reference (integrator.h render_init, form_factors.h formfactor_rand_init)
     po_rng_init(seed, subsequence, state->s);
     state->script = nullptr;
     state->n_script = state->used = state->overrun = 0;

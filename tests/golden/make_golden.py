@@ -4,14 +4,17 @@ Provenance: the oracle (oracle/ptmi_oracle.c) is a restatement whose geometry la
 against the reference's own headers compiled from /root/reference (tests/test_oracle_vs_ref.py) and whose
 loader/BVH/camera are checked against the known answers in SURVEY.md §8c; the integrator, the guided sampling and
 the tone-map are checked against the reference's own integrator.h / grid.h compiled with a stand-in for the closed
-cuRAND API (tests/test_integrator_vs_ref.py); cuRAND's seed scramble and float mapping stay unpinned.  These files
+cuRAND API (tests/test_integrator_vs_ref.py); the radiosity pre-pass - form factors, Jacobi step, grids, filters, subdivision -
+is checked against the reference's own form_factors.h / grid_filter.h compiled the same way (tests/test_solver_vs_ref.py), so the
+solver_*.npz files below are the oracle's output of code that is pinned stage by stage; only runSolver's launch sequence,
+convertQuadsToTriangles and precomputeCDFs (GL headers) remain restated.  cuRAND's seed scramble and float mapping stay unpinned.  These files
 pin the ORACLE (regression) and give the GPU tests a fixture that does not need the oracle library.
 
 Run from the repo root:  python tests/golden/make_golden.py
 With --ref-only, only what the compiled reference (oracle/_ref) answers to tests/test_oracle_vs_ref.py,
-tests/test_pbrt_loader.py, tests/test_integrator_vs_ref.py, tests/test_intersect_edge_sets_host.py and
-tests/test_guided_record_sets_host.py: golden/ref_geometry.npz, golden/ref_pbrt.npz, golden/ref_integrator.npz,
-golden/ref_intersect_edges.npz and golden/ref_grid_records.npz.
+tests/test_pbrt_loader.py, tests/test_integrator_vs_ref.py, tests/test_intersect_edge_sets_host.py,
+tests/test_guided_record_sets_host.py and tests/test_solver_vs_ref.py: golden/ref_geometry.npz, golden/ref_pbrt.npz,
+golden/ref_integrator.npz, golden/ref_intersect_edges.npz, golden/ref_grid_records.npz and golden/ref_solver.npz.
 """
 import json
 import os
@@ -29,7 +32,8 @@ if "--ref-only" in sys.argv:
                              os.path.join(os.path.dirname(HERE), "test_pbrt_loader.py"),
                              os.path.join(os.path.dirname(HERE), "test_integrator_vs_ref.py"),
                              os.path.join(os.path.dirname(HERE), "test_intersect_edge_sets_host.py"),
-                             os.path.join(os.path.dirname(HERE), "test_guided_record_sets_host.py")],
+                             os.path.join(os.path.dirname(HERE), "test_guided_record_sets_host.py"),
+                             os.path.join(os.path.dirname(HERE), "test_solver_vs_ref.py")],
                              env=dict(os.environ, PTMI_RECORD_REF_ANSWERS="1")))
 
 CASES = [  # scene, subdivision, convert_quads, W, H, spp, max_depth

@@ -3,6 +3,7 @@
 oracle/libptmi_oracle.so  - plain-C CPU restatement (ptmi_oracle.c)
 oracle/_ref/libptmi_ref.so - the reference's own geometry headers compiled from
                              /root/reference (present only where it was built)
+oracle/_ref/libptmi_ref_solver.so - the reference's radiosity pre-pass (ref_solver_harness.cpp), likewise
 """
 import ctypes as C
 import hashlib
@@ -143,6 +144,7 @@ def oracle_lib():
         L.po_radiosity_grid_update.argtypes = [C.c_int] + [vp] * 4 + [C.c_int, C.c_int, f, f, vp]
         L.po_filter_pdfs.argtypes = [C.c_int, vp, vp, C.c_int, f, f, vp, vp]
         L.po_cdf_records.argtypes = [C.c_int, vp, vp]
+        L.po_form_factor_mc_pair_words.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
         _oracle = L
     return _oracle
 
@@ -261,6 +263,15 @@ class OracleScene:
         if rc != 0:
             raise RuntimeError(f"po_form_factor_rows failed: {rc}")
         return ff, grid
+
+    def mc_pair_words(self, i, j, n_samples, words):
+        """po_form_factor_mc_pair_words: dict(F, grid (256), rad_grid (256, 3), used, overrun) of pair (i, j) on scripted raw words."""
+        w = np.ascontiguousarray(words, np.uint32)
+        F = C.c_float(); over = C.c_int(); grid = np.zeros(256, np.float32); rg = np.zeros((256, 3), np.float32)
+        used = self.L.po_form_factor_mc_pair_words(self.h, int(i), int(j), int(n_samples), w.ctypes.data, len(w), C.addressof(F),
+                                                   grid.ctypes.data, rg.ctypes.data, C.addressof(over))
+        assert used >= 0
+        return dict(F=np.float32(F.value), grid=grid, rad_grid=rg, used=np.int32(used), overrun=np.int32(over.value))
 
     def prim_geometry(self, i):
         a = C.c_float(0); c = np.zeros(3, np.float32)
@@ -605,3 +616,150 @@ class RefIntegratorScene:
         rad = np.zeros((height, width, 3), np.float32)
         self.L.ref_radiance(self.h, _camera13(cam).ctypes.data, width, height, spp, max_depth, int(mode), n_threads, rad.ctypes.data)
         return rad
+
+
+# ---- the reference's form_factors.h + grid_filter.h, compiled (oracle/_ref/libptmi_ref_solver.so; oracle/ref_solver_harness.cpp) ----
+REF_SOL_SO = os.path.join(os.path.dirname(REF_SO), "libptmi_ref_solver.so")
+_ref_sol = None
+
+
+def ref_sol_available():
+    return os.path.exists(REF_SOL_SO)
+
+
+def ref_sol_lib():
+    global _ref_sol
+    if _ref_sol is None:
+        L = C.CDLL(REF_SOL_SO)
+        vp, f, i = C.c_void_p, C.c_float, C.c_int
+        L.ref_sol_scene_create.restype = vp; L.ref_sol_scene_create.argtypes = [i] + [vp] * 5
+        L.ref_sol_scene_free.argtypes = [vp]; L.ref_sol_scene_free.restype = None
+        L.ref_sol_scene_num_prims.argtypes = [vp]
+        L.ref_sol_scene_get_prims.argtypes = [vp] * 6; L.ref_sol_scene_get_prims.restype = None
+        L.ref_sol_grid_index.argtypes = [vp, vp]
+        L.ref_sol_visibility.argtypes = [vp, i, i] + [vp] * 6; L.ref_sol_visibility.restype = None
+        L.ref_sol_rand_init.argtypes = [i, i, vp, vp]; L.ref_sol_rand_init.restype = None
+        L.ref_sol_ff_rows.argtypes = [vp, i, i, i, vp, vp, vp, vp]
+        L.ref_sol_mc_pair.argtypes = [vp, i, i, i, vp, i, vp, vp, vp, vp]
+        L.ref_sol_update_grid.argtypes = [vp] * 4; L.ref_sol_update_grid.restype = None
+        L.ref_sol_iterate.argtypes = [vp] * 6; L.ref_sol_iterate.restype = None
+        L.ref_sol_solve.argtypes = [vp, i, i, i, i, i, f, f] + [vp] * 5
+        L.ref_sol_filter_grids.argtypes = [i, vp, i, f, f, vp]; L.ref_sol_filter_grids.restype = None
+        L.ref_sol_filter_pdfs.argtypes = [i, vp, vp, i, f, f, vp, vp]; L.ref_sol_filter_pdfs.restype = None
+        L.ref_sol_subdivide.restype = vp; L.ref_sol_subdivide.argtypes = [vp, i]
+        _ref_sol = L
+    return _ref_sol
+
+
+def ref_sol_grid_index(dirs, normals):
+    """direction_to_grid_indices_local per call: theta * 16 + phi of each (direction, normal) row."""
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3); n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    L = ref_sol_lib()
+    return np.array([L.ref_sol_grid_index(d[k].ctypes.data, n[k].ctypes.data) for k in range(len(d))], np.int32)
+
+
+def ref_sol_rand_init(num_pairs, idx):
+    idx = np.ascontiguousarray(idx, np.int32); out = np.zeros((len(idx), 6), np.uint32)
+    ref_sol_lib().ref_sol_rand_init(int(num_pairs), len(idx), idx.ctypes.data, out.ctypes.data)
+    return out
+
+
+def ref_sol_filter_grids(rgb, use_bilateral, sigma_spatial, sigma_range):
+    rgb = np.ascontiguousarray(rgb, np.float32); assert rgb.ndim == 3 and rgb.shape[1:] == (256, 3)
+    out = np.zeros_like(rgb)
+    ref_sol_lib().ref_sol_filter_grids(len(rgb), rgb.ctypes.data, int(use_bilateral), sigma_spatial, sigma_range, out.ctypes.data)
+    return out
+
+
+def ref_sol_filter_pdfs(rgb, counts, use_bilateral, sigma_spatial, sigma_range):
+    rgb = np.ascontiguousarray(rgb, np.float32); assert rgb.ndim == 3 and rgb.shape[1:] == (256, 3)
+    counts = None if counts is None else np.ascontiguousarray(counts, np.float32)
+    ff = np.zeros(rgb.shape[:2], np.float32); rad = np.zeros(rgb.shape[:2], np.float32)
+    ref_sol_lib().ref_sol_filter_pdfs(len(rgb), rgb.ctypes.data, None if counts is None else counts.ctypes.data, int(use_bilateral),
+                                      sigma_spatial, sigma_range, ff.ctypes.data, rad.ctypes.data)
+    return ff, rad
+
+
+class RefSolverScene:
+    """The reference's Primitive[] + BVHBuilder tree, fed from arrays, under the reference's own solver kernels."""
+
+    def __init__(self, types=None, verts=None, normal=None, bsdf=None, Le=None, handle=None):
+        self.L = ref_sol_lib()
+        if handle is not None:
+            self.h = handle; return
+        types = np.ascontiguousarray(types, np.int32)
+        verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 4, 3)
+        normal, bsdf, Le = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (normal, bsdf, Le))
+        self.h = self.L.ref_sol_scene_create(len(types), types.ctypes.data, verts.ctypes.data, normal.ctypes.data, bsdf.ctypes.data,
+                                             Le.ctypes.data)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.ref_sol_scene_free(self.h)
+            self.h = None
+
+    @property
+    def n(self):
+        return self.L.ref_sol_scene_num_prims(self.h)
+
+    def prims(self):
+        n = self.n
+        t = np.zeros(n, np.int32); v = np.zeros((n, 4, 3), np.float32)
+        nr = np.zeros((n, 3), np.float32); b = np.zeros((n, 3), np.float32); le = np.zeros((n, 3), np.float32)
+        self.L.ref_sol_scene_get_prims(self.h, t.ctypes.data, v.ctypes.data, nr.ctypes.data, b.ctypes.data, le.ctypes.data)
+        return dict(type=t, verts=v, normal=nr, bsdf=b, Le=le)
+
+    def visibility(self, o, d, max_dist, source, target, use_bvh=True):
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3); d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        m = len(o)
+        md = np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, np.float32), (m,)))
+        src = np.ascontiguousarray(np.broadcast_to(np.asarray(source, np.int32), (m,)))
+        tgt = np.ascontiguousarray(np.broadcast_to(np.asarray(target, np.int32), (m,)))
+        out = np.zeros(m, np.int32)
+        self.L.ref_sol_visibility(self.h, int(use_bvh), m, o.ctypes.data, d.ctypes.data, md.ctypes.data, src.ctypes.data, tgt.ctypes.data,
+                                  out.ctypes.data)
+        return out
+
+    def ff_rows(self, rows, use_monte_carlo=True, mc_samples=64):
+        rows = np.ascontiguousarray(rows, np.int32); n = self.n
+        ff = np.zeros((len(rows), n), np.float32); grid = np.zeros((len(rows), 256), np.float32); rg = np.zeros((len(rows), 256, 3), np.float32)
+        rc = self.L.ref_sol_ff_rows(self.h, int(use_monte_carlo), int(mc_samples), len(rows), rows.ctypes.data, ff.ctypes.data,
+                                    grid.ctypes.data, rg.ctypes.data)
+        assert rc == 0
+        return ff, grid, rg
+
+    def mc_pair_words(self, i, j, n_samples, words):
+        w = np.ascontiguousarray(words, np.uint32)
+        F = C.c_float(); over = C.c_int(); grid = np.zeros(256, np.float32); rg = np.zeros((256, 3), np.float32)
+        used = self.L.ref_sol_mc_pair(self.h, int(i), int(j), int(n_samples), w.ctypes.data, len(w), C.addressof(F), grid.ctypes.data,
+                                      rg.ctypes.data, C.addressof(over))
+        return dict(F=np.float32(F.value), grid=grid, rad_grid=rg, used=np.int32(used), overrun=np.int32(over.value))
+
+    def update_grid(self, form_factors, radiosity):
+        n = self.n
+        ff = np.ascontiguousarray(form_factors, np.float32); rad = np.ascontiguousarray(radiosity, np.float32)
+        assert ff.shape == (n, n) and rad.shape == (n, 3)
+        out = np.zeros((n, 256, 3), np.float32)
+        self.L.ref_sol_update_grid(self.h, ff.ctypes.data, rad.ctypes.data, out.ctypes.data)
+        return out
+
+    def iterate(self, form_factors, radiosity, unshot):
+        n = self.n
+        ff, rad, un = (np.ascontiguousarray(a, np.float32) for a in (form_factors, radiosity, unshot))
+        assert ff.shape == (n, n) and rad.shape == (n, 3) and un.shape == (n, 3)
+        o_rad = np.zeros((n, 3), np.float32); o_un = np.zeros((n, 3), np.float32)
+        self.L.ref_sol_iterate(self.h, ff.ctypes.data, rad.ctypes.data, un.ctypes.data, o_rad.ctypes.data, o_un.ctypes.data)
+        return o_rad, o_un
+
+    def solve(self, **params):
+        p = RadiosityParams(**params); n = self.n
+        out = dict(form_factors=np.zeros((n, n), np.float32), radiosity=np.zeros((n, 3), np.float32), unshot=np.zeros((n, 3), np.float32),
+                   grid=np.zeros((n, 256), np.float32), radiosity_grid=np.zeros((n, 256, 3), np.float32))
+        rc = self.L.ref_sol_solve(self.h, p.num_iterations, p.mc_samples, p.use_monte_carlo, p.enable_filtering, p.use_bilateral,
+                                  p.filter_sigma_spatial, p.filter_sigma_range, *(out[k].ctypes.data for k in
+                                  ("form_factors", "radiosity", "unshot", "grid", "radiosity_grid")))
+        assert rc == 0
+        return out
+
+    def subdivide(self, levels):
+        return RefSolverScene(handle=self.L.ref_sol_subdivide(self.h, int(levels)))

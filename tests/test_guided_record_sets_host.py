@@ -1,8 +1,8 @@
 """The constructed sets of tests/guided_record_sets.py, proved on the host: every label sits on the edge it names, the oracle's
 C (oracle/ptmi_oracle.c) equals the REFERENCE's own Grid::initFromRadiosity / initFromFormFactor + buildCDFs (compiled into
 oracle/_ref/libptmi_ref_integrator.so; its answers are recorded in tests/golden/ref_grid_records.npz) on every record case, the
-oracle's C equals the numpy restatement on every filter and grid-update case (the reference's filter and grid update hold kernel
-launches and cannot be compiled on the host: two independent restatements must agree instead), the float32 restatements stay
+oracle's C equals the numpy restatement on every filter and grid-update case (two independent restatements; the reference's own
+filter and grid update, compiled, answer the same worlds and a subset of the filter cases in tests/test_solver_vs_ref.py), the float32 restatements stay
 within a measured bound of the same formulas in binary64, and each mutant of the kernels' arithmetic changes a named case.
 
 Re-record (where oracle/_ref is built):  python tests/golden/make_golden.py --ref-only

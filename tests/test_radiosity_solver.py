@@ -1,6 +1,6 @@
 """The radiosity pre-pass: RadiosityState::runSolver (application_state.h:688-777), form_factors.h,
-grid_filter.h.  CPU: properties of the oracle's restatement (form_factors.h cannot be compiled here; the primitive.h
-pieces it uses are pinned in test_oracle_vs_ref.py).  GPU: the HIP solver against the oracle, bit for bit - except the
+grid_filter.h.  CPU: properties of the oracle's restatement (its bits are pinned to the compiled reference in
+tests/test_solver_vs_ref.py).  GPU: the HIP solver against the oracle, bit for bit - except the
 num_iterations == 0 radiosity grid, which the reference itself accumulates with float atomics in arbitrary order."""
 import json
 import os
