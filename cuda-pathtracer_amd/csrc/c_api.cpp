@@ -1500,6 +1500,30 @@ int ptmi_denoise_temporal(ptmi_ctx* c, const ptmi_denoise_params* params) {
     });
 }
 
+// ---- the history's luminance statistics and the variance-guided filter steered by them ----
+static_assert(PTMI_TEMPORAL_MIN_FRAMES == kTemporalMinFrames, "the header's constant is the kernel's");
+int ptmi_set_temporal_moments(ptmi_ctx* c, int on) {
+    return guarded([&] { need(c != nullptr, "ctx is NULL"); setTemporalMoments(c->app, on); });
+}
+int ptmi_get_temporal_moments(const ptmi_ctx* c, int* on) {
+    return guarded([&] { need(c && on, "NULL argument"); *on = c->app.temporal_moments; });
+}
+int ptmi_read_temporal_moments(const ptmi_ctx* c, float* mean, float* variance, float* frames) {
+    return guarded([&] { need(c != nullptr, "ctx is NULL"); readTemporalMoments(c->app, mean, variance, frames); });
+}
+int ptmi_denoise_temporal_variance(ptmi_ctx* c, const ptmi_variance_params* params) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        ptmi_variance_params p;
+        ptmi_default_variance_params(&p);
+        denoiseTemporalVariance(c->app, variance_params_from(params ? *params : p));
+    });
+}
+// test hook: the statistics of the history's current side, given instead of accumulated
+int ptmi_debug_set_temporal_moments(ptmi_ctx* c, const float* mean, const float* variance, const float* frames) {
+    return guarded([&] { need(c && mean && variance && frames, "NULL argument"); debugSetTemporalMoments(c->app, mean, variance, frames); });
+}
+
 // ---- test hook: the filters' inputs, given instead of rendered ----
 int ptmi_debug_set_filter_inputs(ptmi_ctx* c, const float* radiance, const float* albedo, const float* normal, const float* position,
                                  const float* hit_fraction, int grid) {

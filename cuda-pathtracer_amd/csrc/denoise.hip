@@ -162,14 +162,15 @@ void launch_denoise(const DenoiseArgs& a, const FeatureBuffers& fb, const float*
 
 void launch_denoise_variance(const VarianceArgs& a, const FeatureBuffers& fb, const float* radiance, const TileMap& tm,
                              const AccumBuffers* moments, const unsigned int* counts, int iterations, float4* buf, float* var_in,
-                             float* var_out, unsigned char* out_rgb8, float* out_radiance, hipEvent_t estimated, hipStream_t s) {
+                             float* var_out, unsigned char* out_rgb8, float* out_radiance, hipEvent_t estimated, hipStream_t s,
+                             const TemporalVariance* temporal) {
     const int n = a.width * a.height;
     if (n <= 0) { (void)hipEventRecord(estimated, s); return; }
     const dim3 grid1((n + kBlock - 1) / kBlock), block1(kBlock);
     const dim3 grid2((a.width + kTileX - 1) / kTileX, (a.height + kTileY - 1) / kTileY), block2(kTileX * kTileY);
     float4* ping[2] = {buf, buf + n};
     hipLaunchKernelGGL(ptmi_denoise_demod, grid1, block1, 0, s, n, radiance, fb.albedo, a.demodulate, ping[0]);
-    launch_variance_estimate(a, fb, radiance, tm, moments, counts, ping[0], ping[1], var_in, s);
+    launch_variance_estimate(a, fb, radiance, tm, moments, counts, ping[0], ping[1], var_in, s, temporal);
     (void)hipEventRecord(estimated, s);
     for (int i = 0; i < iterations; i++)                              // (c, v) starts in ping[1]
         hipLaunchKernelGGL(ptmi_variance_atrous, grid2, block2, 0, s, a, fb, 1 << i, ping[(i + 1) & 1], ping[i & 1]);

@@ -38,6 +38,6 @@ __device__ __forceinline__ float denoise_wx(const float4 xp, const float4 xq, fl
 // -> (c.xyz, v) in `out` and v in var_in
 void launch_variance_estimate(const VarianceArgs& a, const FeatureBuffers& fb, const float* radiance, const TileMap& tm,
                               const AccumBuffers* moments, const unsigned int* counts, const float4* in, float4* out, float* var_in,
-                              hipStream_t s);
+                              hipStream_t s, const TemporalVariance* temporal = nullptr);
 
 }  // namespace ptmi

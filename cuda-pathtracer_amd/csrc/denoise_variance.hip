@@ -5,6 +5,7 @@
 //
 // Kernels
 //   ptmi_variance_moments  the accumulation's variance of the pixels with two passes or more (one thread per slot) -> (c.xyz, v)
+//   ptmi_variance_temporal the history's variance of the pixels with PTMI_TEMPORAL_MIN_FRAMES frames or more -> (c.xyz, v), and the mask
 //   ptmi_variance_spatial  every other pixel: the weighted variance of the luminance over a (2r + 1)^2 window -> (c.xyz, v)
 //   ptmi_pass_moments      mean, M2 and pass count of the stopping test, by slot -> local row-major (ptmi_read_pass_moments)
 // One thread per pixel in every kernel; nothing but the staged tile of ptmi_variance_spatial is shared between threads, and that
@@ -30,6 +31,29 @@ __global__ __launch_bounds__(kBlock) void ptmi_variance_moments(TileMap tm, Accu
     const float4 c = in[p];
     float v = fmaxf(0.0f, ab.m2[slot] / (float)(k * (k - 1u)));
     const float lr_ = denoise_lum(radiance[3 * p], radiance[3 * p + 1], radiance[3 * p + 2]);
+    if (lr_ > 0.0f) {
+        const float s = denoise_lum(c.x, c.y, c.z) / lr_;
+        v = (v * s) * s;
+    }
+    var_in[p] = v;
+    out[p] = make_float4(c.x, c.y, c.z, v);
+}
+
+// ptmi_denoise_temporal_variance's step 2: the variance of the mean of the k frames behind a pixel of the history, from the
+// history's luminance statistics (mu, s2, k, 0), in the filtered signal's units.  mask: 1 where this kernel owns the pixel (k >=
+// kTemporalMinFrames; a NaN k fails the test), else 0 - ptmi_variance_spatial takes it as its counts with two_spp = 1.
+__global__ __launch_bounds__(kBlock) void ptmi_variance_temporal(int n, const float4* __restrict__ moments, const float* __restrict__ radiance,
+                                                                 const float4* __restrict__ in, float4* __restrict__ out,
+                                                                 float* __restrict__ var_in, unsigned int* __restrict__ mask) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const float4 mo = moments[p];
+    const bool own = mo.z >= kTemporalMinFrames;
+    mask[p] = own ? 1u : 0u;
+    if (!own) return;                                                 // the spatial estimate's pixel
+    const float4 c = in[p];
+    float v = fmaxf(0.0f, mo.y / (mo.z - 1.0f));
+    const float lr_ = denoise_lum(radiance[3 * (size_t)p], radiance[3 * (size_t)p + 1], radiance[3 * (size_t)p + 2]);
     if (lr_ > 0.0f) {
         const float s = denoise_lum(c.x, c.y, c.z) / lr_;
         v = (v * s) * s;
@@ -120,12 +144,14 @@ __global__ __launch_bounds__(kBlock) void ptmi_pass_moments(TileMap tm, AccumBuf
 
 void launch_variance_estimate(const VarianceArgs& a, const FeatureBuffers& fb, const float* radiance, const TileMap& tm,
                               const AccumBuffers* moments, const unsigned int* counts, const float4* in, float4* out, float* var_in,
-                              hipStream_t s) {
+                              hipStream_t s, const TemporalVariance* temporal) {
     const int n = a.width * a.height;
     const dim3 grid1((n + kBlock - 1) / kBlock), block1(kBlock);
     const dim3 grid2((a.width + kTileX - 1) / kTileX, (a.height + kTileY - 1) / kTileY), block2(kTileX * kTileY);
-    if (moments) hipLaunchKernelGGL(ptmi_variance_moments, grid1, block1, 0, s, tm, *moments, radiance, in, out, var_in);
-    const unsigned int* skip = moments ? counts : nullptr;
+    const bool history = temporal && temporal->source == 0;           // the third route (a.two_spp is 1 there: the mask is 0 / 1)
+    if (history) hipLaunchKernelGGL(ptmi_variance_temporal, grid1, block1, 0, s, n, temporal->moments, radiance, in, out, var_in, temporal->mask);
+    else if (moments) hipLaunchKernelGGL(ptmi_variance_moments, grid1, block1, 0, s, tm, *moments, radiance, in, out, var_in);
+    const unsigned int* skip = history ? temporal->mask : moments ? counts : nullptr;
     if (a.radius == 1) hipLaunchKernelGGL(ptmi_variance_spatial<1>, grid2, block2, 0, s, a, fb, skip, in, out, var_in);
     else if (a.radius == 2) hipLaunchKernelGGL(ptmi_variance_spatial<2>, grid2, block2, 0, s, a, fb, skip, in, out, var_in);
     else hipLaunchKernelGGL(ptmi_variance_spatial<3>, grid2, block2, 0, s, a, fb, skip, in, out, var_in);

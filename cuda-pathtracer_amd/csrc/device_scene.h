@@ -253,9 +253,19 @@ struct VarianceArgs : FilterArgs {
 // iterations passes of the variance-guided a-trous filter over radiance guided by fb; the filtered radiance -> out_radiance, its
 // tone map -> out_rgb8, the filtered variance -> var_out.  buf: 2 x width x height float4 of scratch.  `estimated` is recorded
 // between the estimate and the filter.
+// temporal != nullptr (ptmi_denoise_temporal_variance): radiance and fb are the history's, moments and counts are nullptr, and the
+// estimate is the third route - the history's luminance statistics where a pixel has kTemporalMinFrames frames or more (with
+// temporal->source = 0), the spatial estimate elsewhere.
+struct TemporalVariance {
+    const float4* moments = nullptr; // (mu, s2, k, 0) of the history, local row-major
+    unsigned int* mask = nullptr;    // width x height of scratch: 1 where the temporal estimate wrote the pixel, else 0
+    int source = 0;                  // 1: the spatial estimate everywhere (moments and mask are not touched)
+};
+constexpr float kTemporalMinFrames = 4.0f;   // PTMI_TEMPORAL_MIN_FRAMES
 void launch_denoise_variance(const VarianceArgs& a, const FeatureBuffers& fb, const float* radiance, const TileMap& tm,
                              const AccumBuffers* moments, const unsigned int* counts, int iterations, float4* buf, float* var_in,
-                             float* var_out, unsigned char* out_rgb8, float* out_radiance, hipEvent_t estimated, hipStream_t s);
+                             float* var_out, unsigned char* out_rgb8, float* out_radiance, hipEvent_t estimated, hipStream_t s,
+                             const TemporalVariance* temporal = nullptr);
 // the stopping test's state by slot -> local row-major arrays of n_local each
 void launch_pass_moments(const TileMap& tm, const AccumBuffers& ab, float* mean, float* m2, unsigned int* passes, hipStream_t s);
 
@@ -282,10 +292,13 @@ struct TemporalHistory {
 };
 // One step: the current radiance (3 floats per pixel) with its sample counts (counts, or a.m everywhere where counts ==
 // nullptr) and features fb over the history prev -> next; the result -> out_radiance and its tone map
-// -> rgb8; accepted / rejected / missed pixels are added to stats[0..2].
+// -> rgb8; accepted / rejected / missed pixels are added to stats[0..2].  next_moments != nullptr (ptmi_set_temporal_moments):
+// the luminance statistics (mu, s2, k, 0) per pixel travel with the history, prev_moments -> next_moments (both sides of a
+// ping-pong of their own, so that TemporalHistory and the plain kernel's argument block stay what they were).
 void launch_temporal(const TemporalArgs& a, const FeatureBuffers& fb, const float* radiance, const unsigned int* counts,
                      const TemporalHistory& prev, const TemporalHistory& next, unsigned char* rgb8,
-                     float* out_radiance, unsigned long long* stats, hipStream_t s);
+                     float* out_radiance, unsigned long long* stats, hipStream_t s, const float4* prev_moments = nullptr,
+                     float4* next_moments = nullptr);
 
 // ---- next-event estimation (include/ptmi.h: ptmi_config.next_event) ------------------------------------------------------
 // The emitter table of the loaded scene (host: SceneState::buildEmitters / upload; include/ptmi.h states which primitives are

@@ -3,23 +3,27 @@
 // (ptmi_temporal_accumulate); every value here is float32 in the order written there (built with -ffp-contract=off and
 // correctly rounded division), so a numpy float32 restatement reproduces it bit for bit.
 //
-// Kernel
-//   ptmi_temporal_reproject  per pixel: the reprojection point into the history's view, 4 bilinear taps of the history gated by
-//                            normal, position and albedo, the blend by sample count; the new history (colour and count, features) goes
-//                            to the other side of the ping-pong, the result through the frame's tone map -> rgb8 + radiance
+// Kernels
+//   ptmi_temporal_reproject          per pixel: the reprojection point into the history's view, 4 bilinear taps of the history gated by
+//                                    normal, position and albedo, the blend by sample count; the new history (colour and count, features) goes
+//                                    to the other side of the ping-pong, the result through the frame's tone map -> rgb8 + radiance
+//   ptmi_temporal_reproject_moments  the same step (one body, temporal_pixel) with the luminance statistics (mu, s2, k) of
+//                                    ptmi_set_temporal_moments resampled by the same taps and blended by the same alpha
 // One thread per pixel; a thread reads only the previous side of the history and writes only its own pixel of the next side,
 // so the result does not depend on the launch geometry.
-#include "pt_device.h"
+#include "denoise_common.h"
 
 namespace ptmi {
 
 enum : int { kTemporalAccepted = 0, kTemporalRejected = 1, kTemporalMissed = 2 };
 
-__global__ __launch_bounds__(kBlock) void ptmi_temporal_reproject(TemporalArgs a, FeatureBuffers fb, const float* __restrict__ radiance,
-                                                                  const unsigned int* __restrict__ counts, TemporalHistory prev,
-                                                                  TemporalHistory next,
-                                                                  unsigned char* __restrict__ rgb8, float* __restrict__ out_radiance,
-                                                                  unsigned long long* __restrict__ stats) {
+// THE STEP of one pixel.  MOMENTS: prev_mom / next_mom are the two sides of the statistics' ping-pong (else not touched).
+template <bool MOMENTS>
+__device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const FeatureBuffers& fb, const float* __restrict__ radiance,
+                                               const unsigned int* __restrict__ counts, const TemporalHistory& prev,
+                                               const TemporalHistory& next, unsigned char* __restrict__ rgb8,
+                                               float* __restrict__ out_radiance, unsigned long long* __restrict__ stats,
+                                               const float4* __restrict__ prev_mom, float4* __restrict__ next_mom) {
     const int n = a.width * a.height;
     const int p = blockIdx.x * kBlock + threadIdx.x;
     const bool live = p < n;
@@ -32,9 +36,11 @@ __global__ __launch_bounds__(kBlock) void ptmi_temporal_reproject(TemporalArgs a
         bool reuse = false;
         f3 h = mk3(0.0f, 0.0f, 0.0f);
         float nacc = 0.0f;
+        float mu_h = 0.0f, s2_h = 0.0f, k_h = 0.0f;
         if (a.history && a.still) {                          // the only tap is the pixel itself, weight 1
             const float4 c = prev.color[p];
             h = mk3(c.x, c.y, c.z); nacc = c.w;
+            if (MOMENTS) { const float4 hm = prev_mom[p]; mu_h = hm.x; s2_h = hm.y; k_h = hm.z; }
             reuse = true;
         } else if (a.history && hf != 0.0f) {
             const f3 x = mk3(ps.x / hf, ps.y / hf, ps.z / hf);
@@ -61,6 +67,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_temporal_reproject(TemporalArgs a
                     const int x0 = (int)x0f, y0 = (int)y0f;
                     const float gx = 1.0f - fx, gy = 1.0f - fy;
                     float W = 0.0f, Sx = 0.0f, Sy = 0.0f, Sz = 0.0f, Sn = 0.0f;
+                    float Sm = 0.0f, Ss = 0.0f, Sk = 0.0f;
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
                         const int tx = x0 + (k & 1), ty = y0 + (k >> 1);
@@ -81,10 +88,15 @@ __global__ __launch_bounds__(kBlock) void ptmi_temporal_reproject(TemporalArgs a
                         W = W + w;
                         Sx = Sx + w * hc.x; Sy = Sy + w * hc.y; Sz = Sz + w * hc.z;
                         Sn = Sn + w * hc.w;
+                        if (MOMENTS) {
+                            const float4 hm = prev_mom[t];
+                            Sm = Sm + w * hm.x; Ss = Ss + w * hm.y; Sk = Sk + w * hm.z;
+                        }
                     }
                     if (W > 0.01f) {
                         h = mk3(Sx / W, Sy / W, Sz / W);
                         nacc = Sn / W;
+                        if (MOMENTS) { mu_h = Sm / W; s2_h = Ss / W; k_h = Sk / W; }
                         reuse = true;
                     }
                 }
@@ -92,15 +104,24 @@ __global__ __launch_bounds__(kBlock) void ptmi_temporal_reproject(TemporalArgs a
         }
         f3 c = cur;                                                          // a restart: the input as it is
         float cnt = m;
+        float mu = 0.0f, s2 = 0.0f, kf = 1.0f;
+        if (MOMENTS) mu = denoise_lum(cur.x, cur.y, cur.z);
         if (reuse) {
             cnt = fminf(nacc + m, a.max_history * m);
             const float alpha = m / cnt;
             c = mk3(h.x + alpha * (cur.x - h.x), h.y + alpha * (cur.y - h.y), h.z + alpha * (cur.z - h.z));
+            if (MOMENTS) {                                                   // West's weighted update in blend form
+                const float d = mu - mu_h;
+                mu = mu_h + alpha * d;
+                s2 = (1.0f - alpha) * (s2_h + alpha * (d * d));
+                kf = fminf(k_h + 1.0f, a.max_history);
+            }
             outcome = kTemporalAccepted;
         } else {
             outcome = hf == 0.0f ? kTemporalMissed : kTemporalRejected;
         }
         next.color[p] = make_float4(c.x, c.y, c.z, cnt);
+        if (MOMENTS) next_mom[p] = make_float4(mu, s2, kf, 0.0f);
         float4 hn = nr;
         hn.w = hf;                                                           // (the feature pass writes 0 there)
         next.normal[p] = hn;
@@ -119,13 +140,35 @@ __global__ __launch_bounds__(kBlock) void ptmi_temporal_reproject(TemporalArgs a
     }
 }
 
+__global__ __launch_bounds__(kBlock) void ptmi_temporal_reproject(TemporalArgs a, FeatureBuffers fb, const float* __restrict__ radiance,
+                                                                  const unsigned int* __restrict__ counts, TemporalHistory prev,
+                                                                  TemporalHistory next,
+                                                                  unsigned char* __restrict__ rgb8, float* __restrict__ out_radiance,
+                                                                  unsigned long long* __restrict__ stats) {
+    temporal_pixel<false>(a, fb, radiance, counts, prev, next, rgb8, out_radiance, stats, nullptr, nullptr);
+}
+
+// the statistics' two sides are trailing arguments of their own: the argument block above does not move
+__global__ __launch_bounds__(kBlock) void ptmi_temporal_reproject_moments(TemporalArgs a, FeatureBuffers fb, const float* __restrict__ radiance,
+                                                                          const unsigned int* __restrict__ counts, TemporalHistory prev,
+                                                                          TemporalHistory next,
+                                                                          unsigned char* __restrict__ rgb8, float* __restrict__ out_radiance,
+                                                                          unsigned long long* __restrict__ stats,
+                                                                          const float4* __restrict__ prev_mom, float4* __restrict__ next_mom) {
+    temporal_pixel<true>(a, fb, radiance, counts, prev, next, rgb8, out_radiance, stats, prev_mom, next_mom);
+}
+
 void launch_temporal(const TemporalArgs& a, const FeatureBuffers& fb, const float* radiance, const unsigned int* counts,
                      const TemporalHistory& prev, const TemporalHistory& next, unsigned char* rgb8,
-                     float* out_radiance, unsigned long long* stats, hipStream_t s) {
+                     float* out_radiance, unsigned long long* stats, hipStream_t s, const float4* prev_moments, float4* next_moments) {
     const int n = a.width * a.height;
     if (n <= 0) return;
-    hipLaunchKernelGGL(ptmi_temporal_reproject, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, a, fb, radiance, counts, prev, next,
-                       rgb8, out_radiance, stats);
+    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+    if (next_moments)
+        hipLaunchKernelGGL(ptmi_temporal_reproject_moments, grid, block, 0, s, a, fb, radiance, counts, prev, next, rgb8, out_radiance,
+                           stats, prev_moments, next_moments);
+    else
+        hipLaunchKernelGGL(ptmi_temporal_reproject, grid, block, 0, s, a, fb, radiance, counts, prev, next, rgb8, out_radiance, stats);
 }
 
 }  // namespace ptmi

@@ -310,6 +310,7 @@ struct RenderState {
         float* d_var_in = nullptr;                   // the variance that steered the last run, local row-major
         float* d_var_out = nullptr;                  // that variance after the last iteration
         bool variance_valid = false;                 // they hold a run's values; stale under the rules of features_valid
+        unsigned int* d_owned = nullptr;             // denoiseTemporalVariance: 1 where the history's statistics gave the variance; its own first run allocates it
         double estimate_ms = 0.0, filter_ms = 0.0;   // device time of the last variance estimate / variance-guided filter
     } dn;
     // The temporal accumulation's history (temporalAccumulate) and outputs; allocated at first use, freed with the other
@@ -325,6 +326,9 @@ struct RenderState {
         float* d_radiance = nullptr;
         unsigned long long* d_stats = nullptr;       // accepted, rejected, missed of the last step
         bool stepped = false;                        // d_rgb8 / d_radiance hold a result
+        // ptmi_set_temporal_moments: (mu, s2, k, 0) per pixel, a ping-pong that turns with side[]; allocated by the first step
+        // with the switch on, meaningful while `valid` (the switch empties the history whenever it changes)
+        float4* moments[2] = {nullptr, nullptr};
     } tp;
 
     void allocateBuffers();                         // application_state.h:91-123 (+ render_init)
@@ -416,6 +420,7 @@ struct ApplicationState {
     DistState dist;
     AppConfig config;
     int feature_shading = 0;                         // PTMI_FEATURE_* (include/ptmi.h: ptmi_set_feature_shading); the context's, not the scene's
+    int temporal_moments = 0;                        // ptmi_set_temporal_moments; the context's, not the scene's
     EnvState env;
     LensState lens;
     std::vector<uint32_t> h_jump;                    // 32 x 160 x 5 words
@@ -500,6 +505,11 @@ void temporalAccumulate(ApplicationState& g_state, const TemporalParams& p, Temp
 void readTemporal(const ApplicationState& g_state, unsigned char* rgb8, float* radiance);
 void readHistoryCounts(const ApplicationState& g_state, float* counts);
 void denoiseTemporal(ApplicationState& g_state, const DenoiseParams& p);
+// The history's luminance statistics (include/ptmi.h: ptmi_set_temporal_moments) and the variance-guided filter steered by them.
+void setTemporalMoments(ApplicationState& g_state, int on);          // a new value empties the history
+void readTemporalMoments(const ApplicationState& g_state, float* mean, float* variance, float* frames);
+void debugSetTemporalMoments(ApplicationState& g_state, const float* mean, const float* variance, const float* frames);
+void denoiseTemporalVariance(ApplicationState& g_state, const VarianceParams& p);
 
 bool packBvhNodes(const std::vector<BVHNode>& bvh_nodes, int top_records, std::vector<float4>& g, int& n_pos, int& n_top, int& top_depth);
 

@@ -310,6 +310,11 @@ void temporalAccumulate(ApplicationState& g, const TemporalParams& p, TemporalSt
             t.d_rgb8 = (unsigned char*)hipMallocSafe(n * 3, "temporal.rgb8");
         } catch (...) { r.freeTemporal(); throw; }
     }
+    if (g.temporal_moments && !t.moments[0]) {
+        try {
+            for (float4*& q : t.moments) q = (float4*)hipMallocSafe(n * sizeof(float4), "temporal.moments");
+        } catch (...) { r.freeTemporal(); throw; }
+    }
     a.history = t.valid ? 1 : 0;
     a.still = t.valid && std::memcmp(cam, t.cam, sizeof cam) == 0 && t.width == a.width && t.height == a.height ? 1 : 0;
     std::memcpy(a.cam, t.cam, sizeof a.cam);
@@ -321,7 +326,8 @@ void temporalAccumulate(ApplicationState& g, const TemporalParams& p, TemporalSt
     PTMI_HIP(hipMemsetAsync(t.d_stats, 0, sizeof h_stats, r.stream));
     if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));
     PTMI_HIP(hipEventRecord(g.event_pool[0], r.stream));
-    launch_temporal(a, d.fb, r.d_radiance, counts, t.side[t.cur], t.side[next], t.d_rgb8, t.d_radiance, t.d_stats, r.stream);
+    launch_temporal(a, d.fb, r.d_radiance, counts, t.side[t.cur], t.side[next], t.d_rgb8, t.d_radiance, t.d_stats, r.stream,
+                    g.temporal_moments ? t.moments[t.cur] : nullptr, g.temporal_moments ? t.moments[next] : nullptr);
     PTMI_HIP(hipGetLastError());
     PTMI_HIP(hipEventRecord(g.event_pool[1], r.stream));
     PTMI_HIP(hipMemcpyAsync(h_stats, t.d_stats, sizeof h_stats, hipMemcpyDeviceToHost, r.stream));
@@ -365,6 +371,74 @@ void denoiseTemporal(ApplicationState& g, const DenoiseParams& p) {
     FeatureBuffers fb;
     fb.albedo = t.side[t.cur].albedo; fb.normal = t.side[t.cur].normal; fb.position = t.side[t.cur].position;
     denoiseRun(g, a, p.iterations, sigma_c, fb, t.d_radiance);        // the last step's radiance is the history's colour
+}
+
+// ------------------------------------------------------------------------------------------------
+// the history's luminance statistics (include/ptmi.h: ptmi_set_temporal_moments, ptmi_denoise_temporal_variance)
+// ------------------------------------------------------------------------------------------------
+void setTemporalMoments(ApplicationState& g, int on) {
+    if (on != 0 && on != 1) throw ArgError("temporal_moments: on must be 0 or 1");
+    if (on == g.temporal_moments) return;
+    g.temporal_moments = on;
+    temporalReset(g);                                  // a history without statistics cannot go on with them, nor the reverse
+}
+
+// the statistics of the history's current side, or the reason there are none
+static float4* currentMoments(const ApplicationState& g, const char* who) {
+    const RenderState::Temporal& t = g.render.tp;
+    if (!g.temporal_moments) throw ArgError(std::string(who) + ": the temporal moments are off (ptmi_set_temporal_moments first)");
+    if (!t.valid || !t.moments[t.cur]) throw ArgError(std::string(who) + ": the history is empty (ptmi_temporal_accumulate first)");
+    return t.moments[t.cur];
+}
+
+void readTemporalMoments(const ApplicationState& g, float* mean, float* variance, float* frames) {
+    const float4* d_mom = currentMoments(g, "read_temporal_moments");
+    const size_t n = g.render.n_local;
+    PTMI_HIP(hipSetDevice(g.device_id));
+    std::vector<float4> h(n);
+    if (n) PTMI_HIP(hipMemcpy(h.data(), d_mom, n * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) {
+        if (mean) mean[i] = h[i].x;
+        if (variance) variance[i] = h[i].y;
+        if (frames) frames[i] = h[i].z;
+    }
+}
+
+void debugSetTemporalMoments(ApplicationState& g, const float* mean, const float* variance, const float* frames) {
+    float4* d_mom = currentMoments(g, "debug_set_temporal_moments");
+    const size_t n = g.render.n_local;
+    PTMI_HIP(hipSetDevice(g.device_id));
+    std::vector<float4> h(n);
+    for (size_t i = 0; i < n; i++) h[i] = make_float4(mean[i], variance[i], frames[i], 0.0f);
+    if (n) PTMI_HIP(hipMemcpy(d_mom, h.data(), n * sizeof(float4), hipMemcpyHostToDevice));   // (every step ends with a synchronise)
+}
+
+void denoiseTemporalVariance(ApplicationState& g, const VarianceParams& p) {
+    RenderState& r = g.render;
+    RenderState::Denoise& d = r.dn;
+    const RenderState::Temporal& t = r.tp;
+    TemporalVariance tv;
+    tv.moments = currentMoments(g, "denoise_temporal_variance");
+    checkVarianceParams(p);
+    if (p.feature_grid != t.grid) throw ArgError("denoise_temporal_variance: feature_grid differs from the history's");
+    VarianceArgs a;
+    filterArgs(g, p, a);
+    a.sigma_l2 = p.sigma_luminance * p.sigma_luminance;
+    a.epsilon = p.epsilon;
+    a.radius = p.spatial_radius;
+    a.two_spp = 1u;                                    // the spatial estimate skips the pixels whose mask is 1
+    PTMI_HIP(hipSetDevice(g.device_id));
+    if (!d.d_owned) d.d_owned = (unsigned int*)hipMallocSafe(std::max<size_t>(r.n_local, 1) * sizeof(unsigned int), "denoise.owned");
+    tv.mask = d.d_owned;
+    tv.source = p.source;
+    FeatureBuffers fb;
+    fb.albedo = t.side[t.cur].albedo; fb.normal = t.side[t.cur].normal; fb.position = t.side[t.cur].position;
+    d.variance_valid = false;
+    runFilter(g, [&](hipEvent_t estimated) {           // the last step's radiance is the history's colour
+        launch_denoise_variance(a, fb, t.d_radiance, r.tile, nullptr, nullptr, p.iterations, d.d_buf, d.d_var_in, d.d_var_out, d.d_rgb8,
+                                d.d_radiance, estimated, r.stream, &tv);
+    }, &d.estimate_ms, &d.filter_ms);
+    d.variance_valid = true;
 }
 
 }  // namespace ptmi

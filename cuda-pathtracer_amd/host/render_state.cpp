@@ -145,14 +145,14 @@ void RenderState::freeAccum() {
 }
 
 void RenderState::freeDenoise() {
-    void* ptrs[] = {dn.fb.albedo, dn.fb.normal, dn.fb.position, dn.d_rgb8, dn.d_radiance, dn.d_buf, dn.d_var_in, dn.d_var_out};
+    void* ptrs[] = {dn.fb.albedo, dn.fb.normal, dn.fb.position, dn.d_rgb8, dn.d_radiance, dn.d_buf, dn.d_var_in, dn.d_var_out, dn.d_owned};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     dn = Denoise();
 }
 
 void RenderState::freeTemporal() {
     void* ptrs[] = {tp.side[0].color, tp.side[0].normal, tp.side[0].position, tp.side[0].albedo, tp.side[1].color, tp.side[1].normal,
-                    tp.side[1].position, tp.side[1].albedo, tp.d_rgb8, tp.d_radiance, tp.d_stats};
+                    tp.side[1].position, tp.side[1].albedo, tp.d_rgb8, tp.d_radiance, tp.d_stats, tp.moments[0], tp.moments[1]};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     tp = Temporal();
 }

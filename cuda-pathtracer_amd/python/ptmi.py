@@ -39,6 +39,8 @@ EXPORTS = [
     "ptmi_variance_timing", "ptmi_read_pass_moments",
     "ptmi_default_temporal_params", "ptmi_check_temporal_params", "ptmi_temporal_reset", "ptmi_temporal_accumulate",
     "ptmi_read_temporal", "ptmi_read_history_counts", "ptmi_denoise_temporal",
+    "ptmi_set_temporal_moments", "ptmi_get_temporal_moments", "ptmi_read_temporal_moments", "ptmi_denoise_temporal_variance",
+    "ptmi_debug_set_temporal_moments",
     "ptmi_host_emitters",
     "ptmi_debug_math", "ptmi_debug_grid_index", "ptmi_debug_nee_call",
     "ptmi_default_env_params", "ptmi_check_env_params", "ptmi_set_environment", "ptmi_environment_info", "ptmi_host_env_table",
@@ -287,6 +289,12 @@ def lib():
             L.ptmi_host_lens_block.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_float, C.c_float, vp]
             L.ptmi_debug_lens_block.argtypes = [vp, vp]
             L.ptmi_debug_lens_ray.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        if hasattr(L, "ptmi_set_temporal_moments"):    # likewise
+            L.ptmi_set_temporal_moments.argtypes = [vp, C.c_int]
+            L.ptmi_get_temporal_moments.argtypes = [vp, ip]
+            L.ptmi_read_temporal_moments.argtypes = [vp, vp, vp, vp]
+            L.ptmi_denoise_temporal_variance.argtypes = [vp, C.POINTER(VarianceParams)]
+            L.ptmi_debug_set_temporal_moments.argtypes = [vp, vp, vp, vp]
         if hasattr(L, "ptmi_debug_set_filter_inputs"): # likewise
             L.ptmi_debug_set_filter_inputs.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int]
         if hasattr(L, "ptmi_debug_accum_step"):        # likewise
@@ -1174,6 +1182,41 @@ class Renderer:
         p = default_denoise_params(**params)
         self._ck(self.L.ptmi_denoise_temporal(self.h, C.byref(p)))
         return self.read_denoised()
+
+    # --- the history's luminance statistics (include/ptmi.h: ptmi_set_temporal_moments) ---
+    def set_temporal_moments(self, on):
+        """ptmi_set_temporal_moments: the history carries (mean, variance, frames) of its luminance.  The context's, kept over
+        scene loads; a new value empties the history."""
+        self._ck(self.L.ptmi_set_temporal_moments(self.h, int(on)))
+
+    def get_temporal_moments(self):
+        on = C.c_int()
+        self._ck(self.L.ptmi_get_temporal_moments(self.h, C.byref(on)))
+        return on.value
+
+    def temporal_moments(self):
+        """(mean, variance, frames) of the history's luminance, (local rows, width) float32 each."""
+        shape = (len(self.local_rows()), self.width)
+        mean, var, frames = (np.zeros(shape, np.float32) for _ in range(3))
+        self._ck(self.L.ptmi_read_temporal_moments(self.h, mean.ctypes.data, var.ctypes.data, frames.ctypes.data))
+        return mean, var, frames
+
+    def denoise_temporal_variance(self, **params):
+        """The variance-guided a-trous filter over the history's colour, guided by the history's features and steered by the
+        history's luminance variance (keyword parameters: fields of VarianceParams over the defaults); returns (rgb8, radiance)
+        like denoise; variance() reads the variances."""
+        p = default_variance_params(**params)
+        self._ck(self.L.ptmi_denoise_temporal_variance(self.h, C.byref(p)))
+        return self.read_denoised()
+
+    def debug_set_temporal_moments(self, mean, variance, frames):
+        """ptmi_debug_set_temporal_moments: (local rows, width) arrays become the history's (mean, variance, frames), unchecked."""
+        shape = (len(self.local_rows()), self.width)
+        arrs = [np.ascontiguousarray(a, np.float32) for a in (mean, variance, frames)]
+        for a in arrs:
+            if a.shape != shape:
+                raise ValueError(f"expected arrays of shape {shape}")
+        self._ck(self.L.ptmi_debug_set_temporal_moments(self.h, *[a.ctypes.data for a in arrs]))
 
     def device_image(self):
         a = C.c_void_p(); b = C.c_void_p()

@@ -781,6 +781,65 @@ int  ptmi_read_temporal(const ptmi_ctx*, unsigned char* rgb8, float* radiance);
 int  ptmi_read_history_counts(const ptmi_ctx*, float* counts);
 int  ptmi_denoise_temporal(ptmi_ctx*, const ptmi_denoise_params* /* NULL: defaults */);
 
+/* ---- temporal luminance statistics: the history steers the variance filter (new in this implementation) -------------------
+ * ptmi_set_temporal_moments(ctx, 1) makes the history carry, per pixel, the weighted mean and variance of the luminances that
+ * went into it and the number of frames behind it; ptmi_denoise_temporal_variance is ptmi_denoise_variance's filter over the
+ * history with that variance in the place of the accumulation's (the temporal and spatial stages of SVGF joined).  The switch
+ * belongs to the context and is kept over scene loads, as ptmi_set_feature_shading's flags are; the default is 0.  A call that
+ * changes the value empties the history, as ptmi_temporal_reset does, and changes nothing else (image, accumulation, features and
+ * the denoiser's results stay); a call with the current value does nothing; a value other than 0 and 1 is PTMI_E_INVALID.
+ * With 0 nothing of this section runs or is allocated and ptmi_temporal_accumulate is, bit for bit, what it is without it.
+ *
+ * With 1, each side of the history's ping-pong gains one float4 per pixel, (mu, s2, k, 0): mu the weighted mean luminance of the
+ * inputs behind the pixel, s2 their weighted population variance, k the number of frames behind it (a float).  They are
+ * allocated by the first step that needs them, freed with the history's other buffers and empty whenever the history is.
+ *
+ * ADDITION TO THE STEP of ptmi_temporal_accumulate, float32 in the order written; lum is ptmi_denoise's:
+ *   l = lum(c_cur).
+ *   RESTART (steps 1, 3 and 4, whatever the reason):  mu = l;  s2 = +0;  k = 1.
+ *   STILL CAMERA (step 0):  mu_h, s2_h, k_h = the pixel's own.
+ *   REPROJECTED (step 4): over the taps kept for the colour, in the same order and with the same weights w, from +0:
+ *      Sm = Sm + w * mu_t;  Ss = Ss + w * s2_t;  Sk = Sk + w * k_t;   then  mu_h = Sm / W;  s2_h = Ss / W;  k_h = Sk / W.
+ *   BLEND, with step 5's own alpha = m / n':
+ *      d = l - mu_h;   mu = mu_h + alpha * d;   s2 = (1 - alpha) * (s2_h + alpha * (d * d));
+ *      k = fminf(k_h + 1, (float)max_history).
+ * This is West's weighted incremental variance (1979) in blend form: with weights m_i and an uncapped history s2 is the population
+ * variance of the inputs' luminances (Welford's M2 / n for equal m); once max_history binds alpha is constant and s2 is the
+ * exponentially weighted variance.  The raw-moment form E[l^2] - E[l]^2 is not used, for the reason given under
+ * ptmi_denoise_variance step 3: carried over 2 .. 32 frames of 627 pixels it is off by up to 2e-5 of the variance at l = 1 +- 0.2
+ * and by 4e3 x the variance at l = 1e3 +- 1e-2, where the blend form stays within 8e-7 and 8e-3 (the input's own quantisation) of
+ * binary64 (tests/test_temporal_moments_host.py).
+ * The bilinear resampling of s2 ignores the spread between the taps' means (the variance of a mixture is the mean variance plus
+ * the variance of the means); SVGF does the same.
+ * NON-FINITE VALUES, from IEEE arithmetic and fminf: a non-finite c_cur makes mu and s2 non-finite, and they travel with that
+ * surface point only, as a non-finite colour does; a NaN k_h gives k = max_history; alpha = 1 (max_history = 1) gives
+ * s2 = 0 * (...), which is 0, or NaN for a non-finite operand.
+ * ptmi_read_temporal_moments returns (mu, s2, k) of the history, local row-major, any pointer may be NULL.
+ *
+ * ptmi_denoise_temporal_variance runs THE FILTER of ptmi_denoise_variance, steps 1 and 3 - 5 unchanged, over the history's
+ * colour guided by the history's features, exactly as ptmi_denoise_temporal does for ptmi_denoise.  Step 2 is replaced by
+ *   2. TEMPORAL VARIANCE, with source = 0, where the pixel has k >= PTMI_TEMPORAL_MIN_FRAMES (SVGF's choice):
+ *         v  = fmaxf(0, s2 / (k - 1))                    the variance of the mean of k equally weighted frames;
+ *         lr = lum(history colour_p);  if lr > 0:  s = l_p / lr;  v = (v * s) * s      (the unit conversion of step 2)
+ *      Every other pixel (a NaN k included), and every pixel with source = 1, takes the spatial estimate of step 3.
+ * Once max_history binds the mean is exponential and its variance is sigma^2 alpha / (2 - alpha), about half of sigma^2 / (k - 1)
+ * at k = max_history: the estimate is then about 2 x too large; for unequal m it is approximate as well.  It errs towards more
+ * blur, never towards a negative or zero tolerance (fmaxf(0, NaN) = 0; epsilon keeps the tolerance positive).
+ * Results: ptmi_read_denoised and ptmi_read_variance; ptmi_variance_timing times it.  A ptmi_denoise_temporal or
+ * ptmi_denoise_variance after it gives what it gives alone.
+ * ptmi_debug_set_temporal_moments (test hook) overwrites (mu, s2, k) of the history's current side, local row-major, with
+ * unchecked values (non-finite ones are legitimate) and touches nothing else: with ptmi_debug_set_filter_inputs every decision
+ * above can be reached on constructed state.  It has no kernel: a host-side interleave and one copy.
+ * PTMI_E_INVALID: ptmi_read_temporal_moments, ptmi_denoise_temporal_variance and ptmi_debug_set_temporal_moments with the switch
+ * off or the history empty; ptmi_denoise_temporal_variance with a feature_grid other than the history's or parameters
+ * ptmi_check_variance_params refuses (its messages); a NULL array for the hook. */
+#define PTMI_TEMPORAL_MIN_FRAMES 4.0f
+int  ptmi_set_temporal_moments(ptmi_ctx*, int on);
+int  ptmi_get_temporal_moments(const ptmi_ctx*, int* on);
+int  ptmi_read_temporal_moments(const ptmi_ctx*, float* mean, float* variance, float* frames);
+int  ptmi_denoise_temporal_variance(ptmi_ctx*, const ptmi_variance_params* /* NULL: defaults */);
+int  ptmi_debug_set_temporal_moments(ptmi_ctx*, const float* mean /* n */, const float* variance /* n */, const float* frames /* n */);
+
 /* ---- next-event estimation with multiple importance sampling (new in this implementation) --------------------------------------
  * ptmi_config.next_event = 1: at every path vertex a point on an emitter is sampled and one shadow ray traced to it, and the power
  * heuristic combines that sample with the BSDF sample (Veach 1997), so the estimator stays unbiased.  It applies to

@@ -13,6 +13,8 @@
   python tools/ptmi_render.py --scene ... --spp 8 --aov-png aov                              (aov_albedo/normal/depth.png)
   python tools/ptmi_render.py --scene ... --spp 4 --orbit 16 --yaw-step 2 --temporal --denoise --out-prefix orbit_
                                (16 views 2 degrees apart, each through the temporal accumulation and the denoiser)
+  python tools/ptmi_render.py --scene ... --spp 4 --orbit 16 --temporal --denoise --variance-guided --variance-png sd.png --out last.png
+                               (the history carries its luminance variance; the variance-guided filter over it is steered by that)
   python tools/ptmi_render.py --scene ... --sky --next-event --out sky.png                    (procedural sky with a sun)
   python tools/ptmi_render.py --scene ... --env map.npy --env-rotation 90 --out lit.png      ((h, w, 3) float radiance, row 0 up)
   python tools/ptmi_render.py --scene ... --mirror 12-21 --glass 22-31 --ior 1.5 --max-depth 8 --out blocks.png
@@ -80,7 +82,8 @@ def main():
     ap.add_argument("--denoise", type=int, nargs="?", const=-1, default=None, metavar="ITERATIONS",
                     help="--out gets the image through the edge-avoiding a-trous denoiser (ITERATIONS, default 5)")
     ap.add_argument("--variance-guided", action="store_true", help="--denoise runs the variance-guided filter: steered by the "
-                    "accumulation's per-pixel statistics after --adaptive / --passes, by a spatial estimate after a frame")
+                    "accumulation's per-pixel statistics after --adaptive / --passes, by the history's own luminance variance with "
+                    "--orbit --temporal, by a spatial estimate after a frame")
     ap.add_argument("--variance-png", default=None, metavar="FILE", help="with --variance-guided: the standard deviation left after "
                     "the filter, sqrt(variance_out), through the tone map")
     ap.add_argument("--aov-png", default=None, metavar="PREFIX", help="write PREFIX_albedo.png, PREFIX_normal.png, PREFIX_depth.png "
@@ -237,8 +240,8 @@ def main():
             ap.error(f"--aperture / --focus: {e}")
         print("lens: radius %g, focus distance %g" % r.lens())
     if a.orbit > 0:
-        if a.variance_guided and a.temporal:
-            ap.error("--variance-guided does not filter the temporal history (no variance is carried in it)")
+        if a.variance_png and not (a.variance_guided and a.denoise is not None):
+            ap.error("--variance-png needs --denoise --variance-guided")
         orbit(r, a, cam)
         r.close()
         return
@@ -271,11 +274,7 @@ def main():
         ems, fms = r.variance_timing()
         print(f"denoise (variance-guided): features {r.denoise_timing()[0]:.3f} ms, variance estimate {ems:.3f} ms, filter {fms:.3f} ms")
         if a.variance_png:
-            import numpy as np
-            sd = np.sqrt(r.variance()[1].astype(np.float64))
-            grey = (255.99 * np.minimum((sd / (sd + 1.0)) ** (1.0 / 2.2), 1.0)).astype(np.uint8)
-            ptmi.write_png(a.variance_png, grey[:, :, None].repeat(3, axis=2))
-            print(f"wrote {a.variance_png}")
+            write_variance_png(r, a.variance_png)
     elif a.denoise is not None:
         prm = {} if a.denoise < 0 else {"iterations": a.denoise}
         rgb, _ = r.denoise(**prm)
@@ -296,6 +295,9 @@ def orbit(r, a, cam):
     accumulation (--temporal) and the denoiser (--denoise: over the history with --temporal, else over the frame)"""
     prm = {} if a.denoise is None or a.denoise < 0 else {"iterations": a.denoise}
     yaw0 = cam.yaw_deg
+    guided_history = a.temporal and a.variance_guided and a.denoise is not None
+    if guided_history:
+        r.set_temporal_moments(1)                      # the history carries its luminance variance: it steers the filter over it
     for i in range(a.orbit):
         cam.yaw_deg = yaw0 + i * a.yaw_step
         r.set_camera(cam)
@@ -304,7 +306,9 @@ def orbit(r, a, cam):
         if a.temporal:
             rgb, _, ts = r.temporal_accumulate()
             line += f", temporal {ts.seconds * 1e3:.3f} ms (accepted {ts.accepted}, rejected {ts.rejected}, missed {ts.missed})"
-            if a.denoise is not None:
+            if guided_history:
+                rgb, _ = r.denoise_temporal_variance(**prm)
+            elif a.denoise is not None:
                 rgb, _ = r.denoise_temporal(**prm)
         elif a.denoise is not None:
             rgb, _ = r.denoise_variance(**prm) if a.variance_guided else r.denoise(**prm)
@@ -316,6 +320,17 @@ def orbit(r, a, cam):
     if a.out:
         ptmi.write_png(a.out, rgb)
         print(f"wrote {a.out}")
+    if a.variance_png and a.orbit > 0:
+        write_variance_png(r, a.variance_png)
+
+
+def write_variance_png(r, path):
+    """the standard deviation left after the last variance-guided filter, sqrt(variance_out), through the tone map"""
+    import numpy as np
+    sd = np.sqrt(r.variance()[1].astype(np.float64))
+    grey = (255.99 * np.minimum((sd / (sd + 1.0)) ** (1.0 / 2.2), 1.0)).astype(np.uint8)
+    ptmi.write_png(path, grey[:, :, None].repeat(3, axis=2))
+    print(f"wrote {path}")
 
 
 def write_aovs(r, prefix):
