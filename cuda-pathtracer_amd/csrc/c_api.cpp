@@ -458,6 +458,10 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
             need(cfg->sampling_mode == 0, "a lens is set: it needs sampling_mode 0 (BSDF): the guided modes run through the bounce kernels");
             need(cfg->fast_tree == 0, "a lens is set: it needs fast_tree 0: frames through a lens always trace the reference's hits");
         }
+        if (c->app.scene.medium.on()) {                  // (integrator 1 is allowed: the Radiosity view sees vacuum)
+            need(cfg->sampling_mode == 0, "a medium is set: it needs sampling_mode 0 (BSDF): the guided modes run through the bounce kernels");
+            need(cfg->fast_tree == 0, "a medium is set: it needs fast_tree 0: frames through a medium always trace the reference's hits");
+        }
         AppConfig& a = c->app.config;                    // every check is above this line: a rejected config changes nothing
         a.spp = cfg->spp; a.max_depth = cfg->max_depth; a.sampling_mode = (SamplingMode)cfg->sampling_mode;
         a.mis_bsdf_fraction = cfg->mis_bsdf_fraction;
@@ -751,6 +755,81 @@ int ptmi_debug_lens_ray(ptmi_ctx* c, int n, const int* px, const int* py, const 
         PTMI_HIP(hipGetLastError());
         PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
         d_o.download(out, 6 * (size_t)n);
+    });
+}
+
+// ---- participating medium --------------------------------------------------------------------------------------------------------
+static Medium mediumOf(const ptmi_medium* p) {
+    Medium m;
+    for (int k = 0; k < 3; k++) { m.lo[k] = p->lo[k]; m.hi[k] = p->hi[k]; m.albedo[k] = p->albedo[k]; }
+    m.sigma_t = p->sigma_t; m.g = p->g;
+    return m;
+}
+static void mediumTo(const Medium& m, ptmi_medium* p) {
+    for (int k = 0; k < 3; k++) { p->lo[k] = m.lo[k]; p->hi[k] = m.hi[k]; p->albedo[k] = m.albedo[k]; }
+    p->sigma_t = m.sigma_t; p->g = m.g;
+}
+void ptmi_default_medium(ptmi_medium* p) {
+    if (p) mediumTo(Medium(), p);
+}
+int ptmi_check_medium(const ptmi_medium* p) {
+    return guarded([&] { need(p != nullptr, "NULL argument"); checkMedium(mediumOf(p)); });
+}
+int ptmi_host_medium_block(const ptmi_medium* p, float* out12) {
+    return guarded([&] {
+        need(p && out12, "NULL argument");
+        float block[kMediumBlockFloats];
+        mediumBlock(mediumOf(p), block);
+        std::memcpy(out12, block, sizeof block);         // a rejected call writes nothing
+    });
+}
+int ptmi_set_medium(ptmi_ctx* c, const ptmi_medium* p) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        MediumState& s = c->app.scene.medium;
+        Medium m;                                        // NULL: no medium
+        if (p) { m = mediumOf(p); checkMedium(m); }
+        if (m.sigma_t > 0.0f) {
+            need(c->app.scene.d_nodes != nullptr, "no scene loaded");
+            const AppConfig& a = c->app.config;
+            need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "medium: the config has a guided sampling_mode, which runs through the bounce kernels");
+            need(!a.fast_tree, "medium: the config has fast_tree 1; frames through a medium always trace the reference's hits");
+            float corners[24];                           // rays now start inside the box: its corners are the farthest such points
+            mediumCorners(m, corners);
+            for (int i = 0; i < 8; i++) c->app.scene.checkQuadOrigin(corners + 3 * i, nullptr, "medium");
+        } else m = Medium();                             // sigma_t 0 is no medium, whatever the other fields say
+        bool same = m.sigma_t == s.m.sigma_t && m.g == s.m.g;       // by value: -0 is the 0 the scene has
+        for (int k = 0; k < 3; k++) same = same && m.lo[k] == s.m.lo[k] && m.hi[k] == s.m.hi[k] && m.albedo[k] == s.m.albedo[k];
+        if (same) return;                                // every check is above this line
+        s.m = m;
+        accumReset(c->app);                              // the feature buffers and the temporal history do not see the medium:
+        c->app.render.dn.image_current = false;          // they stay; the image and the accumulation's variance show the old one
+        c->app.render.dn.variance_valid = false;
+    });
+}
+int ptmi_medium_info(const ptmi_ctx* c, ptmi_medium* out, int* on) {
+    return guarded([&] {
+        need(c != nullptr, "ctx is NULL");
+        const MediumState& s = c->app.scene.medium;
+        if (out) mediumTo(s.m, out);
+        if (on) *on = s.on() ? 1 : 0;
+    });
+}
+int ptmi_debug_medium_call(ptmi_ctx* c, int op, int n, const float* in, float* out) {
+    static_assert(kMediumCallIn == PTMI_MEDIUM_CALL_IN && kMediumCallOut == PTMI_MEDIUM_CALL_OUT && kMediumBlockFloats == PTMI_MEDIUM_BLOCK_FLOATS,
+                  "ptmi.h, device_scene.h and medium.h disagree");
+    return guarded([&] {
+        need(c && in && out, "NULL argument");
+        need(op >= 0 && op <= 3, "op must be 0 .. 3");
+        need(n >= 0, "n must not be negative");
+        if (n == 0) return;
+        PTMI_HIP(hipSetDevice(c->app.device_id));
+        DevBuf<float> d_in((size_t)n * kMediumCallIn), d_out((size_t)n * kMediumCallOut);
+        d_in.upload(in, (size_t)n * kMediumCallIn);
+        launch_debug_medium_call(n, op, d_in.p, d_out.p, c->app.render.stream);
+        PTMI_HIP(hipGetLastError());
+        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
+        d_out.download(out, (size_t)n * kMediumCallOut);
     });
 }
 

@@ -5,6 +5,7 @@
 #include "vertex_normal.h"
 #include "albedo_texture.h"
 #include "lens.h"
+#include "medium.h"
 #include "../../include/ptmi.h"      // PTMI_MATH_*
 
 namespace ptmi {
@@ -515,6 +516,42 @@ __global__ __launch_bounds__(kBlock) void ptmi_debug_lens_ray_k(const float4* __
 void launch_debug_lens_ray(const float4* lens, int n, const int* px, const int* py, const float* r, float* out, hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL(ptmi_debug_lens_ray_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, lens, n, px, py, r, out);
+}
+
+// The functions of medium.h as ptmi_render_nee calls them, once per case (test hook; include/ptmi.h: ptmi_debug_medium_call states
+// the layouts).  Each case carries its own block in front of its ray: 20 floats are 80 bytes, so the block stays 16-byte aligned.
+__global__ __launch_bounds__(kBlock) void ptmi_debug_medium_call_k(int n, int op, const float* __restrict__ in, float* __restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float* a = in + (size_t)i * kMediumCallIn;
+    const float4* medium = reinterpret_cast<const float4*>(a);
+    const f3 o = mk3(a[12], a[13], a[14]), d = mk3(a[15], a[16], a[17]);
+    const float t_end = a[18], u = a[19], g = a[7];
+    float f[kMediumCallOut];
+    for (int c = 0; c < kMediumCallOut; c++) f[c] = 0.0f;
+    if (op == 0) {
+        float t0, t1;
+        f[0] = medium_segment(medium, o, d, t_end, t0, t1) ? 1.0f : 0.0f;
+        f[1] = t0; f[2] = t1;
+        f[3] = medium_transmittance(medium, o, d, t_end);
+    } else if (op == 1) {
+        float tm;
+        f[0] = medium_free_flight(medium, o, d, t_end, u, tm) ? 1.0f : 0.0f;
+        const f3 x = o + tm * d;
+        f[1] = tm; f[2] = x.x; f[3] = x.y; f[4] = x.z;
+    } else if (op == 2) {
+        f[0] = hg_value(g, u);
+    } else {
+        const float c = hg_sample(g, u);
+        const f3 nd = hg_direction(d, c, t_end);
+        f[0] = c; f[1] = hg_value(g, c); f[2] = nd.x; f[3] = nd.y; f[4] = nd.z;
+    }
+    for (int c = 0; c < kMediumCallOut; c++) out[(size_t)i * kMediumCallOut + c] = f[c];
+}
+
+void launch_debug_medium_call(int n, int op, const float* in, float* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ptmi_debug_medium_call_k, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n, op, in, out);
 }
 
 }  // namespace ptmi

@@ -379,7 +379,7 @@ struct AlbedoTable {
 void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, const VertexNormalTable& vn,
                        const AlbedoTable& at, bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp,
                        const int* queue, int n, bool first, const float4* lens /* the thin lens's block (host/lens.cpp); nullptr: the pinhole */,
-                       hipStream_t s);
+                       const float4* medium /* the participating medium's block (host/medium.cpp); nullptr: vacuum */, hipStream_t s);
 
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)
@@ -459,5 +459,8 @@ void launch_debug_albedo(const DeviceScene& sc, const AlbedoTable& at, int n, co
 // ptmi_debug_lens_ray (include/ptmi.h): lens_ray_at (lens.h) over the block `lens` for pixel (px[i], py[i]) and the uniforms
 // r[4i ..] = r3 r4 r1 r2 -> out[6i ..] = o, d
 void launch_debug_lens_ray(const float4* lens, int n, const int* px, const int* py, const float* r, float* out /* 6n */, hipStream_t s);
+// ptmi_debug_medium_call (include/ptmi.h): the functions of medium.h over the block each case carries
+constexpr int kMediumCallIn = 20, kMediumCallOut = 8;
+void launch_debug_medium_call(int n, int op, const float* in /* n * kMediumCallIn, 16-byte aligned */, float* out /* n * kMediumCallOut */, hipStream_t s);
 
 }  // namespace ptmi

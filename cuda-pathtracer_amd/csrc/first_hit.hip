@@ -4,6 +4,7 @@
 #include "vertex_normal.h"
 #include "albedo_texture.h"
 #include "lens.h"
+#include "medium.h"
 
 namespace ptmi {
 
@@ -84,10 +85,31 @@ void launch_render_radiosity(const DeviceScene& sc, const TileMap& tm, const Pat
 // lens (include/ptmi.h: "thin lens"; the block: host/lens.cpp) is a wave-uniform runtime switch too, not a template parameter: with
 // a block the sample's primary ray comes from lens.h - two draws in front of the jitter's, an origin on the lens - and nothing
 // below the camera ray changes.  nullptr: the pinhole.
-template <int MODE, bool HAS_QUADS, bool ENV, int SURF, bool SMOOTH, bool TEX>
+// medium (include/ptmi.h: "participating medium"; the block: host/medium.cpp) is the third such switch: with a block every path ray
+// makes the free-flight draw directly after its walk and may have a medium vertex (mv) in front of the hit or the miss; that vertex
+// goes through the roulette, the light sample and the two draws of the surface vertex below, with the phase function in the place
+// of the BSDF, and every visible shadow ray takes the transmittance of its own segment.  The records are read after the walk,
+// where they are used (medium.h).  MEDIUM is a template parameter and not a fourth runtime switch: as one, it cost 39 of the 144
+// instantiations a wave per SIMD; the MEDIUM = false instantiations keep the parent's registers and waves and
+// give its frames bit for bit (their code differs by the one more kernel argument).
+// the weight of a vertex's light sample of density p towards wi: light_weight of a surface vertex (whose cosine test the caller
+// makes), or the phase function's at a medium vertex (medium.h), which has no such test
+template <int SURF, bool MEDIUM>
+__device__ __forceinline__ bool vertex_light_weight(const float4* __restrict__ medium, bool mv, const f3& d, bool rough, const RoughVertex& rv, const f3& wi,
+                                                    float cos_s, float p, float& w) {
+    if constexpr (MEDIUM) {
+        if (mv) {
+            w = medium_light_weight(medium[1].w, d, wi, p);
+            return true;
+        }
+    }
+    return light_weight<SURF>(rough, rv, wi, cos_s, p, w);
+}
+
+template <int MODE, bool HAS_QUADS, bool ENV, int SURF, bool SMOOTH, bool TEX, bool MEDIUM>
 __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, EmitterTable em, EnvTable ev, SurfaceTable sf, TileMap tm, PathState st, FrameParams fp,
                                                           const int* __restrict__ queue, int n, int first, int next_event, VertexNormalTable vn, AlbedoTable at,
-                                                          const float4* __restrict__ lens) {
+                                                          const float4* __restrict__ lens, const float4* __restrict__ medium) {
     extern __shared__ float4 smem[];
     constexpr bool SPEC = SURF != 0;
     const int idx = blockIdx.x * kBlock + threadIdx.x;
@@ -100,8 +122,8 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     f3 color = first ? mk3(0.0f, 0.0f, 0.0f) : xyz(st.D[slot]);
     LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
     // wave-uniform switches of the ENV, SPEC, SMOOTH and TEX instantiations; without any of them they fold to the NEE kernel
-    // (a lens brings next_event = 0 to the instantiation without any of them, which only next_event = 1 reached before)
-    const bool nee_on = ENV || SPEC || SMOOTH || TEX || lens ? next_event != 0 : true;   // light samples and MIS weights at all
+    // (a lens or a medium brings next_event = 0 to the instantiation without any of them, which only next_event = 1 reached before)
+    const bool nee_on = ENV || SPEC || SMOOTH || TEX || MEDIUM || lens ? next_event != 0 : true;   // light samples and MIS weights at all
     const bool env_on = ENV ? ev.sampled != 0 : false;       // the environment is one of the lights: five draws, selection by q
     const float q = ENV ? ev.q : 0.0f, omq = 1.0f - q;
     for (int frame = 0; frame < fp.n_frames; frame++) {
@@ -126,12 +148,23 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                 float t = 0.0f; int k = -1;
                 const bool hit = first_hit<MODE, HAS_QUADS>(sc, smem, true, ro, rd, 1e-4f, t, k, cn);
                 if (shadow) {                                // visible iff the closest hit is the sampled emitter
-                    if (ENV && s_slot < 0 ? !hit : (hit && k == s_slot)) L = L + contrib;
+                    if (ENV && s_slot < 0 ? !hit : (hit && k == s_slot)) {
+                        if constexpr (MEDIUM) {              // the transmittance of the shadow ray's own segment
+                            const float T = medium_transmittance(medium, so, sd, ENV && s_slot < 0 ? INFINITY : t);
+                            L = L + mk3(contrib.x * T, contrib.y * T, contrib.z * T);
+                        } else L = L + contrib;
+                    }
                     shadow = false;
                     if (SURF == 2 && ended) break;
                     continue;
                 }
-                if (!hit) {                                                               // integrator.h:198-201
+                [[maybe_unused]] bool mv = false;                                         // a medium vertex in front of the hit or the miss
+                [[maybe_unused]] float tm = 0.0f;
+                if constexpr (MEDIUM) {                                                          // one draw per path ray, whatever comes of it
+                    const float u_m = rng_uniform(rng);
+                    mv = medium_free_flight(medium, o, d, hit ? t : INFINITY, u_m, tm);
+                }
+                if (!hit && !mv) {                                                        // integrator.h:198-201
                     if constexpr (ENV) {                                                  // the path ray leaves the scene: E(d)
                         const float4 te = ev.texel[env_texel(ev, d)];
                         const f3 c = tp * xyz(te);
@@ -142,36 +175,39 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                     }
                     break;
                 }
+                if (MEDIUM && mv) k = 0;                                                          // nothing of primitive k is used: x emits nothing, albedo for Kd
                 f3 nrm = xyz(sc.mats[3 * k]);
-                f3 bsdf = xyz(sc.mats[3 * k + 1]);
+                f3 bsdf = MEDIUM && mv ? xyz(medium[2]) : xyz(sc.mats[3 * k + 1]);
                 const f3 Le = xyz(sc.mats[3 * k + 2]);
-                const f3 hp = o + t * d;                                                  // triangle.h:90
-                const float4 pe = depth > 0 && nee_on && !(SPEC && spec_prev) ? em.pdf_area[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                const float pa = pe.w;
-                if (pa > 0.0f) {                                                          // an emitter found by the BSDF sample
-                    float p_l = (pa * (t * t)) / fabsf(dot(xyz(pe), d));                 // the geometric normal: area -> solid angle
-                    if (env_on) p_l = omq * p_l;
-                    const float w = mis_power_heuristic(pb_prev, p_l);
-                    const f3 c = tp * Le;
-                    L = L + mk3(c.x * w, c.y * w, c.z * w);
-                } else L = L + tp * Le;                                                   // integrator.h:204
+                const f3 hp = o + (MEDIUM && mv ? tm : t) * d;                                     // triangle.h:90; the medium vertex x
+                if (!mv) {
+                    const float4 pe = depth > 0 && nee_on && !(SPEC && spec_prev) ? em.pdf_area[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    const float pa = pe.w;
+                    if (pa > 0.0f) {                                                      // an emitter found by the BSDF sample
+                        float p_l = (pa * (t * t)) / fabsf(dot(xyz(pe), d));             // the geometric normal: area -> solid angle
+                        if (env_on) p_l = omq * p_l;
+                        const float w = mis_power_heuristic(pb_prev, p_l);
+                        const f3 c = tp * Le;
+                        L = L + mk3(c.x * w, c.y * w, c.z * w);
+                    } else L = L + tp * Le;                                               // integrator.h:204
+                }
                 if (depth > 2) {                                                          // integrator.h:207-212
                     const float max_tp = fmaxf(tp.x, fmaxf(tp.y, tp.z));
                     const float rr_prob = fminf(max_tp, 0.95f);
                     if (rng_uniform(rng) > rr_prob) break;
                     tp = div_scalar(tp, rr_prob);
                 }
-                if constexpr (TEX) albedo_at<HAS_QUADS>(sc, at, k, hp, bsdf);             // Kd(p) = Kd_k * T, after the roulette
+                if constexpr (TEX) { if (!mv) albedo_at<HAS_QUADS>(sc, at, k, hp, bsdf); }   // Kd(p) = Kd_k * T, after the roulette
                 tp = tp * bsdf;                                                           // integrator.h:215
                 if (length(tp) < 1e-5f) break;                                            // integrator.h:218
-                if constexpr (SMOOTH) vertex_normal<HAS_QUADS>(sc, vn, k, hp, nrm);       // after the throughput exit, not at the hit
+                if constexpr (SMOOTH) { if (!mv) vertex_normal<HAS_QUADS>(sc, vn, k, hp, nrm); }   // after the throughput exit, not at the hit
                 const f3 sn = dot(d, nrm) < 0 ? nrm : -nrm;                               // integrator.h:221-222
-                const f3 o2 = hp + 1e-4f * sn;                                            // integrator.h:266
+                const f3 o2 = MEDIUM && mv ? hp : hp + 1e-4f * sn;                            // integrator.h:266; a medium vertex has no offset
                 [[maybe_unused]] bool rough = false;                                      // SURF = 2: this vertex is rough metal (rv)
                 [[maybe_unused]] RoughVertex rv;
                 if constexpr (SPEC) {
                     const float2 sr = sf.rec[k];
-                    const int kind = __float_as_int(sr.x);
+                    const int kind = mv ? 0 : __float_as_int(sr.x);
                     if (SURF == 2 ? kind == 1 || kind == 2 : kind != 0) {                 // no light sample, no cosine sample
                         float u = 1.0f;
                         if (kind == 2) u = rng_uniform(rng);                              // glass: one draw whatever comes of it
@@ -209,7 +245,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                             const float cos_s = dot(sn, wi);
                             const float p_e = q * te.w;
                             float w;
-                            if (cos_s > 0.0f && p_e > 0.0f && p_e <= FLT_MAX && light_weight<SURF>(rough, rv, wi, cos_s, p_e, w)) {
+                            if (((MEDIUM && mv) || cos_s > 0.0f) && p_e > 0.0f && p_e <= FLT_MAX && vertex_light_weight<SURF, MEDIUM>(medium, mv, d, rough, rv, wi, cos_s, p_e, w)) {
                                 const f3 c = tp * xyz(te);
                                 contrib = mk3(c.x * w, c.y * w, c.z * w);
                                 so = o2; sd = wi; s_slot = -1;
@@ -222,7 +258,7 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                         const f3 wi = es.wi;
                         const float cos_s = dot(sn, wi);
                         float w;
-                        if (cos_s > 0.0f && es.ok && light_weight<SURF>(rough, rv, wi, cos_s, es.p_l, w)) {
+                        if (((MEDIUM && mv) || cos_s > 0.0f) && es.ok && vertex_light_weight<SURF, MEDIUM>(medium, mv, d, rough, rv, wi, cos_s, es.p_l, w)) {
                             const f3 c = tp * xyz(es.rec[5]);
                             contrib = mk3(c.x * w, c.y * w, c.z * w);
                             so = o2; sd = wi; s_slot = es.slot;
@@ -234,6 +270,14 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
                 const float vv = rng_uniform(rng);
                 depth++;
                 if (depth >= fp.max_depth) break;                                         // (no shadow ray pending: NEE needs depth + 1 < max_depth)
+                if (MEDIUM && mv) {                                                       // the phase sample: u is the cosine's draw, vv the azimuth's
+                    const float g = medium[1].w;
+                    const float c = hg_sample(g, u);
+                    pb_prev = hg_value(g, c);                                             // of the sampled cosine itself
+                    d = hg_direction(d, c, vv);
+                    o = hp;
+                    continue;
+                }
                 if constexpr (SURF == 2) {
                     if (rough) {                                                          // u, vv are the contract's u1, u2
                         f3 next;
@@ -270,17 +314,20 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
 
 void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, const VertexNormalTable& vn,
                        const AlbedoTable& at, bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp,
-                       const int* queue, int n, bool first, const float4* lens, hipStream_t s) {
+                       const int* queue, int n, bool first, const float4* lens, const float4* medium, hipStream_t s) {
     if (n <= 0) return;
     first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
         with_bool(env.texel != nullptr, [&](auto with_env) {
             auto launch = [&](auto surf_kinds) {
                 with_bool(vn.rec != nullptr, [&](auto smooth) {
                     with_bool(at.rec != nullptr, [&](auto tex) {
-                        hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value,
-                                                            decltype(surf_kinds)::value, decltype(smooth)::value, decltype(tex)::value>),
-                                           dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, surf, tm, st, fp, queue, n, first ? 1 : 0,
-                                           next_event ? 1 : 0, vn, at, lens);
+                        with_bool(medium != nullptr, [&](auto with_medium) {
+                            hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value,
+                                                                decltype(surf_kinds)::value, decltype(smooth)::value, decltype(tex)::value,
+                                                                decltype(with_medium)::value>),
+                                               dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, surf, tm, st, fp, queue, n, first ? 1 : 0,
+                                               next_event ? 1 : 0, vn, at, lens, medium);
+                        });
                     });
                 });
             };

@@ -21,7 +21,9 @@
 //                                         its SMOOTH instantiation every frame of a scene with a smooth primitive (ptmi_set_vertex_normals;
 //                                         vertex_normal.h), its TEX instantiation every frame of a scene with a textured primitive
 //                                         (ptmi_set_albedo_texture; albedo_texture.h); every instantiation starts its samples on a thin
-//                                         lens where the context has one (ptmi_set_lens; lens.h): an argument, not a parameter
+//                                         lens where the context has one (ptmi_set_lens; lens.h): an argument, not a parameter;
+//                                         its MEDIUM instantiation every frame of a scene with a participating medium
+//                                         (ptmi_set_medium; medium.h)
 //   features.hip       ptmi_features      the feature pass; its SHADED instantiation where ptmi_set_feature_shading asks for a table the context has
 //   debug_hooks.hip    the test hooks
 #include "bounce.h"

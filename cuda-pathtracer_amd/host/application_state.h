@@ -21,6 +21,7 @@
 #include "vertex_normals.h"
 #include "albedo_texture.h"
 #include "lens.h"
+#include "medium.h"
 #include "file_manager.h"
 #include "pbrt_loader.h"
 #include "sensor.h"
@@ -70,6 +71,18 @@ struct AppConfig {                                   // application_state.h:262-
     IntegratorType current_integrator = IntegratorType::PathTracing;   // application_state.h:283
     bool fast_tree = false;                          // new: walk the opt-in 8-wide SAH tree instead of the reference's (csrc/wide_bvh.h)
     bool next_event = false;                         // new: next-event estimation with MIS (include/ptmi.h: ptmi_config.next_event)
+};
+
+// The participating medium of a scene (include/ptmi.h: "participating medium"): the caller's numbers and the device copy of the
+// block (host/medium.cpp).  sigma_t 0 is no medium.
+struct MediumState {
+    Medium m;
+    float4* d_block = nullptr;                       // three float4, allocated by the first run that needs them
+    float h_block[kMediumBlockFloats] = {};          // what d_block holds
+    bool uploaded = false;
+    bool on() const { return m.sigma_t > 0.0f; }
+    void drop() { m = Medium(); }
+    ~MediumState();
 };
 
 struct SceneState {
@@ -184,6 +197,8 @@ struct SceneState {
     AlbedoTable albedoTable() const {
         AlbedoTable t; t.rec = d_albedo_rec; t.texel = d_albedo_texels; t.width = tex_width; t.height = tex_height; t.filter = tex_filter; return t;
     }
+    // participating medium (include/ptmi.h: ptmi_set_medium): its box is in scene coordinates, so it goes with the scene (cleanup)
+    MediumState medium;
     int sweep_max_prims = 64;                        // scenes up to this many primitives use the wave-uniform sweep
     int force_traversal = -1;                        // test/benchmark override (TraversalMode), -1 = automatic
 
@@ -528,5 +543,8 @@ float lensFocus(const ApplicationState& g_state);
 // where it differs from what the device holds, so no setter has to remember it.  nullptr: the pinhole.  Throws LensError where
 // the block is not finite.  Nothing may be in flight on the context's streams (every run ends with a synchronise).
 const float4* lensDeviceBlock(ApplicationState& g_state);
+// The medium block of the scene's medium on the device, uploaded where it differs from what the device holds.  nullptr: no medium.
+// Nothing may be in flight on the context's streams.
+const float4* mediumDeviceBlock(ApplicationState& g_state);
 
 }  // namespace ptmi

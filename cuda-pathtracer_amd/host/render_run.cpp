@@ -63,6 +63,7 @@ struct Run {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> kernel_events = {};   // (e0, e1) around every bounce / NEE launch of a timed run
     uint64_t launches = 0, visits = 0;
     const float4* lens = nullptr;                      // the thin lens's block on the device (lensDeviceBlock); nullptr: the pinhole
+    const float4* medium = nullptr;                    // the medium's block on the device (mediumDeviceBlock); nullptr: vacuum
 
     // the run's next event: from the context's pool, in the order asked for - none is created once the pool is warm
     hipEvent_t event() {
@@ -170,7 +171,8 @@ void prepareCostOrder(Run& run, int order_classes) {
 // a context with an environment (ptmi_set_environment) takes the same route for both values of next_event: the per-lane kernel
 // is the one that looks the map up where a path ray misses; so does a scene with a mirror, glass or rough-metal primitive (ptmi_set_surfaces, ptmi_set_surfaces_rough)
 // or with a smooth primitive (ptmi_set_vertex_normals) or a textured one (ptmi_set_albedo_texture); and a context with a thin
-// lens (ptmi_set_lens): the per-lane kernel is the one that starts a sample on the lens
+// lens (ptmi_set_lens): the per-lane kernel is the one that starts a sample on the lens; and a scene with a participating medium
+// (ptmi_set_medium): the per-lane kernel is the one that samples a free flight after each walk
 void runNeeLaunch(Run& run) {
     ApplicationState& g = run.g;
     const int n = run.queueLength();
@@ -178,7 +180,7 @@ void runNeeLaunch(Run& run) {
     launch_render_nee(g.scene.d_scene, g.scene.d_emitters, g.env.table(g.config.next_event, g.scene.d_emitters.n), g.scene.surfaceTable(),
                       g.scene.vertexNormalTable(), g.scene.albedoTable(), g.scene.hasRough(), g.config.next_event, run.r.tile, run.r.d_state, run.fp,
                       run.pass ? run.chunks[0].d_queue_init : nullptr, n,
-                      run.pass ? run.pass->rule.first != 0 : true, run.lens, run.s);
+                      run.pass ? run.pass->rule.first != 0 : true, run.lens, run.medium, run.s);
     PTMI_HIP(hipGetLastError());
     const hipEvent_t e1 = run.stamp(run.s);
     if (run.timed) run.kernel_events.push_back({e0, e1});
@@ -355,8 +357,9 @@ void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pa
 
     const bool path_tracing = g.config.current_integrator == IntegratorType::PathTracing;
     const bool nee = (g.config.next_event || g.env.present() || g.scene.hasSpecular() || g.scene.hasVertexNormals() || g.scene.hasAlbedoTexture() ||
-                      g.lens.on()) && path_tracing;
+                      g.lens.on() || g.scene.medium.on()) && path_tracing;
     const float4* lens = path_tracing ? lensDeviceBlock(g) : nullptr;   // (the Radiosity view keeps the pinhole) throws before anything is launched
+    const float4* medium = path_tracing ? mediumDeviceBlock(g) : nullptr;   // (the Radiosity view sees vacuum)
     const DeviceScene scene = effectiveScene(g);
     const LaunchOverrides over = LaunchOverrides::fromEnv();
     const LaunchRule rule = planLaunches(g, scene, fp, n_frames, pass != nullptr, nee, over);
@@ -367,6 +370,7 @@ void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pa
     run.chunks = pass ? &r.accum.chunk : r.chunk;
     run.n_chunks = nee ? 0 : pass ? 1 : r.n_chunks;
     run.lens = lens;
+    run.medium = medium;
 
     const hipEvent_t ev_begin = run.record(run.s);
     if (g.config.collect_stats) PTMI_HIP(hipMemsetAsync(r.d_stats, 0, sizeof(StatCounters), run.s));

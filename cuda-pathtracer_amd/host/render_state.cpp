@@ -333,4 +333,22 @@ const float4* lensDeviceBlock(ApplicationState& g) {
     return l.d_block;
 }
 
+// ---- participating medium (include/ptmi.h: ptmi_set_medium) ---------------------------------------------------------------------
+MediumState::~MediumState() { if (d_block) (void)hipFree(d_block); }
+
+const float4* mediumDeviceBlock(ApplicationState& g) {
+    MediumState& s = g.scene.medium;
+    if (!s.on()) return nullptr;
+    float block[kMediumBlockFloats];
+    mediumBlock(s.m, block);
+    PTMI_HIP(hipSetDevice(g.device_id));
+    if (!s.d_block) { s.d_block = (float4*)hipMallocSafe(sizeof block, "d_medium"); s.uploaded = false; }
+    if (!s.uploaded || std::memcmp(block, s.h_block, sizeof block) != 0) {
+        PTMI_HIP(hipMemcpy(s.d_block, block, sizeof block, hipMemcpyHostToDevice));
+        std::memcpy(s.h_block, block, sizeof block);
+        s.uploaded = true;
+    }
+    return s.d_block;
+}
+
 }  // namespace ptmi

@@ -30,6 +30,7 @@ void SceneState::cleanup() {
     if (d_albedo_rec) (void)hipFree(d_albedo_rec);
     if (d_albedo_texels) (void)hipFree(d_albedo_texels);
     d_albedo_rec = d_albedo_texels = nullptr; n_textured = tex_width = tex_height = tex_filter = 0;
+    medium.drop();
     d_emit_rec = d_pdf_area = nullptr; d_emit_cdf = nullptr; d_emitters = EmitterTable();
     h_emit_prim.clear(); h_emit_cdf.clear(); h_emit_normal.clear(); h_pdf_area.clear(); h_emit_total = 0.0f;
     freePacked();

@@ -51,12 +51,22 @@ EXPORTS = [
     "ptmi_check_albedo_texture", "ptmi_set_albedo_texture", "ptmi_albedo_texture_info", "ptmi_debug_albedo",
     "ptmi_check_feature_shading", "ptmi_set_feature_shading", "ptmi_feature_shading",
     "ptmi_check_lens", "ptmi_set_lens", "ptmi_lens", "ptmi_host_lens_block", "ptmi_debug_lens_block", "ptmi_debug_lens_ray",
+    "ptmi_default_medium", "ptmi_check_medium", "ptmi_set_medium", "ptmi_medium_info", "ptmi_host_medium_block", "ptmi_debug_medium_call",
     "ptmi_debug_set_filter_inputs",
     "ptmi_debug_accum_step", "ptmi_debug_order_by_cost",
     "ptmi_debug_cdf_records", "ptmi_debug_filter_pdfs", "ptmi_debug_radiosity_grid",
 ]
 
 FEATURE_TEXTURED_ALBEDO, FEATURE_SHADING_NORMAL = 1, 2      # PTMI_FEATURE_*
+
+
+class Medium(C.Structure):
+    """ptmi_medium: a homogeneous medium inside the axis-aligned box [lo, hi] (include/ptmi.h: "participating medium")"""
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3), ("sigma_t", C.c_float), ("albedo", C.c_float * 3), ("g", C.c_float)]
+
+
+MEDIUM_CALL_IN, MEDIUM_CALL_OUT = 20, 8                     # PTMI_MEDIUM_CALL_*
+MEDIUM_SEGMENT, MEDIUM_FREE_FLIGHT, MEDIUM_HG_VALUE, MEDIUM_HG_SAMPLE = 0, 1, 2, 3      # ptmi_debug_medium_call's ops
 
 
 class Camera(C.Structure):
@@ -289,6 +299,14 @@ def lib():
             L.ptmi_host_lens_block.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_float, C.c_float, vp]
             L.ptmi_debug_lens_block.argtypes = [vp, vp]
             L.ptmi_debug_lens_ray.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        if hasattr(L, "ptmi_set_medium"):              # likewise
+            mp = C.POINTER(Medium)
+            L.ptmi_default_medium.argtypes = [mp]; L.ptmi_default_medium.restype = None
+            L.ptmi_check_medium.argtypes = [mp]
+            L.ptmi_set_medium.argtypes = [vp, mp]
+            L.ptmi_medium_info.argtypes = [vp, mp, ip]
+            L.ptmi_host_medium_block.argtypes = [mp, vp]
+            L.ptmi_debug_medium_call.argtypes = [vp, C.c_int, C.c_int, vp, vp]
         if hasattr(L, "ptmi_set_temporal_moments"):    # likewise
             L.ptmi_set_temporal_moments.argtypes = [vp, C.c_int]
             L.ptmi_get_temporal_moments.argtypes = [vp, ip]
@@ -427,6 +445,30 @@ def default_camera():
 def check_lens(radius, focus_distance):
     """ptmi_check_lens: raises PtmiError with the message of the first rejection; no context and no GPU"""
     _check(lib().ptmi_check_lens(float(radius), float(focus_distance)))
+
+
+def make_medium(lo, hi, sigma_t, albedo=(1.0, 1.0, 1.0), g=0.0):
+    """a Medium of the given numbers; albedo a scalar or three values"""
+    m = Medium()
+    lib().ptmi_default_medium(C.byref(m))
+    a = np.broadcast_to(np.asarray(albedo, np.float32), (3,))
+    for k in range(3):
+        m.lo[k] = float(lo[k]); m.hi[k] = float(hi[k]); m.albedo[k] = float(a[k])
+    m.sigma_t = float(sigma_t); m.g = float(g)
+    return m
+
+
+def check_medium(medium):
+    """ptmi_check_medium: raises PtmiError with the message of the first rejection; no context and no GPU"""
+    _check(lib().ptmi_check_medium(C.byref(medium)))
+
+
+def host_medium_block(medium):
+    """ptmi_host_medium_block: the three records (3, 4) float32 of a medium - (lo, sigma_t) (hi, g) (albedo, 0); no context and
+    no GPU"""
+    out = np.zeros((3, 4), np.float32)
+    _check(lib().ptmi_host_medium_block(C.byref(medium), out.ctypes.data))
+    return out
 
 
 def host_lens_block(cam, width, height, radius, focus_distance):
@@ -938,6 +980,34 @@ class Renderer:
             raise ValueError("px and py must be (n,) and r (n, 4)")
         out = np.zeros((len(px), 6), np.float32)
         self._ck(self.L.ptmi_debug_lens_ray(self.h, len(px), px.ctypes.data, py.ctypes.data, r.ctypes.data, out.ctypes.data))
+        return out
+
+    # --- participating medium (include/ptmi.h: "participating medium") ---
+    def set_medium(self, lo, hi=None, sigma_t=0.0, albedo=(1.0, 1.0, 1.0), g=0.0):
+        """ptmi_set_medium: a homogeneous medium of extinction sigma_t per scene unit inside the box [lo, hi] (scene coordinates),
+        with a single-scattering albedo (a scalar or r, g, b) and the Henyey-Greenstein asymmetry g.  set_medium(None), or sigma_t
+        0, drops it.  lo may also be a Medium.  The scene's: a scene load drops it.  The feature pass, the Radiosity view and the
+        solver ignore it; a changed medium restarts an accumulation."""
+        if lo is None:
+            self._ck(self.L.ptmi_set_medium(self.h, None))
+            return
+        m = lo if isinstance(lo, Medium) else make_medium(lo, hi, sigma_t, albedo, g)
+        self._ck(self.L.ptmi_set_medium(self.h, C.byref(m)))
+
+    def medium(self):
+        """ptmi_medium_info: the scene's Medium, or None without one"""
+        m, on = Medium(), C.c_int()
+        self._ck(self.L.ptmi_medium_info(self.h, C.byref(m), C.byref(on)))
+        return m if on.value else None
+
+    def debug_medium_call(self, op, inputs):
+        """ptmi_debug_medium_call: op (MEDIUM_*) of the kernel's medium functions on the cases inputs (n, MEDIUM_CALL_IN) float32 -
+        the block, o, d, t_end, u.  Returns (n, MEDIUM_CALL_OUT) float32."""
+        a = np.ascontiguousarray(inputs, np.float32)
+        if a.ndim != 2 or a.shape[1] != MEDIUM_CALL_IN:
+            raise ValueError("inputs must be (n, %d)" % MEDIUM_CALL_IN)
+        out = np.zeros((len(a), MEDIUM_CALL_OUT), np.float32)
+        self._ck(self.L.ptmi_debug_medium_call(self.h, int(op), len(a), a.ctypes.data, out.ctypes.data))
         return out
 
     def camera_frame(self):

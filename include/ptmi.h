@@ -1338,6 +1338,93 @@ int  ptmi_lens(const ptmi_ctx*, float* radius, float* focus_distance);   /* eith
 int  ptmi_debug_lens_block(ptmi_ctx*, float* out24);
 int  ptmi_debug_lens_ray(ptmi_ctx*, int n, const int* px, const int* py, const float* r /* 4n */, float* out /* 6n */);
 
+/* ---- participating medium: a homogeneous fog box (new in this implementation) --------------------------------------------------
+ * Without this section every ray travels through vacuum.  ptmi_set_medium gives the loaded SCENE one homogeneous medium inside an
+ * axis-aligned box [lo, hi] in scene coordinates: extinction sigma_t per scene unit (achromatic, so one distance sample serves
+ * all three channels), single-scattering albedo per channel in [0, 1], and the Henyey-Greenstein asymmetry g, |g| <= 0.9, g > 0
+ * scattering forward.  The medium belongs to the scene, because its box is in scene coordinates: a scene load drops it, as it
+ * drops the surface table.
+ *
+ * sigma_t == 0, or a NULL medium, is NO MEDIUM (not a medium of density 0): no extra draw, no block, and the frame takes the
+ * route and the launch counts it takes without this section and comes out bit for bit the same (a next-event frame runs the
+ * per-lane kernel's instantiation without the medium, which has one more, unread, argument).  A scene with a medium renders both values
+ * of next_event through the per-lane kernel of next-event estimation (one launch), as a context with a lens does; frames,
+ * batches, ptmi_select_frame, passes and tiled contexts work as they do without one.
+ * WHAT THE MEDIUM DOES NOT TOUCH.  ptmi_render_features, the Radiosity view (integrator = 1) and ptmi_run_radiosity_solver ignore
+ * the medium: the guides of the filters and of the temporal step stay those of the surfaces.  The guided sampling modes and
+ * fast_tree are refused with a medium, by ptmi_set_medium and by ptmi_set_config.
+ *
+ * THE MEDIUM BLOCK, three records of four floats, the caller's numbers unchanged: (lo, sigma_t) (hi, g) (albedo, 0).
+ * Everything below is binary32, every operation rounded, no fused multiply-add, unless binary64 is named.
+ * THE SEGMENT [t0, t1] of a ray (o, d) that ends at t_end (the walk's t at a hit, +inf at a miss):
+ *       t0 = 0      t1 = t_end      inside = true
+ *       per axis a = x, y, z in this order:
+ *         d_a != 0:   ta = (lo_a - o_a) / d_a      tb = (hi_a - o_a) / d_a           (IEEE divisions)
+ *                     near = fminf(ta, tb)         far = fmaxf(ta, tb)
+ *                     if (near > t0) t0 = near     if (far < t1) t1 = far
+ *         d_a == 0:   if not (lo_a <= o_a and o_a <= hi_a) inside = false
+ *       the segment is non-empty iff inside and t1 > t0
+ * TRANSMITTANCE  T = ptmi_expf of -(sigma_t * (t1 - t0)) for a non-empty segment; an empty one has T = 1 exactly.
+ * FREE FLIGHT.  With a medium every path ray makes ONE draw u_m directly after its walk returns, before anything else happens at
+ * the vertex, whether or not the ray meets the box; shadow rays make none.
+ *       s = -((float)l) / sigma_t, l = ptmi_log_d of (double)u_m     tm = t0 + s
+ * If the segment is non-empty and tm < t1 the ray has a MEDIUM VERTEX at x = o + tm * d.  Otherwise the hit or the miss is
+ * processed exactly as without a medium, with weight 1: the probability of passing is the transmittance.
+ * THE PHASE FUNCTION, binary64 from the float inputs, +, -, *, / and the IEEE square root only, rounded once to float:
+ *       hg(c):  c = fminf(fmaxf(c, -1), 1);  g == 0: (float)(1 / (4 pi))
+ *               else  t = (1 + g * g) - (2 * g) * c       (float)((1 - g * g) / ((4 pi) * (t * sqrt(t))))
+ *       the sampled cosine of a uniform u:   g == 0: (float)(1 - 2 * u)
+ *               else  s = 2 * u - 1      den = 1 + g * s      g2 = g * g
+ *                     num = ((s + (g * (s * s + 3)) * 0.5) + g2 * s) + (g2 * g) * ((s * s - 1) * 0.5)
+ *                     c = num / (den * den)                          (float)min(max(c, -1), 1)
+ *       (the textbook inversion ((1 + g^2) - q^2) / (2 g), q = (1 - g^2) / (1 - g + 2 g u), expanded over s: the same rational
+ *       function without its difference of two numbers near 1, which below |g| ~ 1e-8 returned the cosine 0 for every u)
+ * THE MEDIUM VERTEX follows the order of a surface vertex of "next-event estimation":
+ *   1. nothing is emitted;
+ *   2. the roulette at depth > 2 on tp, then tp = tp * albedo and the length(tp) < 1e-5f exit;
+ *   3. the light sample, with the same three draws (five with a sampled environment) under the same condition
+ *      nee_on && depth + 1 < max_depth && (emitters or a sampled environment): the emitter or the environment is sampled from x
+ *      itself - no offset, no test of a cosine at the vertex - and with wi the unit direction and p_l the sample's density
+ *            ph = hg(dot(d, wi))      w = (ph / p_l) * mis_power_heuristic(p_l, ph)      contrib = (tp * Le) * w
+ *      the shadow ray starts at x;
+ *   4. the phase sample with the two draws u, v; depth++ and the depth exit; then
+ *            c = the sampled cosine of u      s = sqrtf(fmaxf(0, 1 - c * c))      phi = (float)(2 pi v), the product in binary64
+ *            (sp, cp) = ptmi_sincosf of phi   (T, B) the tangent frame of "rough metal" about d
+ *            d' = unit_vector(((s * cp) * T + (s * sp) * B) + c * d)      o' = x
+ *      pb_prev = hg(c) of the sampled cosine itself (not of a recomputed dot product), and the path ray is no specular one: the
+ *      next hit or miss takes its MIS weight from pb_prev, as after a cosine sample.
+ * SHADOW RAYS.  Every shadow ray, from a surface vertex or a medium vertex, multiplies its contribution by T of its own segment
+ * when it is found visible: L = L + contrib * T, with t_end the shadow walk's t for an emitter and +inf for the environment.
+ * Both strategies weigh with the same pair (pb, p_l): the transmittance to the next vertex is common to both and cancels against
+ * the free-flight density, so the weights of a path sum to 1.
+ *
+ * ptmi_check_medium: host only.  PTMI_E_INVALID with a message of its own for: a field that is not finite, lo >= hi on an axis,
+ * sigma_t < 0, an albedo outside [0, 1], |g| > 0.9.
+ * ptmi_set_medium: NULL, or sigma_t == 0 (checked like any other), drops the medium.  Otherwise PTMI_E_INVALID with nothing
+ * changed: what ptmi_check_medium rejects; no scene loaded; a config with sampling_mode != 0 or fast_tree = 1; and, with quads
+ * in the scene, a corner of the box that fails the bound every ray origin outside the scene is held to (rays now start inside
+ * the box).  A medium other than the scene's restarts an accumulation; the feature buffers and the temporal history stay.
+ * ptmi_medium_info: the medium in force (ptmi_default_medium's values without one) and whether there is one.
+ * ptmi_host_medium_block: the block, 12 floats; host only; PTMI_E_INVALID, out12 untouched: what ptmi_check_medium rejects.
+ * ptmi_debug_medium_call: test hook; the kernel's own functions (csrc/medium.h) once per case over the block of the GIVEN medium
+ * in `in`, PTMI_MEDIUM_CALL_IN floats per case, PTMI_MEDIUM_CALL_OUT floats out per case (zero where an op writes nothing):
+ *       in[0..11] the block   in[12..14] o   in[15..17] d   in[18] t_end   in[19] u (u_m, the cosine, or the uniform)
+ *   op 0  segment and T:  out = nonempty (0 | 1), t0, t1, T          (t0, t1 as the loop leaves them, also where empty)
+ *   op 1  free flight:    out = vertex (0 | 1), tm, x
+ *   op 2  hg value:       out = hg(u) with g = in[7]
+ *   op 3  hg sample:      out = the sampled cosine of u, hg of it, d' about d with v = in[18]
+ * u_m must lie in [2^-33, 1], a uniform's range, and sigma_t > 0. */
+typedef struct { float lo[3], hi[3]; float sigma_t; float albedo[3]; float g; } ptmi_medium;
+#define PTMI_MEDIUM_BLOCK_FLOATS 12
+#define PTMI_MEDIUM_CALL_IN  20
+#define PTMI_MEDIUM_CALL_OUT 8
+void ptmi_default_medium(ptmi_medium*);                    /* the unit box [0, 1]^3, sigma_t 0 (no medium), albedo 1, g 0 */
+int  ptmi_check_medium(const ptmi_medium*);
+int  ptmi_set_medium(ptmi_ctx*, const ptmi_medium* /* NULL drops it */);
+int  ptmi_medium_info(const ptmi_ctx*, ptmi_medium* out, int* on);   /* either may be NULL */
+int  ptmi_host_medium_block(const ptmi_medium*, float* out12);
+int  ptmi_debug_medium_call(ptmi_ctx*, int op, int n, const float* in /* n * PTMI_MEDIUM_CALL_IN */, float* out /* n * PTMI_MEDIUM_CALL_OUT */);
+
 /* test hook: the inputs of ptmi_denoise, ptmi_denoise_variance (source = 1) and ptmi_temporal_accumulate, given instead of
  * rendered, so that every data-dependent decision of their kernels can be reached on constructed images.  n = width x height
  * of the current resolution; all arrays local row-major like ptmi_read_image.  The call

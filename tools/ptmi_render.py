@@ -34,6 +34,9 @@
   python tools/ptmi_render.py --scene ... --aperture 0.3 --focus-at 400,300 --spp 64 --out dof.png
                                (a thin lens of radius 0.3 scene units, focused on what pixel (400, 300) shows - x from the left, y
                                 from the bottom; --focus D names the distance along the optical axis instead; neither: the look-at point)
+  python tools/ptmi_render.py --scene ... --fog 0.15 --fog-albedo 0.9,0.9,0.95 --fog-g 0.6 --next-event --spp 64 --out fog.png
+                               (a homogeneous medium of extinction 0.15 per scene unit filling the scene's bounds, scattering
+                                forward; --fog-box=x0,y0,z0,x1,y1,z1 names another box.  The denoisers' guides do not see the fog)
 """
 import argparse
 import os
@@ -119,6 +122,10 @@ def main():
     ap.add_argument("--focus", type=float, default=None, metavar="D", help="with --aperture: the focus distance along the optical axis "
                     "(default: the distance to the look-at point)")
     ap.add_argument("--focus-at", default=None, metavar="X,Y", help="with --aperture: focus on what the pixel shows (x from the left, y from the bottom)")
+    ap.add_argument("--fog", type=float, default=0.0, metavar="SIGMA", help="participating medium: the extinction per scene unit (0: none)")
+    ap.add_argument("--fog-albedo", default="1,1,1", metavar="R,G,B", help="with --fog: the single-scattering albedo, each in [0, 1]")
+    ap.add_argument("--fog-g", type=float, default=0.0, metavar="G", help="with --fog: the Henyey-Greenstein asymmetry, |G| <= 0.9, > 0 forward")
+    ap.add_argument("--fog-box", default=None, metavar="x0,y0,z0,x1,y1,z1", help="with --fog: the medium's box (default: the scene's bounds, padded by a thousandth of their largest extent; write --fog-box=-1,0,... where it starts with a minus)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="PNG file (top row first, like the reference's Save PNG)")
     a = ap.parse_args()
@@ -239,6 +246,25 @@ def main():
         except ptmi.PtmiError as e:
             ap.error(f"--aperture / --focus: {e}")
         print("lens: radius %g, focus distance %g" % r.lens())
+    if a.fog != 0:
+        try:
+            albedo = [float(x) for x in a.fog_albedo.split(",")]
+            box = None if a.fog_box is None else [float(x) for x in a.fog_box.split(",")]
+        except ValueError:
+            ap.error("--fog-albedo takes R,G,B and --fog-box x0,y0,z0,x1,y1,z1")
+        if len(albedo) != 3 or (box is not None and len(box) != 6):
+            ap.error("--fog-albedo takes R,G,B and --fog-box x0,y0,z0,x1,y1,z1")
+        if box is None:                                # the scene's bounds, padded: a flat scene still has a box, and geometry
+            b = r.scene_bvh()                          # on the bounds lies inside the medium and not on its face
+            lo, hi = b["bmin"][0].astype(float), b["bmax"][0].astype(float)
+            pad = 1e-3 * max(float((hi - lo).max()), 1e-3)
+            box = [float(x) for x in lo - pad] + [float(x) for x in hi + pad]
+        try:
+            r.set_medium(box[:3], box[3:], a.fog, albedo, a.fog_g)
+        except ptmi.PtmiError as e:
+            ap.error(f"--fog: {e}")
+        m = r.medium()
+        print("fog: sigma_t %g, albedo (%g, %g, %g), g %g, box (%g, %g, %g) - (%g, %g, %g)" % ((m.sigma_t,) + tuple(m.albedo) + (m.g,) + tuple(m.lo) + tuple(m.hi)))
     if a.orbit > 0:
         if a.variance_png and not (a.variance_guided and a.denoise is not None):
             ap.error("--variance-png needs --denoise --variance-guided")
