@@ -36,6 +36,15 @@ int guarded(Fn&& fn) {
     catch (...) { g_last_error = "unknown error"; return PTMI_E_INVALID; }
 }
 void need(bool ok, const char* what) { if (!ok) throw ArgError(what); }
+void needNone(const std::string& refusal) { if (!refusal.empty()) throw ArgError(refusal); }
+void needRoute(const ptmi_ctx* c, RouteFeature f) {   // a per-lane feature is being switched on: the config as it is must allow it (host/route_rule.h)
+    needNone(featureRefusal(f, (int)c->app.config.current_integrator, (int)c->app.config.sampling_mode, c->app.config.fast_tree));
+}
+void needScene(ptmi_ctx* c) {                          // what the setter of a per-primitive table begins with
+    need(c != nullptr, "ctx is NULL");
+    need(c->app.scene.d_nodes != nullptr, "no scene loaded");
+    PTMI_HIP(hipSetDevice(c->app.device_id));
+}
 
 // a call that changes what a frame would show: the accumulation restarts, the feature buffers go stale and the temporal
 // history empties (ptmi_set_camera keeps the history: reprojecting it into the new view is the temporal step's job)
@@ -74,10 +83,21 @@ void run_vote_hook(ptmi_ctx* c, int n, const float* in, int in_per, const int* l
     PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
     d_o.download(out, (size_t)out_per * n);
 }
+std::vector<Primitive> prims_from_arrays(int n, const int* type, const float* verts, const float* normal, const float* bsdf, const float* Le) {
+    need(type && verts && normal && bsdf && Le, "NULL argument");
+    need(n > 0, "n must be positive");
+    std::vector<Primitive> prims((size_t)n);
+    for (int i = 0; i < n; i++) {
+        Primitive& p = prims[i];
+        need(type[i] == 0 || type[i] == 1, "type must be 0 (triangle) or 1 (quad)");
+        p.type = type[i] ? PRIM_QUAD : PRIM_TRIANGLE;
+        for (int k = 0; k < 4; k++) p.v[k] = v3(verts + ((size_t)i * 4 + k) * 3);
+        if (p.type == PRIM_TRIANGLE) p.v[3] = mk3(0, 0, 0);
+        p.normal = v3(normal + (size_t)i * 3); p.bsdf = v3(bsdf + (size_t)i * 3); p.Le = v3(Le + (size_t)i * 3);
+    }
+    return prims;
+}
 }  // namespace
-
-static std::vector<Primitive> prims_from_arrays(int n, const int* type, const float* verts, const float* normal,
-                                                const float* bsdf, const float* Le);
 
 extern "C" {
 
@@ -161,21 +181,6 @@ static void scene_get_bvh(const SceneState& s, float* bmin, float* bmax, int* le
         }
         if (indices) std::memcpy(indices, s.bvh_indices.data(), s.bvh_indices.size() * sizeof(int));
     }
-}
-static std::vector<Primitive> prims_from_arrays(int n, const int* type, const float* verts, const float* normal,
-                                                const float* bsdf, const float* Le) {
-    need(type && verts && normal && bsdf && Le, "NULL argument");
-    need(n > 0, "n must be positive");
-    std::vector<Primitive> prims((size_t)n);
-    for (int i = 0; i < n; i++) {
-        Primitive& p = prims[i];
-        need(type[i] == 0 || type[i] == 1, "type must be 0 (triangle) or 1 (quad)");
-        p.type = type[i] ? PRIM_QUAD : PRIM_TRIANGLE;
-        for (int k = 0; k < 4; k++) p.v[k] = v3(verts + ((size_t)i * 4 + k) * 3);
-        if (p.type == PRIM_TRIANGLE) p.v[3] = mk3(0, 0, 0);
-        p.normal = v3(normal + (size_t)i * 3); p.bsdf = v3(bsdf + (size_t)i * 3); p.Le = v3(Le + (size_t)i * 3);
-    }
-    return prims;
 }
 
 int ptmi_scene_info(const ptmi_ctx* c, int* n_prims, int* n_tris, int* n_quads, int* n_bvh_nodes, int* bvh_depth) {
@@ -429,39 +434,7 @@ int ptmi_set_config(ptmi_ctx* c, const ptmi_config* cfg) {
         need(cfg->segments_per_launch >= 0, "segments_per_launch must be >= 0");
         need(cfg->streams >= 0 && cfg->streams <= RenderState::kMaxChunks, "streams must be 0..4");
         need(cfg->next_event == 0 || cfg->next_event == 1, "next_event must be 0 or 1");
-        if (cfg->next_event) {
-            need(cfg->integrator == 0, "next_event needs integrator 0 (PathTracing): the Radiosity view traces first hits only");
-            need(cfg->sampling_mode == 0, "next_event needs sampling_mode 0 (BSDF): MIS against the guided modes' grid pdf is not implemented");
-            need(cfg->fast_tree == 0, "next_event needs fast_tree 0: NEE frames always trace the reference's hits");
-        }
-        if (c->app.env.present()) {
-            need(cfg->integrator == 0, "an environment is set: it needs integrator 0 (PathTracing): the Radiosity view traces first hits only");
-            need(cfg->sampling_mode == 0, "an environment is set: it needs sampling_mode 0 (BSDF): the guided modes do not look the environment up");
-            need(cfg->fast_tree == 0, "an environment is set: it needs fast_tree 0: environment frames always trace the reference's hits");
-        }
-        if (c->app.scene.hasSpecular()) {
-            need(cfg->integrator == 0, "specular surfaces are set: they need integrator 0 (PathTracing): the Radiosity view traces first hits only");
-            need(cfg->sampling_mode == 0, "specular surfaces are set: they need sampling_mode 0 (BSDF): the guided modes sample a diffuse lobe at every vertex");
-            need(cfg->fast_tree == 0, "specular surfaces are set: they need fast_tree 0: specular frames always trace the reference's hits");
-        }
-        if (c->app.scene.hasVertexNormals()) {
-            need(cfg->integrator == 0, "vertex normals are set: they need integrator 0 (PathTracing): the Radiosity view shades nothing");
-            need(cfg->sampling_mode == 0, "vertex normals are set: they need sampling_mode 0 (BSDF): the guided modes' grids lie about the stored normal");
-            need(cfg->fast_tree == 0, "vertex normals are set: they need fast_tree 0: frames with vertex normals always trace the reference's hits");
-        }
-        if (c->app.scene.hasAlbedoTexture()) {
-            need(cfg->integrator == 0, "an albedo texture is set: it needs integrator 0 (PathTracing): the Radiosity view ignores the texture");
-            need(cfg->sampling_mode == 0, "an albedo texture is set: it needs sampling_mode 0 (BSDF): the guided modes run through the bounce kernels");
-            need(cfg->fast_tree == 0, "an albedo texture is set: it needs fast_tree 0: textured frames always trace the reference's hits");
-        }
-        if (c->app.lens.on()) {                          // (integrator 1 is allowed: the Radiosity view keeps the pinhole)
-            need(cfg->sampling_mode == 0, "a lens is set: it needs sampling_mode 0 (BSDF): the guided modes run through the bounce kernels");
-            need(cfg->fast_tree == 0, "a lens is set: it needs fast_tree 0: frames through a lens always trace the reference's hits");
-        }
-        if (c->app.scene.medium.on()) {                  // (integrator 1 is allowed: the Radiosity view sees vacuum)
-            need(cfg->sampling_mode == 0, "a medium is set: it needs sampling_mode 0 (BSDF): the guided modes run through the bounce kernels");
-            need(cfg->fast_tree == 0, "a medium is set: it needs fast_tree 0: frames through a medium always trace the reference's hits");
-        }
+        needNone(configRefusal(presentFeatures(c->app, cfg->next_event != 0), cfg->integrator, cfg->sampling_mode, cfg->fast_tree));
         AppConfig& a = c->app.config;                    // every check is above this line: a rejected config changes nothing
         a.spp = cfg->spp; a.max_depth = cfg->max_depth; a.sampling_mode = (SamplingMode)cfg->sampling_mode;
         a.mis_bsdf_fraction = cfg->mis_bsdf_fraction;
@@ -494,10 +467,7 @@ int ptmi_set_environment(ptmi_ctx* c, int width, int height, const float* rgb, c
         need(c != nullptr, "ctx is NULL");
         PTMI_HIP(hipSetDevice(c->app.device_id));
         if (rgb) {
-            const AppConfig& a = c->app.config;
-            need(a.current_integrator == IntegratorType::PathTracing, "environment: the config has integrator 1 (Radiosity), which traces first hits only");
-            need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "environment: the config has a guided sampling_mode, which does not look the environment up");
-            need(!a.fast_tree, "environment: the config has fast_tree 1; environment frames always trace the reference's hits");
+            needRoute(c, kRouteEnvironment);
             c->app.env.set(width, height, rgb, env_params(p));       // every check is done before anything changes
         } else c->app.env.drop();
         viewChanged(c->app);                                         // other light: the temporal history holds another image
@@ -530,21 +500,14 @@ int ptmi_check_surfaces(int n_prims, const int* kind, const float* ior) {
 }
 // ptmi_set_surfaces (rough_api false: kinds 0 .. 2, no roughness) and ptmi_set_surfaces_rough
 static void setSurfacesChecked(ptmi_ctx* c, int n_prims, const int* kind, const float* ior, const float* roughness, bool rough_api) {
-    need(c != nullptr, "ctx is NULL");
-    need(c->app.scene.d_nodes != nullptr, "no scene loaded");
-    PTMI_HIP(hipSetDevice(c->app.device_id));
+    needScene(c);
     if (kind) {
         need(n_prims == (int)c->app.scene.h_primitives.size(), "n_prims does not match the loaded scene");
         if (rough_api) checkSurfacesRough(n_prims, kind, ior, roughness);
         else checkSurfaces(n_prims, kind, ior);
         bool specular = false;
         for (int i = 0; i < n_prims; i++) specular = specular || kind[i] != kSurfaceDiffuse;
-        if (specular) {
-            const AppConfig& a = c->app.config;
-            need(a.current_integrator == IntegratorType::PathTracing, "surfaces: the config has integrator 1 (Radiosity), which traces first hits only");
-            need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "surfaces: the config has a guided sampling_mode, which samples a diffuse lobe at every vertex");
-            need(!a.fast_tree, "surfaces: the config has fast_tree 1; specular frames always trace the reference's hits");
-        }
+        if (specular) needRoute(c, kRouteSurfaces);
     }
     c->app.scene.setSurfaces(kind, ior, roughness);              // every check is done before anything changes
     viewChanged(c->app);                                         // other materials: the temporal history holds another image
@@ -594,20 +557,13 @@ int ptmi_host_classify_vertex_normals(int n_prims, const int* type, const float*
 }
 int ptmi_set_vertex_normals(ptmi_ctx* c, int n_prims, const float* normals) {
     return guarded([&] {
-        need(c != nullptr, "ctx is NULL");
-        need(c->app.scene.d_nodes != nullptr, "no scene loaded");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
+        needScene(c);
         std::vector<unsigned char> smooth;
         int smooth_count = 0;
         if (normals) {
             checkVertexNormals(c->app.scene.h_primitives, n_prims, normals);
             smooth_count = classifyVertexNormals(c->app.scene.h_primitives, normals, smooth);
-            if (smooth_count > 0) {
-                const AppConfig& a = c->app.config;
-                need(a.current_integrator == IntegratorType::PathTracing, "vertex normals: the config has integrator 1 (Radiosity), which shades nothing");
-                need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "vertex normals: the config has a guided sampling_mode, whose grids lie about the stored normal");
-                need(!a.fast_tree, "vertex normals: the config has fast_tree 1; frames with vertex normals always trace the reference's hits");
-            }
+            if (smooth_count > 0) needRoute(c, kRouteVertexNormals);
         }
         c->app.scene.setVertexNormals(normals, smooth, smooth_count);   // every check is done before anything changes
         viewChanged(c->app);                                         // other shading: the temporal history holds another image
@@ -625,17 +581,10 @@ int ptmi_check_albedo_texture(int width, int height, const float* texels, int fi
 }
 int ptmi_set_albedo_texture(ptmi_ctx* c, int width, int height, const float* texels, int filter, int n_prims, const float* uv, const int* textured) {
     return guarded([&] {
-        need(c != nullptr, "ctx is NULL");
-        need(c->app.scene.d_nodes != nullptr, "no scene loaded");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
+        needScene(c);
         if (texels) {
             checkAlbedoTexture(c->app.scene.h_primitives, width, height, texels, filter, n_prims, uv, textured);
-            if (countTextured(n_prims, textured) > 0) {
-                const AppConfig& a = c->app.config;
-                need(a.current_integrator == IntegratorType::PathTracing, "albedo texture: the config has integrator 1 (Radiosity), which ignores the texture");
-                need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "albedo texture: the config has a guided sampling_mode, which runs through the bounce kernels");
-                need(!a.fast_tree, "albedo texture: the config has fast_tree 1; textured frames always trace the reference's hits");
-            }
+            if (countTextured(n_prims, textured) > 0) needRoute(c, kRouteAlbedoTexture);
         }
         c->app.scene.setAlbedoTexture(width, height, texels, filter, uv, textured);   // every check is done before anything changes
         viewChanged(c->app);                                         // other colours: the temporal history holds another image
@@ -710,12 +659,10 @@ int ptmi_set_lens(ptmi_ctx* c, float radius, float focus_distance) {
         if (radius == 0.0f && !(focus_distance > 0.0f) && !std::isnan(focus_distance)) focus = 0.0f;   // "no lens": the focus is the default again
         else checkLens(radius, focus_distance);
         if (radius > 0.0f) {
-            const AppConfig& a = c->app.config;
-            need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "lens: the config has a guided sampling_mode, which runs through the bounce kernels");
-            need(!a.fast_tree, "lens: the config has fast_tree 1; frames through a lens always trace the reference's hits");
+            needRoute(c, kRouteLens);
             if (c->app.render.tile.width > 0) {          // a resolution is set: the block over the camera as it is now must be finite
                 float frame[12], block[kLensBlockFloats];
-                cameraFrame12(c->app.render.h_camera, a.orbit, frame);
+                cameraFrame12(c->app.render.h_camera, c->app.config.orbit, frame);
                 lensBlock(frame, c->app.render.tile.width, c->app.render.tile.height, radius, focus, block);
             }
         }
@@ -791,9 +738,7 @@ int ptmi_set_medium(ptmi_ctx* c, const ptmi_medium* p) {
         if (p) { m = mediumOf(p); checkMedium(m); }
         if (m.sigma_t > 0.0f) {
             need(c->app.scene.d_nodes != nullptr, "no scene loaded");
-            const AppConfig& a = c->app.config;
-            need(a.sampling_mode == SamplingMode::SAMPLING_BSDF, "medium: the config has a guided sampling_mode, which runs through the bounce kernels");
-            need(!a.fast_tree, "medium: the config has fast_tree 1; frames through a medium always trace the reference's hits");
+            needRoute(c, kRouteMedium);
             float corners[24];                           // rays now start inside the box: its corners are the farthest such points
             mediumCorners(m, corners);
             for (int i = 0; i < 8; i++) c->app.scene.checkQuadOrigin(corners + 3 * i, nullptr, "medium");

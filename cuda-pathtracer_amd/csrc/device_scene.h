@@ -369,17 +369,17 @@ struct AlbedoTable {
     const float4* texel = nullptr;
     int width = 0, height = 0, filter = 0;
 };
-// fp.n_frames x spp samples per queued pixel.  env.texel == nullptr, surf.rec == nullptr, vn.rec == nullptr and at.rec == nullptr:
+// What the per-lane features (host/route_rule.h) hand the per-lane kernel; an absent table or block selects the instantiation without its code
+struct PerLaneTables {
+    EnvTable env; SurfaceTable surf; VertexNormalTable vn; AlbedoTable at;
+    bool rough = false;                // surf holds a rough-metal record (SURF = 2; else the delta kinds' SURF = 1, which never reads a kind 3)
+    const float4 *lens = nullptr, *medium = nullptr;   // the thin lens's block (host/lens.cpp) and the medium's (host/medium.cpp); nullptr: the pinhole, vacuum
+};
+// fp.n_frames x spp samples per queued pixel.  t.env.texel == nullptr, t.surf.rec == nullptr, t.vn.rec == nullptr and t.at.rec == nullptr:
 // the NEE kernel exactly as it was; that instantiation IGNORES next_event (the host routes a frame here only when it is set, and
-// the switch folds to true).  Else the ENV, SPEC, SMOOTH and / or TEX instantiation, which reads next_event and runs either
-// estimator, looks the map up where a path ray misses, continues a path through mirror and glass, shades a smooth primitive's
-// vertex with the interpolated normal (csrc/vertex_normal.h) and multiplies a textured primitive's Kd by the image's value at the
-// vertex (csrc/albedo_texture.h).  rough: the table holds a rough-metal record (SURF = 2; else the delta kinds' SURF = 1, which
-// never reads a kind 3).
-void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, const VertexNormalTable& vn,
-                       const AlbedoTable& at, bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp,
-                       const int* queue, int n, bool first, const float4* lens /* the thin lens's block (host/lens.cpp); nullptr: the pinhole */,
-                       const float4* medium /* the participating medium's block (host/medium.cpp); nullptr: vacuum */, hipStream_t s);
+// the switch folds to true).  Else the ENV, SPEC, SMOOTH and / or TEX instantiation, which reads next_event and runs either estimator.
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const PerLaneTables& t, bool next_event, const TileMap& tm, const PathState& st,
+                       const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s);
 
 size_t bounce_lds_bytes(const DeviceScene& sc);
 size_t bounce_lds_bytes_wide(const DeviceScene& sc);      // dynamic LDS of the 8-wide walks for this scene (top of the tree + stacks)

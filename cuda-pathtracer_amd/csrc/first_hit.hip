@@ -312,27 +312,26 @@ __global__ __launch_bounds__(kBlock) void ptmi_render_nee(DeviceScene sc, Emitte
     st.F[slot] = make_uint2(rng.v4, rng.d);
 }
 
-void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const EnvTable& env, const SurfaceTable& surf, const VertexNormalTable& vn,
-                       const AlbedoTable& at, bool rough, bool next_event, const TileMap& tm, const PathState& st, const FrameParams& fp,
-                       const int* queue, int n, bool first, const float4* lens, const float4* medium, hipStream_t s) {
+void launch_render_nee(const DeviceScene& sc, const EmitterTable& em, const PerLaneTables& t, bool next_event, const TileMap& tm, const PathState& st,
+                       const FrameParams& fp, const int* queue, int n, bool first, hipStream_t s) {
     if (n <= 0) return;
     first_hit_walk(sc, [&](auto mode, auto quads, size_t lds) {
-        with_bool(env.texel != nullptr, [&](auto with_env) {
+        with_bool(t.env.texel != nullptr, [&](auto with_env) {
             auto launch = [&](auto surf_kinds) {
-                with_bool(vn.rec != nullptr, [&](auto smooth) {
-                    with_bool(at.rec != nullptr, [&](auto tex) {
-                        with_bool(medium != nullptr, [&](auto with_medium) {
+                with_bool(t.vn.rec != nullptr, [&](auto smooth) {
+                    with_bool(t.at.rec != nullptr, [&](auto tex) {
+                        with_bool(t.medium != nullptr, [&](auto with_medium) {
                             hipLaunchKernelGGL((ptmi_render_nee<decltype(mode)::value, decltype(quads)::value, decltype(with_env)::value,
                                                                 decltype(surf_kinds)::value, decltype(smooth)::value, decltype(tex)::value,
                                                                 decltype(with_medium)::value>),
-                                               dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, env, surf, tm, st, fp, queue, n, first ? 1 : 0,
-                                               next_event ? 1 : 0, vn, at, lens, medium);
+                                               dim3((n + kBlock - 1) / kBlock), dim3(kBlock), lds, s, sc, em, t.env, t.surf, tm, st, fp, queue, n, first ? 1 : 0,
+                                               next_event ? 1 : 0, t.vn, t.at, t.lens, t.medium);
                         });
                     });
                 });
             };
-            if (surf.rec == nullptr) launch(std::integral_constant<int, 0>{});
-            else if (!rough) launch(std::integral_constant<int, 1>{});
+            if (t.surf.rec == nullptr) launch(std::integral_constant<int, 0>{});
+            else if (!t.rough) launch(std::integral_constant<int, 1>{});
             else launch(std::integral_constant<int, 2>{});
         });
     });

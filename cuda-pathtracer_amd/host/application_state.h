@@ -24,6 +24,7 @@
 #include "medium.h"
 #include "file_manager.h"
 #include "pbrt_loader.h"
+#include "route_rule.h"
 #include "sensor.h"
 #include "wide_bvh.h"
 
@@ -444,6 +445,11 @@ struct ApplicationState {
     explicit ApplicationState(int device);
     ~ApplicationState();
 };
+// The per-lane features present (route_rule.h: a mask of 1 << RouteFeature); next_event: the config's, or the one coming in
+inline unsigned presentFeatures(const ApplicationState& g, bool next_event) {
+    return next_event << kRouteNextEvent | g.env.present() << kRouteEnvironment | g.scene.hasSpecular() << kRouteSurfaces | g.scene.hasVertexNormals() << kRouteVertexNormals |
+           g.scene.hasAlbedoTexture() << kRouteAlbedoTexture | g.lens.on() << kRouteLens | g.scene.medium.on() << kRouteMedium;
+}
 
 // renderFrame — application.h:157-216: camera update, launches, device sync.  Results stay on the device.
 void renderFrame(ApplicationState& g_state, FrameStats* stats);

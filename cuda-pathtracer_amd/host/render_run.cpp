@@ -62,8 +62,6 @@ struct Run {
     size_t n_ev = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> kernel_events = {};   // (e0, e1) around every bounce / NEE launch of a timed run
     uint64_t launches = 0, visits = 0;
-    const float4* lens = nullptr;                      // the thin lens's block on the device (lensDeviceBlock); nullptr: the pinhole
-    const float4* medium = nullptr;                    // the medium's block on the device (mediumDeviceBlock); nullptr: vacuum
 
     // the run's next event: from the context's pool, in the order asked for - none is created once the pool is warm
     hipEvent_t event() {
@@ -166,21 +164,19 @@ void prepareCostOrder(Run& run, int order_classes) {
     r.cost_valid = false;                              // until this frame is through
 }
 
-// next-event estimation (include/ptmi.h: ptmi_config.next_event) replaces the frame-begin / bounce loop with ONE launch
-// of ptmi_render_nee on the frame's stream: no chunks, no refill, no launch order by cost; the whole frame, batch or pass
-// a context with an environment (ptmi_set_environment) takes the same route for both values of next_event: the per-lane kernel
-// is the one that looks the map up where a path ray misses; so does a scene with a mirror, glass or rough-metal primitive (ptmi_set_surfaces, ptmi_set_surfaces_rough)
-// or with a smooth primitive (ptmi_set_vertex_normals) or a textured one (ptmi_set_albedo_texture); and a context with a thin
-// lens (ptmi_set_lens): the per-lane kernel is the one that starts a sample on the lens; and a scene with a participating medium
-// (ptmi_set_medium): the per-lane kernel is the one that samples a free flight after each walk
-void runNeeLaunch(Run& run) {
+// the per-lane features' tables as they are now; blocks (route_rule.h): with the lens and the medium blocks, which throw before anything is launched
+PerLaneTables perLaneTables(ApplicationState& g, bool blocks) {
+    return {g.env.table(g.config.next_event, g.scene.d_emitters.n), g.scene.surfaceTable(), g.scene.vertexNormalTable(), g.scene.albedoTable(),
+            g.scene.hasRough(), blocks ? lensDeviceBlock(g) : nullptr, blocks ? mediumDeviceBlock(g) : nullptr};
+}
+
+// the per-lane route (route_rule.h): ONE launch of ptmi_render_nee on the frame's stream; the whole frame, batch or pass
+void runNeeLaunch(Run& run, const PerLaneTables& tables) {
     ApplicationState& g = run.g;
     const int n = run.queueLength();
     const hipEvent_t e0 = run.stamp(run.s);
-    launch_render_nee(g.scene.d_scene, g.scene.d_emitters, g.env.table(g.config.next_event, g.scene.d_emitters.n), g.scene.surfaceTable(),
-                      g.scene.vertexNormalTable(), g.scene.albedoTable(), g.scene.hasRough(), g.config.next_event, run.r.tile, run.r.d_state, run.fp,
-                      run.pass ? run.chunks[0].d_queue_init : nullptr, n,
-                      run.pass ? run.pass->rule.first != 0 : true, run.lens, run.medium, run.s);
+    launch_render_nee(g.scene.d_scene, g.scene.d_emitters, tables, g.config.next_event, run.r.tile, run.r.d_state, run.fp,
+                      run.pass ? run.chunks[0].d_queue_init : nullptr, n, run.pass ? run.pass->rule.first != 0 : true, run.s);
     PTMI_HIP(hipGetLastError());
     const hipEvent_t e1 = run.stamp(run.s);
     if (run.timed) run.kernel_events.push_back({e0, e1});
@@ -356,10 +352,9 @@ void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pa
     r.dn.image_current = false;                        // what ptmi_denoise may filter: likewise, only a completed path-tracing run
 
     const bool path_tracing = g.config.current_integrator == IntegratorType::PathTracing;
-    const bool nee = (g.config.next_event || g.env.present() || g.scene.hasSpecular() || g.scene.hasVertexNormals() || g.scene.hasAlbedoTexture() ||
-                      g.lens.on() || g.scene.medium.on()) && path_tracing;
-    const float4* lens = path_tracing ? lensDeviceBlock(g) : nullptr;   // (the Radiosity view keeps the pinhole) throws before anything is launched
-    const float4* medium = path_tracing ? mediumDeviceBlock(g) : nullptr;   // (the Radiosity view sees vacuum)
+    const Route route = routeOf(presentFeatures(g, g.config.next_event), (int)g.config.current_integrator);
+    const bool nee = route.per_lane;
+    const PerLaneTables tables = perLaneTables(g, route.blocks);
     const DeviceScene scene = effectiveScene(g);
     const LaunchOverrides over = LaunchOverrides::fromEnv();
     const LaunchRule rule = planLaunches(g, scene, fp, n_frames, pass != nullptr, nee, over);
@@ -369,8 +364,6 @@ void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pa
     Run run{g, r, scene, fp, n_frames, pass, stats != nullptr, r.stream};
     run.chunks = pass ? &r.accum.chunk : r.chunk;
     run.n_chunks = nee ? 0 : pass ? 1 : r.n_chunks;
-    run.lens = lens;
-    run.medium = medium;
 
     const hipEvent_t ev_begin = run.record(run.s);
     if (g.config.collect_stats) PTMI_HIP(hipMemsetAsync(r.d_stats, 0, sizeof(StatCounters), run.s));
@@ -382,7 +375,7 @@ void renderRun(ApplicationState& g, int n_frames, FrameStats* stats, PassRun* pa
         else launch_frame_begin(r.tile, r.d_state, fp, run.s);
         if (rule.costOrder(run.n_chunks)) prepareCostOrder(run, rule.order_classes);
         const hipEvent_t ev_ready = run.record(run.s);
-        if (nee) runNeeLaunch(run);
+        if (nee) runNeeLaunch(run, tables);
         else runQueueLoop(run, rule, over.publish, ev_ready);
         ev_end = finishRun(run);
     }
