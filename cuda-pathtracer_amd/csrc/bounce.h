@@ -56,10 +56,12 @@ inline bool is_guided(const BounceArgs& a) { return a.fp.sampling_mode != 0 && a
 // the primitives and the materials, the frame block of fp / tm (frame_block.h: ptmi_sweep_lds_vecs vectors in all; the hook, which
 // has no frame, passes none and leaves the block's place unwritten).  The block is at mats - PTMI_FRAME_BLOCK_VECS: frame_block_of(mats).
 // SWEEP_FORM: the form of the walk that will read the records (traversal.h: sweep_form) - with SWEEP_NEAR_FAR the nodes are the
-// near/far records of sweep_near_far.h, 4 vectors each (ptmi_sweep_near_far_lds_vecs vectors in all), otherwise 2 each.
+// near/far records of sweep_near_far.h, 4 vectors each (ptmi_sweep_near_far_lds_vecs vectors in all), otherwise 2 each; with
+// SWEEP_LEAVES the scene's sc.sweep_leaves leaf records (sweep_leaves.h) follow the materials and `leaves` names them
+// (ptmi_sweep_leaves_lds_vecs vectors in all; none where the scene's count is 0).
 template <bool LDS_GEOM, bool SWEEP_RECORDS = false, int SWEEP_FORM = 0>
 __device__ __forceinline__ float4* stage_scene(const DeviceScene& sc, float4* lds, const float4*& nodes, const float4*& prims, const float4*& mats,
-                                               const FrameParams* fp = nullptr, const TileMap* tm = nullptr) {
+                                               const FrameParams* fp, const TileMap* tm, SweepLeaves& leaves) {
     static_assert(LDS_GEOM || !SWEEP_RECORDS, "the sweep's records exist in LDS only");
     static_assert(SWEEP_RECORDS || SWEEP_FORM == 0, "a form belongs to the sweep's records");
     constexpr bool NEAR_FAR = (SWEEP_FORM & SWEEP_NEAR_FAR) != 0;
@@ -83,9 +85,26 @@ __device__ __forceinline__ float4* stage_scene(const DeviceScene& sc, float4* ld
         for (int i = threadIdx.x; i < n_mat_vec; i += kBlock) lds[mats_at + i] = sc.mats[i];
         nodes = lds; prims = lds + n_node_vec; mats = lds + mats_at;
         lds += mats_at + n_mat_vec;
+        if constexpr ((SWEEP_FORM & SWEEP_LEAVES) != 0) {
+            if (sc.sweep_leaves > 0)
+                ptmi_sweep_leaves_prepare(reinterpret_cast<const ptmi_vec_bits*>(sc.nodes), sc.n_nodes, sc.prim_stride, reinterpret_cast<ptmi_vec_bits*>(lds),
+                                          lds_address(prims), (int)threadIdx.x, kBlock);
+            leaves.at = lds_address(lds);
+            leaves.n = sc.sweep_leaves;
+            lds += PTMI_SWEEP_LEAF_VECS * sc.sweep_leaves;
+        }
         __syncthreads();
     }
     return lds;
+}
+
+// the same for the callers whose form has no leaf image (every walk but the sweep's builds that take SWEEP_LEAVES)
+template <bool LDS_GEOM, bool SWEEP_RECORDS = false, int SWEEP_FORM = 0>
+__device__ __forceinline__ float4* stage_scene(const DeviceScene& sc, float4* lds, const float4*& nodes, const float4*& prims, const float4*& mats,
+                                               const FrameParams* fp = nullptr, const TileMap* tm = nullptr) {
+    static_assert((SWEEP_FORM & SWEEP_LEAVES) == 0, "a form with SWEEP_LEAVES stages the leaf image: pass the SweepLeaves it fills");
+    SweepLeaves none;
+    return stage_scene<LDS_GEOM, SWEEP_RECORDS, SWEEP_FORM>(sc, lds, nodes, prims, mats, fp, tm, none);
 }
 
 // the frame block of a scene staged with SWEEP_RECORDS (mats: what stage_scene handed out)

@@ -33,7 +33,8 @@ __device__ __forceinline__ void bounce_body(const BounceArgs& a) {
     const bool active = idx < n_in;
     const float4 *nodes, *prims, *mats;
     float4* lds;
-    if constexpr (MODE == TRAVERSAL_SWEEP) lds = stage_scene<LDS_GEOM, true, sweep_form<HAS_QUADS, STATS, GUIDED>()>(a.sc, smem, nodes, prims, mats, &a.fp, &a.tm);      // the records of this build's walk, with the frame block
+    SweepLeaves leaves;
+    if constexpr (MODE == TRAVERSAL_SWEEP) lds = stage_scene<LDS_GEOM, true, sweep_form<HAS_QUADS, STATS, GUIDED>()>(a.sc, smem, nodes, prims, mats, &a.fp, &a.tm, leaves);      // the records of this build's walk, with the frame block
     else lds = stage_scene<LDS_GEOM>(a.sc, smem, nodes, prims, mats);
     constexpr bool LEAN = MODE == TRAVERSAL_SWEEP && !STATS && !GUIDED;      // shading.h: shade_step
     constexpr bool LATE = LEAN && PTMI_SWEEP_LATE;                           // shading.h: shade_step_sweep
@@ -55,7 +56,7 @@ __device__ __forceinline__ void bounce_body(const BounceArgs& a) {
         float t = 0.0f; int k = -1;
         if (STATS && alive) cn.rays++;
         const bool hit = scene_intersect<MODE, HAS_QUADS, STATS, GUIDED>(nodes, prims, a.sc.prim_stride, a.sc.n_nodes, stack, alive,
-                                                                       p.o, p.d, 1e-4f, FLT_MAX, t, k, cn);
+                                                                       p.o, p.d, 1e-4f, FLT_MAX, t, k, cn, leaves);
         if constexpr (LATE) {
             if (alive) alive = shade_step_sweep<BATCH, FRAME>(a.fp, a.tm, fb, mats, p, hit, t, k, slot);
         } else {

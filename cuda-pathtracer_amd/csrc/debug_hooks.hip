@@ -21,14 +21,15 @@ __global__ __launch_bounds__(kBlock) void ptmi_debug_intersect_k(DeviceScene sc,
     // SWEEP walks the records ptmi_bounce's sweep walks, in the timed build's form: staged by the same stage_scene (LANE and STACK
     // read global memory here)
     const float4 *nodes, *prims, *mats;
-    stage_scene<MODE == TRAVERSAL_SWEEP, MODE == TRAVERSAL_SWEEP, MODE == TRAVERSAL_SWEEP ? sweep_form<HAS_QUADS, false, false>() : 0>(sc, smem, nodes, prims, mats);
+    SweepLeaves leaves;
+    stage_scene<MODE == TRAVERSAL_SWEEP, MODE == TRAVERSAL_SWEEP, MODE == TRAVERSAL_SWEEP ? sweep_form<HAS_QUADS, false, false>() : 0>(sc, smem, nodes, prims, mats, nullptr, nullptr, leaves);
     const int i = blockIdx.x * kBlock + threadIdx.x;
     const bool live = i < n;
     const int j = live ? i : 0;
     const f3 ro = mk3(o[3 * j], o[3 * j + 1], o[3 * j + 2]), rd = mk3(d[3 * j], d[3 * j + 1], d[3 * j + 2]);
     LaneCounters cn = {0, 0, 0, 0, 0, 0, 0};
     float t = 0.0f; int k = -1;
-    const bool h = scene_intersect<MODE, HAS_QUADS, false>(nodes, prims, sc.prim_stride, sc.n_nodes, stack, live, ro, rd, t_min, t_max, t, k, cn);
+    const bool h = scene_intersect<MODE, HAS_QUADS, false>(nodes, prims, sc.prim_stride, sc.n_nodes, stack, live, ro, rd, t_min, t_max, t, k, cn, leaves);
     if (!live) return;
     hit[i] = h ? 1 : 0;
     prim[i] = h ? __float_as_int(sc.mats[3 * k].w) : -1;

@@ -43,6 +43,8 @@ struct DeviceScene {
     int stack_entries = 1;    // min(bvh depth + 1, 64); only the STACK traversal uses it
     int lds_resident = 0;     // 1: nodes+prims+mats are staged into LDS by every workgroup (LANE/STACK traversal)
     int traversal = 1;        // TraversalMode
+    int sweep_leaves = 0;     // leaves of the tree where the sweep may test the leaf boxes alone (sweep_leaves.h: the verdict holds and the
+                              // launch rule takes it); 0: it walks every node.  Stands in what was padding: no other field moves
     // Guided sampling (SamplingMode != BSDF): one PrecomputedCDF record per primitive in LOAD order
     // (render_config.h:24-31: pdf[256], row_sums[8], marginal_cdf[8], row_cdfs[256], total_weight, is_valid = 530
     // dwords = 2120 B), HBM/L2-resident, read per hit through the load-order index kept in mats[3k].w.  nullptr = none.

@@ -100,8 +100,8 @@ size_t bounce_lds_bytes(const DeviceScene& sc) {
     if (sc.traversal == TRAVERSAL_WIDE || sc.traversal == TRAVERSAL_CERTIFIED) return bounce_lds_bytes_wide(sc);
     size_t b = 0;
     const bool geom = sc.lds_resident || sc.traversal == TRAVERSAL_SWEEP;
-    // the sweep: with the frame block, and the larger of its two node images - which one a build stages is its own matter (sweep_form)
-    if (geom) b += (sc.traversal == TRAVERSAL_SWEEP ? ptmi_sweep_near_far_lds_vecs(sc.n_nodes, sc.prim_stride, sc.n_prims)
+    // the sweep: with the frame block, the larger of its two node images and the leaf image - which of them a build stages is its own matter (sweep_form)
+    if (geom) b += (sc.traversal == TRAVERSAL_SWEEP ? ptmi_sweep_leaves_lds_vecs(sc.n_nodes, sc.prim_stride, sc.n_prims, sc.sweep_leaves)
                                                     : ptmi_scene_lds_vecs(sc.n_nodes, sc.prim_stride, sc.n_prims)) * sizeof(float4);   // what stage_scene lays out (bounce.h)
     if (sc.traversal == TRAVERSAL_STACK) b += (size_t)sc.stack_entries * kBlock * sizeof(int);
     return b;

@@ -5,6 +5,7 @@
 #include "pt_device.h"
 #include "sweep_records.h"
 #include "sweep_near_far.h"
+#include "sweep_leaves.h"
 #include "wide_walk.h"
 
 namespace ptmi {
@@ -47,14 +48,18 @@ __device__ __forceinline__ bool box_hit_near_far(float2 bx, float2 by, float2 bz
 // a zero, a -0, a denormal, an infinity or a NaN component in any live lane - the whole wave takes the division.  A ray direction
 // is a unit vector, so only the lower bound ever acts; the upper one is tested on |x| + |y| + |z|, which is no smaller than any
 // of the three and a NaN or inf when one of them is (v_min3 alone would ignore a NaN).  Lanes that are not live hold no ray.
-__device__ __forceinline__ f3 ray_inv(f3 d, bool live) {
+__device__ __forceinline__ bool ray_inv_long(f3 d, bool live) {       // the vote: true when the wave takes the division
     float lo;
     asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(lo) : "v"(d.x), "v"(d.y), "v"(d.z));
     const float sum = fabsf(d.x) + fabsf(d.y) + fabsf(d.z);
     const bool in_range = (lo >= 0x1p-100f) & (sum <= 0x1p+100f);
-    if (__any(live && !in_range)) return mk3(rcp_rn(d.x), rcp_rn(d.y), rcp_rn(d.z));
+    return __any(live && !in_range);
+}
+__device__ __forceinline__ f3 ray_inv_of(f3 d, bool long_form) {
+    if (long_form) return mk3(rcp_rn(d.x), rcp_rn(d.y), rcp_rn(d.z));
     return mk3(rcp_exact_normal(d.x), rcp_exact_normal(d.y), rcp_exact_normal(d.z));
 }
+__device__ __forceinline__ f3 ray_inv(f3 d, bool live) { return ray_inv_of(d, ray_inv_long(d, live)); }
 
 // Primitive::intersect (primitive.h:83-90) + the closer-hit update of scene.h:89-96 for leaf slot k (per-lane k).
 template <bool HAS_QUADS>
@@ -220,9 +225,46 @@ __device__ __forceinline__ bool intersect_lane(const float4* __restrict__ nodes,
 // other; each move alone, two runs: the hit's 8 379 and 8 445, the cursor's 8 386 and 8 403; c4 9 751 -> 9 873 (+1.2 %, one pair).
 // A third item, keeping s = o - v0 from one triangle test to the next where two records of a leaf share v0, is not built: in
 // cbox.obj 2 of 32 records follow a record with the same v0 in their leaf (tests/test_sweep_shared_s_host.py).
+//
+// SWEEP_LEAVES, taken by the builds that take SWEEP_NEAR_FAR: the wave slab-tests the LEAVES alone.  closest_t and slot_hit change
+// only inside leaves, and which leaves a lane enters is decided by the leaf's own slab test, so the interior tests are work the
+// result does not need - where the claim below holds.  One wave-uniform decision per segment: ray_inv's vote and the scene's leaf
+// count (DeviceScene::sweep_leaves, 0 where the host's verdict on the node array is false).  Hot side: sweep_leaves_walk over the
+// leaf image (sweep_leaves.h), one pass per leaf with all live lanes.  Cold side - a vote that fails, a scene without a verdict,
+// every STATS build (node_visits are the reference's) - the walk above, unchanged.
+//   CLAIM.  For a ray that takes ray_inv's short form, every leaf whose slab test passes has only ancestors whose slab tests
+//   passed when the reference's walk (scene.h:50-110, restated in intersect_lane) visited them.  Hence the leaf-only walk enters
+//   exactly the leaves the reference enters, in pre-order, with the same closest_t (induction over the leaves: closest_t changes
+//   only in entered leaves), and every t and slot is the reference's, bit for bit.
+//   1. Containment, as bits.  Every node's six planes bound its children's, lo_parent <= lo_child and hi_parent >= hi_child per
+//      axis, and all planes are finite.  host/bvh.cpp: computeBounds gives that by construction (an exact fminf / fmaxf over a
+//      superset of padded primitive boxes), but the walk does not rely on it: ptmi_sweep_leaves_verdict checks every child against
+//      its parent, and the links, on the very array the kernels read, once per scene load (host/scene_state.cpp).
+//   2. No NaN is born in the slab arithmetic.  The vote gives every live lane 2^-100 <= |d.a| <= 2^100 per component, so 1 / d is
+//      a finite non-zero normal number and (plane - o) * inv is never 0 * inf (plane - o may overflow to +-inf: still ordered).
+//      The vote does not look at o: a NaN component of o makes the two products of that axis NaN for every box, which max / min
+//      ignore alike; an infinite one makes plane - o the same -+inf for every finite plane, so the two products of that axis
+//      are the same +-inf for ancestor and leaf.  Either way ancestor and leaf decide alike on that axis.
+//   3. Monotonicity.  Rounded subtraction of a fixed o, rounded multiplication by a fixed non-zero factor, max / max3 / min / min3
+//      and flush-to-zero are monotone in numeric order (-0 and +0 count as equal: the final comparison cannot tell them apart),
+//      and which plane is near is chosen by inv < 0 alone, identically for ancestor and leaf.  So tmin_box(ancestor) <=
+//      tmin_box(leaf); closest_t never grows and the ancestor is visited earlier, so tmax_box(ancestor) >= tmax_box(leaf);
+//      !(tmax < tmin) at the leaf implies the same at every ancestor.
+//   4. Tree depth <= 62, the reference's stack rule, which the sweep and LANE assume already (SceneState::chooseTraversal).
+// A leaf pass is 19 VALU (six v_sub, six v_mul, v_max, v_min, v_max3, v_min3, v_cmp and the two v_readfirstlane of the link pair;
+// + 1 v_mov of the leaf's record address under the passing lanes) against 24 of a node pass: no cursor compare, no v_add_u32 of
+// the three addresses (kSweepLeavesUnroll records per trip at immediate offsets), no skip move, and `pass & live` is an s_and.
+// cbox.obj: 11 leaf passes per wave-segment against 17.2 node passes of 21 (tools/sweep_union_sim.py; cbox_quads.obj 7 against
+// 10.8, the 64-triangle soup of tests/test_gpu_sweep_passes.py 24 against 30.7), so every scene with a verdict takes it.
 // EXPERIMENTS.md has the runs and the counters.
-enum : int { SWEEP_VOTED_UPDATE = 1, SWEEP_PINNED = 2, SWEEP_LEAF_BASE = 4, SWEEP_ONE_SELECT = 8, SWEEP_NEAR_FAR = 16, SWEEP_MASKED_HIT = 32, SWEEP_MASKED_CURSOR = 64 };
+enum : int { SWEEP_VOTED_UPDATE = 1, SWEEP_PINNED = 2, SWEEP_LEAF_BASE = 4, SWEEP_ONE_SELECT = 8, SWEEP_NEAR_FAR = 16, SWEEP_MASKED_HIT = 32, SWEEP_MASKED_CURSOR = 64,
+              SWEEP_LEAVES = 128 };
 constexpr int kSweepLeafUnroll = 4;
+// leaf records per trip of sweep_leaves_walk, read at immediate offsets from the lane's three addresses (-DPTMI_SWEEP_LEAVES_UNROLL=1, 2 or 4)
+#ifndef PTMI_SWEEP_LEAVES_UNROLL
+#define PTMI_SWEEP_LEAVES_UNROLL 2
+#endif
+constexpr int kSweepLeavesUnroll = PTMI_SWEEP_LEAVES_UNROLL;
 
 // experiment libraries (make ab-lib DEFS="-DPTMI_SWEEP_MASKED_HIT=0 -DPTMI_SWEEP_MASKED_CURSOR=0"): the builds that take
 // SWEEP_NEAR_FAR without one or both of the masked moves.  Here and not beside bounce_sync.hip's switches: the intersect hook
@@ -232,6 +274,10 @@ constexpr int kSweepLeafUnroll = 4;
 #endif
 #ifndef PTMI_SWEEP_MASKED_CURSOR
 #define PTMI_SWEEP_MASKED_CURSOR 1
+#endif
+// -DPTMI_SWEEP_LEAVES=0: the builds that take SWEEP_NEAR_FAR without the leaf-only walk; they walk as the parent's do
+#ifndef PTMI_SWEEP_LEAVES
+#define PTMI_SWEEP_LEAVES 1
 #endif
 
 // The form of each instantiation, judged by registers, waves per SIMD and spills against the walk before these items (DESIGN.md
@@ -245,9 +291,13 @@ constexpr int kSweepLeafUnroll = 4;
 // c3 ran 1.8 % slower (EXPERIMENTS.md); the GUIDED builds stand at their cap.  Those keep the two-vector records.
 // SWEEP_MASKED_HIT and SWEEP_MASKED_CURSOR go to the builds that take SWEEP_NEAR_FAR, which give a VGPR back with them (61 -> 60,
 // BATCH 62 -> 61); every other build is the code it was, byte for byte.
+// SWEEP_LEAVES goes to the same builds: both walks stand in the kernel, 60 -> 62 VGPRs and, BATCH, 61 -> 63, 8 waves, no scratch.
+// The quad builds were compiled with it (the leaf image beside their two-vector nodes): 64 VGPRs at 8 waves with 8 bytes of scratch
+// and, BATCH, 12, where they had none - new scratch, so by the standing rule they keep their walk, byte for byte.
 template <bool HAS_QUADS, bool STATS, bool GUIDED>
 constexpr int sweep_form() {
-    constexpr int timed = SWEEP_NEAR_FAR | (PTMI_SWEEP_MASKED_HIT ? SWEEP_MASKED_HIT : 0) | (PTMI_SWEEP_MASKED_CURSOR ? SWEEP_MASKED_CURSOR : 0);
+    constexpr int timed = SWEEP_NEAR_FAR | (PTMI_SWEEP_MASKED_HIT ? SWEEP_MASKED_HIT : 0) | (PTMI_SWEEP_MASKED_CURSOR ? SWEEP_MASKED_CURSOR : 0) |
+                          (PTMI_SWEEP_LEAVES ? SWEEP_LEAVES : 0);
     return HAS_QUADS ? 0 : ((SWEEP_ONE_SELECT | SWEEP_VOTED_UPDATE | SWEEP_PINNED | SWEEP_LEAF_BASE) | (!STATS && !GUIDED ? timed : 0));
 }
 // 16-byte vectors per node record in the LDS image of a form (stage_scene lays them out, the walk strides by them)
@@ -344,19 +394,81 @@ __device__ __forceinline__ void leaf_prim_sweep(unsigned int rec, int at, f3 o, 
     }
 }
 
+// The leaf image a kernel staged (sweep_leaves.h; stage_scene hands it out): the LDS address of the first leaf record and their
+// number.  n == 0: there is none - the scene's verdict is false, or the build does not take SWEEP_LEAVES - and every wave walks
+// every node.
+struct SweepLeaves { unsigned int at = 0; int n = 0; };
+
+// SWEEP_LEAVES, the hot side: the wave slab-tests the n leaf records in pre-order with all its live lanes and runs each leaf's
+// primitives under the lanes that pass - no cursor, no skip select, no compare of a cursor with the trip.  The three addresses are
+// fixed per ray (the image's address + where (near, far) stands for the sign of 1 / d, pinned); kSweepLeavesUnroll records per
+// trip are read at immediate offsets from them, the link pair at the x address + 48 (it stands twice, so both x offsets read it).
+// Triangles only, no STATS (sweep_form).  inv must be ray_inv's short form for every live lane: the proof above rests on it.
+template <int FORM>
+__device__ __forceinline__ void sweep_leaves_walk(SweepLeaves leaves, bool live, f3 o, f3 d, f3 inv, float t_min, float eps, float t_lo,
+                                                  float& closest_t, int& slot_hit) {
+    constexpr unsigned int kPrimBytes = 3 * PTMI_SWEEP_VEC_BYTES;
+    unsigned int ax = leaves.at + (inv.x < 0.0f ? PTMI_SWEEP_NF_FAR_FIRST : 0);      // box_hit's own predicates
+    unsigned int ay = leaves.at + (inv.y < 0.0f ? PTMI_SWEEP_NF_FAR_FIRST : 0);
+    unsigned int az = leaves.at + (inv.z < 0.0f ? PTMI_SWEEP_NF_FAR_FIRST : 0);
+    asm("" : "+v"(ax));
+    asm("" : "+v"(ay));
+    asm("" : "+v"(az));
+    const auto leaf = [&](int j) {                                // record j of this trip
+        constexpr int kPairs = PTMI_SWEEP_LEAF_BYTES / 8;
+        const float2 bx = lds_pair(ax, kPairs * j), by = lds_pair(ay, kPairs * j + 2), bz = lds_pair(az, kPairs * j + 4);
+        const float2 w = lds_pair(ax, kPairs * j + PTMI_SWEEP_LEAF_LINK / 8);
+        const unsigned int first = (unsigned int)__builtin_amdgcn_readfirstlane(__float_as_int(w.x));
+        const int count = __builtin_amdgcn_readfirstlane(__float_as_int(w.y));
+        const bool pass = box_hit_near_far(bx, by, bz, o, inv, t_min, closest_t) & live;
+        if (pass) {
+            unsigned int rec = first;
+            asm("" : "+v"(rec));
+            const auto test = [&](int i) { leaf_prim_sweep<false, FORM>(rec, i * 3, o, d, eps, eps, t_lo, closest_t, slot_hit); };
+            static_assert(kSweepLeafUnroll == 4, "the four calls below");
+            for (int left = count; left > 0; left -= kSweepLeafUnroll, rec += kSweepLeafUnroll * kPrimBytes) {
+                test(0);
+                if (left > 1) test(1);
+                if (left > 2) test(2);
+                if (left > 3) test(3);
+            }
+        }
+    };
+    static_assert(kSweepLeavesUnroll == 1 || kSweepLeavesUnroll == 2 || kSweepLeavesUnroll == 4, "the calls below");
+    constexpr unsigned int kTripBytes = kSweepLeavesUnroll * PTMI_SWEEP_LEAF_BYTES;
+    for (int left = leaves.n; left > 0; left -= kSweepLeavesUnroll, ax += kTripBytes, ay += kTripBytes, az += kTripBytes) {
+        leaf(0);
+        if constexpr (kSweepLeavesUnroll > 1) { if (left > 1) leaf(1); }
+        if constexpr (kSweepLeavesUnroll > 2) {
+            if (left > 2) leaf(2);
+            if (left > 3) leaf(3);
+        }
+    }
+}
+
 template <bool HAS_QUADS, bool STATS, int FORM>
 __device__ __forceinline__ bool intersect_sweep(const float4* nodes, const float4* prims, int n_nodes, bool live, f3 o, f3 d,
-                                                float t_min, float t_max, float& t_hit, int& slot_hit, LaneCounters& cn) {
+                                                float t_min, float t_max, float& t_hit, int& slot_hit, LaneCounters& cn,
+                                                SweepLeaves leaves = SweepLeaves()) {
     constexpr int kPrimVecs = HAS_QUADS ? 4 : 3;
     constexpr unsigned int kPrimBytes = kPrimVecs * PTMI_SWEEP_VEC_BYTES;
     float closest_t = t_max;
     slot_hit = -1;
-    const f3 inv = ray_inv(d, live);
+    const bool long_form = ray_inv_long(d, live);
+    const f3 inv = ray_inv_of(d, long_form);
     float t_lo = mt_t_lo(t_min), eps = 1e-8f, eps_up = __uint_as_float(__float_as_uint(1e-8f) + 1u);
     if (FORM & SWEEP_PINNED) {
         asm("" : "+v"(t_lo));
         asm("" : "+v"(eps));
         if (HAS_QUADS) asm("" : "+v"(eps_up));
+    }
+    if constexpr ((FORM & SWEEP_LEAVES) != 0) {                  // one wave-uniform decision per segment: ray_inv's vote and the scene's leaf count
+        static_assert(!HAS_QUADS && !STATS && (FORM & SWEEP_NEAR_FAR) && (FORM & SWEEP_LEAF_BASE) && (FORM & SWEEP_VOTED_UPDATE), "sweep_form");
+        if (!long_form && leaves.n > 0) {                        // inv is the short form here
+            sweep_leaves_walk<FORM>(leaves, live, o, d, inv, t_min, eps, t_lo, closest_t, slot_hit);
+            t_hit = closest_t;
+            return slot_hit >= 0;
+        }
     }
     constexpr bool NEAR_FAR = (FORM & SWEEP_NEAR_FAR) != 0;
     constexpr unsigned int kNodeBytes = sweep_node_vecs(FORM) * PTMI_SWEEP_VEC_BYTES;
@@ -441,12 +553,13 @@ __device__ __forceinline__ bool intersect_sweep(const float4* nodes, const float
     return slot_hit >= 0;
 }
 
-// GUIDED: only the sweep's form depends on it (sweep_form); the caller stages the records of that form
+// GUIDED: only the sweep's form depends on it (sweep_form); the caller stages the records of that form and passes the leaf image
+// stage_scene handed out (the sweep's builds that take SWEEP_LEAVES read it; every other walk ignores it)
 template <int MODE, bool HAS_QUADS, bool STATS, bool GUIDED = false>
 __device__ __forceinline__ bool scene_intersect(const float4* __restrict__ nodes, const float4* __restrict__ prims, int prim_stride,
                                                 int n_nodes, int* stack, bool live, f3 o, f3 d, float t_min, float t_max,
-                                                float& t_hit, int& slot_hit, LaneCounters& cn) {
-    if (MODE == TRAVERSAL_SWEEP) return intersect_sweep<HAS_QUADS, STATS, sweep_form<HAS_QUADS, STATS, GUIDED>()>(nodes, prims, n_nodes, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
+                                                float& t_hit, int& slot_hit, LaneCounters& cn, SweepLeaves leaves = SweepLeaves()) {
+    if (MODE == TRAVERSAL_SWEEP) return intersect_sweep<HAS_QUADS, STATS, sweep_form<HAS_QUADS, STATS, GUIDED>()>(nodes, prims, n_nodes, live, o, d, t_min, t_max, t_hit, slot_hit, cn, leaves);
     if (MODE == TRAVERSAL_LANE) return intersect_lane<HAS_QUADS, STATS>(nodes, prims, prim_stride, n_nodes, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
     return intersect_stack<HAS_QUADS, STATS>(nodes, prims, prim_stride, stack, live, o, d, t_min, t_max, t_hit, slot_hit, cn);
 }

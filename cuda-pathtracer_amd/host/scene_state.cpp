@@ -1,6 +1,7 @@
 // scene_state.cpp — SceneState: host loading, the emitter table, upload, and the packed / fast layouts
 #include "application_state.h"
 #include "../csrc/sweep_near_far.h"
+#include "../csrc/sweep_leaves.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -278,6 +279,12 @@ void SceneState::upload() {
     d_scene.n_nodes = (int)bvh_nodes.size(); d_scene.n_prims = n;
     d_scene.prim_stride = stride; d_scene.has_quads = num_quads ? 1 : 0;
     d_scene.stack_entries = std::min(bvh_depth + 1, 64);
+    // the sweep's leaf-only walk (csrc/traversal.h): taken only where the node array itself shows every box inside its parent's,
+    // all planes finite - once per scene load; 0 leaves: the sweep walks every node
+    {
+        const ptmi_vec_bits* nb = reinterpret_cast<const ptmi_vec_bits*>(nodes.data());
+        d_scene.sweep_leaves = ptmi_sweep_leaves_verdict(nb, d_scene.n_nodes, n) ? ptmi_sweep_leaf_count(nb, d_scene.n_nodes) : 0;
+    }
     // LDS residency: the whole scene is staged per workgroup while it leaves room for >= 2 workgroups per CU
     const size_t scene_bytes = (nodes.size() + prims.size() + mats.size()) * sizeof(float4);
     d_scene.lds_resident = (scene_bytes + (size_t)d_scene.stack_entries * kBlock * sizeof(int)) <= 64 * 1024 ? 1 : 0;
@@ -729,8 +736,8 @@ void SceneState::chooseTraversal() {
     // PHASED: measured faster than the segment-synchronous LANE walk from 128 primitives up (LDS-resident or not); PACKED: the
     // phased walk over the packed layout of scenes too large for LDS; LANE stays available through the override
     if (force_traversal >= 0 && !(force_traversal != TRAVERSAL_STACK && bvh_depth > 62)) d_scene.traversal = force_traversal;
-    // the sweep reads through LDS, and its image - near/far node records, frame block (csrc/kernels.hip: bounce_lds_bytes) - is the larger one
-    const bool sweep_fits = d_scene.lds_resident && ptmi_sweep_near_far_lds_vecs(d_scene.n_nodes, d_scene.prim_stride, d_scene.n_prims) * sizeof(float4) <= 64 * 1024;
+    // the sweep reads through LDS, and its image - near/far node records, frame block, leaf records (csrc/kernels.hip: bounce_lds_bytes) - is the larger one
+    const bool sweep_fits = d_scene.lds_resident && ptmi_sweep_leaves_lds_vecs(d_scene.n_nodes, d_scene.prim_stride, d_scene.n_prims, d_scene.sweep_leaves) * sizeof(float4) <= 64 * 1024;
     if (d_scene.traversal == TRAVERSAL_SWEEP && !sweep_fits) d_scene.traversal = TRAVERSAL_LANE;
     if (d_scene.traversal == TRAVERSAL_PACKED && !d_scene.gnodes) d_scene.traversal = TRAVERSAL_PHASED;
     // CERTIFIED needs the fast tree and the ancestor lists (triangle scenes of depth <= 62); otherwise the exact walk it stands for

@@ -21,7 +21,7 @@ _SHARED_SOURCES = _csrc("pt_device.h", "pt_vec.h", "device_scene.h", "wide_bvh.h
     os.path.join(ROOT, "include", "ptmi_math.h"), os.path.join(PKG, "Makefile")]
 # everything that reaches the render kernels' objects (the Makefile's RENDER_HIP and what those files include)
 KERNEL_SOURCES = _csrc("kernels.hip", "bounce_sync.hip", "bounce_phased.hip", "bounce_wide.hip", "first_hit.hip", "debug_hooks.hip",
-                       "traversal.h", "sweep_records.h", "sweep_near_far.h", "frame_block.h", "shading.h", "shade_lean.h", "bounce.h") + _SHARED_SOURCES + [
+                       "traversal.h", "sweep_records.h", "sweep_near_far.h", "sweep_leaves.h", "frame_block.h", "shading.h", "shade_lean.h", "bounce.h") + _SHARED_SOURCES + [
     # the host loop that issues the kernels and the rule that decides how (chunks, run-ahead, segments per launch)
     os.path.join(PKG, "host", "render_run.cpp"), os.path.join(PKG, "host", "launch_rule.h"),
     # the builder of the opt-in fast tree: the tree's shape decides what ptmi_bounce_wide fetches

@@ -22,7 +22,11 @@ Reported, per wave-segment:
   the 256 rays of a workgroup are sorted by a key before they are cut into waves, relative to today's order;
   how many second-half passes remain if a lane latches one pending second half and the wave flushes only when a lane needs
   a second latch or the leaf ends (closest_t must be final before the next slab test); if every lane keeps a list of its own and
-  works it off at the leaf's end; if the wave keeps one queue across its lanes; and the bound, every leaf packed 64 to a pass.
+  works it off at the leaf's end; if the wave keeps one queue across its lanes; and the bound, every leaf packed 64 to a pass;
+  the slab-test passes of the leaf-only walk (SWEEP_LEAVES: one per leaf, whatever the rays do) against today's node passes
+  (2 x the interior nodes the wave's union enters + 1), which is what decides whether a scene takes that walk.
+
+--scene takes a file of the scenes directory or the name of a scene of tests/test_gpu_sweep_passes.py (tri64: its 64-triangle soup).
 """
 import argparse
 import os
@@ -198,7 +202,12 @@ def main():
     a = ap.parse_args()
     n = a.width * a.rows
     assert n % BLOCK == 0, "width * rows must be a multiple of 256"
-    scene = OracleScene.load(os.path.join(SCENES, a.scene))
+    if a.scene.endswith(".obj"):
+        scene = OracleScene.load(os.path.join(SCENES, a.scene))
+    else:
+        sys.path.insert(0, os.path.join(ROOT, "cuda-pathtracer_amd", "python"))
+        from test_gpu_sweep_passes import scene as test_scene
+        scene = test_scene(a.scene)[1]
     walk = Walk(scene)
     P = walk.prims
     cf = camera_frame(default_camera(), a.width, a.height).as_array()
@@ -282,6 +291,9 @@ def main():
     print(f"second-half passes with a one-deep latch and flush on conflict: {acc['latched'] / w:.1f} against {acc['second'] / w:.1f} today")
     print(f"lane-private pending lists, worked off at the leaf's end: {acc['private'] / w:.1f}; a per-wave queue across lanes, worked off above "
           f"{WAVE} items and at the leaf's end: {acc['queued'] / w:.1f}; every leaf's second halves packed {WAVE} to a pass: {acc['packed'] / w:.1f}")
+    n_leaves = int((walk.bvh["count"] > 0).sum())
+    print(f"slab-test passes per wave-segment: leaf-only walk {n_leaves} (the leaves), today {acc['nodes'] / w:.1f} "
+          f"(the union enters {(acc['nodes'] / w - 1) / 2:.1f} of {n_nodes - n_leaves} interior nodes)")
     print("| regrouping key (256 rays sorted, then cut into waves) | relative traversal cost |")
     print("|---|---|")
     for k in keys:
