@@ -1,49 +1,18 @@
 // c_api.cpp — the C ABI of libptmi.so (include/ptmi.h) over the host-side state objects.
-#include "../../include/ptmi.h"
+#include "c_api_common.h"
 
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <new>
-#include <string>
-
-#include "../host/application_state.h"
-#include "shade_lean.h"
 
 using namespace ptmi;
 
-struct ptmi_ctx { ApplicationState app; explicit ptmi_ctx(int dev) : app(dev) {} };
-struct ptmi_host_scene { SceneState scene; };
+std::string& ptmi::lastErrorText() { thread_local std::string text; return text; }
 
 namespace {
-thread_local std::string g_last_error;
-
-template <class Fn>
-int guarded(Fn&& fn) {
-    try { fn(); return PTMI_OK; }
-    catch (const HipError& e) {
-        g_last_error = e.what();
-        if (e.code == hipErrorNoDevice || e.code == hipErrorInvalidDevice) return PTMI_E_NO_DEVICE;
-        if (e.code == hipErrorOutOfMemory) return PTMI_E_NOMEM;
-        return PTMI_E_HIP;
-    }
-    catch (const IoError& e) { g_last_error = e.what(); return PTMI_E_IO; }
-    catch (const ArgError& e) { g_last_error = e.what(); return PTMI_E_INVALID; }
-    catch (const DistError& e) { g_last_error = e.what(); return PTMI_E_DIST; }
-    catch (const std::bad_alloc&) { g_last_error = "host allocation failed"; return PTMI_E_NOMEM; }
-    catch (const std::exception& e) { g_last_error = e.what(); return PTMI_E_INVALID; }
-    catch (...) { g_last_error = "unknown error"; return PTMI_E_INVALID; }
-}
-void need(bool ok, const char* what) { if (!ok) throw ArgError(what); }
-void needNone(const std::string& refusal) { if (!refusal.empty()) throw ArgError(refusal); }
 void needRoute(const ptmi_ctx* c, RouteFeature f) {   // a per-lane feature is being switched on: the config as it is must allow it (host/route_rule.h)
     needNone(featureRefusal(f, (int)c->app.config.current_integrator, (int)c->app.config.sampling_mode, c->app.config.fast_tree));
-}
-void needScene(ptmi_ctx* c) {                          // what the setter of a per-primitive table begins with
-    need(c != nullptr, "ctx is NULL");
-    need(c->app.scene.d_nodes != nullptr, "no scene loaded");
-    PTMI_HIP(hipSetDevice(c->app.device_id));
 }
 
 // a call that changes what a frame would show: the accumulation restarts, the feature buffers go stale and the temporal
@@ -59,30 +28,6 @@ void copy_frame_stats(const FrameStats& fs, Dst& d) {
     d.top_node_visits = fs.top_node_visits; d.cert_chain = fs.cert_chain; d.cert_fallback = fs.cert_fallback;
 }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    explicit DevBuf(size_t n) { p = (T*)hipMallocSafe(n * sizeof(T), "debug buffer"); }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    void upload(const T* h, size_t n) { PTMI_HIP(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice)); }
-    void download(T* h, size_t n) { PTMI_HIP(hipMemcpy(h, p, n * sizeof(T), hipMemcpyDeviceToHost)); }
-};
-
-// the wave-vote hooks: n cases of in_per floats in waves of 64, live[i] == 0 a lane that is not active; one launch, out_per
-// floats per case back, zero where a lane was not active
-template <class Launch>
-void run_vote_hook(ptmi_ctx* c, int n, const float* in, int in_per, const int* live, float* out, int out_per, Launch launch) {
-    need(c && in && live && out, "NULL argument");
-    need(n > 0, "n must be positive");
-    PTMI_HIP(hipSetDevice(c->app.device_id));
-    DevBuf<float> d_in((size_t)in_per * n), d_o((size_t)out_per * n); DevBuf<int> d_l(n);
-    d_in.upload(in, (size_t)in_per * n); d_l.upload(live, n);
-    PTMI_HIP(hipMemsetAsync(d_o.p, 0, (size_t)out_per * n * sizeof(float), c->app.render.stream));
-    launch(d_in.p, d_l.p, d_o.p, c->app.render.stream);
-    PTMI_HIP(hipGetLastError());
-    PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-    d_o.download(out, (size_t)out_per * n);
-}
 std::vector<Primitive> prims_from_arrays(int n, const int* type, const float* verts, const float* normal, const float* bsdf, const float* Le) {
     need(type && verts && normal && bsdf && Le, "NULL argument");
     need(n > 0, "n must be positive");
@@ -101,7 +46,7 @@ std::vector<Primitive> prims_from_arrays(int n, const int* type, const float* ve
 
 extern "C" {
 
-const char* ptmi_last_error(void) { return g_last_error.c_str(); }
+const char* ptmi_last_error(void) { return lastErrorText().c_str(); }
 
 void ptmi_default_camera(ptmi_camera* c) {
     const AppConfig d;
@@ -679,31 +624,6 @@ int ptmi_lens(const ptmi_ctx* c, float* radius, float* focus_distance) {
         if (focus_distance) *focus_distance = lensFocus(c->app);
     });
 }
-int ptmi_debug_lens_block(ptmi_ctx* c, float* out24) {
-    return guarded([&] {
-        need(c && out24, "NULL argument");
-        need(c->app.lens.on(), "no lens set (radius 0 is the pinhole)");
-        need(c->app.render.tile.width > 0, "no resolution set");
-        const float4* d = lensDeviceBlock(c->app);
-        PTMI_HIP(hipMemcpy(out24, d, kLensBlockFloats * sizeof(float), hipMemcpyDeviceToHost));
-    });
-}
-int ptmi_debug_lens_ray(ptmi_ctx* c, int n, const int* px, const int* py, const float* r, float* out) {
-    return guarded([&] {
-        need(c && px && py && r && out, "NULL argument");
-        need(n >= 0, "n must not be negative");
-        need(c->app.lens.on(), "no lens set (radius 0 is the pinhole)");
-        need(c->app.render.tile.width > 0, "no resolution set");
-        if (n == 0) return;
-        const float4* d = lensDeviceBlock(c->app);
-        DevBuf<int> d_x(n), d_y(n); DevBuf<float> d_r(4 * (size_t)n), d_o(6 * (size_t)n);
-        d_x.upload(px, n); d_y.upload(py, n); d_r.upload(r, 4 * (size_t)n);
-        launch_debug_lens_ray(d, n, d_x.p, d_y.p, d_r.p, d_o.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_o.download(out, 6 * (size_t)n);
-    });
-}
 
 // ---- participating medium --------------------------------------------------------------------------------------------------------
 static Medium mediumOf(const ptmi_medium* p) {
@@ -758,23 +678,6 @@ int ptmi_medium_info(const ptmi_ctx* c, ptmi_medium* out, int* on) {
         const MediumState& s = c->app.scene.medium;
         if (out) mediumTo(s.m, out);
         if (on) *on = s.on() ? 1 : 0;
-    });
-}
-int ptmi_debug_medium_call(ptmi_ctx* c, int op, int n, const float* in, float* out) {
-    static_assert(kMediumCallIn == PTMI_MEDIUM_CALL_IN && kMediumCallOut == PTMI_MEDIUM_CALL_OUT && kMediumBlockFloats == PTMI_MEDIUM_BLOCK_FLOATS,
-                  "ptmi.h, device_scene.h and medium.h disagree");
-    return guarded([&] {
-        need(c && in && out, "NULL argument");
-        need(op >= 0 && op <= 3, "op must be 0 .. 3");
-        need(n >= 0, "n must not be negative");
-        if (n == 0) return;
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<float> d_in((size_t)n * kMediumCallIn), d_out((size_t)n * kMediumCallOut);
-        d_in.upload(in, (size_t)n * kMediumCallIn);
-        launch_debug_medium_call(n, op, d_in.p, d_out.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_out.download(out, (size_t)n * kMediumCallOut);
     });
 }
 
@@ -922,131 +825,6 @@ int ptmi_dist_allreduce_max(ptmi_ctx* c, double* value) {
 int ptmi_dist_comm_count(ptmi_ctx* c, int* n_ranks) {
     return guarded([&] { need(c && n_ranks, "NULL argument"); PTMI_HIP(hipSetDevice(c->app.device_id)); *n_ranks = c->app.dist.commCount(); });
 }
-int ptmi_debug_place_tiles(ptmi_ctx* c, int width, int height, int n_ranks, int row_block, const unsigned char* tiles_rgb8,
-                           const float* tiles_radiance, unsigned char* out_rgb8, float* out_radiance) {
-    return guarded([&] {
-        need(c != nullptr, "ctx is NULL");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        debugPlaceTiles(width, height, n_ranks, row_block, tiles_rgb8, tiles_radiance, out_rgb8, out_radiance, c->app.render.stream);
-    });
-}
-
-int ptmi_debug_set_traversal(ptmi_ctx* c, int force_mode, int sweep_max_prims, int* out_mode) {
-    return guarded([&] {
-        need(c != nullptr, "ctx is NULL");
-        need(force_mode >= -1 && (force_mode <= 4 || force_mode == TRAVERSAL_CERTIFIED), "force_mode must be -1..4 or 6");
-        need(sweep_max_prims >= 0, "sweep_max_prims must be >= 0");
-        SceneState& s = c->app.scene;
-        s.force_traversal = force_mode; s.sweep_max_prims = sweep_max_prims;
-        if (force_mode == TRAVERSAL_CERTIFIED && s.d_nodes && !s.fastReady()) {
-            PTMI_HIP(hipSetDevice(c->app.device_id));
-            s.buildFast();
-        }
-        s.chooseTraversal();
-        if (out_mode) *out_mode = s.d_nodes ? s.d_scene.traversal : -1;
-    });
-}
-
-int ptmi_debug_get_traversal(const ptmi_ctx* c, int* out_mode) {
-    return guarded([&] {
-        need(c != nullptr && out_mode != nullptr, "ctx / out_mode is NULL");
-        *out_mode = c->app.scene.d_nodes ? c->app.scene.d_scene.traversal : -1;
-    });
-}
-
-int ptmi_debug_set_solver_walk(ptmi_ctx* c, int force_walk, int min_prims) {
-    return guarded([&] {
-        need(c != nullptr, "ctx is NULL");
-        need(force_walk == -1 || force_walk == 0 || (force_walk >= 2 && force_walk <= 4), "force_walk must be -1, 0, 2, 3 or 4");
-        need(min_prims >= 0, "min_prims must be >= 0");
-        c->app.radiosity.force_walk = force_walk; c->app.radiosity.cert_min_prims = min_prims;
-    });
-}
-
-int ptmi_debug_set_packed_min_nodes(ptmi_ctx* c, int min_nodes, int* n_positions) {
-    return guarded([&] {
-        need(c != nullptr, "ctx is NULL");
-        need(min_nodes >= 0, "min_nodes must be >= 0");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        SceneState& s = c->app.scene;
-        s.packed_min_nodes = min_nodes;
-        if (s.d_nodes) { s.buildPacked(); s.chooseTraversal(); }
-        if (n_positions) *n_positions = s.d_scene.n_pos;
-    });
-}
-
-int ptmi_debug_set_packed_top(ptmi_ctx* c, int top_records, int* n_top, int* top_depth) {
-    return guarded([&] {
-        need(c != nullptr, "ctx is NULL");
-        need(top_records >= 0 && top_records <= 2048, "top_records must be in [0, 2048] (64 KB of LDS)");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        SceneState& s = c->app.scene;
-        s.packed_top_records = top_records;
-        if (s.d_nodes) { s.buildPacked(); s.chooseTraversal(); }
-        if (n_top) *n_top = s.d_scene.n_top;
-        if (top_depth) *top_depth = s.d_scene.top_depth;
-    });
-}
-
-int ptmi_debug_set_fast_tree(ptmi_ctx* c, int max_leaf, float c_trav, float c_tri, int top_nodes, int* n_nodes, int* depth, int* n_top) {
-    return guarded([&] {
-        need(c != nullptr, "ctx is NULL");
-        need(max_leaf >= 1 && max_leaf <= kWideMaxLeaf, "max_leaf must be 1..3");
-        need(c_trav >= 0.0f && c_tri > 0.0f, "c_trav must be >= 0 and c_tri > 0");
-        need(top_nodes >= 0 && top_nodes <= 600, "top_nodes must be in [0, 600] (75 KB of LDS)");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        SceneState& s = c->app.scene;
-        s.wide_params.max_leaf = max_leaf; s.wide_params.c_trav = c_trav; s.wide_params.c_tri = c_tri; s.wide_top_nodes = top_nodes;
-        if (s.d_nodes) s.buildFast();
-        if (n_nodes) *n_nodes = s.d_scene.w_nodes;
-        if (depth) *depth = s.h_wide.depth;
-        if (n_top) *n_top = s.d_scene.w_top;
-    });
-}
-
-// the hooks take rays from anywhere: each origin is held to the bound the scene and the camera are held to (SceneState::upload)
-static void check_hook_rays(const SceneState& s, int n, const float* o, const float* d) {
-    for (int i = 0; i < n; i++) s.checkQuadOrigin(o + 3 * (size_t)i, d + 3 * (size_t)i, "ray");
-}
-
-int ptmi_debug_intersect_fast(ptmi_ctx* c, int n, const float* o, const float* d, float t_min, float t_max,
-                              int* hit, int* prim, float* t, uint64_t* counts) {
-    return guarded([&] {
-        need(c && o && d && hit && prim && t, "NULL argument");
-        need(c->app.scene.d_nodes != nullptr, "no scene loaded");
-        need(n > 0, "n must be positive");
-        check_hook_rays(c->app.scene, n, o, d);
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        if (!c->app.scene.fastReady()) c->app.scene.buildFast();
-        DevBuf<float> d_o(3 * (size_t)n), d_d(3 * (size_t)n), d_t(n);
-        DevBuf<int> d_hit(n), d_prim(n);
-        DevBuf<unsigned long long> d_cnt(2);
-        PTMI_HIP(hipMemset(d_cnt.p, 0, 2 * sizeof(unsigned long long)));
-        d_o.upload(o, 3 * (size_t)n); d_d.upload(d, 3 * (size_t)n);
-        launch_debug_intersect_wide(c->app.scene.d_scene, n, d_o.p, d_d.p, t_min, t_max, d_hit.p, d_prim.p, d_t.p, d_cnt.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_hit.download(hit, n); d_prim.download(prim, n); d_t.download(t, n);
-        if (counts) { unsigned long long h[2]; d_cnt.download(h, 2); counts[0] = h[0]; counts[1] = h[1]; }
-    });
-}
-
-int ptmi_debug_first_hit(ptmi_ctx* c, int n, const float* o, const float* d, float t_min, int* hit, int* prim, float* t) {
-    return guarded([&] {
-        need(c && o && d && hit && prim && t, "NULL argument");
-        need(c->app.scene.d_nodes != nullptr, "no scene loaded");
-        need(n > 0, "n must be positive");
-        check_hook_rays(c->app.scene, n, o, d);
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<float> d_o(3 * (size_t)n), d_d(3 * (size_t)n), d_t(n);
-        DevBuf<int> d_hit(n), d_prim(n);
-        d_o.upload(o, 3 * (size_t)n); d_d.upload(d, 3 * (size_t)n);
-        launch_debug_first_hit(c->app.scene.d_scene, n, d_o.p, d_d.p, t_min, d_hit.p, d_prim.p, d_t.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_hit.download(hit, n); d_prim.download(prim, n); d_t.download(t, n);
-    });
-}
 
 int ptmi_host_fast_tree_build(ptmi_host_scene* s, int max_leaf, float c_trav, float c_tri, int* n_nodes, int* depth, double* sah) {
     return guarded([&] {
@@ -1085,288 +863,6 @@ int ptmi_host_fast_tree_intersect(const ptmi_host_scene* s, int n, const float* 
             t[i] = prim[i] >= 0 ? th : 0.0f;
         }
         if (counts) { counts[0] = cn.node_visits; counts[1] = cn.prim_tests; counts[2] = cn.max_stack; }
-    });
-}
-
-int ptmi_debug_intersect(ptmi_ctx* c, int n, const float* o, const float* d, float t_min, float t_max,
-                         int* hit, int* prim, float* t, float* p, float* nrm) {
-    return guarded([&] {
-        need(c && o && d && hit && prim && t && p && nrm, "NULL argument");
-        need(c->app.scene.d_nodes != nullptr, "no scene loaded");
-        need(n > 0, "n must be positive");
-        check_hook_rays(c->app.scene, n, o, d);
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<float> d_o(3 * (size_t)n), d_d(3 * (size_t)n), d_t(n), d_p(3 * (size_t)n), d_n(3 * (size_t)n);
-        DevBuf<int> d_hit(n), d_prim(n);
-        d_o.upload(o, 3 * (size_t)n); d_d.upload(d, 3 * (size_t)n);
-        launch_debug_intersect(c->app.scene.d_scene, n, d_o.p, d_d.p, t_min, t_max, d_hit.p, d_prim.p, d_t.p, d_p.p, d_n.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_hit.download(hit, n); d_prim.download(prim, n); d_t.download(t, n); d_p.download(p, 3 * (size_t)n); d_n.download(nrm, 3 * (size_t)n);
-    });
-}
-
-int ptmi_debug_rng(ptmi_ctx* c, uint64_t seed_base, int n_pixels, const int* pixels, int count, float* out) {
-    return guarded([&] {
-        need(c && pixels && out, "NULL argument");
-        need(n_pixels > 0 && count > 0, "n_pixels and count must be positive");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<int> d_pix(n_pixels); DevBuf<float> d_out((size_t)n_pixels * count);
-        d_pix.upload(pixels, n_pixels);
-        launch_debug_rng(c->app.render.d_jump, seed_base, n_pixels, d_pix.p, count, d_out.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_out.download(out, (size_t)n_pixels * count);
-    });
-}
-
-int ptmi_debug_rcp_check(ptmi_ctx* c, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad_bits) {
-    return guarded([&] {
-        need(c && mismatches && first_bad_bits, "NULL argument");
-        need(count > 0 && count <= (1ull << 32), "count must be in [1, 2^32]");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<unsigned long long> d(2);
-        const unsigned long long init[2] = {0ull, ~0ull};
-        d.upload(init, 2);
-        launch_debug_rcp(first_bits, count, d.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        unsigned long long h[2];
-        d.download(h, 2);
-        *mismatches = h[0]; *first_bad_bits = h[0] ? (uint32_t)h[1] : 0u;
-    });
-}
-
-int ptmi_debug_sqrt_check(ptmi_ctx* c, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad_bits) {
-    return guarded([&] {
-        need(c && mismatches && first_bad_bits, "NULL argument");
-        need(count > 0 && count <= (1ull << 32), "count must be in [1, 2^32]");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<unsigned long long> d(2);
-        const unsigned long long init[2] = {0ull, ~0ull};
-        d.upload(init, 2);
-        launch_debug_sqrt(first_bits, count, d.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        unsigned long long h[2];
-        d.download(h, 2);
-        *mismatches = h[0]; *first_bad_bits = h[0] ? (uint32_t)h[1] : 0u;
-    });
-}
-
-int ptmi_debug_ray_inv(ptmi_ctx* c, int n, const float* d, const int* live, float* out_inv) {
-    return guarded([&] {
-        need(c && d && live && out_inv, "NULL argument");
-        need(n > 0, "n must be positive");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<float> d_d(3 * (size_t)n), d_o(3 * (size_t)n); DevBuf<int> d_l(n);
-        d_d.upload(d, 3 * (size_t)n); d_l.upload(live, n);
-        launch_debug_ray_inv(n, d_d.p, d_l.p, d_o.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_o.download(out_inv, 3 * (size_t)n);
-    });
-}
-
-int ptmi_debug_sincos_lean_check(ptmi_ctx* c, uint32_t first_bits, uint64_t count, uint64_t* bad_sin, uint64_t* bad_cos,
-                                 uint32_t* first_bad_bits, uint64_t* flagged, uint32_t* flagged_bits, int* n_flagged_bits) {
-    return guarded([&] {
-        need(c && bad_sin && bad_cos && first_bad_bits && flagged && flagged_bits && n_flagged_bits, "NULL argument");
-        need(count > 0 && count <= (1ull << 32), "count must be in [1, 2^32]");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<unsigned long long> d(13);
-        unsigned long long h[13] = {0ull, 0ull, ~0ull};
-        d.upload(h, 13);
-        launch_debug_sincos_lean_check(first_bits, count, d.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d.download(h, 13);
-        *bad_sin = h[0]; *bad_cos = h[1]; *first_bad_bits = (h[0] | h[1]) ? (uint32_t)h[2] : 0u; *flagged = h[3];
-        *n_flagged_bits = (int)std::min<unsigned long long>(h[12], 8ull);
-        for (int i = 0; i < 8; i++) flagged_bits[i] = i < *n_flagged_bits ? (uint32_t)h[4 + i] : 0u;
-    });
-}
-
-int ptmi_debug_sincos_lean(ptmi_ctx* c, int n, const float* x, const int* live, float* out) {
-    return guarded([&] {
-        run_vote_hook(c, n, x, 1, live, out, 4, [&](const float* i, const int* l, float* o, hipStream_t s) { launch_debug_sincos_lean(n, i, l, o, s); });
-    });
-}
-int ptmi_debug_unit_voted(ptmi_ctx* c, int n, const float* w, const int* live, float* out) {
-    return guarded([&] {
-        run_vote_hook(c, n, w, 3, live, out, 6, [&](const float* i, const int* l, float* o, hipStream_t s) { launch_debug_unit_voted(n, i, l, o, s); });
-    });
-}
-
-int ptmi_debug_size_div_check(ptmi_ctx* c, int size, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad_bits, int* lean) {
-    return guarded([&] {
-        need(c && mismatches && first_bad_bits && lean, "NULL argument");
-        need(size >= 1, "size must be positive");
-        need(count > 0 && count <= (1ull << 32), "count must be in [1, 2^32]");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<unsigned long long> d(2);
-        const unsigned long long init[2] = {0ull, ~0ull};
-        d.upload(init, 2);
-        const float inv = ptmi_size_reciprocal(size);                  // as RenderState::allocateBuffers takes TileMap's
-        launch_debug_size_div((float)size, inv, first_bits, count, d.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        unsigned long long h[2];
-        d.download(h, 2);
-        *mismatches = h[0]; *first_bad_bits = h[0] ? (uint32_t)h[1] : 0u; *lean = inv != 0.0f ? 1 : 0;
-    });
-}
-
-int ptmi_debug_cosine_sample(ptmi_ctx* c, int n, const float* normals, const float* u, const float* v, float* out_dirs) {
-    return guarded([&] {
-        need(c && normals && u && v && out_dirs, "NULL argument");
-        need(n > 0, "n must be positive");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<float> d_n(3 * (size_t)n), d_u(n), d_v(n), d_o(3 * (size_t)n);
-        d_n.upload(normals, 3 * (size_t)n); d_u.upload(u, n); d_v.upload(v, n);
-        launch_debug_cosine(n, d_n.p, d_u.p, d_v.p, d_o.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_o.download(out_dirs, 3 * (size_t)n);
-    });
-}
-
-int ptmi_debug_guided_sample(ptmi_ctx* c, int op, int n, int n_recs, const float* recs, const int* rec_idx, const float* normals,
-                             const float* in3, const uint32_t* states, float* out, int* used) {
-    return guarded([&] {
-        need(c && normals && in3 && states && out && used, "NULL argument");
-        need(n > 0, "n must be positive");
-        need(op >= 0 && op <= 5, "op must be in [0, 5]");
-        const bool grid = op >= 1 && op <= 3;
-        if (grid) {
-            need(recs && rec_idx && n_recs > 0, "ops 1-3 need CDF records and their indices");
-            for (int i = 0; i < n; i++) need(rec_idx[i] >= 0 && rec_idx[i] < n_recs, "record index out of range");
-        }
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<float> d_r(grid ? (size_t)n_recs * kCdfDwords : 1), d_n(3 * (size_t)n), d_a(3 * (size_t)n), d_o(6 * (size_t)n);
-        DevBuf<int> d_i(grid ? (size_t)n : 1), d_u(n);
-        DevBuf<uint32_t> d_s(6 * (size_t)n);
-        if (grid) { d_r.upload(recs, (size_t)n_recs * kCdfDwords); d_i.upload(rec_idx, n); }
-        d_n.upload(normals, 3 * (size_t)n); d_a.upload(in3, 3 * (size_t)n); d_s.upload(states, 6 * (size_t)n);
-        launch_debug_guided(n, op, grid ? d_r.p : nullptr, grid ? d_i.p : nullptr, d_n.p, d_a.p, d_s.p, d_o.p, d_u.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_o.download(out, 6 * (size_t)n); d_u.download(used, n);
-    });
-}
-
-int ptmi_debug_math(ptmi_ctx* c, int op, int n, const float* a, const float* b, double* out) {
-    return guarded([&] {
-        need(c && a && b && out, "NULL argument");
-        need(n > 0, "n must be positive");
-        need(op >= 0 && op < PTMI_MATH_OPS, "unknown op");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<float> d_a(n), d_b(n);
-        DevBuf<double> d_o(2 * (size_t)n);
-        d_a.upload(a, n); d_b.upload(b, n);
-        launch_debug_math(n, op, d_a.p, d_b.p, d_o.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_o.download(out, 2 * (size_t)n);
-    });
-}
-
-int ptmi_debug_grid_index(ptmi_ctx* c, int n, const float* dirs, const float* normals, int* out) {
-    return guarded([&] {
-        need(c && dirs && normals && out, "NULL argument");
-        need(n > 0, "n must be positive");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<float> d_d(3 * (size_t)n), d_n(3 * (size_t)n);
-        DevBuf<int> d_o(n);
-        d_d.upload(dirs, 3 * (size_t)n); d_n.upload(normals, 3 * (size_t)n);
-        launch_debug_grid_index(n, d_d.p, d_n.p, d_o.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_o.download(out, n);
-    });
-}
-
-int ptmi_debug_nee_call(ptmi_ctx* c, int op, int n, const float* in, float* out_f, int* out_i) {
-    static_assert(kNeeCallIn == PTMI_NEE_CALL_IN && kNeeCallOutF == PTMI_NEE_CALL_OUT_F && kNeeCallOutI == PTMI_NEE_CALL_OUT_I, "ptmi.h and device_scene.h disagree");
-    return guarded([&] {
-        need(c && in && out_f && out_i, "NULL argument");
-        need(n >= 0, "n must not be negative");
-        need(op >= 0 && op < PTMI_NEE_CALL_OPS, "unknown op");
-        const EnvTable ev = c->app.env.table(true, c->app.scene.d_emitters.n);
-        if (op == PTMI_NEE_CALL_ENV_LOOKUP || op == PTMI_NEE_CALL_ENV_SAMPLE) need(ev.texel != nullptr, "the op needs an environment (ptmi_set_environment)");
-        if (op == PTMI_NEE_CALL_EMITTER_SAMPLE) need(c->app.scene.d_emitters.n > 0, "the op needs a scene with an emitter");
-        if (op == PTMI_NEE_CALL_ENV_LOOKUP)                   // (int)(NaN * w) is no column: the kernel never looks a non-finite direction up
-            for (size_t i = 0; i < (size_t)n * kNeeCallIn; i += kNeeCallIn)
-                need(std::isfinite(in[i]) && std::isfinite(in[i + 1]) && std::isfinite(in[i + 2]), "ENV_LOOKUP needs finite directions");
-        if (n == 0) return;
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<float> d_in((size_t)n * kNeeCallIn), d_f((size_t)n * kNeeCallOutF);
-        DevBuf<int> d_i((size_t)n * kNeeCallOutI);
-        d_in.upload(in, (size_t)n * kNeeCallIn);
-        launch_debug_nee_call(c->app.scene.d_scene.has_quads != 0, n, op, c->app.scene.d_emitters, ev, d_in.p, d_f.p, d_i.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_f.download(out_f, (size_t)n * kNeeCallOutF); d_i.download(out_i, (size_t)n * kNeeCallOutI);
-    });
-}
-
-int ptmi_debug_vertex_normal(ptmi_ctx* c, int n, const int* prim, const float* p, float* out) {
-    return guarded([&] {
-        need(c && prim && p && out, "NULL argument");
-        need(n >= 0, "n must not be negative");
-        const SceneState& sc = c->app.scene;
-        need(sc.d_nodes != nullptr, "no scene loaded");
-        const int n_prims = (int)sc.h_primitives.size();
-        for (int i = 0; i < n; i++) need(prim[i] >= 0 && prim[i] < n_prims, "prim out of range");
-        if (n == 0) return;
-        if (!sc.hasVertexNormals()) {                         // no table: the kernel never calls the function
-            for (int i = 0; i < n; i++) {
-                const f3 s = sc.h_primitives[prim[i]].normal;
-                out[4 * i] = s.x; out[4 * i + 1] = s.y; out[4 * i + 2] = s.z; out[4 * i + 3] = 0.0f;
-            }
-            return;
-        }
-        std::vector<int> slot_of((size_t)n_prims), slots((size_t)n);
-        for (int k = 0; k < n_prims; k++) slot_of[sc.bvh_indices[k]] = k;
-        for (int i = 0; i < n; i++) slots[i] = slot_of[prim[i]];
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<int> d_s((size_t)n);
-        DevBuf<float> d_p(3 * (size_t)n), d_o(4 * (size_t)n);
-        d_s.upload(slots.data(), (size_t)n); d_p.upload(p, 3 * (size_t)n);
-        launch_debug_vertex_normal(sc.d_scene, sc.vertexNormalTable(), n, d_s.p, d_p.p, d_o.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_o.download(out, 4 * (size_t)n);
-    });
-}
-
-int ptmi_debug_albedo(ptmi_ctx* c, int n, const int* prim, const float* p, float* out) {
-    return guarded([&] {
-        need(c && prim && p && out, "NULL argument");
-        need(n >= 0, "n must not be negative");
-        const SceneState& sc = c->app.scene;
-        need(sc.d_nodes != nullptr, "no scene loaded");
-        const int n_prims = (int)sc.h_primitives.size();
-        for (int i = 0; i < n; i++) need(prim[i] >= 0 && prim[i] < n_prims, "prim out of range");
-        if (n == 0) return;
-        if (!sc.hasAlbedoTexture()) {                         // no table: the kernel never calls the function
-            for (int i = 0; i < n; i++) {
-                out[6 * i] = out[6 * i + 1] = out[6 * i + 5] = 0.0f;
-                out[6 * i + 2] = out[6 * i + 3] = out[6 * i + 4] = 1.0f;
-            }
-            return;
-        }
-        std::vector<int> slot_of((size_t)n_prims), slots((size_t)n);
-        for (int k = 0; k < n_prims; k++) slot_of[sc.bvh_indices[k]] = k;
-        for (int i = 0; i < n; i++) slots[i] = slot_of[prim[i]];
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        DevBuf<int> d_s((size_t)n);
-        DevBuf<float> d_p(3 * (size_t)n), d_o(6 * (size_t)n);
-        d_s.upload(slots.data(), (size_t)n); d_p.upload(p, 3 * (size_t)n);
-        launch_debug_albedo(sc.d_scene, sc.albedoTable(), n, d_s.p, d_p.p, d_o.p, c->app.render.stream);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(c->app.render.stream));
-        d_o.download(out, 6 * (size_t)n);
     });
 }
 
@@ -1541,162 +1037,6 @@ int ptmi_denoise_temporal_variance(ptmi_ctx* c, const ptmi_variance_params* para
         ptmi_variance_params p;
         ptmi_default_variance_params(&p);
         denoiseTemporalVariance(c->app, variance_params_from(params ? *params : p));
-    });
-}
-// test hook: the statistics of the history's current side, given instead of accumulated
-int ptmi_debug_set_temporal_moments(ptmi_ctx* c, const float* mean, const float* variance, const float* frames) {
-    return guarded([&] { need(c && mean && variance && frames, "NULL argument"); debugSetTemporalMoments(c->app, mean, variance, frames); });
-}
-
-// ---- test hook: the filters' inputs, given instead of rendered ----
-int ptmi_debug_set_filter_inputs(ptmi_ctx* c, const float* radiance, const float* albedo, const float* normal, const float* position,
-                                 const float* hit_fraction, int grid) {
-    return guarded([&] {
-        need(c && radiance && albedo && normal && position && hit_fraction, "NULL argument");
-        ApplicationState& g = c->app;
-        RenderState& r = g.render;
-        RenderState::Denoise& d = r.dn;
-        need(g.scene.d_nodes != nullptr, "no scene loaded");
-        need(r.d_state.A != nullptr && r.d_image != nullptr && r.d_radiance != nullptr, "buffers not allocated (call updateResolution first)");
-        need(r.tile.n_ranks == 1, "the context is tiled over more than one rank");
-        need(g.config.current_integrator != IntegratorType::Radiosity, "the Radiosity integrator's image is not filtered");
-        need(grid >= 1 && grid <= 4, "grid must be in [1, 4]");
-        PTMI_HIP(hipSetDevice(g.device_id));
-        const size_t n = r.n_local;                     // every size is the context's: width x height of the current resolution
-        if (!d.fb.albedo) {                             // as renderFeatures allocates them
-            const size_t cap = n > 0 ? n : 1;
-            try {
-                d.fb.albedo = (float4*)hipMallocSafe(cap * sizeof(float4), "features.albedo");
-                d.fb.normal = (float4*)hipMallocSafe(cap * sizeof(float4), "features.normal");
-                d.fb.position = (float4*)hipMallocSafe(cap * sizeof(float4), "features.position");
-            } catch (...) { r.freeDenoise(); throw; }
-        }
-        // the uploads are enqueued behind whatever the stream still holds of an earlier filter run, and waited for below
-        std::vector<float4> h_a(n), h_n(n), h_x(n);
-        for (size_t i = 0; i < n; i++) {
-            h_a[i] = make_float4(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], hit_fraction[i]);
-            h_n[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], 0.0f);
-            h_x[i] = make_float4(position[3 * i], position[3 * i + 1], position[3 * i + 2], 0.0f);
-        }
-        d.features_valid = false;
-        d.image_current = false;
-        if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));   // a gather may still read the image
-        if (n) {
-            PTMI_HIP(hipMemcpyAsync(d.fb.albedo, h_a.data(), n * sizeof(float4), hipMemcpyHostToDevice, r.stream));
-            PTMI_HIP(hipMemcpyAsync(d.fb.normal, h_n.data(), n * sizeof(float4), hipMemcpyHostToDevice, r.stream));
-            PTMI_HIP(hipMemcpyAsync(d.fb.position, h_x.data(), n * sizeof(float4), hipMemcpyHostToDevice, r.stream));
-            PTMI_HIP(hipMemcpyAsync(r.d_radiance, radiance, n * 3 * sizeof(float), hipMemcpyHostToDevice, r.stream));
-            // rgb8 by the product's resolve at k = 1: the denoiser's tone map in its 0-iteration form reads the radiance alone
-            DenoiseArgs a{};
-            a.width = r.tile.width; a.height = r.tile.local_rows;
-            launch_denoise(a, d.fb, r.d_radiance, 0, nullptr, nullptr, r.d_image, nullptr, r.stream);
-            PTMI_HIP(hipGetLastError());
-        }
-        PTMI_HIP(hipStreamSynchronize(r.stream));
-        d.grid = grid;
-        d.features_valid = true;
-        d.image_current = true;
-        d.image_pass = false;
-        d.variance_valid = false;
-        d.denoised = false;
-    });
-}
-
-// ---- test hooks: the accumulation's stopping test and resolve, and the launch order by cost, on given state ----
-int ptmi_debug_accum_step(ptmi_ctx* c, const float* sums, const float* prev, const float* m2, const uint32_t* passes, const int* queue,
-                          int n_queue, const ptmi_adaptive_params* params, int first, int* queue_out, int* n_out) {
-    return guarded([&] {
-        need(c && sums && prev && m2 && passes && queue_out && n_out, "NULL argument");
-        AdaptiveParams prm;
-        if (params) { prm.min_passes = params->min_passes; prm.max_passes = params->max_passes; prm.threshold = params->threshold; prm.floor = params->floor; }
-        *n_out = debugAccumStep(c->app, sums, prev, m2, passes, queue, n_queue, params ? &prm : nullptr, first != 0, queue_out);
-    });
-}
-int ptmi_debug_order_by_cost(ptmi_ctx* c, int n, const int* queue_in, const uint32_t* cost, int n_cost, uint32_t cost_max, int classes,
-                             int* queue_out, int* hist) {
-    return guarded([&] {
-        need(c && cost && queue_out && hist, "NULL argument");
-        need(n > 0 && n_cost > 0, "n and n_cost must be positive");
-        need(classes >= 1, "classes must be positive");
-        need(queue_in != nullptr || n <= n_cost, "the identity queue needs n <= n_cost");
-        if (queue_in) for (int i = 0; i < n; i++) need(queue_in[i] >= 0 && queue_in[i] < n_cost, "a queue entry lies outside cost[]");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        const hipStream_t s = c->app.render.stream;
-        DevBuf<int> d_in(queue_in ? (size_t)n : 1), d_out(n), d_hist(512);
-        DevBuf<unsigned int> d_cost(n_cost), d_max(1);
-        if (queue_in) d_in.upload(queue_in, n);
-        d_cost.upload(cost, n_cost); d_max.upload(&cost_max, 1);
-        PTMI_HIP(hipMemsetAsync(d_out.p, 0xff, (size_t)n * sizeof(int), s));      // a position the pass does not write reads -1
-        launch_order_by_cost(queue_in ? d_in.p : nullptr, n, d_cost.p, d_max.p, d_hist.p, d_out.p, classes, s);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(s));
-        d_out.download(queue_out, n); d_hist.download(hist, 512);
-    });
-}
-
-// ---- test hooks: the guided-record kernels (csrc/radiosity.hip) on given grids and form factors ----
-int ptmi_debug_cdf_records(ptmi_ctx* c, int n, int src_kind, const float* src, float* out) {
-    return guarded([&] {
-        need(c && src && out, "NULL argument");
-        need(n >= 1, "n must be positive");
-        need(src_kind >= 0 && src_kind <= 2, "src_kind must be 0, 1 or 2");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        const hipStream_t s = c->app.render.stream;
-        const size_t per = (size_t)kGridSize * (src_kind == 0 ? 4 : src_kind == 1 ? 3 : 1);
-        DevBuf<float> d_src(per * n), d_out((size_t)n * kCdfDwords);
-        d_src.upload(src, per * n);
-        launch_cdf_records(n, d_src.p, src_kind, d_out.p, s);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(s));
-        d_out.download(out, (size_t)n * kCdfDwords);
-    });
-}
-int ptmi_debug_filter_pdfs(ptmi_ctx* c, int n, const float* rgb, const float* counts, int use_bilateral, float sigma_spatial,
-                           float sigma_range, float* out_formfactor, float* out_radiosity) {
-    return guarded([&] {
-        need(c && rgb && out_formfactor && out_radiosity, "NULL argument");
-        need(n >= 1, "n must be positive");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        const hipStream_t s = c->app.render.stream;
-        const size_t cells = (size_t)n * kGridSize;
-        DevBuf<float> d_rgb(3 * cells), d_cnt(counts ? cells : 1), d_ff(cells), d_rad(cells);
-        d_rgb.upload(rgb, 3 * cells);
-        if (counts) d_cnt.upload(counts, cells);
-        launch_filter_pdfs(n, d_rgb.p, counts ? d_cnt.p : nullptr, d_ff.p, d_rad.p, use_bilateral != 0, sigma_spatial, sigma_range, s);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(s));
-        d_ff.download(out_formfactor, cells); d_rad.download(out_radiosity, cells);
-    });
-}
-int ptmi_debug_radiosity_grid(ptmi_ctx* c, int n, const float* centre, const float* normal, const float* form_factors,
-                              const float* radiosity, int enable_filtering, int use_bilateral, float sigma_spatial, float sigma_range,
-                              float* out) {
-    return guarded([&] {
-        need(c && centre && normal && form_factors && radiosity && out, "NULL argument");
-        need(n >= 1, "n must be positive");
-        PTMI_HIP(hipSetDevice(c->app.device_id));
-        const hipStream_t s = c->app.render.stream;
-        const size_t cells = (size_t)n * kGridSize;
-        // geo: only the normal [4] and the centroid [5] of each primitive's six records are read by the kernel
-        std::vector<float4> h_geo(6 * (size_t)n, make_float4(0.0f, 0.0f, 0.0f, 0.0f)), h_rad(n), h_grid(cells);
-        for (int i = 0; i < n; i++) {
-            h_geo[6 * (size_t)i + 4] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], 0.0f);
-            h_geo[6 * (size_t)i + 5] = make_float4(centre[3 * i], centre[3 * i + 1], centre[3 * i + 2], 0.0f);
-            h_rad[i] = make_float4(radiosity[3 * i], radiosity[3 * i + 1], radiosity[3 * i + 2], 0.0f);
-        }
-        DevBuf<float4> d_geo(6 * (size_t)n), d_rad(n), d_grid(cells);
-        DevBuf<float> d_ff((size_t)n * n);
-        d_geo.upload(h_geo.data(), 6 * (size_t)n); d_rad.upload(h_rad.data(), n); d_ff.upload(form_factors, (size_t)n * n);
-        RadiosityBuffers rb;
-        rb.geo = d_geo.p; rb.radiosity = d_rad.p; rb.form_factors = d_ff.p; rb.rad_grid = d_grid.p; rb.n = n;
-        RadiosityParams prm{};
-        prm.enable_filtering = enable_filtering != 0; prm.use_bilateral = use_bilateral != 0;
-        prm.filter_sigma_spatial = sigma_spatial; prm.filter_sigma_range = sigma_range;
-        launch_radiosity_grid(rb, prm, s);
-        PTMI_HIP(hipGetLastError());
-        PTMI_HIP(hipStreamSynchronize(s));
-        d_grid.download(h_grid.data(), cells);
-        for (size_t k = 0; k < cells; k++) { out[3 * k] = h_grid[k].x; out[3 * k + 1] = h_grid[k].y; out[3 * k + 2] = h_grid[k].z; }
     });
 }
 

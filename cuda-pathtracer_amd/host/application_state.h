@@ -530,6 +530,9 @@ void denoiseTemporal(ApplicationState& g_state, const DenoiseParams& p);
 void setTemporalMoments(ApplicationState& g_state, int on);          // a new value empties the history
 void readTemporalMoments(const ApplicationState& g_state, float* mean, float* variance, float* frames);
 void debugSetTemporalMoments(ApplicationState& g_state, const float* mean, const float* variance, const float* frames);
+// Test hook (include/ptmi.h: ptmi_debug_set_filter_inputs): radiance and features of the current resolution, given instead of rendered
+void debugSetFilterInputs(ApplicationState& g_state, const float* radiance, const float* albedo, const float* normal, const float* position,
+                          const float* hit_fraction, int grid);
 void denoiseTemporalVariance(ApplicationState& g_state, const VarianceParams& p);
 
 bool packBvhNodes(const std::vector<BVHNode>& bvh_nodes, int top_records, std::vector<float4>& g, int& n_pos, int& n_top, int& top_depth);

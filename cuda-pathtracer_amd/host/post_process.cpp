@@ -81,6 +81,56 @@ void readFeatures(const ApplicationState& g, float* albedo, float* normal, float
 }
 
 // the parameters the two a-trous filters share
+// test hook: the filters' inputs, given instead of rendered
+void debugSetFilterInputs(ApplicationState& g, const float* radiance, const float* albedo, const float* normal, const float* position,
+                          const float* hit_fraction, int grid) {
+    RenderState& r = g.render;
+    RenderState::Denoise& d = r.dn;
+    if (!g.scene.d_nodes) throw ArgError("no scene loaded");
+    if (!r.d_state.A || !r.d_image || !r.d_radiance) throw ArgError("buffers not allocated (call updateResolution first)");
+    if (r.tile.n_ranks != 1) throw ArgError("the context is tiled over more than one rank");
+    if (g.config.current_integrator == IntegratorType::Radiosity) throw ArgError("the Radiosity integrator's image is not filtered");
+    if (grid < 1 || grid > 4) throw ArgError("grid must be in [1, 4]");
+    PTMI_HIP(hipSetDevice(g.device_id));
+    const size_t n = r.n_local;                         // every size is the context's: width x height of the current resolution
+    if (!d.fb.albedo) {                                 // as renderFeatures allocates them
+        const size_t cap = n > 0 ? n : 1;
+        try {
+            d.fb.albedo = (float4*)hipMallocSafe(cap * sizeof(float4), "features.albedo");
+            d.fb.normal = (float4*)hipMallocSafe(cap * sizeof(float4), "features.normal");
+            d.fb.position = (float4*)hipMallocSafe(cap * sizeof(float4), "features.position");
+        } catch (...) { r.freeDenoise(); throw; }
+    }
+    // the uploads are enqueued behind whatever the stream still holds of an earlier filter run, and waited for below
+    std::vector<float4> h_a(n), h_n(n), h_x(n);
+    for (size_t i = 0; i < n; i++) {
+        h_a[i] = make_float4(albedo[3 * i], albedo[3 * i + 1], albedo[3 * i + 2], hit_fraction[i]);
+        h_n[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], 0.0f);
+        h_x[i] = make_float4(position[3 * i], position[3 * i + 1], position[3 * i + 2], 0.0f);
+    }
+    d.features_valid = false;
+    d.image_current = false;
+    if (r.resolve_gate) PTMI_HIP(hipStreamWaitEvent(r.stream, r.resolve_gate, 0));   // a gather may still read the image
+    if (n) {
+        PTMI_HIP(hipMemcpyAsync(d.fb.albedo, h_a.data(), n * sizeof(float4), hipMemcpyHostToDevice, r.stream));
+        PTMI_HIP(hipMemcpyAsync(d.fb.normal, h_n.data(), n * sizeof(float4), hipMemcpyHostToDevice, r.stream));
+        PTMI_HIP(hipMemcpyAsync(d.fb.position, h_x.data(), n * sizeof(float4), hipMemcpyHostToDevice, r.stream));
+        PTMI_HIP(hipMemcpyAsync(r.d_radiance, radiance, n * 3 * sizeof(float), hipMemcpyHostToDevice, r.stream));
+        // rgb8 by the product's resolve at k = 1: the denoiser's tone map in its 0-iteration form reads the radiance alone
+        DenoiseArgs a{};
+        a.width = r.tile.width; a.height = r.tile.local_rows;
+        launch_denoise(a, d.fb, r.d_radiance, 0, nullptr, nullptr, r.d_image, nullptr, r.stream);
+        PTMI_HIP(hipGetLastError());
+    }
+    PTMI_HIP(hipStreamSynchronize(r.stream));
+    d.grid = grid;
+    d.features_valid = true;
+    d.image_current = true;
+    d.image_pass = false;
+    d.variance_valid = false;
+    d.denoised = false;
+}
+
 static void checkIterations(int iterations) {
     if (iterations < 0 || iterations > 10) throw ArgError("denoise: iterations must be in [0, 10]");
 }
